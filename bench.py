@@ -2,8 +2,15 @@
 """Headline benchmark: PCD epochs/sec on BASELINE config 2 (degree=2, n_components=30,
 regularizer='squaredl12', solver='pcd', 1M x 100k synthetic CSR, ~50 nnz/row).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4}] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line; everything else it can
+measure (the `roofline` object, `cpu_baseline`, the N = 1 extras and the N > 1 `weak` family and
+`independent_fits` below) runs only with ``--full``.  ``--dump-outputs DIR`` writes what the last
+timed step left behind -- the model P and w, the predictions y_pred, that step's violation sum --
+as float64 ``DIR/<name>.npy``; the inputs are seeded, so two builds can be compared array by array.
 
 ``--gpus N`` without a launcher (WORLD_SIZE unset) starts the N ranks itself: N child processes
 of this script with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, started BEFORE anything in
@@ -20,7 +27,7 @@ epochs (fit_lower='explicit') and the top-order epoch, on data already resident 
 timed region calls exactly what the estimators call per iteration (``HipEngine.*_epoch`` through
 the C ABI).
 
-Prints ONE JSON line (rank 0).  Extra objects at N = 1:
+Prints ONE JSON line (rank 0).  Extra objects at N = 1 (``--full``):
   roofline        dominant kernel: algorithmic bytes per launch / average launch duration (HIP
                   events on the engine's stream) vs 8 TB/s HBM.  `traffic` = HBM bytes per
                   launch from the rocprofv3 --pmc passes committed under profiles/ -- only if
@@ -37,13 +44,14 @@ Prints ONE JSON line (rank 0).  Extra objects at N = 1:
                   path; sparsepoly_amd/concurrent.py): aggregate epochs/s and bytes/s.  `value`
                   stays the rate of ONE fit
 N > 1: rows are sharded over the ranks; the persistent passes exchange their per-step totals
-through peer-mapped slabs inside the kernels (no per-step collective).  ONE line carries both
-families: ``value`` = STRONG scaling (the 1M x 100k matrix of config 2 itself, sharded by rows:
-the same epoch on N GPUs, so value(1) is the single-GPU figure), the extra ``weak`` = N times the
-rows AND columns (the family that ends in BASELINE configs[4]: 10M x 1M on 8 GPUs), its value =
-N x epochs/s of that N-times larger problem, and the extra ``independent_fits`` = one whole
-config-2 fit per GPU with nothing exchanged (a parameter grid fanned out over the devices).
-``--scaling strong|weak`` runs one family only.  Set-up is O(1/N) per rank: a rank draws only its
+through peer-mapped slabs inside the kernels (no per-step collective).  ``value`` = STRONG scaling
+(the 1M x 100k matrix of config 2 itself, sharded by rows: the same epoch on N GPUs, so value(1)
+is the single-GPU figure).  With ``--full`` the ONE line carries both families: the extra
+``weak`` = N times the rows AND columns (the family that ends in BASELINE configs[4]: 10M x 1M on
+8 GPUs), its value = N x epochs/s of that N-times larger problem, and the extra
+``independent_fits`` = one whole config-2 fit per GPU with nothing exchanged (a parameter grid
+fanned out over the devices).  ``--scaling strong|weak`` runs one family only, ``--scaling both``
+both (the default with ``--full``).  Set-up is O(1/N) per rank: a rank draws only its
 own rows from the counter-based generator and hands them to the library as CSR; rank 0 alone
 draws the global STRUCTURE (no values), colours it and broadcasts order / batch boundaries, which
 the other ranks install with spfm_set_schedule_raw.
@@ -387,9 +395,11 @@ class Bench(object):
         return v
 
     # ---- one measured workload ---------------------------------------------------------
-    def measure(self, data, cfg_id, precision, schedule, steps, warmup, want_y0=False):
+    def measure(self, data, cfg_id, precision, schedule, steps, warmup, want_y0=False,
+                roofline=True, want_outputs=False):
         """warmup untimed + `steps` timed iterations (barrier + synchronize on both sides, MAX
-        over ranks), then one profiled epoch for the roofline object.  Returns a dict."""
+        over ranks), then (`roofline`) one profiled epoch for the roofline object.  Returns a
+        dict; `want_outputs` adds the state the last timed step left as res["outputs"]."""
         torch, dist = self.torch, self.dist if data["sharded"] else None
         cfg = CONFIGS[cfg_id]
         K, DEGREE = cfg["k"], cfg["degree"]
@@ -460,11 +470,45 @@ class Bench(object):
             elapsed = float(t.item())
         ms_per_step = 1e3 * elapsed / max(steps, 1)
         loss_after = eng.loss_sum()
-        P_end, _ = eng.get_params()
+        P_end, w_end = eng.get_params()
         nnz_frac_P = float((P_end != 0).mean())
+        outputs = None
+        if want_outputs:  # before the profiled epoch below moves the state on
+            outputs = {"P": P_end, "w": w_end, "y_pred": eng.get_y_pred(),
+                       "viol": np.array(viols[-1:], dtype=np.float64)}
 
-        # ---- roofline of the dominant kernel (profiled epoch, outside the timed region): HIP
-        # events on the engine's stream around every launch of that kernel
+        tsz = 4 if precision == "f32" else 8
+        roof = self.roofline(eng, cfg_id, precision, schedule, n_batches) if roofline else None
+        # what really ran: the ranks of the engine's communicator, the exchange it used, whether
+        # a persistent pass had to be redone on the multi-kernel engine; per-rank set-up cost
+        res = dict(
+            cfg_id=cfg_id, n=n, d=data["d"], nnz=nnz, schedule=schedule, precision=precision,
+            ms_per_step=ms_per_step, elapsed=elapsed, steps=steps, viols=viols,
+            loss_after=float(loss_after), nnz_frac_P=nnz_frac_P, n_batches=n_batches, roof=roof,
+            ranks_seen=int(eng.get_option("n_ranks")),
+            peer_exchange=bool(eng.get_option("peer_ready")),
+            fallbacks=int(eng.get_option("persistent_fallbacks")),
+            order=order, P0=P0, y_pred0=y_pred0, outputs=outputs)
+        setup["peak_rss_gb"] = round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1048576.0, 2)
+        setup["rank"] = self.rank
+        setups = [setup]
+        if dist is not None:
+            setups = [None] * self.world
+            dist.all_gather_object(setups, setup)
+        res["setups"] = setups
+        b_alg = alg_bytes(cfg, n, nnz, tsz)
+        res["b_alg"] = b_alg
+        res["iter_gbs"] = b_alg / (ms_per_step * 1e-3) / 1e9
+        res["steps_per_iter"] = (1 + (K * (DEGREE - 1) if cfg["solver"] == "pcd"
+                                      else (DEGREE - 1))) * n_batches
+        eng.close()
+        return res
+
+    def roofline(self, eng, cfg_id, precision, schedule, n_batches):
+        """Roofline of the dominant kernel (profiled epoch, outside the timed region): HIP events
+        on the engine's stream around every launch of that kernel."""
+        cfg = CONFIGS[cfg_id]
+        K, DEGREE = cfg["k"], cfg["degree"]
         tsz = 4 if precision == "f32" else 8
         ic = np.arange(K, dtype=np.int32)
         roof = None
@@ -529,30 +573,7 @@ class Bench(object):
                     # (wide pass: 2 = the blocks' first rows in LDS, the others in global memory)
                     roof["row_block_in_lds"] = int(eng.get_option(
                         "wide_lds_active" if eng.get_option("wide_active") else "prb_lds_active"))
-        # what really ran: the ranks of the engine's communicator, the exchange it used, whether
-        # a persistent pass had to be redone on the multi-kernel engine; per-rank set-up cost
-        res = dict(
-            cfg_id=cfg_id, n=n, d=data["d"], nnz=nnz, schedule=schedule, precision=precision,
-            ms_per_step=ms_per_step, elapsed=elapsed, steps=steps, viols=viols,
-            loss_after=float(loss_after), nnz_frac_P=nnz_frac_P, n_batches=n_batches, roof=roof,
-            ranks_seen=int(eng.get_option("n_ranks")),
-            peer_exchange=bool(eng.get_option("peer_ready")),
-            fallbacks=int(eng.get_option("persistent_fallbacks")),
-            order=order, P0=P0, y_pred0=y_pred0)
-        setup["peak_rss_gb"] = round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1048576.0, 2)
-        setup["rank"] = self.rank
-        setups = [setup]
-        if dist is not None:
-            setups = [None] * self.world
-            dist.all_gather_object(setups, setup)
-        res["setups"] = setups
-        b_alg = alg_bytes(cfg, n, nnz, tsz)
-        res["b_alg"] = b_alg
-        res["iter_gbs"] = b_alg / (ms_per_step * 1e-3) / 1e9
-        res["steps_per_iter"] = (1 + (K * (DEGREE - 1) if cfg["solver"] == "pcd"
-                                      else (DEGREE - 1))) * n_batches
-        eng.close()
-        return res
+        return roof
 
     # ---- summaries -------------------------------------------------------------------
     @staticmethod
@@ -624,6 +645,27 @@ def cpu_baseline(data, res):
             "sample": "one full iteration (cd_linear + every component pass / block epoch) of "
                       "the same %dx%d workload in the same column order: %.1f s" % (n, d, cpu_s),
             "host_cpus": os.cpu_count()}
+
+
+DUMP_LIMIT = 64 << 20  # bytes that --dump-outputs writes at most
+
+
+def dump_outputs(out_dir, arrays):
+    """One float64 .npy per array.  When the arrays exceed DUMP_LIMIT in all, an array larger
+    than its share of the budget is replaced by its entries at a fixed, seeded set of flat
+    indices (sorted), so that the same arguments always pick the same entries."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    share = (DUMP_LIMIT - 4096 * len(arrays)) // 8 // len(arrays)  # entries; room for headers
+    for name, a in sorted(arrays.items()):
+        if total > DUMP_LIMIT and a.size > share:
+            idx = np.unique(np.random.RandomState(0).randint(0, a.size, share, dtype=np.int64))
+            log("--dump-outputs: %s has %d entries, writing a sample of %d" % (name, a.size,
+                                                                               idx.size))
+            a = a.ravel()[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("--dump-outputs: %s written to %s" % (", ".join(sorted(arrays)), out_dir))
 
 
 def single_gpu_extras(b, data, head, args):
@@ -735,18 +777,29 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the roofline object, the "
+                         "CPU baseline, the N = 1 extras and the N > 1 weak family and "
+                         "independent fits (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip other_configs, exact-schedule, f64 and concurrent-fits measurements")
+                    help="with --full: skip other_configs, exact-schedule, f64 and concurrent-fits "
+                         "measurements (N > 1: independent_fits)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step left (P, w, y_pred, viol) as "
+                         "float64 DIR/<name>.npy")
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
     ap.add_argument("--schedule", default="colored", choices=["colored", "exact"])
-    ap.add_argument("--scaling", default="both", choices=["both", "weak", "strong"],
+    ap.add_argument("--scaling", default=None, choices=["both", "weak", "strong"],
                     help="N > 1: strong = the 1M x 100k matrix of the config sharded over the "
                          "ranks (`value` of the default line); weak = N times the rows AND "
                          "columns (rows sharded; same dependent steps per sweep, fixed work per "
                          "GPU and step; the family that ends in BASELINE configs[4] = 10M x 1M "
-                         "on 8 GPUs); both (default) = strong as `value`, weak as an extra")
+                         "on 8 GPUs); both = strong as `value`, weak as an extra (default: "
+                         "both with --full, else strong)")
     args = ap.parse_args()
+    if args.scaling is None:
+        args.scaling = "both" if args.full else "strong"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: start the ranks ourselves (children, never a re-exec; nothing in this
         # process has touched the GPU)
@@ -772,12 +825,13 @@ def main():
     if world == 1:
         data = b.make_data(N_SAMPLES, N_FEATURES, sharded=False)
         head = b.measure(data, args.config, args.precision, args.schedule, args.steps, args.warmup,
-                         want_y0=not args.no_cpu_baseline)
+                         want_y0=args.full and not args.no_cpu_baseline, roofline=args.full,
+                         want_outputs=bool(args.dump_outputs))
         value = args.steps / head["elapsed"]
         scaling = "weak"
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             extras = single_gpu_extras(b, data, head, args)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(data, head)
         note = "single GPU: " + ("the configuration BASELINE.json's metric is quoted on"
                                  if not RESIZED else
@@ -792,7 +846,8 @@ def main():
             sc = world if fam == "weak" else 1
             data = b.make_data(N_SAMPLES * sc, N_FEATURES * sc, sharded=True)
             results[fam] = b.measure(data, args.config, args.precision, args.schedule, args.steps,
-                                     args.warmup)
+                                     args.warmup, roofline=args.full,
+                                     want_outputs=bool(args.dump_outputs) and fam == fams[0])
             del data
         head_fam = fams[0]
         head = results[head_fam]
@@ -823,7 +878,7 @@ def main():
             note += "; REHEARSAL: %d ranks time-slice %d device(s)" % (world, b.devices_used)
         # ---- one independent fit per GPU: nothing is exchanged (a parameter grid fanned out over
         # the devices, sparsepoly_amd.concurrent.fit_concurrently(devices=...))
-        if not b.rehearsal and not args.no_extras and args.scaling == "both":
+        if args.full and not b.rehearsal and not args.no_extras and args.scaling == "both":
             data = b.make_data(N_SAMPLES, N_FEATURES, sharded=False)
             r = b.measure(data, args.config, args.precision, args.schedule, args.steps, 1)
             del data
@@ -836,6 +891,8 @@ def main():
                 "note": "every rank runs the whole config on its own GPU (different models of a "
                         "grid); no exchange, so this scales with N by construction"}
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, head["outputs"])
     if rank == 0:
         par = "single GPU"
         if world > 1:
