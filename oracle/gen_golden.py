@@ -31,6 +31,9 @@ Fixture families:
   g10 regularizer eval() of all six plug-ins (2-D and stacked 3-D inputs, both `transpose`
       settings, degrees 2-4 and -1) -- never called by a solver, but part of the plug-in
       surface a user of the reference can call
+  g11 degrees 4-6: trajectories (pcd l1/omegati, pbcd l1/l21/omegacs, k = 5-8 and 31),
+      permuted orders, anova_kernel at degree 6 with k = 65, estimator _get_output at degree
+      4-6, psgd at degree 5 and 6
 """
 import contextlib
 import io
@@ -784,7 +787,202 @@ def gen_g10():
     save("g10_reg_eval.npz", **out)
 
 
+# -------------------------------------------------------------------- g11
+# Trajectory cases at degree 4-6: tag, solver, regularizer, degree, k, fit_lower, loss, gamma.
+# Each (solver, regularizer) pair meets every loss once across the three degrees.  On g3's
+# problem (about 6 entries per row, P0 = 0.01 randn, gamma 0.1) the top-order P of degree 5 and
+# 6 goes to exactly zero in the first epoch: these cases use a denser problem, P0 = 0.5 randn,
+# beta 1 and small gammas so that the top order stays live (G11_META records how live, and how
+# well conditioned the iteration is).
+G11_TRAJ = [
+    ("pcd_l1_d4", "pcd", "l1", 4, 6, "explicit", "squared", 1e-3),
+    ("pcd_l1_d5", "pcd", "l1", 5, 5, None, "squared_hinge", 1e-3),
+    ("pcd_l1_d6", "pcd", "l1", 6, 7, "explicit", "logistic", 1e-3),
+    ("pcd_ti_d4", "pcd", "omegati", 4, 8, None, "squared_hinge", 1e-3),
+    ("pcd_ti_d5", "pcd", "omegati", 5, 6, "explicit", "logistic", 1e-3),
+    ("pcd_ti_d6", "pcd", "omegati", 6, 5, "explicit", "squared", 1e-3),
+    ("pbcd_l1_d4", "pbcd", "l1", 4, 7, "explicit", "logistic", 1e-3),
+    ("pbcd_l1_d5", "pbcd", "l1", 5, 8, "explicit", "squared", 1e-3),
+    ("pbcd_l1_d6", "pbcd", "l1", 6, 6, "explicit", "squared_hinge", 1e-3),
+    ("pbcd_l21_d4", "pbcd", "l21", 4, 31, "explicit", "squared", 1e-3),
+    ("pbcd_l21_d5", "pbcd", "l21", 5, 6, "explicit", "squared_hinge", 1e-3),
+    ("pbcd_l21_d6", "pbcd", "l21", 6, 8, None, "logistic", 1e-3),
+    ("pbcd_cs_d4", "pbcd", "omegacs", 4, 5, None, "squared_hinge", 1e-3),
+    ("pbcd_cs_d5", "pbcd", "omegacs", 5, 7, "explicit", "logistic", 1e-4),
+    ("pbcd_cs_d6", "pbcd", "omegacs", 6, 6, "explicit", "squared", 1e-5),
+]
+# permuted coordinate orders (as g4): tag, solver, regularizer, degree, k, loss, gamma
+G11_PERM = [
+    ("perm_pcd_ti_d5", "pcd", "omegati", 5, 6, "squared", 1e-3),
+    ("perm_pbcd_l21_d6", "pbcd", "l21", 6, 5, "logistic", 1e-3),
+]
+G11_PARAMS = dict(alpha=1e-2, beta=1.0, eta0=1.0, p0_scale=0.5, n_epochs=3)
+
+
+def g11_problem():
+    """300 x 40, density 0.25 (10 entries per row on average), float32-exact X and y."""
+    return small_problem(n=300, d=40, density=0.25, seed=31)
+
+
+def g11_labels(y, loss):
+    return y if loss == "squared" else np.where(y > np.median(y), 1.0, -1.0)
+
+
+def g11_oracle_run(orc, X, y, case, P0, lams):
+    """The case through the CPU oracle (oracle/oracle.py): final P_."""
+    tag, solver, regname, degree, k, fit_lower, loss, gamma = case
+    fm = orc.OracleFM(degree=degree, loss=loss, n_components=k, solver=solver,
+                      regularizer=regname, alpha=G11_PARAMS["alpha"], beta=G11_PARAMS["beta"],
+                      gamma=gamma, eta0=G11_PARAMS["eta0"], tol=0, fit_lower=fit_lower,
+                      fit_linear=True, max_iter=G11_PARAMS["n_epochs"])
+    fm.fit(X, y, P_init=P0, lams_init=lams)
+    return fm.P_
+
+
+def gen_g11():
+    """Degrees 4-6: trajectories of pcd l1/omegati and pbcd l1/l21/omegacs,
+    permuted orders, anova_kernel / poly_predict at degree 6 with k = 65 and rows sparser than
+    the degree, estimator _get_output at degree 4-6 (the reference adds no lower orders beyond
+    degree 3: sparse_factorization_machines.py:445), psgd at degree 5 and 6."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from oracle import oracle as orc
+
+    orc.build()
+    X, y = g11_problem()
+    n, d = X.shape
+    out = {"X_data": X.data, "X_indices": X.indices, "X_indptr": X.indptr,
+           "X_shape": np.array(X.shape), "y": y}
+    p = G11_PARAMS
+    names = []
+    for case in G11_TRAJ:
+        tag, solver, regname, degree, k, fit_lower, loss, gamma = case
+        n_orders = degree - 1 if fit_lower == "explicit" else 1
+        P0 = p["p0_scale"] * np.random.RandomState(0).randn(n_orders, k, d)
+        lams = np.sign(np.random.RandomState(5).randn(k))
+        yy = g11_labels(y, loss)
+        r = drive(X, yy, solver, regname, loss, degree, k, alpha=p["alpha"], beta=p["beta"],
+                  gamma=gamma, eta0=p["eta0"], n_epochs=p["n_epochs"], fit_linear=True,
+                  fit_lower=fit_lower, P0=P0, lams=lams)
+        # conditioning, measured with the oracle: a 1e-9 relative perturbation of P0
+        base = g11_oracle_run(orc, X, yy, case, P0, lams)
+        eps = 1e-9
+        P0e = P0 * (1.0 + eps * np.random.RandomState(7).uniform(-1, 1, P0.shape))
+        pert = g11_oracle_run(orc, X, yy, case, P0e, lams)
+        amp = float(np.abs(pert - base).max() / eps)
+        live = float(np.mean(r["P"][0] != 0))
+        names.append(tag)
+        out["meta|" + tag] = np.array(json.dumps(dict(
+            solver=solver, regularizer=regname, degree=degree, k=k, fit_lower=fit_lower,
+            loss=loss, alpha=p["alpha"], beta=p["beta"], gamma=gamma, eta0=p["eta0"],
+            n_epochs=p["n_epochs"], top_nonzero=live, amplification=amp)))
+        out["P0|" + tag] = P0
+        out["lams|" + tag] = lams
+        for kk, v in r.items():
+            out["%s|%s" % (kk, tag)] = v
+        print("%-18s live %.2f amp %.3g |P|max %.3g viol %s" % (
+            tag, live, amp, np.abs(r["P"]).max(), r["viol"]))
+    out["cases"] = np.array(names)
+    # ---- permuted orders
+    prm = np.random.RandomState(13)
+    pnames = []
+    for tag, solver, regname, degree, k, loss, gamma in G11_PERM:
+        ne = p["n_epochs"]
+        forders = np.stack([prm.permutation(d) for _ in range(ne)]).astype(np.int32)
+        corders = np.stack([prm.permutation(k) for _ in range(ne)]).astype(np.int32)
+        P0 = p["p0_scale"] * np.random.RandomState(1).randn(degree - 1, k, d)
+        lams = np.sign(np.random.RandomState(2).randn(k))
+        yy = g11_labels(y, loss)
+        r = drive(X, yy, solver, regname, loss, degree, k, alpha=p["alpha"], beta=p["beta"],
+                  gamma=gamma, eta0=p["eta0"], n_epochs=ne, fit_linear=True,
+                  fit_lower="explicit", P0=P0, lams=lams, feature_orders=forders,
+                  component_orders=corders)
+        pnames.append(tag)
+        out["meta|" + tag] = np.array(json.dumps(dict(
+            solver=solver, regularizer=regname, degree=degree, k=k, fit_lower="explicit",
+            loss=loss, alpha=p["alpha"], beta=p["beta"], gamma=gamma, eta0=p["eta0"],
+            n_epochs=ne, top_nonzero=float(np.mean(r["P"][0] != 0)))))
+        out["forders|" + tag] = forders
+        out["corders|" + tag] = corders
+        out["P0|" + tag] = P0
+        out["lams|" + tag] = lams
+        for kk, v in r.items():
+            out["%s|%s" % (kk, tag)] = v
+        print("%-18s live %.2f" % (tag, np.mean(r["P"][0] != 0)))
+    out["pcases"] = np.array(pnames)
+    # ---- anova_kernel / poly_predict at degree 6, k = 65: rows with fewer entries than the
+    # degree (0..5) and one empty row
+    rng = np.random.RandomState(41)
+    na, da, ka = 24, 11, 65
+    Xa = rng.randn(na, da) * (rng.rand(na, da) < 0.7)
+    for i, m in enumerate([0, 1, 2, 3, 4, 5]):
+        Xa[i] = 0.0
+        Xa[i, rng.choice(da, m, replace=False)] = rng.randn(m)
+    Xa = Xa.astype(np.float32).astype(np.float64)
+    Pa = rng.randn(ka, da) * 0.7
+    lamsa = np.sign(rng.randn(ka))
+    out["a_X"], out["a_P"], out["a_lams"] = Xa, Pa, lamsa
+    out["a_K_dense"] = anova_kernel(Xa, Pa, 6)
+    out["a_K_sparse"] = np.asarray(anova_kernel(sp.csr_matrix(Xa), Pa, 6))
+    out["a_pred_dense"] = poly_predict(Xa, Pa, lamsa, kernel="anova", degree=6)
+    out["a_pred_sparse"] = np.asarray(poly_predict(sp.csr_matrix(Xa), Pa, lamsa, kernel="anova",
+                                                   degree=6))
+    # ---- estimator _get_output, fit_lower='explicit' (lower orders ignored beyond degree 3)
+    for degree in (4, 5, 6):
+        est = SparseFactorizationMachineRegressor(degree=degree, n_components=7,
+                                                  fit_lower="explicit")
+        est.P_ = rng.randn(degree - 1, 7, da)
+        est.w_ = rng.randn(da)
+        est.lams_ = np.sign(rng.randn(7))
+        tag = "deg%d" % degree
+        out["est_P|" + tag] = est.P_
+        out["est_w|" + tag] = est.w_
+        out["est_lams|" + tag] = est.lams_
+        out["est_pred|" + tag] = est.predict(sp.csr_matrix(Xa))
+    # ---- psgd at degree 5 and 6, n_orders = degree - 1 (estimator fit as in g9)
+    snames = []
+    for tag, regname, degree, k, lr, batch, gamma in [
+            ("l1d5", "l1", 5, 6, "optimal", 20, 1e-3),
+            ("l21d5", "l21", 5, 5, "constant", 32, 1e-3),
+            ("l1d6", "l1", 6, 5, "constant", 16, 1e-3),
+            ("l21d6", "l21", 6, 6, "optimal", "auto", 1e-3)]:
+        P0 = 0.3 * np.random.RandomState(0).randn(degree - 1, k, d)
+        lam = np.sign(np.random.RandomState(5).randn(k))
+        for loss in ("squared", "logistic"):
+            yy = g11_labels(y, loss)
+            kw = dict(degree=degree, n_components=k, fit_lower="explicit", fit_linear=True,
+                      alpha=1e-2, beta=0.1, gamma=gamma, regularizer=regname, learning_rate=lr,
+                      eta0=0.02, power_t=1.0, warm_start=True, tol=-1.0, n_iter_no_change=1000,
+                      max_iter=3, random_state=3, shuffle=False, solver="psgd",
+                      batch_size=batch)
+            if loss == "squared":
+                est = SparseFactorizationMachineRegressor(**kw)
+            else:
+                est = SparseFactorizationMachineClassifier(loss=loss, **kw)
+            est.P_ = np.array(P0)
+            est.w_ = np.zeros(d)
+            est.lams_ = np.array(lam)
+            losses = fit_psgd_verbose(est, X, yy)
+            key = "%s|%s" % (tag, loss)
+            snames.append(key)
+            out["smeta|" + key] = np.array(json.dumps(dict(
+                regularizer=regname, degree=degree, k=k, fit_lower="explicit",
+                learning_rate=lr, batch_size=batch, shuffle=False, gamma=gamma, power_t=1.0,
+                loss=loss, alpha=1e-2, beta=0.1, eta0=0.02, max_iter=3, random_state=3)))
+            out["sP0|" + key] = P0
+            out["slams|" + key] = lam
+            out["sloss|" + key] = losses
+            out["sP|" + key] = est.P_
+            out["sw|" + key] = est.w_
+            out["sit|" + key] = np.array([est.n_iter_, est.it_])
+            assert np.isfinite(est.P_).all() and np.isfinite(losses).all(), key
+            print(key, "loss", losses, "nnz(P[0])=%.2f" % np.mean(est.P_[0] != 0),
+                  "|P|max=%.3g" % np.abs(est.P_).max())
+    out["scases"] = np.array(snames)
+    save("g11_high_degree.npz", **out)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10",
+                             "g11"]
     for g in which:
         globals()["gen_" + g]()

@@ -149,6 +149,8 @@ def lib():
     L.spo_prox_squaredl12.argtypes = [_dp, C.c_int64, C.c_int64, C.c_double]
     L.spo_reg_prox.restype = C.c_int
     L.spo_reg_prox.argtypes = [C.c_int, _dp, C.c_int, C.c_int, C.c_double]
+    L.spo_set_store_f32.restype = None
+    L.spo_set_store_f32.argtypes = [C.c_int]
     L.spo_psgd_get_eta.restype = None
     L.spo_psgd_get_eta.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_int64, _dp, _dp]
@@ -160,6 +162,18 @@ def lib():
     ]
     _lib = L
     return L
+
+
+_store_f32 = False
+
+
+def set_store_f32(on):
+    """Emulate float32 storage of the A caches and y_pred in cd_linear_epoch / pcd_epoch and
+    OracleFM's initial y_pred (spfm_oracle.c spo_set_store_f32).  Off by default: the oracle
+    is the reference's float64 arithmetic."""
+    global _store_f32
+    lib().spo_set_store_f32(int(bool(on)))
+    _store_f32 = bool(on)
 
 
 def _d(a):
@@ -527,6 +541,8 @@ class OracleFM(object):
             raise ValueError("bad init_lambdas")
         ds = CSC(X)
         y_pred = np.ascontiguousarray(self._get_output(X), dtype=np.float64)
+        if _store_f32:
+            y_pred = y_pred.astype(np.float32).astype(np.float64)
         if sp.issparse(X):
             col_norm_sq = np.asarray(X.multiply(X).sum(axis=0)).ravel().astype(np.float64)
         else:

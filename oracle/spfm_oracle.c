@@ -29,6 +29,16 @@
 
 #define SPO_MAX_DEGREE 16
 
+/* Storage-precision emulation (off by default; never part of the reference's arithmetic): with
+ * it on, the cd_linear and pcd paths round every stored A cache entry and y_pred value to
+ * float32, as an engine with float32 storage does (include/spfm.h: values, A caches and y_pred
+ * in the handle's dtype; sums, prox and parameters in float64).  The precompute rounds once per
+ * entry after accumulating in float64, as the device's precompute pass does.  Used to measure
+ * how much of a float32 engine's distance from the float64 oracle is storage rounding. */
+static int spo_f32_store = 0;
+void spo_set_store_f32(int on) { spo_f32_store = on != 0; }
+static inline double st(double v) { return spo_f32_store ? (double)(float)v : v; }
+
 enum { SPO_LOSS_SQUARED = 0, SPO_LOSS_SQUARED_HINGE = 1, SPO_LOSS_LOGISTIC = 2 };
 enum {
     SPO_REG_L1 = 0,
@@ -466,7 +476,7 @@ double spo_cd_linear_epoch(double* w, int64_t n, int d, const int64_t* indptr,
         sum_viol += fabs(update);
         for (int64_t ii = b; ii < e; ++ii) {
             const int i = indices[ii];
-            y_pred[i] -= update * data[ii];
+            y_pred[i] = st(y_pred[i] - update * data[ii]);
         }
     }
     return sum_viol;
@@ -491,6 +501,8 @@ void spo_pcd_precompute_A(int64_t n, int d, const int64_t* indptr, const int32_t
                 Ai[degree - t] += Ai[degree - t - 1] * p_sj * x_ij;
         }
     }
+    if (spo_f32_store)
+        for (int64_t q = 0; q < n * a_cols; ++q) A[q] = st(A[q]);
 }
 
 /* sparsepoly/optimizer/pcd.py:71-137 (with _update :33-68 and _grad_anova :8-12 inlined) */
@@ -544,10 +556,10 @@ double spo_pcd_epoch(double* P, int k, int64_t n, int d, const int64_t* indptr,
                 dA[0] = x_ij;
                 for (int deg = 1; deg < degree; ++deg) {
                     dA[deg] = x_ij * (Ai[deg] - p_sj_old * dA[deg - 1]);
-                    Ai[deg] -= update * dA[deg - 1];
+                    Ai[deg] = st(Ai[deg] - update * dA[deg - 1]);
                 }
-                Ai[degree] -= update * dA[degree - 1];
-                y_pred[i] -= lam * update * dA[degree - 1];
+                Ai[degree] = st(Ai[degree] - update * dA[degree - 1]);
+                y_pred[i] = st(y_pred[i] - lam * update * dA[degree - 1]);
             }
             spo_reg_update_cache_pcd(reg, P, degree, s, j);
         }

@@ -50,6 +50,8 @@ from .schedule import Schedule
 from .loss import CLASSIFICATION_LOSSES, REGRESSION_LOSSES
 from .regularizer import REGULARIZATION
 
+MAX_DEGREE = 6  # include/spfm.h SPFM_MAX_DEGREE
+
 
 def _default_device():
     return int(os.environ.get("LOCAL_RANK", "0"))
@@ -390,6 +392,11 @@ class _BaseSparseFactorizationMachine(BaseSparsePoly, metaclass=ABCMeta):
         # device chains: its epochs are stepped from the host, calling the object's own prox and
         # cache hooks (include/spfm.h "host-stepped epochs")
         self._plugin_reg = None if self._is_builtin_regularizer(reg_obj) else reg_obj
+        # deviation: the reference takes any degree; the device kernels stop at SPFM_MAX_DEGREE.
+        # Raised before w_ / P_ exist, so a refused fit leaves the estimator unfitted.
+        if self.degree > MAX_DEGREE:
+            raise NotImplementedError("degree > %d is not supported by the HIP engine"
+                                      % MAX_DEGREE)
 
         if not (self.warm_start and hasattr(self, "w_")):
             self.w_ = np.zeros(n_features, dtype=np.double)

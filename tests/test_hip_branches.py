@@ -12,6 +12,20 @@ n_b goes negative at column b) or ABOVE it ("pos": the second-order cache goes n
 column a).  A third column carries the data and starts at 0, so the initial sums do not depend on
 the summation order.  The device's branch counters (spfm_debug_branch_counts) must tick, and the
 result must equal the oracle's, for the persistent and the multi-kernel engine.
+
+What the degree-5 and degree-6 rows show, and what they cannot: they prove that the omegacs
+recompute branch and the omegati clip run at these degrees and leave the oracle's result.  They
+cannot catch a wrong degree index in the recompute (cache[M - 1], the t < M / t <= M loop
+bounds of spfm_pbcd.hip.h): with at most two non-zero norms, and only one left once column a is
+emptied, every cache entry of order >= 2 that the recompute builds is an exact zero, so a wrong
+index reads the same zeros; checking that indexing needs a construction with at least
+degree - 1 non-zero norms, which these rows do not have.  For the same reason this construction
+cannot make omegacs_cache tick at degree 5 and 6, only omegacs_dcache: dcache[degree] is
+already <= 0 at column a, and the recompute that follows zeroes the column's norm, which
+leaves the cache update nothing to subtract (measured on the device: omegacs_dcache 1,
+omegacs_cache 0 for both pairs).  pbcd at degree 5 and 6 always runs on the multi-kernel
+engine (the persistent pbcd pass takes degree <= 4), so its "persistent" and "multi_kernel"
+rows run the same engine there.
 Needs a real MI355X: ``pytest -m gpu``."""
 import numpy as np
 import pytest
@@ -99,6 +113,14 @@ CASES = [
     ("pbcd", "squaredl21", 2, 3, "neg", "squaredl21_resum"),
     ("pcd", "omegati", 2, 1, "neg", "omegati_clip"),
     ("pcd", "omegati", 3, 1, "neg", "omegati_clip"),
+    # degree 5 and 6: the branches run at these degrees (see above for what they cannot check,
+    # and why omegacs_cache cannot be forced here)
+    ("pbcd", "omegacs", 5, 3, "neg", "omegacs_dcache"),
+    ("pbcd", "omegacs", 5, 3, "pos", "omegacs_dcache"),
+    ("pbcd", "omegacs", 6, 3, "neg", "omegacs_dcache"),
+    ("pbcd", "omegacs", 6, 3, "pos", "omegacs_dcache"),
+    ("pcd", "omegati", 5, 1, "neg", "omegati_clip"),
+    ("pcd", "omegati", 6, 1, "neg", "omegati_clip"),
 ]
 
 
@@ -106,8 +128,8 @@ CASES = [
 @pytest.mark.parametrize("solver,reg,degree,k,pair,counter", CASES)
 def test_forced_numerical_error_branch(oracle, solver, reg, degree, k, pair, counter, engine):
     X, y, P0 = _problem(pair, k)
-    if degree == 3:  # P_ has one order per degree (fit_lower='explicit'); the top order is used
-        P0 = np.concatenate([P0, np.zeros_like(P0)], axis=0)
+    if degree >= 3:  # P_ has one order per degree (fit_lower='explicit'); the top order is used
+        P0 = np.concatenate([P0] + [np.zeros_like(P0)] * (degree - 2), axis=0)
     options = {} if engine == "persistent" else {"persistent": 0, "pbcd_persistent": 0}
     v, P, yp, y0, counts = _run_engine(X, y, P0, solver, reg, degree, options)
     assert counts[counter] > 0, (counts, "the forced branch did not run on the device")

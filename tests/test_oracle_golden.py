@@ -417,3 +417,179 @@ def test_g9_psgd_sparse_trajectories(oracle, case):
     np.testing.assert_allclose(fm.P_, z["tP|" + case], rtol=0, atol=TOL)
     np.testing.assert_allclose(fm.w_, z["tw|" + case], rtol=0, atol=TOL)
     assert [fm.n_iter_, fm.it_] == [int(v) for v in z["tit|" + case]]
+
+
+# ------------------------------------------------------------ g11: degrees 4-6
+G11 = "g11_high_degree.npz"
+
+
+def _g11_y(z, loss):
+    y = z["y"]
+    return y if loss == "squared" else np.where(y > np.median(y), 1.0, -1.0)
+
+
+def _g11_cases(key="cases"):
+    return [str(c) for c in load_golden(G11)[key]]
+
+
+@pytest.mark.parametrize("case", _g11_cases())
+def test_g11_trajectories(oracle, case):
+    """pcd l1/omegati and pbcd l1/l21/omegacs at degree 4-6: viol, sum-loss, P, w, y_pred per
+    case.  The fixture's metadata must show a live top order (a fixture whose top-order P is
+    all zero would pin nothing) and a well-conditioned iteration (the oracle's amplification of
+    a 1e-9 relative perturbation of P0)."""
+    z = load_golden(G11)
+    X = golden_csr(z)
+    m = json.loads(str(z["meta|" + case]))
+    assert m["top_nonzero"] >= 0.1, m
+    assert m["amplification"] <= 50.0, m
+    fm = oracle.OracleFM(degree=m["degree"], loss=m["loss"], n_components=m["k"],
+                         solver=m["solver"], regularizer=m["regularizer"], alpha=m["alpha"],
+                         beta=m["beta"], gamma=m["gamma"], eta0=m["eta0"], tol=0,
+                         fit_lower=m["fit_lower"], fit_linear=True, max_iter=m["n_epochs"])
+    fm.fit(X, _g11_y(z, m["loss"]), P_init=z["P0|" + case], lams_init=z["lams|" + case])
+    np.testing.assert_allclose([h[0] for h in fm.history], z["viol|" + case], rtol=1e-10,
+                               atol=TOL)
+    np.testing.assert_allclose([h[1] for h in fm.history], z["loss|" + case], rtol=1e-10,
+                               atol=TOL)
+    np.testing.assert_allclose(fm.P_, z["P|" + case], rtol=0, atol=TOL)
+    np.testing.assert_allclose(fm.w_, z["w|" + case], rtol=0, atol=TOL)
+    np.testing.assert_allclose(fm.y_pred_, z["y_pred|" + case], rtol=0, atol=1e-9)
+    # (counted on the fixture: where the reference cancels to an exact 0 the oracle may keep a
+    # 1e-123 residue -- a summation-order effect far below TOL)
+    assert np.mean(z["P|" + case][0] != 0) == m["top_nonzero"]
+
+
+@pytest.mark.parametrize("case", _g11_cases("pcases"))
+def test_g11_permuted_orders(oracle, case):
+    """Per-epoch permuted feature / component orders at degree 5 (pcd) and 6 (pbcd)."""
+    z = load_golden(G11)
+    X = golden_csr(z)
+    m = json.loads(str(z["meta|" + case]))
+    y = _g11_y(z, m["loss"])
+    n, d = X.shape
+    k, degree = m["k"], m["degree"]
+    ds = oracle.CSC(X)
+    reg = oracle.Regularizer(m["regularizer"])
+    P_ = np.array(z["P0|" + case])
+    lams = np.ascontiguousarray(z["lams|" + case])
+    w = np.zeros(d)
+    fm = oracle.OracleFM(degree=degree, n_components=k)
+    fm.P_, fm.w_, fm.lams_ = P_, w, lams
+    y_pred = np.ascontiguousarray(fm._get_output(X))
+    col_norm_sq = np.asarray(X.multiply(X).sum(axis=0)).ravel()
+    viols = []
+    if m["solver"] == "pcd":
+        A = np.zeros((n, degree + 1))
+        reg.init_cache_pcd(degree, d, k)
+        P = P_
+    else:
+        A = np.zeros((n, degree + 1, k))
+        dA = np.zeros((n, degree, k))
+        reg.init_cache_pbcd(degree, d, k)
+        P = np.ascontiguousarray(P_.swapaxes(1, 2))
+    for it in range(m["n_epochs"]):
+        jf, ic = z["forders|" + case][it], z["corders|" + case][it]
+        v = oracle.cd_linear_epoch(w, ds, y, y_pred, col_norm_sq, m["alpha"], m["loss"], jf)
+        for deg in list(range(2, degree)) + [degree]:
+            o = degree - deg if deg != degree else 0
+            if m["solver"] == "pcd":
+                v += oracle.pcd_epoch(P[o], ds, y, y_pred, lams, deg, m["beta"], m["gamma"],
+                                      m["eta0"], reg, m["loss"], A, ic, jf)
+            else:
+                v += oracle.pbcd_epoch(P[o], ds, y, y_pred, lams, deg, m["beta"], m["gamma"],
+                                       m["eta0"], reg, m["loss"], A, dA, jf)
+        viols.append(v)
+    if m["solver"] == "pbcd":
+        P_ = np.array(P.swapaxes(1, 2))
+    assert np.mean(P_[0] != 0) >= 0.1
+    np.testing.assert_allclose(viols, z["viol|" + case], rtol=1e-10, atol=TOL)
+    np.testing.assert_allclose(P_, z["P|" + case], rtol=0, atol=TOL)
+    np.testing.assert_allclose(w, z["w|" + case], rtol=0, atol=TOL)
+    np.testing.assert_allclose(y_pred, z["y_pred|" + case], rtol=0, atol=1e-9)
+
+
+def test_g11_anova_degree6(oracle):
+    """kernels.py:71-115,140-153 at degree 6, k = 65, rows with 0..5 entries (fewer than the
+    degree: their ANOVA term is exactly zero) -- dense, sparse and the row-DP evaluator."""
+    import scipy.sparse as sp
+
+    z = load_golden(G11)
+    X, P, lams = z["a_X"], z["a_P"], z["a_lams"]
+    assert P.shape[0] == 65 and (np.count_nonzero(X, axis=1) < 6).sum() >= 6
+    K = oracle.anova_kernel(X, P, 6)
+    scale = max(1.0, float(np.abs(z["a_K_dense"]).max()))
+    np.testing.assert_allclose(K, z["a_K_dense"], rtol=0, atol=1e-12 * scale)
+    np.testing.assert_allclose(oracle.anova_kernel(sp.csr_matrix(X), P, 6), z["a_K_sparse"],
+                               rtol=0, atol=1e-12 * scale)
+    pscale = max(1.0, float(np.abs(z["a_pred_dense"]).max()))
+    np.testing.assert_allclose(oracle.poly_predict(X, P, lams, 6), z["a_pred_dense"], rtol=0,
+                               atol=1e-12 * pscale)
+    out = np.zeros(X.shape[0])
+    oracle.anova_predict_dp(sp.csr_matrix(X), P, lams, 6, out)
+    np.testing.assert_allclose(out, z["a_pred_sparse"], rtol=0, atol=1e-10 * pscale)
+    short = np.count_nonzero(X, axis=1) < 6
+    assert np.all(out[short] == 0.0)
+
+
+@pytest.mark.parametrize("degree", [4, 5, 6])
+def test_g11_get_output(oracle, degree):
+    """_get_output with fit_lower='explicit' beyond degree 3: the reference adds no lower
+    orders (sparse_factorization_machines.py:445)."""
+    import scipy.sparse as sp
+
+    z = load_golden(G11)
+    tag = "deg%d" % degree
+    fm = oracle.OracleFM(degree=degree, n_components=7, fit_lower="explicit")
+    fm.P_, fm.w_, fm.lams_ = z["est_P|" + tag], z["est_w|" + tag], z["est_lams|" + tag]
+    got = fm.predict(sp.csr_matrix(z["a_X"]))
+    scale = max(1.0, float(np.abs(z["est_pred|" + tag]).max()))
+    np.testing.assert_allclose(got, z["est_pred|" + tag], rtol=0, atol=1e-12 * scale)
+
+
+@pytest.mark.parametrize("case", _g11_cases("scases"))
+def test_g11_psgd(oracle, case):
+    """psgd at degree 5 and 6 with n_orders = degree - 1 (estimator fit as in g9)."""
+    z = load_golden(G11)
+    m = json.loads(str(z["smeta|" + case]))
+    X = golden_csr(z)
+    fm = oracle.OracleFM(degree=m["degree"], loss=m["loss"], n_components=m["k"],
+                         solver="psgd", regularizer=m["regularizer"], alpha=m["alpha"],
+                         beta=m["beta"], gamma=m["gamma"], tol=-1.0, fit_lower=m["fit_lower"],
+                         fit_linear=True, max_iter=m["max_iter"], shuffle=m["shuffle"],
+                         random_state=m["random_state"], learning_rate=m["learning_rate"],
+                         eta0=m["eta0"], power_t=m["power_t"], batch_size=m["batch_size"],
+                         n_iter_no_change=1000)
+    fm.fit(X, _g11_y(z, m["loss"]), P_init=z["sP0|" + case], lams_init=z["slams|" + case])
+    np.testing.assert_allclose([h[0] for h in fm.history], z["sloss|" + case], rtol=1e-11)
+    np.testing.assert_allclose(fm.P_, z["sP|" + case], rtol=0, atol=TOL)
+    np.testing.assert_allclose(fm.w_, z["sw|" + case], rtol=0, atol=TOL)
+    assert [fm.n_iter_, fm.it_] == [int(v) for v in z["sit|" + case]]
+
+
+def test_oracle_f32_storage_emulation(oracle):
+    """oracle.set_store_f32 (used to measure a float32 engine's storage sensitivity) rounds
+    y_pred and the A caches to float32, stays close to the float64 trajectory, and leaves the
+    oracle's float64 arithmetic untouched once it is switched off."""
+    z = load_golden(G11)
+    X = golden_csr(z)
+    case = "pcd_l1_d5"
+    m = json.loads(str(z["meta|" + case]))
+
+    def fit():
+        fm = oracle.OracleFM(degree=m["degree"], loss=m["loss"], n_components=m["k"],
+                             solver="pcd", regularizer=m["regularizer"], alpha=m["alpha"],
+                             beta=m["beta"], gamma=m["gamma"], eta0=m["eta0"], tol=0,
+                             fit_lower=m["fit_lower"], fit_linear=True, max_iter=m["n_epochs"])
+        fm.fit(X, _g11_y(z, m["loss"]), P_init=z["P0|" + case], lams_init=z["lams|" + case])
+        return fm
+
+    oracle.set_store_f32(True)
+    try:
+        f32 = fit()
+    finally:
+        oracle.set_store_f32(False)
+    assert np.array_equal(f32.y_pred_, f32.y_pred_.astype(np.float32).astype(np.float64))
+    assert np.abs(f32.P_ - z["P|" + case]).max() > 0
+    np.testing.assert_allclose(f32.P_, z["P|" + case], rtol=0, atol=1e-4)
+    np.testing.assert_allclose(fit().P_, z["P|" + case], rtol=0, atol=TOL)
