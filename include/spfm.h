@@ -389,6 +389,49 @@ int spfm_debug_stream_probe(spfm_handle h, int64_t* bytes_out);
 int spfm_debug_write_probe(spfm_handle h, int bytes_per_record, int64_t* bytes_out);
 int spfm_debug_branch_counts(spfm_handle h, unsigned* out8, int reset);
 
+/* -- Gram matrices (sparsepoly/kernels.py) -------------------------------------
+ * The Gram matrices of kernels.py:51-137 and poly_predict (:140-153) on the device, for
+ * sparsepoly_amd.kernels.  Any handle: no data, parameters or configuration are needed (only
+ * its device and stream are used).
+ *   kind SPFM_GRAM_ANOVA        anova_kernel (:71-115), K[i][j] = sum over i1 < ... < i_degree
+ *                               of prod x_i p_i.  degree <= 1 gives X P^T (the else-branch with
+ *                               an empty recursion, :98-115); degree > SPFM_GRAM_MAX_DEGREE ->
+ *                               SPFM_ERR_UNSUPPORTED.
+ *        SPFM_GRAM_POLY         homogeneous_kernel (:51-68) = polynomial_kernel(gamma=1,
+ *                               coef0=0): (X P^T) ** degree, degree >= 0 (else UNSUPPORTED)
+ *        SPFM_GRAM_ALL_SUBSETS  all_subsets_kernel (:117-137): prod_c (1 + x_c p_c); degree unused
+ *   X is CSR: indptr[n1+1] (int64, indptr[0] = 0), indices (int32 column ids in [0,d), sorted and
+ *   duplicate-free inside each row), data (double).
+ *   lams   NULL: out receives K (n1 x n2, row-major).  Otherwise lams[n2] and out[n1] = K @ lams
+ *          (poly_predict): reduced on the device in the pass that evaluates K, which is never
+ *          stored whole.
+ *   max_block_bytes  device memory of one block of the work (0 = library default, 4 GiB or half
+ *          the free memory): X is processed in row blocks and the second operand in tiles of
+ *          64-column chunks, each block of the result copied into `out` as it completes (at least
+ *          one row and one 64-column tile per block, whatever the budget).  The result is
+ *          bit-identical for every budget: one lane per output element, products in feature
+ *          order, the K * lams sum of each 64-column chunk by a fixed tree, chunks in order.
+ * Errors: bad shapes, index out of range, unsorted or duplicate indices -> SPFM_ERR_INVALID. */
+#define SPFM_GRAM_ANOVA 0
+#define SPFM_GRAM_POLY 1
+#define SPFM_GRAM_ALL_SUBSETS 2
+#define SPFM_GRAM_MAX_DEGREE 64
+
+/* CSR X (n1 x d) against a dense B (n2 x d, row-major).  transpose_out = 1 writes K^T
+ * (n2 x n1, row-major) instead: the dense-first call K(B, X) evaluated as K(X, B)^T in place
+ * (not with lams: SPFM_ERR_INVALID). */
+int spfm_gram_csr_dense(spfm_handle h, int kind, int degree, int64_t n1, int32_t d,
+                        const int64_t* indptr, const int32_t* indices, const double* data,
+                        int64_t n2, const double* B, const double* lams, int transpose_out,
+                        int64_t max_block_bytes, double* out);
+/* CSR X (n1 x d) against CSR P (n2 x d), both as above: every output element is a merge of two
+ * sorted index lists (the rows of P staged in LDS per 64-row chunk when they fit). */
+int spfm_gram_csr_csr(spfm_handle h, int kind, int degree, int64_t n1, int32_t d,
+                      const int64_t* indptr1, const int32_t* indices1, const double* data1,
+                      int64_t n2, const int64_t* indptr2, const int32_t* indices2,
+                      const double* data2, const double* lams, int64_t max_block_bytes,
+                      double* out);
+
 #ifdef __cplusplus
 }
 #endif

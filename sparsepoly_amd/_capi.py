@@ -79,6 +79,8 @@ REGULARIZERS = {"l1": 0, "l21": 1, "squaredl12": 2, "squaredl21": 3, "omegati": 
 SOLVERS = {"pcd": 0, "pbcd": 1, "psgd": 2}
 LEARNING_RATE = {"constant": 0, "optimal": 1, "pegasos": 2, "invscaling": 3}
 SCHEDULES = {"exact": 0, "colored": 1}
+GRAM_KINDS = {"anova": 0, "poly": 1, "all-subsets": 2}  # SPFM_GRAM_*
+GRAM_MAX_DEGREE = 64  # SPFM_GRAM_MAX_DEGREE
 
 # every symbol include/spfm.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
@@ -93,6 +95,7 @@ SYMBOLS = [
     "spfm_profile_enable", "spfm_profile_get", "spfm_profile_reset", "spfm_set_use_graph",
     "spfm_set_option", "spfm_get_option", "spfm_debug_prb_stamps", "spfm_debug_hop_latency", "spfm_debug_exchange_cost",
     "spfm_debug_branch_counts", "spfm_debug_stream_probe", "spfm_debug_write_probe",
+    "spfm_gram_csr_dense", "spfm_gram_csr_csr",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -170,6 +173,10 @@ def load():
     L.spfm_debug_branch_counts.argtypes = [_h, C.POINTER(C.c_uint32), C.c_int]
     L.spfm_debug_stream_probe.argtypes = [_h, _lp]
     L.spfm_debug_write_probe.argtypes = [_h, C.c_int, _lp]
+    L.spfm_gram_csr_dense.argtypes = [_h, C.c_int, C.c_int, C.c_int64, C.c_int32, _lp, _ip, _dp,
+                                      C.c_int64, _dp, _dp, C.c_int, C.c_int64, _dp]
+    L.spfm_gram_csr_csr.argtypes = [_h, C.c_int, C.c_int, C.c_int64, C.c_int32, _lp, _ip, _dp,
+                                    C.c_int64, _lp, _ip, _dp, _dp, C.c_int64, _dp]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in ("spfm_destroy", "spfm_last_error", "spfm_build_tag"):
