@@ -432,6 +432,63 @@ int spfm_gram_csr_csr(spfm_handle h, int kind, int degree, int64_t n1, int32_t d
                       const double* data2, const double* lams, int64_t max_block_bytes,
                       double* out);
 
+/* -- objective, sparsity and held-out loss of the live parameters ----------------------------
+ * What the reference's solvers minimise (sparse_factorization_machines.py:16-60 docstring):
+ *   sum_i loss(y_pred_i, y_i) + alpha/2 |w|^2 + sum_o (beta/2 |P_o|^2 + gamma Omega(P_o)).
+ * spfm_loss_sum gives the first term; spfm_objective_terms gives the ingredients of the others
+ * from the LIVE device parameters -- the image spfm_get_params would return at that moment,
+ * whichever engine ran last (persistent, wide, relaxed, multi-kernel, pbcd, psgd, after a
+ * rolled-back persistent pass) -- without copying P to the host.
+ *   order_idx >= 0: the block P[order_idx] (k x d);  order_idx == -1: w
+ *   out8[0]  0.5 * sum p^2                        (w: 0.5 * sum w^2)
+ *   out8[1]  Omega(P_o; degree) of the configured regularizer   (w: 0)
+ *   out8[2]  number of non-zero entries           (w: non-zeros of w)
+ *   out8[3]  active features: columns j with any P[o, s, j] != 0  (w: 0)
+ *   out8[4]  active components: rows s with any non-zero          (w: 0)
+ *   out8[5..7] reserved, written as 0
+ * Omega is the quantity the device prox chains maintain, i.e. the reference's regularizer cache
+ * after compute_cache_pcd / compute_cache_pbcd:
+ *   l1 sum |p| (l1.py:17-18); l21 sum_j |P[:, j]|_2 (l21.py:19-21); squaredl12
+ *   sum_s (sum_j |p_sj|)^2 (squaredl12.py:20-22, transpose=True); squaredl21 (sum_j |P[:, j]|_2)^2
+ *   (squaredl21.py:23-25); omegati sum_s e_m(|P[s, :]|), m = degree in 1..6, degree = -1:
+ *   sum_s prod_j (1 + |p_sj|) (omegati.py:19-47); omegacs e_m(n), n_j = |P[:, j]|_2, degree = -1:
+ *   prod_j (1 + n_j) (omegacs.py:52-60, compute_cache_pbcd).
+ * For five of the six this is the reference's eval().  DEVIATION, omegacs: the reference's
+ * OmegaCS.eval (omegacs.py:22-39) RESHAPES its input to (k, d) instead of transposing it, so for a
+ * non-square block it is not the function its own prox minimises; the value here follows the prox
+ * cache (compute_cache_pbcd, then _cache[degree]).
+ * Needs parameters and spfm_configure (the regularizer kind) -- and so, because spfm_configure
+ * wants data, a data set; the data itself is not read.  Read-only: no
+ * parameter, cache, y_pred, schedule or regularizer state changes, and a later epoch chooses
+ * the same engine.  Deterministic: fixed-order f64 reductions (a tree over lanes, waves,
+ * workgroups that depends on k and d only), the same bits on every call, for either parameter
+ * layout and for every value of the *_groups / co_tenants options.  Several ranks: parameters are
+ * replicated, the terms are local, nothing is communicated.
+ * Errors: no parameters / no configuration / bad order_idx -> SPFM_ERR_INVALID; degree outside
+ * 1..SPFM_MAX_DEGREE and -1 -> SPFM_ERR_UNSUPPORTED. */
+int spfm_objective_terms(spfm_handle h, int order_idx, int degree, double* out8);
+
+/* A second, held-out CSR matrix kept on the device next to the training data (what a callback
+ * that scores validation data hands predict() every time, sparse_factorization_machines.py
+ * :453-458): indptr[n+1] (int64, indptr[0] = 0), indices (int32 column ids in [0,d), sorted and
+ * duplicate-free inside each row), data, stored in the handle's storage precision; y[n] or NULL.
+ * d must equal the handle's n_features (data or parameters must be present).  Empty rows and
+ * n = 0 are accepted.  Replaced by the next call, freed with the handle.
+ * Errors: wrong d, index out of range, unsorted indices, nothing to take d from ->
+ * SPFM_ERR_INVALID. */
+int spfm_set_eval_csr(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
+                      const int32_t* indices, const double* data, const double* y);
+/* _get_output (spfm_init_pred: same kernels, same arguments; degree = -1: all-subsets) on the
+ * held-out matrix with the LIVE parameters, and *loss_sum = sum_i loss(y_pred_i, y_i) with the
+ * configured loss (f64, fixed order).  Either output may be NULL; y_pred_out[n].  The matrix stays
+ * resident and no parameter crosses the bus.  Read-only and deterministic as
+ * spfm_objective_terms; with several ranks every rank evaluates the whole held-out set.
+ * Errors: no parameters / no held-out set / loss_sum without targets or configuration ->
+ * SPFM_ERR_INVALID; degree outside 1..SPFM_MAX_DEGREE and -1, or a degree the predict pass does not
+ * have (1) -> SPFM_ERR_UNSUPPORTED. */
+int spfm_eval_loss(spfm_handle h, int degree, int fit_linear, int add_lower_deg2,
+                   double* loss_sum, double* y_pred_out);
+
 #ifdef __cplusplus
 }
 #endif

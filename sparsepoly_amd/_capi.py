@@ -96,6 +96,7 @@ SYMBOLS = [
     "spfm_set_option", "spfm_get_option", "spfm_debug_prb_stamps", "spfm_debug_hop_latency", "spfm_debug_exchange_cost",
     "spfm_debug_branch_counts", "spfm_debug_stream_probe", "spfm_debug_write_probe",
     "spfm_gram_csr_dense", "spfm_gram_csr_csr",
+    "spfm_objective_terms", "spfm_set_eval_csr", "spfm_eval_loss",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -177,6 +178,9 @@ def load():
                                       C.c_int64, _dp, _dp, C.c_int, C.c_int64, _dp]
     L.spfm_gram_csr_csr.argtypes = [_h, C.c_int, C.c_int, C.c_int64, C.c_int32, _lp, _ip, _dp,
                                     C.c_int64, _lp, _ip, _dp, _dp, C.c_int64, _dp]
+    L.spfm_objective_terms.argtypes = [_h, C.c_int, C.c_int, _dp]
+    L.spfm_set_eval_csr.argtypes = [_h, C.c_int64, C.c_int32, _lp, _ip, _dp, _dp]
+    L.spfm_eval_loss.argtypes = [_h, C.c_int, C.c_int, C.c_int, _dp, _dp]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in ("spfm_destroy", "spfm_last_error", "spfm_build_tag"):

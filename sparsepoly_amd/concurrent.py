@@ -142,5 +142,7 @@ def fit_path(estimator, X, y, max_concurrent=None, devices=None, **grid):
     for i in range(lengths.pop()):
         e = clone(estimator)
         e.set_params(**{name: values[i] for name, values in grid.items()})
+        if getattr(estimator, "_validation", None) is not None:
+            e._validation = estimator._validation  # set_validation: not a constructor keyword
         ests.append(e)
     return fit_concurrently(ests, X, y, max_concurrent=max_concurrent, devices=devices)

@@ -816,6 +816,29 @@ struct spfm_engine {
     std::vector<int64_t> sg_lpos;
     std::vector<int32_t> sg_lB, sg_gB;
 
+    // ------------------------------- objective terms, held-out set (spfm_engine_objective.hip)
+    // Read-only views of the live state: they use buffers of their own, neither of the
+    // P / Pt validity flags changes, nothing an epoch reads is written.
+    DevBuf obj_rec, obj_fin, obj_out;  // stage-1 records, per-component totals, the 8 slots
+    DevBuf ev_rptr, ev_ridx, ev_rval, ev_y, ev_pred, ev_pt, ev_part;
+    int64_t ev_n = 0;
+    bool have_eval = false, ev_has_y = false;
+    template <int M>
+    int objective_launch(const double* base, int64_t ss, int64_t sj, int kk, int all_subsets,
+                         int is_w);
+    int objective_terms(int order_idx, int degree, double* out8);
+    template <typename T>
+    int set_eval_t(int64_t rows, const int64_t* indptr, const int32_t* indices,
+                   const double* data, const double* y);
+    int set_eval_csr(int64_t rows, int32_t d_, const int64_t* indptr, const int32_t* indices,
+                     const double* data, const double* y);
+    // output_t on a given (d,k) image of all orders (no P <-> Pt bookkeeping)
+    template <typename T>
+    int output_pt_t(int64_t rows, const int64_t* rp, const int32_t* ri, const T* rv, int degree,
+                    int fit_linear, int add_lower, const double* Pt_all, double* out);
+    int eval_loss(int degree, int fit_linear, int add_lower, double* loss_sum_out,
+                  double* y_pred_out);
+
     // diagnostics that need kernels of one translation unit
     int debug_stream_probe(int64_t* bytes_out);  // spfm_engine_pcd.hip
     int debug_write_probe(int bytes, int64_t* bytes_out);

@@ -820,12 +820,20 @@ int spfm_engine::output_t(int64_t rows, const int64_t* rp, const int32_t* ri, co
     pt_valid = false;  // P is the source of truth here
     rc = ensure_pt();
     if (rc) return rc;
+    return output_pt_t<T>(rows, rp, ri, rv, degree, fit_linear, add_lower, Pt.as<double>(), out);
+}
+
+template <typename T>
+int spfm_engine::output_pt_t(int64_t rows, const int64_t* rp, const int32_t* ri, const T* rv,
+                             int degree, int fit_linear, int add_lower, const double* Pt_all,
+                             double* out) {
+    if (rows == 0) return SPFM_OK;
     HIPC(hipMemsetAsync(out, 0, sizeof(double) * (size_t)rows, stream));
-    rc = anova_dispatch<T>(kind_of(degree), rows, rp, ri, rv, Pt.as<double>(), out);
+    int rc = anova_dispatch<T>(kind_of(degree), rows, rp, ri, rv, Pt_all, out);
     if (rc) return rc;
     if (add_lower) {
         if (n_orders < 2) FAIL(SPFM_ERR_INVALID, "add_lower_deg2 needs P_[1]");
-        rc = anova_dispatch<T>(2, rows, rp, ri, rv, Pt.as<double>() + (size_t)k * d, out);
+        rc = anova_dispatch<T>(2, rows, rp, ri, rv, Pt_all + (size_t)k * d, out);
         if (rc) return rc;
     }
     if (fit_linear) {
@@ -1198,6 +1206,29 @@ int spfm_predict_csr(spfm_handle h, int64_t n, const int64_t* indptr, const int3
                : h->predict_csr_t<double>(n, indptr, indices, data, degree, fit_linear,
                                           add_lower_deg2, out);
 }
+
+int spfm_objective_terms(spfm_handle h, int order_idx, int degree, double* out8) {
+    GUARD(h);
+    return h->objective_terms(order_idx, degree, out8);
+}
+
+int spfm_set_eval_csr(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
+                      const int32_t* indices, const double* data, const double* y) {
+    GUARD(h);
+    return h->set_eval_csr(n, d, indptr, indices, data, y);
+}
+
+int spfm_eval_loss(spfm_handle h, int degree, int fit_linear, int add_lower_deg2,
+                   double* loss_sum, double* y_pred_out) {
+    GUARD(h);
+    return h->eval_loss(degree, fit_linear, add_lower_deg2, loss_sum, y_pred_out);
+}
+
+// used by the objective unit (spfm_eval_loss)
+template int spfm_engine::output_pt_t<float>(int64_t, const int64_t*, const int32_t*, const float*,
+                                             int, int, int, const double*, double*);
+template int spfm_engine::output_pt_t<double>(int64_t, const int64_t*, const int32_t*,
+                                              const double*, int, int, int, const double*, double*);
 
 int spfm_set_schedule(spfm_handle h, int mode, const int32_t* indices_feature,
                       const int64_t* conflict_indptr, const int32_t* conflict_indices,

@@ -378,6 +378,63 @@ class HipEngine(object):
             int(bool(add_lower_deg2)), out.ctypes.data_as(_capi._dp)))
         return out
 
+    # --------------------------------- objective terms, held-out set (spfm.h, last section)
+    OBJECTIVE_SLOTS = ("l2", "omega", "nnz", "active_features", "active_components")
+
+    def objective_terms(self, order_idx, degree):
+        """``spfm_objective_terms``: dict with ``l2`` (0.5 * sum of squares), ``omega`` (the
+        configured regularizer of the block at ``degree``), ``nnz``, ``active_features`` and
+        ``active_components`` of the LIVE block ``P[order_idx]`` (``order_idx = -1``: ``w``; then
+        only ``l2`` and ``nnz`` are non-zero).  Nothing is copied to the host but eight doubles.
+
+        ``omega`` equals the reference's ``regularizer.eval`` for five of the six regularizers.
+        For ``omegacs`` it deviates on purpose: the reference's ``OmegaCS.eval`` reshapes its
+        input instead of transposing it (``omegacs.py:22-39``), so for a non-square block it is
+        not the function its own prox minimises; the value here is the prox cache's
+        (``compute_cache_pbcd``, then ``_cache[degree]``)."""
+        out = np.zeros(8)
+        self._check(self._lib.spfm_objective_terms(self._h, int(order_idx), int(degree),
+                                                   out.ctypes.data_as(_capi._dp)))
+        return dict(l2=float(out[0]), omega=float(out[1]), nnz=int(out[2]),
+                    active_features=int(out[3]), active_components=int(out[4]))
+
+    def set_eval_data(self, X, y=None):
+        """``spfm_set_eval_csr``: keep a held-out matrix (and its targets) on the device next to
+        the training data; replaced by the next call."""
+        Xr = sp.csr_matrix(X, dtype=np.float64)
+        Xr.sum_duplicates()
+        Xr.sort_indices()
+        n, d = Xr.shape
+        if self.d is not None and d != self.d:
+            raise ValueError("X has %d features, the model has %d" % (d, self.d))
+        ia, ip = _capi.i64(Xr.indptr)
+        ja, jp = _capi.i32(Xr.indices)
+        da, dp = _capi.f64(Xr.data)
+        yp = None
+        if y is not None:
+            ya, yp = _capi.f64(y)
+            if ya.shape[0] != n:
+                raise ValueError("y has %d entries, X has %d rows" % (ya.shape[0], n))
+        self._check(self._lib.spfm_set_eval_csr(self._h, n, d, ip, jp, dp, yp))
+        self.n_eval, self._eval_has_y = n, y is not None
+
+    def eval_loss(self, degree, fit_linear, add_lower_deg2, return_pred=False):
+        """``spfm_eval_loss``: sum of the configured loss over the held-out set under the live
+        parameters (None when the set has no targets); with ``return_pred`` the pair
+        (loss sum, predictions)."""
+        if getattr(self, "n_eval", None) is None:
+            raise ValueError("eval_loss: call set_eval_data first")
+        ls = C.c_double()
+        lp = C.byref(ls) if self._eval_has_y else None
+        pred, pp = None, None
+        if return_pred:
+            pred = np.zeros(self.n_eval)
+            pp = pred.ctypes.data_as(_capi._dp)
+        self._check(self._lib.spfm_eval_loss(self._h, int(degree), int(bool(fit_linear)),
+                                             int(bool(add_lower_deg2)), lp, pp))
+        val = ls.value if self._eval_has_y else None
+        return (val, pred) if return_pred else val
+
     # -------------------------------------------------------------- schedule
     def set_schedule(self, mode, indices_feature, conflict_csc=None):
         """Fix the coordinate order for the next epochs; returns the order used.

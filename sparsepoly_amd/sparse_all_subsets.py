@@ -22,11 +22,12 @@ from sklearn.utils.validation import NotFittedError, check_array
 from .base import BaseSparsePoly, SparsePolyClassifierMixin, SparsePolyRegressorMixin
 from .engine import HipEngine, canonical_csc
 from .loss import CLASSIFICATION_LOSSES, REGRESSION_LOSSES
+from .monitor import ObjectiveMixin, callback_needs_params
 from .regularizer import L1, L21, OmegaCS, OmegaTI
 from .schedule import Schedule
 
 
-class _BaseSparseAllSubsets(BaseSparsePoly, metaclass=ABCMeta):
+class _BaseSparseAllSubsets(ObjectiveMixin, BaseSparsePoly, metaclass=ABCMeta):
     # sparse_all_subsets.py:33-38
     _REGULARIZERS = {"l1": L1, "l21": L21, "omegacs": OmegaCS, "omegati": OmegaTI}
 
@@ -70,6 +71,7 @@ class _BaseSparseAllSubsets(BaseSparsePoly, metaclass=ABCMeta):
     def fit(self, X, y):
         """sparse_all_subsets.py:203-258 with _fit_pcd (:80-138) / _fit_pbcd (:140-201)."""
         X, y = self._check_X_y(X, y)
+        self._check_validation(X.shape[1])
         n_samples, n_features = X.shape
         rng = check_random_state(self.random_state)
         self._get_loss(self.loss)
@@ -108,6 +110,9 @@ class _BaseSparseAllSubsets(BaseSparsePoly, metaclass=ABCMeta):
             engine.set_params(self.P_[None], np.zeros(n_features), self.lams_)
             engine.configure(self.solver, self.loss, self.regularizer, -1)
             engine.init_pred(-1, False, False)  # y_pred = self._get_output(X) (:241)
+            # objective_terms() / validation_loss() read this session while the loop runs
+            self._upload_validation(engine)
+            self._live = (engine, n_samples)
             indices_feature = np.arange(n_features, dtype=np.int32)
             indices_component = np.arange(self.n_components, dtype=np.int32)
             if not self.shuffle:
@@ -126,7 +131,8 @@ class _BaseSparseAllSubsets(BaseSparsePoly, metaclass=ABCMeta):
                 else:
                     viol += engine.pbcd_epoch(0, -1, beta, gamma, self.eta0)
                 if (self.callback is not None) and it % self.n_calls == 0:
-                    if self.solver == "pcd":  # pbcd trains a transposed copy (:167,199)
+                    # pbcd trains a transposed copy (:167,199)
+                    if self.solver == "pcd" and callback_needs_params(self.callback):
                         engine.get_params(self.P_[None], None)
                     if self.callback(self) is not None:
                         break
@@ -140,11 +146,36 @@ class _BaseSparseAllSubsets(BaseSparsePoly, metaclass=ABCMeta):
             engine.get_params(self.P_[None], None)
             self.n_iter_ = it
             self.n_steps_per_sweep_ = engine.n_batches
+            if getattr(self, "_validation", None) is not None:
+                self.validation_loss_ = engine.eval_loss(*self._obj_pred_args())
         finally:
+            self._live = None
             engine.close()
         if not converged:
             warnings.warn("Objective did not converge. Increase max_iter.")
         return self
+
+    # hooks of ObjectiveMixin (monitor.py): one block, degree -1, no linear term
+    _obj_has_w = False
+
+    def _obj_blocks(self):
+        return [(0, -1)]
+
+    def _obj_scaled(self, n_samples):
+        scale = n_samples if self.mean else 1
+        return 0.0, self.beta * scale, self.gamma * scale
+
+    def _obj_pred_args(self):
+        return -1, False, False
+
+    def _obj_prepare(self, X, checked=False):
+        if not checked:
+            X = check_array(X, accept_sparse=("csr", "csc"), dtype=np.double)
+        return X
+
+    def _obj_configure(self, engine):
+        engine.configure(self.solver, self.loss, self.regularizer, -1)
+        return None
 
     def fit_path(self, X, y, max_concurrent=None, **grid):
         """Clones of this estimator over a parameter grid (``gamma=[...]``, ...), fitted side by

@@ -49,6 +49,7 @@ from .engine import HipEngine, canonical_csc
 from .schedule import Schedule
 from .loss import CLASSIFICATION_LOSSES, REGRESSION_LOSSES
 from .regularizer import REGULARIZATION
+from .monitor import ObjectiveMixin, callback_needs_params
 
 MAX_DEGREE = 6  # include/spfm.h SPFM_MAX_DEGREE
 
@@ -90,7 +91,7 @@ def _fingerprint(Xc, y):
     return (Xc.shape, int(Xc.nnz), fin())
 
 
-class _BaseSparseFactorizationMachine(BaseSparsePoly, metaclass=ABCMeta):
+class _BaseSparseFactorizationMachine(ObjectiveMixin, BaseSparsePoly, metaclass=ABCMeta):
     _REGULARIZERS = REGULARIZATION
 
     @abstractmethod
@@ -272,7 +273,8 @@ class _BaseSparseFactorizationMachine(BaseSparsePoly, metaclass=ABCMeta):
             viol += self._pcd_epoch(engine, 0, self.degree, beta, gamma, indices_component)
 
             if (self.callback is not None) and it % self.n_calls == 0:
-                self._sync_params(engine)  # pcd writes through self.P_[0] (:227-228)
+                if callback_needs_params(self.callback):
+                    self._sync_params(engine)  # pcd writes through self.P_[0] (:227-228)
                 if self.callback(self) is not None:
                     break
             if self.verbose:
@@ -312,7 +314,8 @@ class _BaseSparseFactorizationMachine(BaseSparsePoly, metaclass=ABCMeta):
             viol += self._pbcd_epoch(engine, 0, self.degree, beta, gamma)
 
             if (self.callback is not None) and it % self.n_calls == 0:
-                self._sync_params(engine, with_P=False)
+                if callback_needs_params(self.callback):
+                    self._sync_params(engine, with_P=False)
                 if self.callback(self) is not None:
                     break
             if self.verbose:
@@ -354,7 +357,8 @@ class _BaseSparseFactorizationMachine(BaseSparsePoly, metaclass=ABCMeta):
                 self.power_t, batch_size, indices_samples, self.fit_linear, self.it_,
                 row_lo=self._row_lo if self.distributed else None)
             if (self.callback is not None) and epoch % self.n_calls == 0:
-                self._sync_params(engine, with_P=False)
+                if callback_needs_params(self.callback):
+                    self._sync_params(engine, with_P=False)
                 if self.callback(self) is not None:
                     break
             sum_loss /= n_samples
@@ -383,6 +387,7 @@ class _BaseSparseFactorizationMachine(BaseSparsePoly, metaclass=ABCMeta):
         rank trains on its contiguous block of rows.
         """
         X, y = self._check_X_y(X, y)
+        self._check_validation(X.shape[1])
         X = self._augment(X)
         n_samples, n_features = X.shape
         rng = check_random_state(self.random_state)
@@ -494,11 +499,15 @@ class _BaseSparseFactorizationMachine(BaseSparsePoly, metaclass=ABCMeta):
                 engine.configure(self.solver, self.loss, "l1", self.degree)
             else:
                 engine.configure(self.solver, self.loss, self.regularizer, self.degree)
+            # objective_terms() / validation_loss() read this session while the loops run
+            self._upload_validation(engine)
+            self._live = (engine, n_samples)
             if self.solver == "psgd":
                 # X.count_nonzero() (dataset.py:32,84): stored entries, n*d when dense
                 nnz = X.nnz if sp.issparse(X) else n_samples * n_features
                 converged, self.n_iter_ = self._fit_psgd(engine, n_samples, n_features,
                                                          nnz, rng)
+                self._end_live(engine)
                 keep = key is not None
                 return self._finish_fit(converged)
             # y_pred = self._get_output(X) (:408)
@@ -513,13 +522,46 @@ class _BaseSparseFactorizationMachine(BaseSparsePoly, metaclass=ABCMeta):
             self.__dict__.pop("_Pt_host", None)
             if self.schedule_ is None:
                 self.schedule_ = engine.get_schedule(self.schedule)
+            self._end_live(engine)
             keep = key is not None
         finally:
+            self._live = None
             if keep:
                 self._device_session = (key, engine)
             else:
                 engine.close()
         return self._finish_fit(converged)
+
+    def _end_live(self, engine):
+        """end of fit: the held-out loss of the final parameters (``set_validation``)"""
+        if getattr(self, "_validation", None) is not None:
+            self.validation_loss_ = engine.eval_loss(*self._obj_pred_args())
+
+    # hooks of ObjectiveMixin (monitor.py)
+    def _obj_blocks(self):
+        """(order index, degree) of every block of P_ (:201-205: order degree - deg has degree deg)"""
+        blocks = [(0, self.degree)]
+        if self.fit_lower == "explicit":
+            blocks += [(self.degree - deg, deg) for deg in range(self.degree - 1, 1, -1)]
+        return blocks
+
+    def _obj_scaled(self, n_samples):
+        return self._scaled(n_samples)
+
+    def _obj_pred_args(self):
+        return self.degree, self.fit_linear, self._add_lower_deg2()
+
+    def _obj_prepare(self, X, checked=False):
+        if not checked:
+            X = check_array(X, accept_sparse=("csr", "csc"), dtype=np.double)
+        return self._augment(X)
+
+    def _obj_configure(self, engine):
+        reg_obj = self._get_regularizer(self.regularizer)
+        plugin = None if self._is_builtin_regularizer(reg_obj) else reg_obj
+        engine.configure(self.solver, self.loss,
+                         "l1" if plugin is not None else self.regularizer, self.degree)
+        return plugin
 
     def fit_path(self, X, y, max_concurrent=None, **grid):
         """Clones of this estimator over a parameter grid (``gamma=[...]``, ``beta=[...]``, ... all
