@@ -489,6 +489,62 @@ int spfm_set_eval_csr(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr
 int spfm_eval_loss(spfm_handle h, int degree, int fit_linear, int add_lower_deg2,
                    double* loss_sum, double* y_pred_out);
 
+/* -- selected feature interactions of the live parameters ------------------------------------
+ * What the reference's example notebook inspects with np.dot(P.T, lams * P) != 0: which feature
+ * pairs the fitted model kept.  For the block P_o = P[order_idx] (k x d),
+ *   W = P_o^T diag(lams) P_o,   only j < j' counts (the diagonal is no part of the model);
+ * W[j, j'] is the coefficient of x_j x_j' when P_o is the degree-2 block of a factorization
+ * machine or the block of an all-subsets model.  W has d^2 entries and is NEVER formed: the
+ * features with any non-zero entry (d_a of them) are compacted, the upper-triangular 64 x 64 tiles
+ * of the d_a x d_a product are formed in registers (f64 matrix instructions) and consumed there.
+ * Device scratch is O(d_a k + tiles / 4096 + K) -- it stays allocated between calls and is freed
+ * by spfm_set_params, spfm_destroy or the option "interaction_release"; the cost is d_a^2 k flops
+ * per pass.
+ * All five entries need parameters only (no data, no spfm_configure), read the LIVE image --
+ * whichever of the (k,d) / (d,k) layouts the last epoch left -- and are read-only as
+ * spfm_objective_terms.  Arithmetic is f64 for either storage precision.  Feature ids are ids of
+ * the block as stored.  Several ranks: parameters are replicated, every rank answers locally.
+ *
+ * Deterministic: every value of W is the same chain of operations in every entry, on every call
+ * and for every tile budget; sums are reduced in a fixed tile order without float atomics.
+ *
+ * Options (spfm_set_option): "interaction_tile_budget" = tiles per launch (0 = default, 2^22; a
+ * small value forces many launches and changes no result bit, like max_block_bytes above);
+ * "interaction_features" = n > 0 restricts the stats / topk / list entries to the features
+ * [0, n) (an augmented dummy column is left out this way); 0 = all.  "interaction_release" (any
+ * value) frees the scratch.  spfm_get_option also gives
+ * "interaction_launches" (tile launches of the last pass), "interaction_scratch_kib" (scratch the
+ * entries hold) and "free_mem_mib" (hipMemGetInfo).
+ *
+ * spfm_interaction_stats: counts2 = {pairs with |W| > tol, active features d_a},
+ *   sums3 = {sum W^2, sum |W|, max |W|} over j < j'.  tol >= 0; tol = 0 counts W != 0.
+ * spfm_interaction_topk: the K pairs of largest |W| among W != 0, ordered by |W| descending, then
+ *   j, then j' ascending; rows[K], cols[K] (j < j'), vals[K] (signed); *n_out = pairs written
+ *   (< K when fewer exist).  Exact: a radix select over the f64 patterns of |W| (one product pass
+ *   per 12 bits examined, usually two), then one pass that emits the candidates.  More than
+ *   max(2^20, 2K) pairs tied with the K-th magnitude -> SPFM_ERR_UNSUPPORTED.
+ * spfm_interaction_list: every pair with |W| > tol as (rows, cols, vals), sorted by (row, col);
+ *   *n_out = their number.  If it exceeds `capacity` the call fails (SPFM_ERR_INVALID, the count
+ *   is in *n_out and in the message) and writes nothing to rows / cols / vals.
+ * spfm_interaction_values: vals[q] = W[rows[q], cols[q]] for L given pairs, in any order of the
+ *   two ids; rows[q] == cols[q] gives 0.  Components are summed in order s = 0..k-1.
+ * spfm_interaction_block: out (nJ x nJ2, row-major) = W[J, J2] for two id lists (repeats allowed),
+ *   0 where J[a] == J2[b].  This one does store its result: above
+ *   SPFM_INTERACTION_BLOCK_MAX_BYTES it is refused (SPFM_ERR_INVALID).
+ * Errors: no parameters, bad order_idx, id out of range, negative tol / K / capacity ->
+ * SPFM_ERR_INVALID. */
+#define SPFM_INTERACTION_BLOCK_MAX_BYTES (1LL << 30)
+int spfm_interaction_stats(spfm_handle h, int order_idx, double tol, int64_t* counts2,
+                           double* sums3);
+int spfm_interaction_topk(spfm_handle h, int order_idx, int64_t K, int32_t* rows, int32_t* cols,
+                          double* vals, int64_t* n_out);
+int spfm_interaction_list(spfm_handle h, int order_idx, double tol, int64_t capacity,
+                          int32_t* rows, int32_t* cols, double* vals, int64_t* n_out);
+int spfm_interaction_values(spfm_handle h, int order_idx, int64_t L, const int32_t* rows,
+                            const int32_t* cols, double* vals);
+int spfm_interaction_block(spfm_handle h, int order_idx, int64_t nJ, const int32_t* J,
+                           int64_t nJ2, const int32_t* J2, double* out);
+
 #ifdef __cplusplus
 }
 #endif

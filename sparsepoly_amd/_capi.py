@@ -97,7 +97,10 @@ SYMBOLS = [
     "spfm_debug_branch_counts", "spfm_debug_stream_probe", "spfm_debug_write_probe",
     "spfm_gram_csr_dense", "spfm_gram_csr_csr",
     "spfm_objective_terms", "spfm_set_eval_csr", "spfm_eval_loss",
+    "spfm_interaction_stats", "spfm_interaction_topk", "spfm_interaction_list",
+    "spfm_interaction_values", "spfm_interaction_block",
 ]
+INTERACTION_BLOCK_MAX_BYTES = 1 << 30  # SPFM_INTERACTION_BLOCK_MAX_BYTES
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -181,6 +184,11 @@ def load():
     L.spfm_objective_terms.argtypes = [_h, C.c_int, C.c_int, _dp]
     L.spfm_set_eval_csr.argtypes = [_h, C.c_int64, C.c_int32, _lp, _ip, _dp, _dp]
     L.spfm_eval_loss.argtypes = [_h, C.c_int, C.c_int, C.c_int, _dp, _dp]
+    L.spfm_interaction_stats.argtypes = [_h, C.c_int, C.c_double, _lp, _dp]
+    L.spfm_interaction_topk.argtypes = [_h, C.c_int, C.c_int64, _ip, _ip, _dp, _lp]
+    L.spfm_interaction_list.argtypes = [_h, C.c_int, C.c_double, C.c_int64, _ip, _ip, _dp, _lp]
+    L.spfm_interaction_values.argtypes = [_h, C.c_int, C.c_int64, _ip, _ip, _dp]
+    L.spfm_interaction_block.argtypes = [_h, C.c_int, C.c_int64, _ip, C.c_int64, _ip, _dp]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in ("spfm_destroy", "spfm_last_error", "spfm_build_tag"):

@@ -33,6 +33,7 @@
 #include "spfm_psgd.hip.h"   // PsgdBatch
 
 namespace spfm {
+struct IntArgs;  // spfm_interactions.hip.h
 void schedule_exact(int64_t, int32_t, const int64_t*, const int32_t*, const int32_t*, int,
                     std::vector<int32_t>&);
 void schedule_colored(int64_t, int32_t, const int64_t*, const int32_t*, const int32_t*, int,
@@ -838,6 +839,45 @@ struct spfm_engine {
                     int fit_linear, int add_lower, const double* Pt_all, double* out);
     int eval_loss(int degree, int fit_linear, int add_lower, double* loss_sum_out,
                   double* y_pred_out);
+
+    // ------------------------------- selected interactions (spfm_engine_interactions.hip)
+    // Read-only like the objective terms.  W = P_o^T diag(lams) P_o is consumed tile by tile in
+    // registers; the buffers below are O(d_a k + tiles / 4096 + K), nothing is of size d_a^2.  They
+    // are kept between calls and freed by spfm_set_params or the option "interaction_release".
+    DevBuf int_flag, int_pos, int_ids, int_tot, int_tmp;  // compaction
+    DevBuf int_A, int_B;                                  // packed active columns, diag(lams) applied
+    DevBuf int_rec, int_rec2;                             // per-tile records and their reduction
+    DevBuf int_hist, int_cnt, int_keys, int_vals, int_keys2, int_vals2;  // select / list
+    DevBuf int_io, int_out;                               // values / block
+    int int_da = 0, int_kp = 0, int_T = 0;  // of the last compaction
+    int int_tile_budget = 0;  // option "interaction_tile_budget": tiles per launch (0 = default)
+    int int_dlim = 0;         // option "interaction_features": only features < this (0 = all)
+    int int_launches = 0;     // tile launches of the last pass (option "interaction_launches")
+    size_t interaction_scratch_bytes() const {
+        return int_flag.bytes + int_pos.bytes + int_ids.bytes + int_tot.bytes + int_tmp.bytes +
+               int_A.bytes + int_B.bytes + int_rec.bytes + int_rec2.bytes + int_hist.bytes +
+               int_cnt.bytes + int_keys.bytes + int_vals.bytes + int_keys2.bytes +
+               int_vals2.bytes + int_io.bytes + int_out.bytes;
+    }
+    int interaction_view(const char* what, int order_idx, const double** base, int64_t* ss,
+                         int64_t* sj);
+    int interaction_prepare(const char* what, int order_idx);
+    IntArgs interaction_args();
+    template <int MODE>
+    int interaction_tiles(IntArgs a);
+    template <int MODE>
+    int interaction_tiles(IntArgs a, int64_t t0, int64_t t1);
+    void interaction_release();  // frees the scratch (set_params, option "interaction_release")
+    int interaction_emit(double tol, unsigned long long thr_key, int64_t cap, int64_t* n_found);
+    int interaction_stats(int order_idx, double tol, int64_t* counts2, double* sums3);
+    int interaction_topk(int order_idx, int64_t K, int32_t* rows, int32_t* cols, double* vals,
+                         int64_t* n_out);
+    int interaction_list(int order_idx, double tol, int64_t capacity, int32_t* rows,
+                         int32_t* cols, double* vals, int64_t* n_out);
+    int interaction_values(int order_idx, int64_t L, const int32_t* rows, const int32_t* cols,
+                           double* vals);
+    int interaction_block(int order_idx, int64_t nJ, const int32_t* J, int64_t nJ2,
+                          const int32_t* J2, double* out);
 
     // diagnostics that need kernels of one translation unit
     int debug_stream_probe(int64_t* bytes_out);  // spfm_engine_pcd.hip

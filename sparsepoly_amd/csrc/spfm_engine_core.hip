@@ -490,6 +490,7 @@ int spfm_engine::set_params(int n_orders_, int k_, int32_t d_, const double* P_,
     if (!have_data) d = d_;
     for (int s = 0; s < k_; ++s)
         if (std::fabs(lams_[s]) != 1.0) FAIL(SPFM_ERR_INVALID, "Lambdas must be +1 or -1.");
+    interaction_release();  // scratch of the interaction passes (sized by the old block)
     if (n_orders_ != n_orders || k_ != k) {
         configured = false;
         clear_graphs();
@@ -1588,6 +1589,20 @@ int spfm_profile_reset(spfm_handle h) {
 int spfm_set_option(spfm_handle h, const char* key, int value) {
     if (!h || !key) return SPFM_ERR_INVALID;
     const std::string k(key);
+    // the interaction passes are read-only views: their options leave the
+    // captured graphs and every engine choice alone
+    if (k == "interaction_release") {
+        h->interaction_release();
+        return SPFM_OK;
+    }
+    if (k == "interaction_tile_budget" || k == "interaction_features") {
+        if (value < 0) {
+            h->err = k + " must be >= 0";
+            return SPFM_ERR_INVALID;
+        }
+        (k == "interaction_tile_budget" ? h->int_tile_budget : h->int_dlim) = value;
+        return SPFM_OK;
+    }
     if (k == "use_graph") {
         h->use_graph = value != 0;
     } else if (k == "fuse_chain") {
@@ -1790,7 +1805,19 @@ int spfm_get_option(spfm_handle h, const char* key, int* value) {
     else if (k == "n_ranks") *value = h->dist() ? h->n_ranks : 1;
     else if (k == "peer_ready") *value = h->peer_ready;
     else if (k == "wide_min_cols") *value = h->wide_min_cols;
-    else {
+    else if (k == "interaction_tile_budget") *value = h->int_tile_budget;
+    else if (k == "interaction_features") *value = h->int_dlim;
+    else if (k == "interaction_launches") *value = h->int_launches;
+    else if (k == "interaction_scratch_kib")
+        *value = (int)((h->interaction_scratch_bytes() + 1023) / 1024);
+    else if (k == "free_mem_mib") {  // hipMemGetInfo of the handle's device
+        size_t fr = 0, tot = 0;
+        if (hipSetDevice(h->device) != hipSuccess || hipMemGetInfo(&fr, &tot) != hipSuccess) {
+            h->err = "hipMemGetInfo failed";
+            return SPFM_ERR_RUNTIME;
+        }
+        *value = (int)(fr >> 20);
+    } else {
         h->err = "unknown option: " + k;
         return SPFM_ERR_INVALID;
     }

@@ -13,6 +13,7 @@ The methods map one-to-one onto the reference calls they replace
 =====================  =====================================================
 """
 import collections
+import contextlib
 import ctypes as C
 import threading
 
@@ -434,6 +435,102 @@ class HipEngine(object):
                                              int(bool(add_lower_deg2)), lp, pp))
         val = ls.value if self._eval_has_y else None
         return (val, pred) if return_pred else val
+
+    # ------------------------- selected interactions W = P_o^T diag(lams) P_o (spfm.h, last section)
+    @contextlib.contextmanager
+    def _interaction_features(self, n_features):
+        """Restrict ONE stats / topk / list call to the features [0, n_features) (None: all): the
+        handle's option is set for the call and restored with it, so nothing stays behind."""
+        if n_features is None or n_features >= self.d:
+            yield
+            return
+        old = self.get_option("interaction_features")
+        self.set_option("interaction_features", int(n_features))
+        try:
+            yield
+        finally:
+            self.set_option("interaction_features", old)
+
+    def release_interaction_scratch(self):
+        """Free the device scratch the interaction calls keep between calls."""
+        self.set_option("interaction_release", 1)
+
+    def interaction_stats(self, order_idx, tol=0.0, n_features=None):
+        """``spfm_interaction_stats``: dict ``nnz`` (pairs j < j' with ``|W| > tol``),
+        ``active_features``, ``sum_sq``, ``sum_abs``, ``max_abs`` of the LIVE block
+        (``n_features``: of its first features only)."""
+        with self._interaction_features(n_features):
+            return self._interaction_stats(order_idx, tol)
+
+    def _interaction_stats(self, order_idx, tol):
+        cnt = np.zeros(2, dtype=np.int64)
+        sums = np.zeros(3)
+        self._check(self._lib.spfm_interaction_stats(
+            self._h, int(order_idx), float(tol), cnt.ctypes.data_as(_capi._lp),
+            sums.ctypes.data_as(_capi._dp)))
+        return dict(nnz=int(cnt[0]), active_features=int(cnt[1]), sum_sq=float(sums[0]),
+                    sum_abs=float(sums[1]), max_abs=float(sums[2]))
+
+    def interaction_topk(self, order_idx, K, n_features=None):
+        """``spfm_interaction_topk``: ``(rows, cols, vals)`` of the K largest ``|W|`` among
+        ``W != 0``, by ``|W|`` descending, then row, then column."""
+        with self._interaction_features(n_features):
+            return self._interaction_topk(order_idx, K)
+
+    def _interaction_topk(self, order_idx, K):
+        K = int(K)
+        rows = np.zeros(max(K, 1), dtype=np.int32)
+        cols = np.zeros(max(K, 1), dtype=np.int32)
+        vals = np.zeros(max(K, 1))
+        n = C.c_int64()
+        self._check(self._lib.spfm_interaction_topk(
+            self._h, int(order_idx), K, rows.ctypes.data_as(_capi._ip),
+            cols.ctypes.data_as(_capi._ip), vals.ctypes.data_as(_capi._dp), C.byref(n)))
+        return rows[:n.value].copy(), cols[:n.value].copy(), vals[:n.value].copy()
+
+    def interaction_list(self, order_idx, tol, capacity, n_features=None):
+        """``spfm_interaction_list``: ``(rows, cols, vals)`` of every pair with ``|W| > tol``,
+        sorted by (row, col).  ``ValueError`` naming the count when it exceeds ``capacity``."""
+        with self._interaction_features(n_features):
+            return self._interaction_list(order_idx, tol, capacity)
+
+    def _interaction_list(self, order_idx, tol, capacity):
+        capacity = int(capacity)
+        rows = np.zeros(max(capacity, 1), dtype=np.int32)
+        cols = np.zeros(max(capacity, 1), dtype=np.int32)
+        vals = np.zeros(max(capacity, 1))
+        n = C.c_int64()
+        self._check(self._lib.spfm_interaction_list(
+            self._h, int(order_idx), float(tol), capacity, rows.ctypes.data_as(_capi._ip),
+            cols.ctypes.data_as(_capi._ip), vals.ctypes.data_as(_capi._dp), C.byref(n)))
+        return rows[:n.value].copy(), cols[:n.value].copy(), vals[:n.value].copy()
+
+    def interaction_values(self, order_idx, rows, cols):
+        """``spfm_interaction_values``: ``W[rows[q], cols[q]]`` (0 where the two ids are equal)."""
+        ra, rp = _capi.i32(rows)
+        ca, cp = _capi.i32(cols)
+        if ra.ndim != 1 or ra.shape != ca.shape:
+            raise ValueError("rows and cols must be 1-d arrays of one length")
+        vals = np.zeros(ra.shape[0])
+        self._check(self._lib.spfm_interaction_values(
+            self._h, int(order_idx), ra.shape[0], rp, cp, vals.ctypes.data_as(_capi._dp)))
+        return vals
+
+    def interaction_block(self, order_idx, J, J2=None):
+        """``spfm_interaction_block``: the dense ``W[J, J2]`` (``J2 = J`` by default), 0 where
+        ``J[a] == J2[b]``; refused above ``SPFM_INTERACTION_BLOCK_MAX_BYTES``."""
+        ja, jp = _capi.i32(J)
+        j2a, j2p = (ja, jp) if J2 is None else _capi.i32(J2)
+        if ja.ndim != 1 or j2a.ndim != 1:
+            raise ValueError("J and J2 must be 1-d index arrays")
+        if ja.shape[0] * j2a.shape[0] * 8 > _capi.INTERACTION_BLOCK_MAX_BYTES:
+            raise ValueError("interaction_block: %d x %d doubles exceed the budget of %d bytes"
+                             % (ja.shape[0], j2a.shape[0], _capi.INTERACTION_BLOCK_MAX_BYTES))
+        out = np.zeros((ja.shape[0], j2a.shape[0]))
+        self._check(self._lib.spfm_interaction_block(
+            self._h, int(order_idx), ja.shape[0], jp, j2a.shape[0], j2p,
+            out.ctypes.data_as(_capi._dp)))
+        return out
 
     # -------------------------------------------------------------- schedule
     def set_schedule(self, mode, indices_feature, conflict_csc=None):

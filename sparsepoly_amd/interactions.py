@@ -1,0 +1,195 @@
+"""Which feature pairs a fitted model kept, evaluated on the device.
+
+For a block ``P_o`` (k, d) with signs ``lams`` the pairwise weights are
+``W = P_o^T diag(lams) P_o`` over ``j < j'`` (the diagonal is no part of the model).  ``W[j, j']``
+is the coefficient of ``x_j x_j'`` for the degree-2 block of a factorization machine (``P_[0]``
+for ``degree=2``, the explicit lower block otherwise) and for ``P_`` of an all-subsets model.  The
+reference's example notebook forms ``np.dot(P, P.T)`` and tests it against zero; at 10^5..10^6
+features that matrix cannot be formed.  Here it never is: ``spfm_interaction_*``
+(``include/spfm.h``) compact the active features and consume the tiles of
+the product in registers.  There is no CPU path: without the library or a GPU the calls raise.
+
+``InteractionMixin`` gives the estimators ``interaction_stats``, ``top_interactions``,
+``interactions``, ``interaction_block`` and ``interaction_values``; ``support_recovery`` and
+``estimation_error`` restate the notebook's metrics without a d x d array.
+"""
+import contextlib
+
+import numpy as np
+import scipy.sparse as sp
+from sklearn.utils.validation import NotFittedError
+
+_NO_DEGREE2 = ("%s: the model has no degree-2 block (degree=%d without fit_lower='explicit'); "
+               "pairwise interaction weights are defined for degree=2, for the explicit lower "
+               "block of a higher degree, and for all-subsets models.")
+
+
+class InteractionMixin(object):
+    """Shared by the factorization-machine and all-subsets estimators (next to ``ObjectiveMixin``).
+
+    Session rule.  Inside ``fit`` (from a callback) and afterwards while a ``warm_start`` device
+    session is kept, the methods read that session's LIVE parameters: no parameter is copied.
+    Under ``solver='pbcd'`` the fit loops do not refresh ``P_`` for callbacks, so a mid-fit call
+    sees the live block, not the stale ``P_``.  Otherwise a fresh engine receives ``P_`` /
+    ``lams_`` (``set_params`` only: no data, no configuration) and is closed afterwards.
+
+    ``include_augmented``: with ``fit_lower='augment'`` the stored block has dummy columns after
+    the ``n_features`` real ones; they are left out unless this is true (the first dummy is then
+    feature ``n_features``).  Several ranks: parameters are replicated, every rank answers
+    locally."""
+
+    # ---------------------------------------------------------------- which block
+    def _interaction_block_spec(self, what):
+        """(order index of the degree-2 block, number of augmented dummy columns)"""
+        if not hasattr(self, "P_"):
+            raise NotFittedError("Estimator not fitted.")
+        degree = getattr(self, "degree", None)
+        if degree is None:  # all-subsets: one block, never augmented
+            return 0, 0
+        explicit = self.fit_lower == "explicit"
+        if degree != 2 and not (explicit and degree >= 3):
+            raise ValueError(_NO_DEGREE2 % (what, degree))
+        n_dummy = 0
+        if self.fit_lower == "augment":
+            n_dummy = max(0, degree - (2 if self.fit_linear else 1))
+        return degree - 2, n_dummy  # order degree - deg holds degree deg
+
+    @contextlib.contextmanager
+    def _interaction_session(self, what, include_augmented):
+        """-> (engine, order index, number of features in view)"""
+        order_idx, n_dummy = self._interaction_block_spec(what)
+        live = getattr(self, "_live", None)
+        if live is None:
+            cached = getattr(self, "_device_session", None)
+            if cached is not None:
+                live = (cached[1], None)
+        fresh = live is None or getattr(live[0], "_h", None) is None
+        if fresh:
+            engine = self._new_engine()
+            P = np.ascontiguousarray(self.P_, dtype=np.double)
+            P = P[None] if P.ndim == 2 else P
+            w = getattr(self, "w_", None)
+            engine.set_params(P, np.zeros(P.shape[2]) if w is None else w, self.lams_)
+        else:
+            engine = live[0]
+        d_view = engine.d if include_augmented else engine.d - n_dummy
+        try:
+            yield engine, order_idx, d_view
+        finally:
+            if fresh:
+                engine.close()
+
+    @staticmethod
+    def _interaction_ids(ids, d_view, name):
+        ids = np.asarray(ids)
+        if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
+            raise ValueError("%s must be a 1-d array of feature ids" % name)
+        if ids.size and (ids.min() < 0 or ids.max() >= d_view):
+            raise ValueError("%s: feature id out of range [0, %d)" % (name, d_view))
+        return ids.astype(np.int32)
+
+    # ---------------------------------------------------------------- the methods
+    def interaction_stats(self, tol=0.0, include_augmented=False):
+        """dict ``nnz`` (pairs ``j < j'`` with ``|W| > tol``; ``tol = 0``: ``W != 0``),
+        ``active_features``, ``sum_sq``, ``sum_abs``, ``max_abs`` of the pairwise weights."""
+        with self._interaction_session("interaction_stats()", include_augmented) as (eng, o, dv):
+            return eng.interaction_stats(o, tol, n_features=dv)
+
+    def top_interactions(self, K, include_augmented=False):
+        """``(rows, cols, vals)`` of the ``K`` pairs of largest ``|W|`` among ``W != 0``
+        (``rows < cols``), ordered by ``|W|`` descending, then row, then column; fewer than ``K``
+        when fewer exist."""
+        with self._interaction_session("top_interactions()", include_augmented) as (eng, o, dv):
+            return eng.interaction_topk(o, K, n_features=dv)
+
+    def interactions(self, tol=0.0, max_pairs=10_000_000, include_augmented=False):
+        """Every pair with ``|W| > tol`` as an upper-triangular ``scipy.sparse.coo_matrix``
+        (entries sorted by row, then column).  ``ValueError`` naming the count when it exceeds
+        ``max_pairs``."""
+        with self._interaction_session("interactions()", include_augmented) as (eng, o, dv):
+            nnz = eng.interaction_stats(o, tol, n_features=dv)["nnz"]
+            if nnz > max_pairs:
+                raise ValueError("interactions(): %d pairs have |W| > %g, more than max_pairs=%d"
+                                 % (nnz, tol, max_pairs))
+            rows, cols, vals = eng.interaction_list(o, tol, nnz, n_features=dv)
+            return sp.coo_matrix((vals, (rows, cols)), shape=(dv, dv))
+
+    def interaction_block(self, J, J2=None, include_augmented=False):
+        """The dense sub-block ``W[J, J2]`` (``J2 = J`` by default; repeats allowed), 0 where
+        ``J[a] == J2[b]``.  Refused above 1 GiB of result."""
+        with self._interaction_session("interaction_block()", include_augmented) as (eng, o, dv):
+            J = self._interaction_ids(J, dv, "J")
+            J2 = J if J2 is None else self._interaction_ids(J2, dv, "J2")
+            return eng.interaction_block(o, J, J2)
+
+    def interaction_values(self, rows, cols, include_augmented=False):
+        """``W[rows[q], cols[q]]`` for given pairs (either order of the two ids; 0 where they are
+        equal)."""
+        with self._interaction_session("interaction_values()", include_augmented) as (eng, o, dv):
+            rows = self._interaction_ids(rows, dv, "rows")
+            cols = self._interaction_ids(cols, dv, "cols")
+            return eng.interaction_values(o, rows, cols)
+
+    def _interaction_support_query(self, rows, cols, include_augmented=False):
+        """(``interaction_stats(0)``, ``W`` at the given pairs) through ONE session: what the
+        metrics below need."""
+        with self._interaction_session("support query", include_augmented) as (eng, o, dv):
+            rows = self._interaction_ids(rows, dv, "rows")
+            cols = self._interaction_ids(cols, dv, "cols")
+            return (eng.interaction_stats(o, 0.0, n_features=dv),
+                    eng.interaction_values(o, rows, cols))
+
+
+# ------------------------------------------------------------------ the notebook's metrics
+def _true_support(W_true):
+    """(rows, cols, values) of the non-zeros of the symmetric ``W_true`` above the diagonal"""
+    if sp.issparse(W_true):
+        Wt = sp.triu(sp.coo_matrix(W_true), k=1).tocoo()
+        Wt.sum_duplicates()
+        keep = Wt.data != 0
+        rows, cols, vals = Wt.row[keep], Wt.col[keep], Wt.data[keep]
+    else:
+        W = np.asarray(W_true, dtype=np.double)
+        if W.ndim != 2 or W.shape[0] != W.shape[1]:
+            raise ValueError("W_true must be a square matrix")
+        rows, cols = np.nonzero(np.triu(W, k=1))
+        vals = W[rows, cols]
+    order = np.lexsort((cols, rows))
+    return (rows[order].astype(np.int32), cols[order].astype(np.int32),
+            np.asarray(vals, dtype=np.double)[order])
+
+
+def support_recovery(est, W_true, include_augmented=False):
+    """The notebook's support metrics of ``est`` against a symmetric true matrix ``W_true``
+    (dense or scipy-sparse), over pairs ``j < j'``: dict ``fscore``, ``pssr`` (the supports are
+    equal), ``nnz`` (selected pairs), ``tp``, ``fp``, ``fn``.  ``tp`` counts the true pairs whose
+    estimated weight is non-zero (``spfm_interaction_values`` on the true support), ``fp = nnz - tp``,
+    ``fn = |supp| - tp``.  Zero divisions as in the notebook: precision is 0 when nothing is
+    selected, the F-score is 0 when precision + recall is 0; an empty true support, which the
+    notebook does not meet, gives recall 0.  No d x d array is formed."""
+    rows, cols, _ = _true_support(W_true)
+    stats, we = est._interaction_support_query(rows, cols, include_augmented)
+    nnz = stats["nnz"]
+    tp = int(np.count_nonzero(we))
+    fp = int(nnz) - tp
+    fn = int(rows.shape[0]) - tp
+    precision = 0.0 if tp + fp == 0 else tp / (tp + fp)
+    recall = 0.0 if tp + fn == 0 else tp / (tp + fn)
+    fscore = 0.0 if precision + recall == 0 else 2 * precision * recall / (precision + recall)
+    return dict(fscore=fscore, pssr=(fp + fn) == 0, nnz=int(nnz), tp=tp, fp=fp, fn=fn)
+
+
+def estimation_error(est, W_true, scaling=True, include_augmented=False):
+    """The notebook's estimation error, with its convention that the model's ``W`` estimates
+    ``2 W_true``: ``sqrt(sum_{j<j'} (2 W_true - W)^2)``, divided by ``sqrt(sum_{j<j'} (2 W_true)^2)``
+    when ``scaling``.  Evaluated as ``sum_supp (2 W_t - W_e)^2 + (sum_sq - sum_supp W_e^2)`` --
+    the pairs outside the true support contribute their squares, which ``interaction_stats``
+    sums on the device -- clamped at 0 before the root.  No d x d array is formed."""
+    rows, cols, wt = _true_support(W_true)
+    stats, we = est._interaction_support_query(rows, cols, include_augmented)
+    sum_sq = stats["sum_sq"]
+    err2 = float(np.sum((2.0 * wt - we) ** 2)) + (sum_sq - float(np.sum(we ** 2)))
+    err = np.sqrt(max(err2, 0.0))
+    if scaling:
+        err /= np.sqrt(float(np.sum((2.0 * wt) ** 2)))
+    return float(err)

@@ -29,13 +29,19 @@ class Monitor(object):
     (plus ``iteration``, the call index, and ``validation_loss`` when the estimator has a
     validation set and ``validation`` is true) in ``history``.  It returns None, so it never stops
     a fit.  ``needs_params = False`` tells the fit loops that the callback does not read ``P_`` /
-    ``w_``: the parameters are not copied to the host for it."""
+    ``w_``: the parameters are not copied to the host for it.
+
+    ``interactions=True`` (opt-in: one pass over the pairwise product per record,
+    sparsepoly_amd/interactions.py) adds ``nnz_interactions``, the number of feature pairs with
+    ``|W| > interaction_tol``; the default records are unchanged."""
 
     needs_params = False
 
-    def __init__(self, every=1, validation=True):
+    def __init__(self, every=1, validation=True, interactions=False, interaction_tol=0.0):
         self.every = max(1, int(every))
         self.validation = bool(validation)
+        self.interactions = bool(interactions)
+        self.interaction_tol = float(interaction_tol)
         self.history = []
         self._calls = 0
 
@@ -49,6 +55,8 @@ class Monitor(object):
         rec["validation_loss"] = None
         if self.validation and getattr(estimator, "_validation", None) is not None:
             rec["validation_loss"] = estimator.validation_loss()
+        if self.interactions:
+            rec["nnz_interactions"] = estimator.interaction_stats(self.interaction_tol)["nnz"]
         self.history.append(rec)
         return None
 

@@ -49,6 +49,7 @@ from .engine import HipEngine, canonical_csc
 from .schedule import Schedule
 from .loss import CLASSIFICATION_LOSSES, REGRESSION_LOSSES
 from .regularizer import REGULARIZATION
+from .interactions import InteractionMixin
 from .monitor import ObjectiveMixin, callback_needs_params
 
 MAX_DEGREE = 6  # include/spfm.h SPFM_MAX_DEGREE
@@ -91,7 +92,7 @@ def _fingerprint(Xc, y):
     return (Xc.shape, int(Xc.nnz), fin())
 
 
-class _BaseSparseFactorizationMachine(ObjectiveMixin, BaseSparsePoly, metaclass=ABCMeta):
+class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, BaseSparsePoly, metaclass=ABCMeta):
     _REGULARIZERS = REGULARIZATION
 
     @abstractmethod
