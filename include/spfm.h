@@ -92,7 +92,7 @@ int spfm_set_data_csc(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr
 int spfm_set_data_csr(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
                       const int32_t* indices, const double* data, const double* y);
 
-/* Several handles on ONE training matrix (round 4): the fits of a regularisation path or a
+/* Several handles on ONE training matrix: the fits of a regularisation path or a
  * parameter grid -- the use-case the reference serves with warm_start chains
  * (sparse_factorization_machines.py:380-391) -- and one-vs-rest targets (base.py:130-136).  `dst`
  * refers to the device image `src` holds (CSC, CSR, column norms) instead of uploading and
@@ -288,50 +288,97 @@ int spfm_profile_get(spfm_handle h, int which, double* ms, int64_t* launches, in
 int spfm_profile_reset(spfm_handle h);
 /* use hipGraph replay for the per-pass launch sequences (default on) */
 int spfm_set_use_graph(spfm_handle h, int on);
-/* engine tunables, by name: "use_graph" (0/1), "fuse_chain" (0/1: fused chain+sync
- * kernel for steps of <= 64 columns), "max_batch" (columns per dependent step,
- * applies to the next spfm_set_schedule), "persistent" (0/1: one persistent launch
- * per pcd component pass, single GPU; caps steps at 64 columns), "prb_groups"
- * (workgroups of the persistent pass), "prb_long" (entries of one column in one row
- * block above which the whole workgroup, not 4 lanes, processes it), "prb_lds" (0/1, default 1: keep each workgroup's row block -- A and the
- * residual / prediction -- in LDS for the whole pass when it fits: f32 storage, one cache
- * value per row, squared loss or +-1 targets), "prb_stamps" (diagnostic phase timers),
- * "psgd_eager" (1: launch every psgd minibatch eagerly instead of replaying runs of 32 from
- * a hipGraph), "psgd_graph_sweeps" (support-search sweeps recorded per minibatch for the
- * squared-norm prox, default 4; an epoch in which that was not enough is redone eagerly from
- * a snapshot -- spfm_get_option("psgd_redone") counts those).  Round 2: "pbcd_persistent"
- * (0/1: the persistent pbcd pass), "pbprb_groups" (its workgroups, default 256), "wide" (0/1:
- * the wide passes for degree-2 pcd / cd_linear, steps of up to 512 columns), "pcdw_groups"
- * (their workgroups; default 0 = about 160 entries per workgroup and step, at most one per CU),
- * "wide_min_cols" (mean colour-class width below which the schedule is coloured again with 64 columns per class and the 64-column passes run, default
- * 110; 0 = always wide), "peer_exchange" (only 0 can be set: give the in-kernel cross-GPU
- * exchange up after spfm_peer_connect and use the per-step collective), diagnostics
- * "pbprb_stamps", "pcdw_stamps", "probe_xcd" / "probe_lds" (spfm_debug_exchange_cost on one
- * XCD).  They change how a sweep is cut into launches and in which order partial sums are
- * added; "wide" / "wide_min_cols" / "max_batch" also the coloured schedule built next (never an
- * order the caller passed as 'exact'). */
-int spfm_set_option(spfm_handle h, const char* key, int value);
-/* Round 3: "pbprb_owners" (dedicated owner workgroups of the persistent pbcd pass: removed in
- * round 4, only 0 is accepted), "relax" (0/1, default 1: a schedule of tiny steps --
- * the reference order, fewer than 12 columns per step on average -- is run by the degree-2 pcd
- * pass as merged steps of ~20 consecutive columns whose shared rows the chains replay in order;
- * same result as the sequential sweep), "prb_pack" (0/1, default 1: degree-3 passes with their
- * rows in global memory work on packed 16-byte row records), "persistent_failed" (0: try the
- * persistent passes again after a recorded fall-back), test hooks "debug_spin_max" (polls of one
- * in-kernel wait before a persistent pass gives up, default 2^21) and "debug_drop_group" (the next
- * N persistent launches lack their last workgroup, i.e. time out), "ingest_device" (0/1, default 1:
- * spfm_set_data_csr transposes on the device -- one stable radix sort of the entries by column id;
- * 0, or no room for the sort's scratch: host threads), "colour_device" (0/1, default 1: the
- * first-fit colouring of spfm_set_schedule(SPFM_SCHED_COLORED) runs on the device when the
- * conflict structure is the handle's own matrix -- the same order and batch boundaries as the
- * host form; "colour_device_used" tells), "stream_device" (0/1, default 1: the entry stream of
- * the 64-column passes is built on the device, entry for entry the host builder's), "co_tenants" (1..64, default 1: the number
- * of handles of this process whose persistent passes run at the same time on this device --
- * independent fits, one handle and one host thread each; the handle then sizes its passes to
- * 1/co_tenants of the CUs and its residency check to the shared device.  Set it before the
- * schedule.  Handles are independent objects: calls on DIFFERENT handles may be made from
- * different threads at the same time, calls on one handle must not overlap).
+
+/* -- options ------------------------------------------------------------------
+ * String-keyed integer options of a handle.  spfm_set_option returns SPFM_ERR_INVALID for an
+ * unknown key, a read-out or a value outside the key's range; spfm_get_option reads every key
+ * of the table except the action "interaction_release" (every settable key reads back the value
+ * last set, or its default).  No option changes the coordinate order of a sweep, and none
+ * changes an order the caller passed as 'exact'.
  *
+ * Columns: key | values (default) | affects | when to set.  "affects" is one of
+ *   nothing    nothing numerical: the same arithmetic in the same order
+ *   sum order  how a sweep is cut into launches and the order in which partial sums are added
+ *   schedule   also the coloured schedule built next (spfm_set_schedule(SPFM_SCHED_COLORED))
+ *
+ * Tuning
+ *   "use_graph"               | 0/1 (1)        | nothing   | any time; hipGraph replay of the per-pass launch sequences
+ *   "fuse_chain"              | 0/1 (1)        | sum order | any time; fused chain+sync kernel for steps of <= 64 columns
+ *   "max_batch"               | >= 1 (4096)    | schedule  | before the schedule; columns per dependent step
+ *   "persistent"              | 0/1 (1)        | sum order | before the schedule; one persistent launch per pcd component pass, caps steps at 64 columns
+ *   "prb_groups"              | >= 1 (64)      | sum order | any time; workgroups of the 64-column persistent pass
+ *   "prb_long"                | >= 16 (48)     | sum order | any time; entries of one column in one row block above which the whole workgroup, not 4 lanes, processes it
+ *   "prb_lds"                 | 0/1 (1)        | sum order | any time; keep each workgroup's row block (A and the residual / prediction) in LDS for the whole pass when it fits: f32 storage, one cache value per row, squared loss or +-1 targets
+ *   "prb_pack"                | 0/1 (1)        | sum order | any time; degree-3 passes with their rows in global memory work on packed 16-byte row records
+ *   "relax"                   | 0/1 (1)        | sum order | any time; a schedule of tiny steps (the reference order, fewer than 12 columns per step on average) runs as merged steps of ~20 consecutive columns whose shared rows the chains replay in order: same result as the sequential sweep
+ *   "pbcd_persistent"         | 0/1 (1)        | sum order | any time; the persistent pbcd pass
+ *   "pbprb_groups"            | >= 1 (256)     | sum order | any time; workgroups of the persistent pbcd pass
+ *   "pbprb_balance"           | 0/1 (1)        | sum order | any time; balanced slot groups of the persistent pbcd pass (0: slot q -> group q % groups)
+ *   "pbprb_owners"            | 0 (0)          | nothing   | never; dedicated owner workgroups no longer exist, any other value returns SPFM_ERR_UNSUPPORTED
+ *   "pbcd_fuse"               | 0/1 (1)        | sum order | any time; multi-kernel pbcd engine: prep and chain in one launch
+ *   "wide"                    | 0/1 (1)        | schedule  | before the schedule; the wide passes for degree-2 pcd / cd_linear, steps of up to 512 columns
+ *   "wide_min_cols"           | any int (110)  | schedule  | before the schedule; mean colour-class width below which the schedule is coloured again with 64 columns per class and the 64-column passes run; 0 = always wide
+ *   "pcdw_groups"             | >= 1 (0 = auto) | sum order | any time; workgroups of the wide passes; auto = about 160 entries per workgroup and step, at most one per CU; reads back the count in use once the wide stream exists
+ *   "wide_lds_rows"           | any int (-1 = auto) | sum order | any time; wide pass whose row block is too large for LDS: rows of it kept there
+ *   "wide_ep"                 | 0/1 (1)        | sum order | any time; wide pass with rows in global memory: entry-parallel form
+ *   "wide_rec8"               | 0/1 (1)        | sum order | any time; ... with 8-byte (A, residual) row records where they apply (squared loss, f32)
+ *   "ingest_device"           | 0/1 (1)        | nothing   | before spfm_set_data_csr; transpose on the device (one stable radix sort of the entries by column id); 0, or no room for the sort's scratch: host threads
+ *   "colour_device"           | 0/1 (1)        | nothing   | before the schedule; first-fit colouring on the device when the conflict structure is the handle's own matrix: the same order and batch boundaries as the host form
+ *   "stream_device"           | 0/1 (1)        | nothing   | any time; entry streams of the persistent passes built on the device, entry for entry the host builder's
+ *   "co_tenants"              | 1..64 (1)      | sum order | before the schedule; handles of this process whose persistent passes run at the same time on this device (see below)
+ *   "peer_exchange"           | 0 (reads "peer_ready") | sum order | after spfm_peer_connect, then set the schedule again; gives the in-kernel cross-GPU exchange up for the per-step collective
+ *   "persistent_failed"       | 0/1 (0)        | sum order | any time; 0 = try the persistent passes again after a recorded fall-back
+ *   "psgd_eager"              | 0/1 (0)        | nothing   | any time; launch every psgd minibatch eagerly instead of replaying runs of 32 from a hipGraph
+ *   "psgd_graph_sweeps"       | 0..64 (4)      | nothing   | any time; support-search sweeps recorded per minibatch for the squared-norm prox; an epoch in which that was not enough is redone eagerly from a snapshot ("psgd_redone")
+ *   "interaction_tile_budget" | >= 0 (0 = default) | nothing | any time; tiles per launch of an interaction pass
+ *   "interaction_features"    | >= 0 (0 = all) | nothing   | any time; the interaction passes see only features below this
+ *   "interaction_release"     | action, value ignored, not readable | nothing | any time; frees the interaction passes' scratch
+ *
+ * Diagnostics (nothing numerical; set before the epochs they observe)
+ *   "prb_stamps"              | 0/1 (0)        | nothing   | phase timers of the 64-column pass (spfm_debug_prb_stamps)
+ *   "pcdw_stamps"             | 0/1 (0)        | nothing   | phase timers of the wide pass
+ *   "pbprb_stamps"            | 0/1 (0)        | nothing   | phase timers of the persistent pbcd pass
+ *   "pbprb_dbg"               | bit mask (0)   | nothing   | diagnostic counters of the persistent pbcd pass (bit 8: spfm_debug_prb_stamps returns them)
+ *   "probe_xcd"               | any int (0)    | nothing   | spfm_debug_exchange_cost on one XCD
+ *   "probe_lds"               | any int (61440) | nothing  | LDS bytes per workgroup of spfm_debug_exchange_cost
+ *
+ * Test hooks (not for production use)
+ *   "debug_spin_max"          | >= 64 (2^21)   | nothing   | polls of one in-kernel wait before a persistent pass gives up
+ *   "debug_drop_group"        | any int (0)    | nothing   | the next N persistent launches lack their last workgroup, i.e. time out
+ *   "debug_keep_last_error"   | 0/1 (0)        | nothing   | spfm_comm_init does not clear the thread's stale HIP error before calling RCCL
+ *
+ * Read-outs (spfm_get_option only)
+ *   "persistent_active"       | 0/1            | -         | the next pcd epoch will use a persistent pass: option on, steps of <= 64 columns or the wide pass
+ *   "wide_active"             | 0/1            | -         | the next pcd epoch will use the wide pass
+ *   "pbprb_active"            | 0/1            | -         | what the last pbcd epoch used
+ *   "prb_lds_active"          | 0/1/2          | -         | what the last pcd pass used: 0 global rows, 1 LDS residual form, 2 LDS prediction + label sign
+ *   "prb_pack_active"         | 0/1            | -         | the last pcd pass used packed row records
+ *   "wide_lds_active"         | 0/1/2          | -         | what the last wide pass used: 0 global rows, 1 all rows in LDS, 2 the first rows of a block in LDS
+ *   "wide_ep_active"          | 0/1            | -         | the last wide pass used the entry-parallel form
+ *   "relax_steps"             | >= 0           | -         | merged steps per sweep, 0 = strict steps
+ *   "pb_relax_active"         | 0/1            | -         | the last pbcd epoch ran relaxed runs
+ *   "persistent_fallbacks"    | >= 0           | -         | epochs redone on the multi-kernel engine (failure semantics below)
+ *   "psgd_redone"             | >= 0           | -         | psgd epochs that fell back from graph replay to eager launches
+ *   "n_ranks"                 | >= 1           | -         | ranks of the attached communicator
+ *   "peer_ready"              | 0/1            | -         | in-kernel cross-GPU exchange connected and verified
+ *   "ingest_device_used"      | 0/1            | -         | the last spfm_set_data_csr transposed on the device
+ *   "colour_device_used"      | 0/1            | -         | the last coloured schedule was coloured on the device
+ *   "stream_device_used"      | 0/1/2          | -         | 64-column entry stream: 0 host threads, 1 device, 2 taken from a co-tenant
+ *   "pb_stream_device_used"   | 0/1            | -         | the pbcd entry stream was built on the device
+ *   "wide_stream_device_used" | 0/1            | -         | the wide entry stream was built on the device
+ *   "interaction_launches"    | >= 0           | -         | tile launches of the last interaction pass
+ *   "interaction_scratch_kib" | >= 0           | -         | scratch the interaction passes hold, KiB
+ *   "free_mem_mib"            | >= 0           | -         | free memory of the handle's device (hipMemGetInfo; SPFM_ERR_RUNTIME if that fails)
+ *
+ * co_tenants: independent fits, one handle and one host thread each; the handle then sizes its
+ * passes to 1/co_tenants of the CUs (prb_groups and pbprb_groups are capped at once, the wide
+ * pass caps itself) and its residency check to the shared device.  Handles are independent
+ * objects: calls on DIFFERENT handles may be made from different threads at the same time, calls
+ * on one handle must not overlap. */
+int spfm_set_option(spfm_handle h, const char* key, int value);
+int spfm_get_option(spfm_handle h, const char* key, int* value);
+
+/* -- streams, hardware queues and failure semantics -----------------------------
  * The library never issues work on the null stream (every handle owns a non-blocking stream):
  * concurrent handles do not serialise on each other or on the host program's default stream.
  * The HIP runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); a host program
@@ -345,15 +392,6 @@ int spfm_set_option(spfm_handle h, const char* key, int value);
  * spfm_init_pred), the epoch is redone on the multi-kernel engine and the handle keeps using that
  * engine; with several ranks the decision is agreed on through the communicator.  The call
  * still returns SPFM_OK; spfm_get_option("persistent_fallbacks") counts the events. */
-/* read back a tunable, or the derived "persistent_active" (1 if the next pcd epoch
- * will use the persistent pass: option on, single GPU, steps of <= 64 columns) and
- * "prb_lds_active" (what the last pcd pass used: 0 global rows, 1 LDS residual form,
- * 2 LDS prediction + label sign), "pbprb_active", "wide_active", "wide_lds_active",
- * "prb_pack_active", "relax_steps" (merged steps per degree-2 pcd sweep, 0 = strict steps),
- * "persistent_fallbacks", "persistent_failed", "n_ranks" (ranks of the attached communicator),
- * "peer_ready" (in-kernel cross-GPU exchange connected and verified), "ingest_device_used"
- * (1 if the last spfm_set_data_csr transposed on the device), "co_tenants" */
-int spfm_get_option(spfm_handle h, const char* key, int* value);
 
 /* diagnostic ("prb_stamps" option): accumulated shader cycles per phase of the last
  * persistent pass, 16 values per workgroup (8 control-wave, 8 worker-wave phases);
@@ -373,10 +411,6 @@ int spfm_debug_hop_latency(spfm_handle h, int partner, int rounds, double* ns_pe
 int spfm_debug_exchange_cost(spfm_handle h, int groups, int ncols, int readers_mod, int rounds,
                              double* ns_per_round);
 
-/* diagnostic: how often the device chains took the reference's "numerical error" branches
- * since the last reset -- out[0] omegati.py:97-98 (clip), out[1] omegacs.py:90-96, out[2]
- * omegacs.py:75-76, out[3] squaredl21.py:48-49 (out[4..7] reserved).  reset != 0 clears the
- * counters after reading.  Counters are per process (all handles of the device). */
 /* Diagnostic for the counter calibration (profiles/r03_fetch_calibration.txt): one launch that
  * reads the persistent pass's entry stream (slot bounds, rows, values of every step, with the
  * pass's own access pattern) and nothing else; bytes_out receives the bytes it requested.  Run
@@ -387,6 +421,10 @@ int spfm_debug_stream_probe(spfm_handle h, int64_t* bytes_out);
  * the persistent passes that keep their rows in global memory -- and writes nothing else;
  * *bytes_out = the bytes requested (nnz * bytes_per_record).  Calibrates WRITE_SIZE. */
 int spfm_debug_write_probe(spfm_handle h, int bytes_per_record, int64_t* bytes_out);
+/* diagnostic: how often the device chains took the reference's "numerical error" branches
+ * since the last reset -- out[0] omegati.py:97-98 (clip), out[1] omegacs.py:90-96, out[2]
+ * omegacs.py:75-76, out[3] squaredl21.py:48-49 (out[4..7] reserved).  reset != 0 clears the
+ * counters after reading.  Counters are per process (all handles of the device). */
 int spfm_debug_branch_counts(spfm_handle h, unsigned* out8, int reset);
 
 /* -- Gram matrices (sparsepoly/kernels.py) -------------------------------------

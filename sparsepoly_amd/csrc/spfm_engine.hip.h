@@ -254,7 +254,7 @@ struct spfm_engine {
     bool pers_failed = false;
     int pers_fallbacks = 0;
     std::string pers_reason;
-    unsigned spin_max = 1u << 21;  // polls of one in-kernel wait before the pass gives up
+    int spin_max = 1 << 21;  // polls of one in-kernel wait before the pass gives up
     int debug_drop = 0;            // test hook: the next N persistent launches lack a workgroup
     bool keep_last_error = false;  // test hook (spfm_comm_init)
     bool have_pred_args = false;
@@ -368,6 +368,29 @@ struct spfm_engine {
     void clear_graphs() {
         for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
         graphs.clear();
+    }
+
+    // What a change of an option, the schedule or the engine makes stale (the masks of
+    // spfm_options.inc.h).  The only place that resets the readiness and relax flags; the
+    // builders set them again when they next run.
+    enum : unsigned {
+        kInvPrbStream = 1,    // entry stream of the 64-column pass
+        kInvPbStream = 2,     // entry stream of the persistent pbcd pass
+        kInvWideStream = 4,   // entry stream of the wide pass
+        kInvRelax = 8,        // relaxed runs of the pcd pass
+        kInvPbRelax = 16,     // relaxed runs of the pbcd pass
+        kInvSchedule = 32,    // the schedule has to be set again
+        kInvGraphs = 64,      // captured graphs
+        kInvStreams = kInvPrbStream | kInvPbStream | kInvWideStream,
+    };
+    void invalidate(unsigned mask) {
+        if (mask & kInvPrbStream) prb_ready = false;
+        if (mask & kInvPbStream) pb_stream_ready = false;
+        if (mask & kInvWideStream) wide_ready = false;
+        if (mask & kInvRelax) relax_state = 0;
+        if (mask & kInvPbRelax) pbr_state = 0;
+        if (mask & kInvSchedule) have_schedule = false;
+        if (mask & kInvGraphs) clear_graphs();
     }
 
     RegState regstate() {

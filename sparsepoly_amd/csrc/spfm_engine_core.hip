@@ -258,10 +258,9 @@ int spfm_engine::data_installed(const double* y) {
             }
     }
     have_data = true;
-    have_schedule = false;
     configured = false;
     col_norm_reduced = false;
-    clear_graphs();
+    invalidate(kInvSchedule | kInvGraphs);
     HIPC(viol_col.alloc(sizeof(double) * (size_t)d));
     HIPC(pred_tmp.alloc(sizeof(double) * (size_t)(n > 0 ? n : 1)));
     HIPC(partial.alloc(sizeof(double) * 1024));
@@ -739,13 +738,8 @@ int spfm_engine::install_schedule() {
         sched_hash = hsh;
     }
     have_schedule = true;
-    prb_ready = false;
-    pb_stream_ready = false;
-    wide_ready = false;
-    relax_state = 0;
-    pbr_state = 0;
+    invalidate(kInvStreams | kInvRelax | kInvPbRelax | kInvGraphs);
     ++sched_version;
-    clear_graphs();
     return alloc_work();
 }
 
@@ -1553,11 +1547,8 @@ int spfm_peer_connect(spfm_handle h, int n_ranks, int rank, const char* handles)
         }
     }
     h->peer_ready = true;
-    h->have_schedule = false;  // the step cap depends on the engine: set the schedule again
-    h->prb_ready = false;
-    h->pb_stream_ready = false;
-    h->wide_ready = false;
-    h->clear_graphs();
+    // the step cap depends on the engine: set the schedule again
+    h->invalidate(spfm_engine::kInvSchedule | spfm_engine::kInvStreams | spfm_engine::kInvGraphs);
     return SPFM_OK;
 }
 
@@ -1586,243 +1577,7 @@ int spfm_profile_reset(spfm_handle h) {
     return SPFM_OK;
 }
 
-int spfm_set_option(spfm_handle h, const char* key, int value) {
-    if (!h || !key) return SPFM_ERR_INVALID;
-    const std::string k(key);
-    // the interaction passes are read-only views: their options leave the
-    // captured graphs and every engine choice alone
-    if (k == "interaction_release") {
-        h->interaction_release();
-        return SPFM_OK;
-    }
-    if (k == "interaction_tile_budget" || k == "interaction_features") {
-        if (value < 0) {
-            h->err = k + " must be >= 0";
-            return SPFM_ERR_INVALID;
-        }
-        (k == "interaction_tile_budget" ? h->int_tile_budget : h->int_dlim) = value;
-        return SPFM_OK;
-    }
-    if (k == "use_graph") {
-        h->use_graph = value != 0;
-    } else if (k == "fuse_chain") {
-        h->fuse_chain = value != 0;
-    } else if (k == "persistent") {
-        h->persistent = value != 0;
-        h->prb_ready = false;
-    } else if (k == "prb_long") {
-        if (value < 16) {
-            h->err = "prb_long must be >= 16";
-            return SPFM_ERR_INVALID;
-        }
-        h->prb_long = value;
-        h->prb_ready = false;
-        h->relax_state = 0;
-    } else if (k == "prb_pack") {  // packed row records for degree-3 passes (rows in global memory)
-        h->prb_pack = value != 0;
-    } else if (k == "co_tenants") {  // concurrent fits: handles sharing the device's CUs
-        if (value < 1 || value > 64) {
-            h->err = "co_tenants must be in [1, 64]";
-            return SPFM_ERR_INVALID;
-        }
-        h->co_tenants = value;
-        // every tenant keeps to its share of the CUs (one persistent workgroup per CU)
-        int ncu = 256;
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device);
-        const int share = std::max(1, ncu / value);
-        if (h->prb_G > share) {
-            h->prb_G = share;
-            h->prb_ready = false;
-            h->relax_state = 0;
-        }
-        if (h->pbprb_G > share) {
-            h->pbprb_G = share;
-            h->pb_stream_ready = false;
-        }
-        h->wide_ready = false;  // the wide pass caps itself (wide_groups)
-    } else if (k == "stream_device") {  // entry streams of the persistent passes: device or host threads
-        h->stream_device = value != 0;
-        h->prb_ready = false;
-        h->pb_stream_ready = false;
-        h->wide_ready = false;
-    } else if (k == "colour_device") {  // first-fit colouring on the device (default) or by host threads
-        h->colour_device = value != 0;
-    } else if (k == "ingest_device") {  // CSR -> CSC on the device (default) or by host threads
-        h->ingest_device = value != 0;
-    } else if (k == "relax") {  // merged steps for schedules of tiny steps
-        h->relax_on = value != 0;
-        h->relax_state = 0;
-        h->pbr_state = 0;
-    } else if (k == "prb_stamps") {
-        h->prb_stamp_on = value != 0;
-    } else if (k == "debug_spin_max") {  // test hook: polls before a persistent pass gives up
-        if (value < 64) {
-            h->err = "debug_spin_max must be >= 64";
-            return SPFM_ERR_INVALID;
-        }
-        h->spin_max = (unsigned)value;
-    } else if (k == "debug_keep_last_error") {  // test hook: spfm_comm_init does not clear the
-        h->keep_last_error = value != 0;        // thread's stale HIP error before calling RCCL
-    } else if (k == "debug_drop_group") {  // test hook: the next `value` persistent launches
-        h->debug_drop = value;             // lack their last workgroup (they time out)
-    } else if (k == "persistent_failed") {  // 0: try the persistent passes again
-        h->pers_failed = value != 0;
-    } else if (k == "psgd_graph_sweeps") {
-        if (value < 0 || value > 64) {
-            h->err = "psgd_graph_sweeps must be in 0..64";
-            return SPFM_ERR_INVALID;
-        }
-        h->psgd_graph_sweeps = value;
-    } else if (k == "psgd_eager") {
-        h->psgd_force_eager = value != 0;
-    } else if (k == "pbcd_fuse") {
-        h->pbcd_fuse = value != 0;
-    } else if (k == "wide") {
-        h->wide_on = value != 0;
-    } else if (k == "pcdw_groups") {
-        if (value < 1) {
-            h->err = "pcdw_groups must be >= 1";
-            return SPFM_ERR_INVALID;
-        }
-        h->pcdw_G = value;
-        h->wide_ready = false;
-    } else if (k == "pbcd_persistent") {
-        h->pb_persistent = value != 0;
-    } else if (k == "peer_exchange") {
-        // 0: give the in-kernel cross-GPU exchange up (a rank could not map its peers): the
-        // passes fall back to the per-step collective.  (1 is set by spfm_peer_connect only.)
-        if (value != 0) {
-            h->err = "peer_exchange: only 0 can be set; connect with spfm_peer_connect";
-            return SPFM_ERR_INVALID;
-        }
-        h->peer_ready = false;
-        h->have_schedule = false;
-        h->prb_ready = false;
-        h->pb_stream_ready = false;
-        h->wide_ready = false;
-    } else if (k == "probe_xcd") {
-        h->probe_xcd = (int)value;
-    } else if (k == "probe_lds") {
-        h->probe_lds = (int)value;
-    } else if (k == "pbprb_dbg") {
-        h->pb_dbg = value;
-    } else if (k == "wide_min_cols") {
-        h->wide_min_cols = value;
-    } else if (k == "pcdw_stamps") {
-        h->wide_stamp_on = value != 0;
-    } else if (k == "pbprb_stamps") {
-        h->pb_stamp_on = value != 0;
-    } else if (k == "pbprb_balance") {  // balanced slot groups of the persistent pbcd pass
-        h->pb_balance = value != 0;
-        h->pb_stream_ready = false;
-    } else if (k == "pbprb_owners") {
-        // round 3's dedicated owner workgroups: measured, no gain, removed in round 4 (their
-        // pacing rule does not survive the early publish of the partial vectors)
-        if (value != 0) {
-            h->err = "pbprb_owners: dedicated owner workgroups were removed (only 0 is accepted)";
-            return SPFM_ERR_UNSUPPORTED;
-        }
-    } else if (k == "pbprb_groups") {
-        if (value < 1) {
-            h->err = "pbprb_groups must be >= 1";
-            return SPFM_ERR_INVALID;
-        }
-        h->pbprb_G = value;
-        h->pb_stream_ready = false;
-        h->pbr_state = 0;
-    } else if (k == "prb_lds") {
-        h->prb_lds = value != 0;
-    } else if (k == "wide_lds_rows") {  // wide pass, block too large for LDS: rows of it kept there
-        h->wide_lds_cap = value;
-    } else if (k == "wide_ep") {  // wide pass, rows in global memory: entry-parallel form (default)
-        h->wide_ep = value != 0;
-    } else if (k == "wide_rec8") {  // ... with 8-byte (A, residual) records where they apply
-        h->wide_rec8 = value != 0;
-    } else if (k == "prb_groups") {
-        if (value < 1) {
-            h->err = "prb_groups must be >= 1";
-            return SPFM_ERR_INVALID;
-        }
-        h->prb_G = value;
-        h->prb_ready = false;
-        h->relax_state = 0;
-    } else if (k == "max_batch") {
-        if (value < 1) {
-            h->err = "max_batch must be >= 1";
-            return SPFM_ERR_INVALID;
-        }
-        h->max_batch_opt = value;
-    } else {
-        h->err = "unknown option: " + k;
-        return SPFM_ERR_INVALID;
-    }
-    h->clear_graphs();
-    return SPFM_OK;
-}
-
-int spfm_get_option(spfm_handle h, const char* key, int* value) {
-    if (!h || !key || !value) return SPFM_ERR_INVALID;
-    const std::string k(key);
-    if (k == "use_graph") *value = h->use_graph;
-    else if (k == "fuse_chain") *value = h->fuse_chain;
-    else if (k == "max_batch") *value = h->max_batch_opt;
-    else if (k == "persistent") *value = h->persistent;
-    else if (k == "prb_groups") *value = h->prb_G;
-    else if (k == "prb_lds") *value = h->prb_lds;
-    else if (k == "psgd_redone") *value = h->psgd_redone;
-    else if (k == "prb_lds_active") *value = h->prb_lds_active;
-    else if (k == "pbcd_persistent") *value = h->pb_persistent;
-    else if (k == "wide") *value = h->wide_on;
-    else if (k == "wide_active") *value = h->have_schedule && h->wide_usable();
-    else if (k == "wide_lds_active") *value = h->wide_lr_active;
-    else if (k == "wide_lds_rows") *value = h->wide_lds_cap;
-    else if (k == "wide_ep") *value = h->wide_ep;
-    else if (k == "wide_rec8") *value = h->wide_rec8;
-    else if (k == "wide_ep_active") *value = h->wide_ep_active;
-    else if (k == "pbprb_groups") *value = h->pbprb_G;
-    else if (k == "pcdw_groups") *value = h->wide_ready ? h->wide_G : h->pcdw_G;  // 0 = not chosen yet
-    else if (k == "pbprb_owners") *value = 0;
-    else if (k == "pbprb_active") *value = h->pbprb_active;
-    else if (k == "persistent_active")
-        *value = h->have_schedule && (h->prb_usable() || h->wide_usable());
-    else if (k == "relax") *value = h->relax_on;
-    else if (k == "ingest_device") *value = h->ingest_device;
-    else if (k == "colour_device") *value = h->colour_device;
-    else if (k == "colour_device_used") *value = h->colour_device_used;
-    else if (k == "stream_device") *value = h->stream_device;
-    else if (k == "stream_device_used") *value = h->stream_device_used;
-    else if (k == "pb_stream_device_used") *value = h->pb_stream_device_used;
-    else if (k == "wide_stream_device_used") *value = h->wide_stream_device_used;
-    else if (k == "co_tenants") *value = h->co_tenants;
-    else if (k == "ingest_device_used") *value = h->ingest_device_used;
-    else if (k == "prb_pack_active") *value = h->prb_pack_active;
-    else if (k == "relax_steps")
-        *value = h->relax_state == 1 ? (int)h->r_batch_ptr.size() - 1
-                                     : (h->pbr_state == 1 ? (int)h->pbr_batch_ptr.size() - 1 : 0);
-    else if (k == "pb_relax_active") *value = h->pb_relax_active;
-    else if (k == "persistent_fallbacks") *value = h->pers_fallbacks;
-    else if (k == "persistent_failed") *value = h->pers_failed;
-    else if (k == "n_ranks") *value = h->dist() ? h->n_ranks : 1;
-    else if (k == "peer_ready") *value = h->peer_ready;
-    else if (k == "wide_min_cols") *value = h->wide_min_cols;
-    else if (k == "interaction_tile_budget") *value = h->int_tile_budget;
-    else if (k == "interaction_features") *value = h->int_dlim;
-    else if (k == "interaction_launches") *value = h->int_launches;
-    else if (k == "interaction_scratch_kib")
-        *value = (int)((h->interaction_scratch_bytes() + 1023) / 1024);
-    else if (k == "free_mem_mib") {  // hipMemGetInfo of the handle's device
-        size_t fr = 0, tot = 0;
-        if (hipSetDevice(h->device) != hipSuccess || hipMemGetInfo(&fr, &tot) != hipSuccess) {
-            h->err = "hipMemGetInfo failed";
-            return SPFM_ERR_RUNTIME;
-        }
-        *value = (int)(fr >> 20);
-    } else {
-        h->err = "unknown option: " + k;
-        return SPFM_ERR_INVALID;
-    }
-    return SPFM_OK;
-}
+#include "spfm_options.inc.h"  // spfm_set_option, spfm_get_option and their table
 
 int spfm_debug_prb_stamps(spfm_handle h, long long* out, int cap) {
     GUARD(h);
