@@ -3,7 +3,9 @@
 // parameters, schedule, predict, communicators, recovery, C ABI; pcd: multi-kernel pcd /
 // cd_linear and the epoch drivers; prb: persistent 64-column passes, one translation unit per
 // storage type; wide: wide persistent passes; pbcd: multi-kernel pbcd; pbprb: persistent pbcd
-// pass, one unit per storage type; psgd).  See DESIGN.md for the execution model.
+// pass, one unit per storage type; psgd; gram, objective, interactions: the read-only feature
+// units).  Every unit owns the extern "C" block of its entries.  See DESIGN.md for the execution
+// model.
 #pragma once
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -156,6 +158,27 @@ struct DevBuf {
         err = (msg);    \
         return (code);  \
     } while (0)
+
+// propagate the status of an engine call
+#define SPFM_TRY(call)       \
+    do {                     \
+        int _rc = (call);    \
+        if (_rc) return _rc; \
+    } while (0)
+
+// first lines of every extern "C" entry that touches the device
+#define SPFM_GUARD(h)                              \
+    if (!(h)) return SPFM_ERR_INVALID;             \
+    if (hipSetDevice((h)->device) != hipSuccess) { \
+        (h)->err = "hipSetDevice failed";          \
+        return SPFM_ERR_RUNTIME;                   \
+    }
+
+// The one place that maps a handle's storage type to a C++ type: runs the statement with
+// T = float or double, e.g. SPFM_DISPATCH(dtype, return init_pred_t<T>(degree, lin, lower)).
+#define SPFM_DISPATCH(dt, ...)                                    \
+    ((dt) == SPFM_F32 ? [&] { using T = float; __VA_ARGS__; }()   \
+                      : [&] { using T = double; __VA_ARGS__; }())
 
 static inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
@@ -406,6 +429,82 @@ struct spfm_engine {
     int sync() {
         HIPC(hipStreamSynchronize(stream));
         return SPFM_OK;
+    }
+
+    // ---------------------------------------------------------------- typed copies
+    // `count` elements of the host pointer's type, asynchronous on `stream`.  Nothing is issued
+    // for a count of 0 and nothing waits: host memory stays alive until the caller's next sync().
+    template <typename U>
+    int upload_to(void* dst, const U* src, size_t count) {  // into device memory that exists
+        if (count) HIPC(hipMemcpyAsync(dst, src, sizeof(U) * count, hipMemcpyHostToDevice, stream));
+        return SPFM_OK;
+    }
+    // (re)allocates `b` for max(count, min_count) elements first (DevBuf::alloc: detaches when shared)
+    template <typename U>
+    int upload(DevBuf& b, const U* src, size_t count, size_t min_count = 0) {
+        HIPC(b.alloc(sizeof(U) * std::max(count, min_count)));
+        return upload_to(b.p, src, count);
+    }
+    template <typename U>
+    int download(U* dst, const void* src, size_t count) {
+        if (count) HIPC(hipMemcpyAsync(dst, src, sizeof(U) * count, hipMemcpyDeviceToHost, stream));
+        return SPFM_OK;
+    }
+
+    // Rows [r0, r1) of a host CSR matrix into (rp, ri, rv), the values as T (the whole matrix:
+    // r0 = 0).  indptr goes up unshifted: a kernel that is given a block r0 > 0 gets the entry
+    // base indptr[r0] separately.  The entry buffers hold at least `min_entries` elements.  `hv`
+    // is the conversion's staging and stays alive until the caller's next sync().
+    template <typename T>
+    int stage_csr_rows(DevBuf& rp, DevBuf& ri, DevBuf& rv, std::vector<T>& hv,
+                       const int64_t* indptr, const int32_t* indices, const double* data,
+                       int64_t r0, int64_t r1, size_t min_entries = 0) {
+        // (whole matrix: entries from position 0 whatever indptr[0] says -- predict_csr does
+        // not ask for indptr[0] == 0 and its kernels index by indptr as given)
+        const int64_t e0 = r0 ? indptr[r0] : 0, ne = indptr[r1] - e0;
+        const T* vals;
+        if constexpr (std::is_same<T, double>::value) {
+            vals = data + e0;
+        } else {
+            hv.resize((size_t)ne);
+            const int nt = (ne >= (1 << 20)) ? schedule_threads() : 1;
+            const int64_t per = (ne + nt - 1) / nt;
+            auto work = [&](int tid) {
+                const int64_t lo = per * tid, hi = std::min<int64_t>(ne, lo + per);
+                for (int64_t ii = lo; ii < hi; ++ii) hv[(size_t)ii] = (T)data[e0 + ii];
+            };
+            std::vector<std::thread> pool;
+            for (int t = 1; t < nt; ++t) pool.emplace_back(work, t);
+            work(0);
+            for (auto& th : pool) th.join();
+            vals = hv.data();
+        }
+        SPFM_TRY(upload(rp, indptr + r0, (size_t)(r1 - r0 + 1)));
+        SPFM_TRY(upload(ri, indices + e0, (size_t)ne, min_entries));
+        return upload(rv, vals, (size_t)ne, min_entries);
+    }
+
+    // the pairs (0, y_i) -- prediction and target of row i side by side -- into `yy`, which the
+    // caller has allocated; `hy` stays alive until the caller's next sync()
+    template <typename T>
+    int upload_targets(const double* y, std::vector<T>& hy) {
+        hy.resize((size_t)n * 2);
+        for (int64_t i = 0; i < n; ++i) {
+            hy[(size_t)2 * i] = (T)0;
+            hy[(size_t)2 * i + 1] = (T)y[i];
+        }
+        return upload_to(yy.p, hy.data(), hy.size());
+    }
+
+    // Block `order_idx` of the live parameter image as element strides (component, feature):
+    // (k,d) after pcd epochs and spfm_set_params, (d,k) after pbcd / psgd.
+    struct BlockView {
+        const double* base;
+        int64_t ss, sj;
+    };
+    BlockView live_block(int order_idx) const {
+        const double* img = p_valid ? P.as<double>() : Pt.as<double>();
+        return {img + (size_t)order_idx * k * d, p_valid ? (int64_t)d : 1, p_valid ? 1 : (int64_t)k};
     }
 
     // ---------------------------------------------------------------- profiling
@@ -882,8 +981,7 @@ struct spfm_engine {
                int_cnt.bytes + int_keys.bytes + int_vals.bytes + int_keys2.bytes +
                int_vals2.bytes + int_io.bytes + int_out.bytes;
     }
-    int interaction_view(const char* what, int order_idx, const double** base, int64_t* ss,
-                         int64_t* sj);
+    int interaction_view(const char* what, int order_idx, BlockView* v);
     int interaction_prepare(const char* what, int order_idx);
     IntArgs interaction_args();
     template <int MODE>

@@ -1,5 +1,5 @@
 // spfm_engine_core.hip -- host engine: data images, parameters, schedule, predict, communicators,
-// residency / recovery of the persistent passes, and the C ABI (include/spfm.h).
+// residency / recovery of the persistent passes, and their part of the C ABI (include/spfm.h).
 #include "spfm_engine.hip.h"
 #include "spfm_linear.hip.h"   // col_norm_kernel
 #include "spfm_predict.hip.h"
@@ -109,8 +109,7 @@ int spfm_engine::allreduce_shm(double* buf, size_t count) {
 
 int spfm_engine::allreduce_shm_piece(double* buf, size_t count) {
     shm_host.resize(count);
-    HIPC(hipMemcpyAsync(shm_host.data(), buf, sizeof(double) * count, hipMemcpyDeviceToHost,
-                        stream));
+    SPFM_TRY(download(shm_host.data(), buf, count));
     HIPC(hipStreamSynchronize(stream));
     std::memcpy(shm.slots + (size_t)rank * ShmComm::kMaxDoubles, shm_host.data(),
                 sizeof(double) * count);
@@ -123,8 +122,7 @@ int spfm_engine::allreduce_shm_piece(double* buf, size_t count) {
     }
     rc = shm_barrier();  // nobody overwrites a slot before everyone has read it
     if (rc) return rc;
-    HIPC(hipMemcpyAsync(buf, shm_host.data(), sizeof(double) * count, hipMemcpyHostToDevice,
-                        stream));
+    SPFM_TRY(upload_to(buf, shm_host.data(), count));
     HIPC(hipStreamSynchronize(stream));
     return SPFM_OK;
 }
@@ -202,33 +200,16 @@ int spfm_engine::upload_images(const int64_t* h_cp, const int32_t* h_ci, const i
         work(0);
         for (auto& th : pool) th.join();
     }
-    std::vector<T> hy((size_t)n * 2);
-    for (int64_t i = 0; i < n; ++i) {
-        hy[(size_t)2 * i] = (T)0;
-        hy[(size_t)2 * i + 1] = (T)y[i];
-    }
-    HIPC(cptr.alloc(sizeof(int64_t) * ((size_t)d + 1)));
-    HIPC(cidx.alloc(sizeof(int32_t) * (size_t)nnz));
-    HIPC(cval.alloc(sizeof(T) * (size_t)nnz));
-    HIPC(rptr.alloc(sizeof(int64_t) * ((size_t)n + 1)));
-    HIPC(ridx.alloc(sizeof(int32_t) * (size_t)nnz));
-    HIPC(rval.alloc(sizeof(T) * (size_t)nnz));
+    std::vector<T> hy;
+    SPFM_TRY(upload(cptr, h_cp, (size_t)d + 1));
+    SPFM_TRY(upload(cidx, h_ci, (size_t)nnz));
+    SPFM_TRY(upload(cval, cv.data(), (size_t)nnz));
+    SPFM_TRY(upload(rptr, h_rp, (size_t)n + 1));
+    SPFM_TRY(upload(ridx, h_ri, (size_t)nnz));
+    SPFM_TRY(upload(rval, rv.data(), (size_t)nnz));
     HIPC(yy.alloc(sizeof(T) * 2 * (size_t)n));
+    SPFM_TRY(upload_targets(y, hy));
     HIPC(col_norm.alloc(sizeof(double) * (size_t)d));
-    HIPC(hipMemcpyAsync(cptr.p, h_cp, sizeof(int64_t) * ((size_t)d + 1), hipMemcpyHostToDevice,
-                        stream));
-    HIPC(hipMemcpyAsync(cidx.p, h_ci, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice,
-                        stream));
-    HIPC(hipMemcpyAsync(cval.p, cv.data(), sizeof(T) * (size_t)nnz, hipMemcpyHostToDevice,
-                        stream));
-    HIPC(hipMemcpyAsync(rptr.p, h_rp, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice,
-                        stream));
-    HIPC(hipMemcpyAsync(ridx.p, h_ri, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice,
-                        stream));
-    HIPC(hipMemcpyAsync(rval.p, rv.data(), sizeof(T) * (size_t)nnz, hipMemcpyHostToDevice,
-                        stream));
-    HIPC(hipMemcpyAsync(yy.p, hy.data(), sizeof(T) * 2 * (size_t)n, hipMemcpyHostToDevice,
-                        stream));
     hipLaunchKernelGGL((col_norm_kernel<T>), dim3(cdiv((int64_t)d * 64, kBlock)),
                        dim3(kBlock), 0, stream, d, cptr.as<int64_t>(), cval.as<T>(),
                        col_norm.as<double>());
@@ -270,44 +251,15 @@ int spfm_engine::data_installed(const double* y) {
 template <typename T>
 int spfm_engine::set_data_csr_device(const int64_t* indptr, const int32_t* indices, const double* data,
                         const double* y) {
-    std::vector<T> rv((size_t)(nnz > 0 ? nnz : 1));
-    const int T_ = (nnz >= (1 << 20)) ? schedule_threads() : 1;
-    {
-        std::vector<std::thread> pool;
-        auto work = [&](int tid) {
-            const int64_t per = (nnz + T_ - 1) / T_;
-            const int64_t lo = per * tid, hi = std::min<int64_t>(nnz, lo + per);
-            for (int64_t ii = lo; ii < hi; ++ii) rv[(size_t)ii] = (T)data[ii];
-        };
-        for (int t = 1; t < T_; ++t) pool.emplace_back(work, t);
-        work(0);
-        for (auto& th : pool) th.join();
-    }
-    std::vector<T> hy((size_t)n * 2 + 2);
-    for (int64_t i = 0; i < n; ++i) {
-        hy[(size_t)2 * i] = (T)0;
-        hy[(size_t)2 * i + 1] = (T)y[i];
-    }
+    std::vector<T> rv, hy;
     const size_t nz = (size_t)(nnz > 0 ? nnz : 1);
     HIPC(cptr.alloc(sizeof(int64_t) * ((size_t)d + 1)));
     HIPC(cidx.alloc(sizeof(int32_t) * nz));
     HIPC(cval.alloc(sizeof(T) * nz));
-    HIPC(rptr.alloc(sizeof(int64_t) * ((size_t)n + 1)));
-    HIPC(ridx.alloc(sizeof(int32_t) * nz));
-    HIPC(rval.alloc(sizeof(T) * nz));
+    SPFM_TRY(stage_csr_rows(rptr, ridx, rval, rv, indptr, indices, data, 0, n, 1));
     HIPC(yy.alloc(sizeof(T) * 2 * (size_t)(n > 0 ? n : 1)));
+    SPFM_TRY(upload_targets(y, hy));
     HIPC(col_norm.alloc(sizeof(double) * (size_t)d));
-    HIPC(hipMemcpyAsync(rptr.p, indptr, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice,
-                        stream));
-    if (nnz > 0) {
-        HIPC(hipMemcpyAsync(ridx.p, indices, sizeof(int32_t) * (size_t)nnz,
-                            hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync(rval.p, rv.data(), sizeof(T) * (size_t)nnz, hipMemcpyHostToDevice,
-                            stream));
-    }
-    if (n > 0)
-        HIPC(hipMemcpyAsync(yy.p, hy.data(), sizeof(T) * 2 * (size_t)n, hipMemcpyHostToDevice,
-                            stream));
     HIPC(hipStreamSynchronize(stream));
     int invalid = 0;
     hipError_t e = device_csr_to_csc<T>(n, d, nnz, rptr.as<int64_t>(), ridx.as<int32_t>(),
@@ -322,11 +274,8 @@ int spfm_engine::set_data_csr_device(const int64_t* indptr, const int32_t* indic
              "set_data: CSR must have sorted, duplicate-free column indices in [0, d)");
     h_cptr.resize((size_t)d + 1);
     h_cidx.resize((size_t)nnz);
-    HIPC(hipMemcpyAsync(h_cptr.data(), cptr.p, sizeof(int64_t) * ((size_t)d + 1),
-                        hipMemcpyDeviceToHost, stream));
-    if (nnz > 0)
-        HIPC(hipMemcpyAsync(h_cidx.data(), cidx.p, sizeof(int32_t) * (size_t)nnz,
-                            hipMemcpyDeviceToHost, stream));
+    SPFM_TRY(download(h_cptr.data(), cptr.p, (size_t)d + 1));
+    SPFM_TRY(download(h_cidx.data(), cidx.p, (size_t)nnz));
     hipLaunchKernelGGL((col_norm_kernel<T>), dim3(cdiv((int64_t)d * 64, kBlock)), dim3(kBlock), 0,
                        stream, d, cptr.as<int64_t>(), cval.as<T>(), col_norm.as<double>());
     HIPC(hipGetLastError());
@@ -350,8 +299,7 @@ int spfm_engine::set_data_csr(int64_t n_, int32_t d_, const int64_t* indptr, con
         n = n_;
         d = d_;
         nnz = indptr[n_];
-        int rc = dtype == SPFM_F32 ? set_data_csr_device<float>(indptr, indices, data, y)
-                                   : set_data_csr_device<double>(indptr, indices, data, y);
+        int rc = SPFM_DISPATCH(dtype, return set_data_csr_device<T>(indptr, indices, data, y));
         if (rc == SPFM_OK) {
             ingest_device_used = 1;
             return data_installed(y);
@@ -372,12 +320,8 @@ int spfm_engine::set_data_csr(int64_t n_, int32_t d_, const int64_t* indptr, con
     nnz = indptr[n_];
     h_cptr.swap(cp);
     h_cidx.swap(ci);
-    int rc = (dtype == SPFM_F32)
-                 ? upload_images<float>(h_cptr.data(), h_cidx.data(), indptr, indices, nullptr,
-                                        data, perm.data(), y)
-                 : upload_images<double>(h_cptr.data(), h_cidx.data(), indptr, indices, nullptr,
-                                         data, perm.data(), y);
-    if (rc) return rc;
+    SPFM_TRY(SPFM_DISPATCH(dtype, return upload_images<T>(h_cptr.data(), h_cidx.data(), indptr,
+                                                          indices, nullptr, data, perm.data(), y)));
     return data_installed(y);
 }
 
@@ -405,9 +349,7 @@ int spfm_engine::set_data(int64_t n_, int32_t d_, const int64_t* indptr, const i
     nnz = nz;
     h_cptr.assign(indptr, indptr + d + 1);
     h_cidx.assign(indices, indices + nnz);
-    int rc = (dtype == SPFM_F32) ? set_data_t<float>(indptr, indices, data, y)
-                                 : set_data_t<double>(indptr, indices, data, y);
-    if (rc) return rc;
+    SPFM_TRY(SPFM_DISPATCH(dtype, return set_data_t<T>(indptr, indices, data, y)));
     return data_installed(y);
 }
 
@@ -439,34 +381,14 @@ int spfm_engine::share_data_from(spfm_engine* src, const double* y_) {
     ingest_device_used = src->ingest_device_used;
     HIPC(yy.alloc(tsize() * 2 * (size_t)(n > 0 ? n : 1)));
     if (y_ && n > 0) {
-        if (dtype == SPFM_F32) {
-            std::vector<float> hy((size_t)n * 2);
-            for (int64_t i = 0; i < n; ++i) {
-                hy[(size_t)2 * i] = 0.f;
-                hy[(size_t)2 * i + 1] = (float)y_[i];
-            }
-            HIPC(hipMemcpyAsync(yy.p, hy.data(), sizeof(float) * 2 * (size_t)n,
-                                hipMemcpyHostToDevice, stream));
-            HIPC(hipStreamSynchronize(stream));
-        } else {
-            std::vector<double> hy((size_t)n * 2);
-            for (int64_t i = 0; i < n; ++i) {
-                hy[(size_t)2 * i] = 0.0;
-                hy[(size_t)2 * i + 1] = y_[i];
-            }
-            HIPC(hipMemcpyAsync(yy.p, hy.data(), sizeof(double) * 2 * (size_t)n,
-                                hipMemcpyHostToDevice, stream));
-            HIPC(hipStreamSynchronize(stream));
-        }
+        SPFM_TRY(SPFM_DISPATCH(dtype, std::vector<T> hy; SPFM_TRY(upload_targets(y_, hy));
+                               return sync()));
     } else if (n > 0) {
         // the source's targets; its stream may still be writing predictions next to them
         HIPC(hipStreamSynchronize(src->stream));
-        if (dtype == SPFM_F32)
-            hipLaunchKernelGGL((copy_targets_kernel<float>), dim3(cdiv(n, 256)), dim3(256), 0, stream,
-                               n, src->yy.as<float>(), yy.as<float>());
-        else
-            hipLaunchKernelGGL((copy_targets_kernel<double>), dim3(cdiv(n, 256)), dim3(256), 0,
-                               stream, n, src->yy.as<double>(), yy.as<double>());
+        SPFM_DISPATCH(dtype, hipLaunchKernelGGL((copy_targets_kernel<T>), dim3(cdiv(n, 256)),
+                                                dim3(256), 0, stream, n, src->yy.as<T>(),
+                                                yy.as<T>()));
         HIPC(hipGetLastError());
         HIPC(hipStreamSynchronize(stream));
         y_pm1 = src->y_pm1;
@@ -497,14 +419,9 @@ int spfm_engine::set_params(int n_orders_, int k_, int32_t d_, const double* P_,
     n_orders = n_orders_;
     k = k_;
     h_lams.assign(lams_, lams_ + k);
-    HIPC(P.alloc(sizeof(double) * (size_t)n_orders * k * d));
-    HIPC(w.alloc(sizeof(double) * (size_t)d));
-    HIPC(lams.alloc(sizeof(double) * (size_t)k));
-    HIPC(hipMemcpyAsync(P.p, P_, sizeof(double) * (size_t)n_orders * k * d,
-                        hipMemcpyHostToDevice, stream));
-    HIPC(hipMemcpyAsync(w.p, w_, sizeof(double) * (size_t)d, hipMemcpyHostToDevice, stream));
-    HIPC(hipMemcpyAsync(lams.p, lams_, sizeof(double) * (size_t)k, hipMemcpyHostToDevice,
-                        stream));
+    SPFM_TRY(upload(P, P_, (size_t)n_orders * k * d));
+    SPFM_TRY(upload(w, w_, (size_t)d));
+    SPFM_TRY(upload(lams, lams_, (size_t)k));
     HIPC(hipStreamSynchronize(stream));
     p_valid = true;
     pt_valid = false;
@@ -514,14 +431,9 @@ int spfm_engine::set_params(int n_orders_, int k_, int32_t d_, const double* P_,
 
 int spfm_engine::get_params(double* P_, double* w_) {
     if (!have_params) FAIL(SPFM_ERR_INVALID, "get_params: no parameters set");
-    int rc = ensure_p();
-    if (rc) return rc;
-    if (P_)
-        HIPC(hipMemcpyAsync(P_, P.p, sizeof(double) * (size_t)n_orders * k * d,
-                            hipMemcpyDeviceToHost, stream));
-    if (w_)
-        HIPC(hipMemcpyAsync(w_, w.p, sizeof(double) * (size_t)d, hipMemcpyDeviceToHost,
-                            stream));
+    SPFM_TRY(ensure_p());
+    if (P_) SPFM_TRY(download(P_, P.p, (size_t)n_orders * k * d));
+    if (w_) SPFM_TRY(download(w_, w.p, (size_t)d));
     HIPC(hipStreamSynchronize(stream));
     return SPFM_OK;
 }
@@ -570,12 +482,11 @@ int spfm_engine::configure(int solver_, int loss_, int reg_, int top_degree_) {
     const size_t ncache = kMaxDegree + 2;
     HIPC(norms.alloc(sizeof(double) * (size_t)d));
     HIPC(cache.alloc(sizeof(double) * ncache * 2));  // pcd: double-buffered per batch
-    HIPC(dcache.alloc(sizeof(double) * ncache));
     HIPC(hipMemsetAsync(norms.p, 0, sizeof(double) * (size_t)d, stream));
     HIPC(hipMemsetAsync(cache.p, 0, sizeof(double) * ncache * 2, stream));
     double hd[kMaxDegree + 2] = {0};
     hd[1] = 1.0;  // omegacs.py:46 ; omegati sets it in compute_cache_pcd
-    HIPC(hipMemcpyAsync(dcache.p, hd, sizeof(double) * ncache, hipMemcpyHostToDevice, stream));
+    SPFM_TRY(upload(dcache, hd, ncache));
     // pcd keeps the caches of ALL components (one precompute pass per epoch): same
     // footprint as pbcd's (n, (m-1), k) tensor
     const size_t arow = (size_t)(top_degree > 0 ? top_degree - 1 : 1) * k;
@@ -714,16 +625,9 @@ int spfm_engine::install_schedule() {
         hdesc[(size_t)q].len = (int32_t)(h_cptr[(size_t)j + 1] - h_cptr[(size_t)j]);
         hdesc[(size_t)q].j = j;
     }
-    HIPC(d_order.alloc(sizeof(int32_t) * (size_t)d));
-    HIPC(d_desc.alloc(sizeof(ColDesc) * (size_t)d));
-    HIPC(hipMemcpyAsync(d_order.p, order.data(), sizeof(int32_t) * (size_t)d,
-                        hipMemcpyHostToDevice, stream));
-    HIPC(hipMemcpyAsync(d_desc.p, hdesc.data(), sizeof(ColDesc) * (size_t)d,
-                        hipMemcpyHostToDevice, stream));
-    std::vector<int32_t> hb(batch_ptr.begin(), batch_ptr.end());
-    HIPC(d_bptr.alloc(sizeof(int32_t) * hb.size()));
-    HIPC(hipMemcpyAsync(d_bptr.p, hb.data(), sizeof(int32_t) * hb.size(),
-                        hipMemcpyHostToDevice, stream));
+    SPFM_TRY(upload(d_order, order.data(), (size_t)d));
+    SPFM_TRY(upload(d_desc, hdesc.data(), (size_t)d));
+    SPFM_TRY(upload(d_bptr, batch_ptr.data(), batch_ptr.size()));
     HIPC(hipStreamSynchronize(stream));
     {   // FNV-1a over (order, batch_ptr): the schedule's name in a shared stream cache
         uint64_t hsh = 1469598103934665603ull;
@@ -839,6 +743,13 @@ int spfm_engine::output_pt_t(int64_t rows, const int64_t* rp, const int32_t* ri,
     return SPFM_OK;
 }
 
+// The definition above lives in this unit; spfm_eval_loss (spfm_engine_objective.hip) calls it
+// from another one, so the linker needs both storage types emitted here.
+template int spfm_engine::output_pt_t<float>(int64_t, const int64_t*, const int32_t*, const float*,
+                                             int, int, int, const double*, double*);
+template int spfm_engine::output_pt_t<double>(int64_t, const int64_t*, const int32_t*,
+                                              const double*, int, int, int, const double*, double*);
+
 template <typename T>
 int spfm_engine::init_pred_t(int degree, int fit_linear, int add_lower) {
     int rc = output_t<T>(n, rptr.as<int64_t>(), ridx.as<int32_t>(), rval.as<T>(), degree,
@@ -858,8 +769,7 @@ int spfm_engine::init_pred(int degree, int fit_linear, int add_lower) {
     pa_degree = degree;
     pa_lin = fit_linear;
     pa_lower = add_lower;
-    return dtype == SPFM_F32 ? init_pred_t<float>(degree, fit_linear, add_lower)
-                             : init_pred_t<double>(degree, fit_linear, add_lower);
+    return SPFM_DISPATCH(dtype, return init_pred_t<T>(degree, fit_linear, add_lower));
 }
 
 template <typename T>
@@ -868,8 +778,7 @@ int spfm_engine::get_y_pred_t(double* out) {
     hipLaunchKernelGGL((load_pred_kernel<T>), dim3(cdiv(n, 256)), dim3(256), 0, stream, n,
                        yy.as<T>(), pred_tmp.as<double>());
     HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(out, pred_tmp.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost,
-                        stream));
+    SPFM_TRY(download(out, pred_tmp.p, (size_t)n));
     return sync();
 }
 
@@ -883,7 +792,7 @@ int spfm_engine::loss_sum_t(double* out) {
     HIPC(hipGetLastError());
     int rc = allreduce(scalar.as<double>(), 1);
     if (rc) return rc;
-    HIPC(hipMemcpyAsync(h_scalar, scalar.p, sizeof(double), hipMemcpyDeviceToHost, stream));
+    SPFM_TRY(download(h_scalar, scalar.p, 1));
     rc = sync();
     if (rc) return rc;
     *out = h_scalar[0];
@@ -899,24 +808,13 @@ int spfm_engine::predict_csr_t(int64_t rows, const int64_t* indptr, const int32_
     for (int64_t ii = 0; ii < nz; ++ii)
         if (indices[ii] < 0 || indices[ii] >= d)
             FAIL(SPFM_ERR_INVALID, "predict: column index out of range");
-    std::vector<T> hv((size_t)nz);
-    for (int64_t ii = 0; ii < nz; ++ii) hv[(size_t)ii] = (T)data[ii];
+    std::vector<T> hv;
     DevBuf rp, ri, rv, o;
-    HIPC(rp.alloc(sizeof(int64_t) * ((size_t)rows + 1)));
-    HIPC(ri.alloc(sizeof(int32_t) * (size_t)nz));
-    HIPC(rv.alloc(sizeof(T) * (size_t)nz));
+    SPFM_TRY(stage_csr_rows(rp, ri, rv, hv, indptr, indices, data, 0, rows));
     HIPC(o.alloc(sizeof(double) * (size_t)rows));
-    HIPC(hipMemcpyAsync(rp.p, indptr, sizeof(int64_t) * ((size_t)rows + 1),
-                        hipMemcpyHostToDevice, stream));
-    HIPC(hipMemcpyAsync(ri.p, indices, sizeof(int32_t) * (size_t)nz, hipMemcpyHostToDevice,
-                        stream));
-    HIPC(hipMemcpyAsync(rv.p, hv.data(), sizeof(T) * (size_t)nz, hipMemcpyHostToDevice,
-                        stream));
-    int rc = output_t<T>(rows, rp.as<int64_t>(), ri.as<int32_t>(), rv.as<T>(), degree,
-                         fit_linear, add_lower, o.as<double>());
-    if (rc) return rc;
-    HIPC(hipMemcpyAsync(out, o.p, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost,
-                        stream));
+    SPFM_TRY(output_t<T>(rows, rp.as<int64_t>(), ri.as<int32_t>(), rv.as<T>(), degree, fit_linear,
+                         add_lower, o.as<double>()));
+    SPFM_TRY(download(out, o.p, (size_t)rows));
     return sync();
 }
 
@@ -935,7 +833,7 @@ int spfm_engine::epoch_epilogue(double* viol) {
     hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(kBlock), 0, stream,
                        viol_col.as<double>(), d, scalar.as<double>());
     HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(h_scalar, scalar.p, sizeof(double), hipMemcpyDeviceToHost, stream));
+    SPFM_TRY(download(h_scalar, scalar.p, 1));
     HIPC(hipStreamSynchronize(stream));
     prof_collect();
     if (viol) *viol = h_scalar[0];
@@ -976,12 +874,9 @@ bool spfm_engine::resident_ok(const void* fn, int threads, size_t lds, int G) {
     if (ag != resident_agreed.end()) return ag->second;
     double no = mine ? 0.0 : 1.0;
     bool agreed = mine;
-    if (scalar.p && hipMemcpyAsync(scalar.as<double>() + 7, &no, sizeof(double), hipMemcpyHostToDevice,
-                                   stream) == hipSuccess &&
-        hipStreamSynchronize(stream) == hipSuccess && allreduce(scalar.as<double>() + 7, 1) == SPFM_OK &&
-        hipMemcpyAsync(&no, scalar.as<double>() + 7, sizeof(double), hipMemcpyDeviceToHost, stream) ==
-            hipSuccess &&
-        hipStreamSynchronize(stream) == hipSuccess)
+    double* slot = scalar.as<double>() + 7;
+    if (scalar.p && upload_to(slot, &no, 1) == SPFM_OK && sync() == SPFM_OK &&
+        allreduce(slot, 1) == SPFM_OK && download(&no, slot, 1) == SPFM_OK && sync() == SPFM_OK)
         agreed = no == 0.0;
     resident_agreed[key] = agreed;
     return agreed;
@@ -1005,17 +900,15 @@ int spfm_engine::persistent_aborted(bool* out) {
     *out = false;
     if (!prb_abort.p) return SPFM_OK;
     unsigned flag = 0;
-    HIPC(hipMemcpyAsync(&flag, prb_abort.p, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    SPFM_TRY(download(&flag, prb_abort.p, 1));
     HIPC(hipStreamSynchronize(stream));
     double any = flag ? 1.0 : 0.0;
     if (dist()) {
-        HIPC(hipMemcpyAsync(scalar.as<double>() + 6, &any, sizeof(double),
-                            hipMemcpyHostToDevice, stream));
+        double* slot = scalar.as<double>() + 6;
+        SPFM_TRY(upload_to(slot, &any, 1));
         HIPC(hipStreamSynchronize(stream));
-        int rc = allreduce(scalar.as<double>() + 6, 1);
-        if (rc) return rc;
-        HIPC(hipMemcpyAsync(&any, scalar.as<double>() + 6, sizeof(double),
-                            hipMemcpyDeviceToHost, stream));
+        SPFM_TRY(allreduce(slot, 1));
+        SPFM_TRY(download(&any, slot, 1));
         HIPC(hipStreamSynchronize(stream));
     }
     if (flag) HIPC(hipMemsetAsync(prb_abort.p, 0, sizeof(unsigned) * 4, stream));
@@ -1069,13 +962,6 @@ int spfm_engine::host_barrier() {
 }
 
 // ======================================================================= C ABI
-#define GUARD(h)                  \
-    if (!(h)) return SPFM_ERR_INVALID; \
-    if (hipSetDevice((h)->device) != hipSuccess) { \
-        (h)->err = "hipSetDevice failed";          \
-        return SPFM_ERR_RUNTIME;                   \
-    }
-
 extern "C" {
 
 int spfm_create(spfm_handle* out, int device_id, int dtype) {
@@ -1135,100 +1021,74 @@ int spfm_device_name(spfm_handle h, char* out, int cap) {
 
 int spfm_set_data_csc(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
                       const int32_t* indices, const double* data, const double* y) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->set_data(n, d, indptr, indices, data, y);
 }
 
 int spfm_set_data_csr(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
                       const int32_t* indices, const double* data, const double* y) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->set_data_csr(n, d, indptr, indices, data, y);
 }
 
 int spfm_share_data(spfm_handle dst, spfm_handle src, const double* y) {
-    GUARD(dst);
+    SPFM_GUARD(dst);
     return dst->share_data_from(src, y);
 }
 
 int spfm_set_params(spfm_handle h, int n_orders, int k, int32_t d, const double* P,
                     const double* w, const double* lams) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->set_params(n_orders, k, d, P, w, lams);
 }
 
 int spfm_get_params(spfm_handle h, double* P, double* w) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->get_params(P, w);
 }
 
 int spfm_configure(spfm_handle h, int solver, int loss, int regularizer, int top_degree) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->configure(solver, loss, regularizer, top_degree);
 }
 
 int spfm_init_pred(spfm_handle h, int degree, int fit_linear, int add_lower_deg2) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->init_pred(degree, fit_linear, add_lower_deg2);
 }
 
 int spfm_get_y_pred(spfm_handle h, double* out) {
-    GUARD(h);
+    SPFM_GUARD(h);
     if (!h->have_data || !out) return SPFM_ERR_INVALID;
-    return h->dtype == SPFM_F32 ? h->get_y_pred_t<float>(out) : h->get_y_pred_t<double>(out);
+    return SPFM_DISPATCH(h->dtype, return h->get_y_pred_t<T>(out));
 }
 
 int spfm_loss_sum(spfm_handle h, double* out) {
-    GUARD(h);
+    SPFM_GUARD(h);
     if (!h->have_data || !h->configured || !out) {
         h->err = "loss_sum: data and configuration required";
         return SPFM_ERR_INVALID;
     }
-    return h->dtype == SPFM_F32 ? h->loss_sum_t<float>(out) : h->loss_sum_t<double>(out);
+    return SPFM_DISPATCH(h->dtype, return h->loss_sum_t<T>(out));
 }
 
 int spfm_predict_csr(spfm_handle h, int64_t n, const int64_t* indptr, const int32_t* indices,
                      const double* data, int degree, int fit_linear, int add_lower_deg2,
                      double* out) {
-    GUARD(h);
+    SPFM_GUARD(h);
     if (!h->have_params) {
         h->err = "predict: no parameters set";
         return SPFM_ERR_INVALID;
     }
     if (n < 0 || !indptr || !out) return SPFM_ERR_INVALID;
-    return h->dtype == SPFM_F32
-               ? h->predict_csr_t<float>(n, indptr, indices, data, degree, fit_linear,
-                                         add_lower_deg2, out)
-               : h->predict_csr_t<double>(n, indptr, indices, data, degree, fit_linear,
-                                          add_lower_deg2, out);
+    return SPFM_DISPATCH(h->dtype, return h->predict_csr_t<T>(n, indptr, indices, data, degree,
+                                                              fit_linear, add_lower_deg2, out));
 }
-
-int spfm_objective_terms(spfm_handle h, int order_idx, int degree, double* out8) {
-    GUARD(h);
-    return h->objective_terms(order_idx, degree, out8);
-}
-
-int spfm_set_eval_csr(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
-                      const int32_t* indices, const double* data, const double* y) {
-    GUARD(h);
-    return h->set_eval_csr(n, d, indptr, indices, data, y);
-}
-
-int spfm_eval_loss(spfm_handle h, int degree, int fit_linear, int add_lower_deg2,
-                   double* loss_sum, double* y_pred_out) {
-    GUARD(h);
-    return h->eval_loss(degree, fit_linear, add_lower_deg2, loss_sum, y_pred_out);
-}
-
-// used by the objective unit (spfm_eval_loss)
-template int spfm_engine::output_pt_t<float>(int64_t, const int64_t*, const int32_t*, const float*,
-                                             int, int, int, const double*, double*);
-template int spfm_engine::output_pt_t<double>(int64_t, const int64_t*, const int32_t*,
-                                              const double*, int, int, int, const double*, double*);
 
 int spfm_set_schedule(spfm_handle h, int mode, const int32_t* indices_feature,
                       const int64_t* conflict_indptr, const int32_t* conflict_indices,
                       int64_t conflict_n_rows, int32_t* order_out, int32_t* n_batches_out) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->set_schedule(mode, indices_feature, conflict_indptr, conflict_indices,
                            conflict_n_rows, order_out, n_batches_out);
 }
@@ -1236,7 +1096,7 @@ int spfm_set_schedule(spfm_handle h, int mode, const int32_t* indices_feature,
 int spfm_set_schedule_raw(spfm_handle h, const int32_t* order, const int32_t* batch_ptr,
                           int32_t n_batches, const int64_t* conflict_indptr,
                           const int32_t* conflict_indices, int64_t conflict_n_rows) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->set_schedule_raw(order, batch_ptr, n_batches, conflict_indptr, conflict_indices,
                                conflict_n_rows);
 }
@@ -1285,40 +1145,40 @@ int spfm_schedule_build(int mode, int64_t n_rows, int32_t d, const int64_t* indp
 }
 
 int spfm_cd_linear_epoch(spfm_handle h, double alpha, double* viol) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->cd_linear_epoch(alpha, viol);
 }
 
 int spfm_pcd_epoch(spfm_handle h, int order_idx, int degree, double beta, double gamma,
                    double eta, const int32_t* indices_component, int n_comp, double* viol) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->pcd_epoch(order_idx, degree, beta, gamma, eta, indices_component, n_comp, viol);
 }
 
 int spfm_pbcd_epoch(spfm_handle h, int order_idx, int degree, double beta, double gamma,
                     double eta, double* viol) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->pbcd_epoch(order_idx, degree, beta, gamma, eta, viol);
 }
 
 int spfm_host_epoch_begin(spfm_handle h, int order_idx, int degree) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->host_epoch_begin(order_idx, degree);
 }
 int spfm_host_pass_begin(spfm_handle h, int component) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->host_pass_begin(component);
 }
 int spfm_host_step_sums(spfm_handle h, int step, double* sums_out) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->host_step(true, step, sums_out, nullptr, nullptr);
 }
 int spfm_host_step_apply(spfm_handle h, int step, const double* p_new, const double* p_old) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->host_step(false, step, nullptr, p_new, p_old);
 }
 int spfm_host_epoch_end(spfm_handle h, double* viol) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->host_epoch_end(viol);
 }
 
@@ -1326,7 +1186,7 @@ int spfm_psgd_epoch(spfm_handle h, int degree, double alpha, double beta, double
                     double eta0, int learning_rate, double power_t, int64_t batch_size,
                     const int32_t* indices_samples, int64_t n_samples, int fit_linear,
                     int64_t* it, double* sum_loss) {
-    GUARD(h);
+    SPFM_GUARD(h);
     if (h->dist()) {
         h->err = "psgd: several ranks share this handle's communicator -- use spfm_psgd_epoch_sharded";
         return SPFM_ERR_INVALID;
@@ -1339,7 +1199,7 @@ int spfm_psgd_epoch_sharded(spfm_handle h, int degree, double alpha, double beta
                             double eta0, int learning_rate, double power_t, int64_t batch_size,
                             const int32_t* indices_samples, int64_t n_global, int64_t row_lo,
                             int fit_linear, int64_t* it, double* sum_loss) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->psgd_epoch(degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
                          indices_samples, n_global, row_lo, fit_linear, it, sum_loss);
 }
@@ -1361,7 +1221,7 @@ int spfm_comm_unique_id(char* id128) {
 }
 
 int spfm_comm_init(spfm_handle h, const char* id128, int n_ranks, int rank) {
-    GUARD(h);
+    SPFM_GUARD(h);
     if (!id128 || n_ranks < 1 || rank < 0 || rank >= n_ranks) return SPFM_ERR_INVALID;
     if (!g_rccl.load(h->err)) return SPFM_ERR_RUNTIME;
     ncclUniqueId_ id;
@@ -1399,7 +1259,7 @@ int spfm_comm_init(spfm_handle h, const char* id128, int n_ranks, int rank) {
 }
 
 int spfm_comm_init_shm(spfm_handle h, const char* shm_name, int n_ranks, int rank) {
-    GUARD(h);
+    SPFM_GUARD(h);
     if (!shm_name || n_ranks < 1 || n_ranks > 64 || rank < 0 || rank >= n_ranks)
         return SPFM_ERR_INVALID;
     if (h->comm || h->shm.hdr) {
@@ -1437,7 +1297,7 @@ int spfm_comm_init_shm(spfm_handle h, const char* shm_name, int n_ranks, int ran
 }
 
 int spfm_peer_alloc(spfm_handle h, char* handle64) {
-    GUARD(h);
+    SPFM_GUARD(h);
     if (!handle64) return SPFM_ERR_INVALID;
     if (!h->peer_own) {
         void* p = nullptr;
@@ -1474,7 +1334,7 @@ int spfm_peer_alloc(spfm_handle h, char* handle64) {
 }
 
 int spfm_peer_connect(spfm_handle h, int n_ranks, int rank, const char* handles) {
-    GUARD(h);
+    SPFM_GUARD(h);
     if (!handles || n_ranks < 2 || n_ranks > 8 || rank < 0 || rank >= n_ranks)
         return SPFM_ERR_INVALID;
     if (!h->peer_own) {
@@ -1507,13 +1367,8 @@ int spfm_peer_connect(spfm_handle h, int n_ranks, int rank, const char* handles)
         t1[(size_t)r] = reinterpret_cast<double*>(h->peer_ptr[(size_t)r]) + spfm_engine::kPeerPcdOff;
         t2[(size_t)r] = reinterpret_cast<double*>(h->peer_ptr[(size_t)r]) + spfm_engine::kPeerPbOff;
     }
-    if (h->peer_tab_pcd.alloc(sizeof(double*) * 8) != hipSuccess ||
-        h->peer_tab_pb.alloc(sizeof(double*) * 8) != hipSuccess ||
-        hipMemcpyAsync(h->peer_tab_pcd.p, t1.data(), sizeof(double*) * (size_t)n_ranks,
-                       hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-        hipMemcpyAsync(h->peer_tab_pb.p, t2.data(), sizeof(double*) * (size_t)n_ranks,
-                       hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess) {
+    if (h->upload(h->peer_tab_pcd, t1.data(), (size_t)n_ranks, 8) ||
+        h->upload(h->peer_tab_pb, t2.data(), (size_t)n_ranks, 8) || h->sync()) {
         h->err = "peer table upload failed";
         return SPFM_ERR_RUNTIME;
     }
@@ -1534,9 +1389,7 @@ int spfm_peer_connect(spfm_handle h, int n_ranks, int rank, const char* handles)
                            h->peer_tab_pcd.as<double*>(),
                            spfm_engine::kPeerProbeOff - spfm_engine::kPeerPcdOff, n_ranks, rank,
                            word, ticks, okb.as<int>());
-        if (hipMemcpyAsync(&ok, okb.p, sizeof(int), hipMemcpyDeviceToHost, h->stream) !=
-                hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess) {
+        if (h->download(&ok, okb.p, 1) || h->sync()) {
             h->err = "peer handshake kernel failed";
             return SPFM_ERR_RUNTIME;
         }
@@ -1580,7 +1433,7 @@ int spfm_profile_reset(spfm_handle h) {
 #include "spfm_options.inc.h"  // spfm_set_option, spfm_get_option and their table
 
 int spfm_debug_prb_stamps(spfm_handle h, long long* out, int cap) {
-    GUARD(h);
+    SPFM_GUARD(h);
     if ((h->pb_dbg & 8) && out && cap >= 8) {  // diagnostic counters of the persistent pbcd pass
         static unsigned v[16 + 4096];
         if (hipMemcpy(v, h->pb_dbgbuf.p, sizeof v, hipMemcpyDeviceToHost) != hipSuccess)
@@ -1616,7 +1469,7 @@ int spfm_debug_prb_stamps(spfm_handle h, long long* out, int cap) {
 
 int spfm_debug_hop_latency(spfm_handle h, int partner, int rounds, double* ns_per_hop,
                            int* xcc_ids /* [2] */) {
-    GUARD(h);
+    SPFM_GUARD(h);
     if (partner < 1 || partner > 255 || rounds < 1 || rounds > (1 << 20) || !ns_per_hop)
         return SPFM_ERR_INVALID;
     DevBuf words, info;
@@ -1662,7 +1515,7 @@ int spfm_debug_hop_latency(spfm_handle h, int partner, int rounds, double* ns_pe
 
 int spfm_debug_exchange_cost(spfm_handle h, int groups, int ncols, int readers_mod, int rounds,
                              double* ns_per_round) {
-    GUARD(h);
+    SPFM_GUARD(h);
     if (groups < 1 || groups > 256 || ncols < 1 || ncols > 64 || readers_mod == 0 ||
         rounds < 1 || rounds > (1 << 20) || !ns_per_round)
         return SPFM_ERR_INVALID;
@@ -1712,17 +1565,17 @@ int spfm_debug_exchange_cost(spfm_handle h, int groups, int ncols, int readers_m
 }
 
 int spfm_debug_stream_probe(spfm_handle h, int64_t* bytes_out) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->debug_stream_probe(bytes_out);
 }
 
 int spfm_debug_write_probe(spfm_handle h, int bytes_per_record, int64_t* bytes_out) {
-    GUARD(h);
+    SPFM_GUARD(h);
     return h->debug_write_probe(bytes_per_record, bytes_out);
 }
 
 int spfm_debug_branch_counts(spfm_handle h, unsigned* out8, int reset) {
-    GUARD(h);
+    SPFM_GUARD(h);
     if (!out8) return SPFM_ERR_INVALID;
     if (hipStreamSynchronize(h->stream) != hipSuccess) return SPFM_ERR_RUNTIME;
     // one copy of the counters per translation unit that runs chains: add them up

@@ -59,13 +59,18 @@ CsrLaunch pick_csr(int kind, int degree) {
 int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 struct GramRun {
+    spfm_engine& eng;  // the handle: its stream, its typed copies, its error text
     std::string& err;
     hipStream_t stream;
-    int device;
     int kind, degree;
     const double* lams;
     int64_t budget;
     double* out;
+
+    GramRun(spfm_engine& e, int kind_, int degree_, const double* lams_, int64_t budget_,
+            double* out_)
+        : eng(e), err(e.err), stream(e.stream), kind(kind_), degree(degree_), lams(lams_),
+          budget(budget_), out(out_) {}
 
     // kind / degree of kernels.py; degree <= 1 of anova is X P^T (kernels.py:98-115 with an
     // empty recursion), i.e. the DP's a[1]
@@ -148,19 +153,8 @@ struct GramRun {
 
     int upload_rows(DevBuf& rp, DevBuf& ri, DevBuf& rv, const int64_t* indptr,
                     const int32_t* indices, const double* data, int64_t r0, int64_t r1) {
-        const int64_t e0 = indptr[r0], ne = indptr[r1] - e0;
-        HIPC(rp.alloc(sizeof(int64_t) * (size_t)(r1 - r0 + 1)));
-        HIPC(ri.alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(ne, 1)));
-        HIPC(rv.alloc(sizeof(double) * (size_t)std::max<int64_t>(ne, 1)));
-        HIPC(hipMemcpyAsync(rp.p, indptr + r0, sizeof(int64_t) * (size_t)(r1 - r0 + 1),
-                            hipMemcpyHostToDevice, stream));
-        if (ne > 0) {
-            HIPC(hipMemcpyAsync(ri.p, indices + e0, sizeof(int32_t) * (size_t)ne,
-                                hipMemcpyHostToDevice, stream));
-            HIPC(hipMemcpyAsync(rv.p, data + e0, sizeof(double) * (size_t)ne,
-                                hipMemcpyHostToDevice, stream));
-        }
-        return SPFM_OK;
+        std::vector<double> unused;  // double storage: no conversion, nothing staged
+        return eng.stage_csr_rows(rp, ri, rv, unused, indptr, indices, data, r0, r1, 1);
     }
 
     // the K block of rows [r0, r0+rows) x columns [j0, j0+nt) into the caller's array
@@ -171,8 +165,7 @@ struct GramRun {
                                   sizeof(double) * (size_t)rows, sizeof(double) * (size_t)rows,
                                   (size_t)nt, hipMemcpyDeviceToHost, stream));
         } else if (nt == n2) {
-            HIPC(hipMemcpyAsync(out + r0 * n2, o.p, sizeof(double) * (size_t)(rows * nt),
-                                hipMemcpyDeviceToHost, stream));
+            SPFM_TRY(eng.download(out + r0 * n2, o.p, (size_t)(rows * nt)));
         } else {
             HIPC(hipMemcpy2DAsync(out + r0 * n2 + j0, sizeof(double) * (size_t)n2, o.p,
                                   sizeof(double) * (size_t)nt, sizeof(double) * (size_t)nt,
@@ -184,13 +177,10 @@ struct GramRun {
     int finish_lams_block(const DevBuf& o, int64_t r0, int64_t rows, int nch, int64_t nch_all,
                           bool first, std::vector<double>& hpart) {
         if (nch_all == 1) {  // one chunk in the whole call: the partial is the value
-            HIPC(hipMemcpyAsync(out + r0, o.p, sizeof(double) * (size_t)rows,
-                                hipMemcpyDeviceToHost, stream));
-            return SPFM_OK;
+            return eng.download(out + r0, o.p, (size_t)rows);
         }
         hpart.resize((size_t)(rows * nch));
-        HIPC(hipMemcpyAsync(hpart.data(), o.p, sizeof(double) * hpart.size(),
-                            hipMemcpyDeviceToHost, stream));
+        SPFM_TRY(eng.download(hpart.data(), o.p, hpart.size()));
         HIPC(hipStreamSynchronize(stream));
         fold(hpart, rows, nch, first, out + r0);
         return SPFM_OK;
@@ -231,14 +221,8 @@ struct GramRun {
                 for (int32_t c = 0; c < d; ++c) hbt[(size_t)c * nt + j] = src[c];
             }
             HIPC(hipStreamSynchronize(stream));  // the previous tile's readers of bt are done
-            HIPC(bt.alloc(sizeof(double) * hbt.size()));
-            HIPC(hipMemcpyAsync(bt.p, hbt.data(), sizeof(double) * hbt.size(),
-                                hipMemcpyHostToDevice, stream));
-            if (lams) {
-                HIPC(dl.alloc(sizeof(double) * (size_t)nt));
-                HIPC(hipMemcpyAsync(dl.p, lams + j0, sizeof(double) * (size_t)nt,
-                                    hipMemcpyHostToDevice, stream));
-            }
+            SPFM_TRY(eng.upload(bt, hbt.data(), hbt.size()));
+            if (lams) SPFM_TRY(eng.upload(dl, lams + j0, (size_t)nt));
             int group = 1;  // lanes per row: the next power of two >= nt, at most 64
             while (group < nt && group < kGramChunk) group <<= 1;
             const int cpw = nch >= 4 ? 4 : (nch >= 2 ? 2 : 1);
@@ -324,11 +308,7 @@ struct GramRun {
             }
             HIPC(hipStreamSynchronize(stream));
             if ((rc = upload_rows(pp, pi, pv, indptr2, indices2, data2, j0, j0 + nt))) return rc;
-            if (lams) {
-                HIPC(dl.alloc(sizeof(double) * (size_t)nt));
-                HIPC(hipMemcpyAsync(dl.p, lams + j0, sizeof(double) * (size_t)nt,
-                                    hipMemcpyHostToDevice, stream));
-            }
+            if (lams) SPFM_TRY(eng.upload(dl, lams + j0, (size_t)nt));
             const int64_t tile_bytes = (nt + 1) * 8 + (indptr2[j0 + nt] - indptr2[j0]) * 12;
             const int64_t per_row = lams ? (int64_t)nch * 8 : nt * 8;
             row_blocks(n1, indptr1, per_row, std::max<int64_t>(budget - tile_bytes, 1), bounds);
@@ -372,21 +352,14 @@ struct GramRun {
 
 }  // namespace
 
-#define GRAM_GUARD(h)                                  \
-    if (!(h)) return SPFM_ERR_INVALID;                 \
-    if (hipSetDevice((h)->device) != hipSuccess) {     \
-        (h)->err = "hipSetDevice failed";              \
-        return SPFM_ERR_RUNTIME;                       \
-    }
-
 extern "C" {
 
 int spfm_gram_csr_dense(spfm_handle h, int kind, int degree, int64_t n1, int32_t d,
                         const int64_t* indptr, const int32_t* indices, const double* data,
                         int64_t n2, const double* B, const double* lams, int transpose_out,
                         int64_t max_block_bytes, double* out) {
-    GRAM_GUARD(h);
-    GramRun g{h->err, h->stream, h->device, kind, degree, lams, max_block_bytes, out};
+    SPFM_GUARD(h);
+    GramRun g(*h, kind, degree, lams, max_block_bytes, out);
     return g.csr_dense(n1, d, indptr, indices, data, n2, B, transpose_out);
 }
 
@@ -395,8 +368,8 @@ int spfm_gram_csr_csr(spfm_handle h, int kind, int degree, int64_t n1, int32_t d
                       int64_t n2, const int64_t* indptr2, const int32_t* indices2,
                       const double* data2, const double* lams, int64_t max_block_bytes,
                       double* out) {
-    GRAM_GUARD(h);
-    GramRun g{h->err, h->stream, h->device, kind, degree, lams, max_block_bytes, out};
+    SPFM_GUARD(h);
+    GramRun g(*h, kind, degree, lams, max_block_bytes, out);
     return g.csr_csr(n1, d, indptr1, indices1, data1, n2, indptr2, indices2, data2);
 }
 

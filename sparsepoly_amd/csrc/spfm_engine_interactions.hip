@@ -11,25 +11,22 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-// the live image of block `order_idx` as element strides (obj_block_kernel's view)
-int spfm_engine::interaction_view(const char* what, int order_idx, const double** base,
-                                  int64_t* ss, int64_t* sj) {
+// the live image of block `order_idx` (obj_block_kernel's view), behind the entries' checks
+int spfm_engine::interaction_view(const char* what, int order_idx, BlockView* v) {
     if (!have_params) FAIL(SPFM_ERR_INVALID, std::string(what) + ": no parameters set");
     if (order_idx < 0 || order_idx >= n_orders)
         FAIL(SPFM_ERR_INVALID, std::string(what) + ": bad order index");
-    const size_t off = (size_t)order_idx * k * d;
-    *base = (p_valid ? P.as<double>() : Pt.as<double>()) + off;
-    *ss = p_valid ? d : 1;
-    *sj = p_valid ? 1 : k;
+    *v = live_block(order_idx);
     return SPFM_OK;
 }
 
 // compaction: int_ids, the packed images int_A / int_B, int_da / int_kp / int_T
 int spfm_engine::interaction_prepare(const char* what, int order_idx) {
-    const double* base;
-    int64_t ss, sj;
-    int rc = interaction_view(what, order_idx, &base, &ss, &sj);
+    BlockView v;
+    int rc = interaction_view(what, order_idx, &v);
     if (rc) return rc;
+    const double* base = v.base;
+    const int64_t ss = v.ss, sj = v.sj;
     const int dlim = (int_dlim > 0 && int_dlim < d) ? int_dlim : d;
     const unsigned nb = cdiv(d, kBlock);
     HIPC(int_flag.alloc(sizeof(int32_t) * (size_t)d));
@@ -55,7 +52,7 @@ int spfm_engine::interaction_prepare(const char* what, int order_idx) {
                        int_tot.as<int32_t>());
     HIPC(hipGetLastError());
     int32_t da = 0;
-    HIPC(hipMemcpyAsync(&da, int_tot.p, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    SPFM_TRY(download(&da, int_tot.p, 1));
     rc = sync();
     if (rc) return rc;
     if (da < 0 || da > d) FAIL(SPFM_ERR_RUNTIME, std::string(what) + ": compaction failed");
@@ -155,7 +152,7 @@ int spfm_engine::interaction_stats(int order_idx, double tol, int64_t* counts2, 
     }
     HIPC(hipGetLastError());
     IntRec out;
-    HIPC(hipMemcpyAsync(&out, in, sizeof out, hipMemcpyDeviceToHost, stream));
+    SPFM_TRY(download(&out, in, 1));
     rc = sync();
     if (rc) return rc;
     counts2[0] = out.cnt;
@@ -182,7 +179,7 @@ int spfm_engine::interaction_emit(double tol, unsigned long long thr_key, int64_
     int rc = interaction_tiles<INT_EMIT>(a);
     if (rc) return rc;
     uint64_t found = 0;
-    HIPC(hipMemcpyAsync(&found, int_cnt.p, sizeof found, hipMemcpyDeviceToHost, stream));
+    SPFM_TRY(download(&found, int_cnt.p, 1));
     rc = sync();
     if (rc) return rc;
     *n_found = (int64_t)found;
@@ -222,8 +219,7 @@ int spfm_engine::interaction_topk(int order_idx, int64_t K, int32_t* rows, int32
         a.bin_mask = (1u << bits[L]) - 1u;
         rc = interaction_tiles<INT_HIST>(a);
         if (rc) return rc;
-        HIPC(hipMemcpyAsync(hh.data(), int_hist.p, sizeof(uint64_t) * kIntHistBins,
-                            hipMemcpyDeviceToHost, stream));
+        SPFM_TRY(download(hh.data(), int_hist.p, hh.size()));
         rc = sync();
         if (rc) return rc;
         int64_t cum = 0;
@@ -258,10 +254,8 @@ int spfm_engine::interaction_topk(int order_idx, int64_t K, int32_t* rows, int32
     if (found != tail) FAIL(SPFM_ERR_RUNTIME, "interaction_topk: candidate count mismatch");
     std::vector<uint64_t> hk((size_t)tail);
     std::vector<double> hv((size_t)tail);
-    HIPC(hipMemcpyAsync(hk.data(), int_keys.p, sizeof(uint64_t) * (size_t)tail,
-                        hipMemcpyDeviceToHost, stream));
-    HIPC(hipMemcpyAsync(hv.data(), int_vals.p, sizeof(double) * (size_t)tail,
-                        hipMemcpyDeviceToHost, stream));
+    SPFM_TRY(download(hk.data(), int_keys.p, hk.size()));
+    SPFM_TRY(download(hv.data(), int_vals.p, hv.size()));
     rc = sync();
     if (rc) return rc;
     std::vector<int64_t> idx((size_t)tail);
@@ -318,9 +312,8 @@ int spfm_engine::interaction_list(int order_idx, double tol, int64_t capacity, i
                                    int_keys2.as<uint64_t>(), int_vals.as<double>(),
                                    int_vals2.as<double>(), nf, 0, 64, stream));
     std::vector<uint64_t> hk(nf);
-    HIPC(hipMemcpyAsync(hk.data(), int_keys2.p, sizeof(uint64_t) * nf, hipMemcpyDeviceToHost,
-                        stream));
-    HIPC(hipMemcpyAsync(vals, int_vals2.p, sizeof(double) * nf, hipMemcpyDeviceToHost, stream));
+    SPFM_TRY(download(hk.data(), int_keys2.p, nf));
+    SPFM_TRY(download(vals, int_vals2.p, nf));
     rc = sync();
     if (rc) return rc;
     for (size_t i = 0; i < nf; ++i) {
@@ -334,10 +327,8 @@ int spfm_engine::interaction_values(int order_idx, int64_t L, const int32_t* row
                                     const int32_t* cols, double* vals) {
     if (L < 0) FAIL(SPFM_ERR_INVALID, "interaction_values: L must be >= 0");
     if (L > 0 && (!rows || !cols || !vals)) FAIL(SPFM_ERR_INVALID, "interaction_values: NULL array");
-    const double* base;
-    int64_t ss, sj;
-    int rc = interaction_view("interaction_values", order_idx, &base, &ss, &sj);
-    if (rc) return rc;
+    BlockView v;
+    SPFM_TRY(interaction_view("interaction_values", order_idx, &v));
     for (int64_t q = 0; q < L; ++q)
         if (rows[q] < 0 || rows[q] >= d || cols[q] < 0 || cols[q] >= d)
             FAIL(SPFM_ERR_INVALID, "interaction_values: feature id out of range");
@@ -346,12 +337,12 @@ int spfm_engine::interaction_values(int order_idx, int64_t L, const int32_t* row
     HIPC(int_out.alloc(sizeof(double) * (size_t)L));
     int32_t* dr = int_io.as<int32_t>();
     int32_t* dc = dr + L;
-    HIPC(hipMemcpyAsync(dr, rows, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, stream));
-    HIPC(hipMemcpyAsync(dc, cols, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(int_values_kernel, dim3(cdiv(L, kBlock)), dim3(kBlock), 0, stream, base, ss,
-                       sj, k, lams.as<double>(), (long long)L, dr, dc, int_out.as<double>());
+    SPFM_TRY(upload_to(dr, rows, (size_t)L));
+    SPFM_TRY(upload_to(dc, cols, (size_t)L));
+    hipLaunchKernelGGL(int_values_kernel, dim3(cdiv(L, kBlock)), dim3(kBlock), 0, stream, v.base,
+                       v.ss, v.sj, k, lams.as<double>(), (long long)L, dr, dc, int_out.as<double>());
     HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(vals, int_out.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, stream));
+    SPFM_TRY(download(vals, int_out.p, (size_t)L));
     return sync();
 }
 
@@ -359,10 +350,8 @@ int spfm_engine::interaction_block(int order_idx, int64_t nJ, const int32_t* J, 
                                    const int32_t* J2, double* out) {
     if (nJ < 0 || nJ2 < 0) FAIL(SPFM_ERR_INVALID, "interaction_block: negative size");
     if ((nJ > 0 && !J) || (nJ2 > 0 && !J2)) FAIL(SPFM_ERR_INVALID, "interaction_block: NULL array");
-    const double* base;
-    int64_t ss, sj;
-    int rc = interaction_view("interaction_block", order_idx, &base, &ss, &sj);
-    if (rc) return rc;
+    BlockView v;
+    SPFM_TRY(interaction_view("interaction_block", order_idx, &v));
     for (int64_t q = 0; q < nJ; ++q)
         if (J[q] < 0 || J[q] >= d)
             FAIL(SPFM_ERR_INVALID, "interaction_block: feature id out of range");
@@ -383,53 +372,45 @@ int spfm_engine::interaction_block(int order_idx, int64_t nJ, const int32_t* J, 
     HIPC(int_out.alloc(sizeof(double) * (size_t)tot));
     int32_t* dj = int_io.as<int32_t>();
     int32_t* dj2 = dj + nJ;
-    HIPC(hipMemcpyAsync(dj, J, sizeof(int32_t) * (size_t)nJ, hipMemcpyHostToDevice, stream));
-    HIPC(hipMemcpyAsync(dj2, J2, sizeof(int32_t) * (size_t)nJ2, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(int_block_kernel, dim3(cdiv(tot, kBlock)), dim3(kBlock), 0, stream, base, ss,
-                       sj, k, lams.as<double>(), (long long)nJ, dj, (long long)nJ2, dj2,
+    SPFM_TRY(upload_to(dj, J, (size_t)nJ));
+    SPFM_TRY(upload_to(dj2, J2, (size_t)nJ2));
+    hipLaunchKernelGGL(int_block_kernel, dim3(cdiv(tot, kBlock)), dim3(kBlock), 0, stream, v.base,
+                       v.ss, v.sj, k, lams.as<double>(), (long long)nJ, dj, (long long)nJ2, dj2,
                        int_out.as<double>());
     HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(out, int_out.p, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost,
-                        stream));
+    SPFM_TRY(download(out, int_out.p, (size_t)tot));
     return sync();
 }
-
-#define INT_GUARD(h)                               \
-    if (!(h)) return SPFM_ERR_INVALID;             \
-    if (hipSetDevice((h)->device) != hipSuccess) { \
-        (h)->err = "hipSetDevice failed";          \
-        return SPFM_ERR_RUNTIME;                   \
-    }
 
 extern "C" {
 
 int spfm_interaction_stats(spfm_handle h, int order_idx, double tol, int64_t* counts2,
                            double* sums3) {
-    INT_GUARD(h);
+    SPFM_GUARD(h);
     return h->interaction_stats(order_idx, tol, counts2, sums3);
 }
 
 int spfm_interaction_topk(spfm_handle h, int order_idx, int64_t K, int32_t* rows, int32_t* cols,
                           double* vals, int64_t* n_out) {
-    INT_GUARD(h);
+    SPFM_GUARD(h);
     return h->interaction_topk(order_idx, K, rows, cols, vals, n_out);
 }
 
 int spfm_interaction_list(spfm_handle h, int order_idx, double tol, int64_t capacity,
                           int32_t* rows, int32_t* cols, double* vals, int64_t* n_out) {
-    INT_GUARD(h);
+    SPFM_GUARD(h);
     return h->interaction_list(order_idx, tol, capacity, rows, cols, vals, n_out);
 }
 
 int spfm_interaction_values(spfm_handle h, int order_idx, int64_t L, const int32_t* rows,
                             const int32_t* cols, double* vals) {
-    INT_GUARD(h);
+    SPFM_GUARD(h);
     return h->interaction_values(order_idx, L, rows, cols, vals);
 }
 
 int spfm_interaction_block(spfm_handle h, int order_idx, int64_t nJ, const int32_t* J,
                            int64_t nJ2, const int32_t* J2, double* out) {
-    INT_GUARD(h);
+    SPFM_GUARD(h);
     return h->interaction_block(order_idx, nJ, J, nJ2, J2, out);
 }
 

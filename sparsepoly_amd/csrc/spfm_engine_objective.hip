@@ -36,52 +36,32 @@ int spfm_engine::objective_terms(int order_idx, int degree, double* out8) {
     if (order_idx == -1) {
         rc = objective_launch<0>(w.as<double>(), 0, 1, 1, 0, 1);
     } else {
-        // the live image: (k,d) after pcd epochs and spfm_set_params, (d,k) after pbcd / psgd
-        const size_t off = (size_t)order_idx * k * d;
-        const double* base = (p_valid ? P.as<double>() : Pt.as<double>()) + off;
-        const int64_t ss = p_valid ? d : 1, sj = p_valid ? 1 : k;
+        const BlockView v = live_block(order_idx);
         const bool poly = (reg == SPFM_REG_OMEGATI || reg == SPFM_REG_OMEGACS) && degree > 0;
         const int all = degree == -1;
         switch (poly ? degree : 0) {
-            case 0: rc = objective_launch<0>(base, ss, sj, k, all, 0); break;
-            case 1: rc = objective_launch<1>(base, ss, sj, k, all, 0); break;
-            case 2: rc = objective_launch<2>(base, ss, sj, k, all, 0); break;
-            case 3: rc = objective_launch<3>(base, ss, sj, k, all, 0); break;
-            case 4: rc = objective_launch<4>(base, ss, sj, k, all, 0); break;
-            case 5: rc = objective_launch<5>(base, ss, sj, k, all, 0); break;
-            default: rc = objective_launch<6>(base, ss, sj, k, all, 0); break;
+            case 0: rc = objective_launch<0>(v.base, v.ss, v.sj, k, all, 0); break;
+            case 1: rc = objective_launch<1>(v.base, v.ss, v.sj, k, all, 0); break;
+            case 2: rc = objective_launch<2>(v.base, v.ss, v.sj, k, all, 0); break;
+            case 3: rc = objective_launch<3>(v.base, v.ss, v.sj, k, all, 0); break;
+            case 4: rc = objective_launch<4>(v.base, v.ss, v.sj, k, all, 0); break;
+            case 5: rc = objective_launch<5>(v.base, v.ss, v.sj, k, all, 0); break;
+            default: rc = objective_launch<6>(v.base, v.ss, v.sj, k, all, 0); break;
         }
     }
     if (rc) return rc;
-    HIPC(hipMemcpyAsync(out8, obj_out.p, sizeof(double) * 8, hipMemcpyDeviceToHost, stream));
+    SPFM_TRY(download(out8, obj_out.p, 8));
     return sync();
 }
 
 template <typename T>
 int spfm_engine::set_eval_t(int64_t rows, const int64_t* indptr, const int32_t* indices,
                             const double* data, const double* y) {
-    const int64_t nz = indptr[rows];
-    std::vector<T> hv((size_t)nz);
-    for (int64_t ii = 0; ii < nz; ++ii) hv[(size_t)ii] = (T)data[ii];
-    HIPC(ev_rptr.alloc(sizeof(int64_t) * ((size_t)rows + 1)));
-    HIPC(ev_ridx.alloc(sizeof(int32_t) * (size_t)nz));
-    HIPC(ev_rval.alloc(sizeof(T) * (size_t)nz));
+    std::vector<T> hv;
+    SPFM_TRY(stage_csr_rows(ev_rptr, ev_ridx, ev_rval, hv, indptr, indices, data, 0, rows));
     HIPC(ev_pred.alloc(sizeof(double) * (size_t)rows));
     HIPC(ev_part.alloc(sizeof(double) * 520));
-    HIPC(hipMemcpyAsync(ev_rptr.p, indptr, sizeof(int64_t) * ((size_t)rows + 1),
-                        hipMemcpyHostToDevice, stream));
-    if (nz > 0) {
-        HIPC(hipMemcpyAsync(ev_ridx.p, indices, sizeof(int32_t) * (size_t)nz,
-                            hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync(ev_rval.p, hv.data(), sizeof(T) * (size_t)nz, hipMemcpyHostToDevice,
-                            stream));
-    }
-    if (y) {
-        HIPC(ev_y.alloc(sizeof(double) * (size_t)rows));
-        if (rows > 0)
-            HIPC(hipMemcpyAsync(ev_y.p, y, sizeof(double) * (size_t)rows, hipMemcpyHostToDevice,
-                                stream));
-    }
+    if (y) SPFM_TRY(upload(ev_y, y, (size_t)rows));
     return sync();  // hv and the caller's arrays are free again
 }
 
@@ -105,9 +85,7 @@ int spfm_engine::set_eval_csr(int64_t rows, int32_t d_, const int64_t* indptr,
                      "set_eval: CSR must have sorted, duplicate-free column indices");
         }
     have_eval = false;
-    int rc = dtype == SPFM_F32 ? set_eval_t<float>(rows, indptr, indices, data, y)
-                               : set_eval_t<double>(rows, indptr, indices, data, y);
-    if (rc) return rc;
+    SPFM_TRY(SPFM_DISPATCH(dtype, return set_eval_t<T>(rows, indptr, indices, data, y)));
     ev_n = rows;
     ev_has_y = y != nullptr;
     have_eval = true;
@@ -139,14 +117,10 @@ int spfm_engine::eval_loss(int degree, int fit_linear, int add_lower, double* lo
         HIPC(hipGetLastError());
         Pt_all = ev_pt.as<double>();
     }
-    int rc = dtype == SPFM_F32
-                 ? output_pt_t<float>(ev_n, ev_rptr.as<int64_t>(), ev_ridx.as<int32_t>(),
-                                      ev_rval.as<float>(), degree, fit_linear, add_lower, Pt_all,
-                                      ev_pred.as<double>())
-                 : output_pt_t<double>(ev_n, ev_rptr.as<int64_t>(), ev_ridx.as<int32_t>(),
-                                       ev_rval.as<double>(), degree, fit_linear, add_lower, Pt_all,
-                                       ev_pred.as<double>());
-    if (rc) return rc;
+    SPFM_TRY(SPFM_DISPATCH(
+        dtype, return output_pt_t<T>(ev_n, ev_rptr.as<int64_t>(), ev_ridx.as<int32_t>(),
+                                     ev_rval.as<T>(), degree, fit_linear, add_lower, Pt_all,
+                                     ev_pred.as<double>())));
     double total = 0.0;
     if (loss_sum_out) {
         const int nb = 512;
@@ -155,14 +129,31 @@ int spfm_engine::eval_loss(int degree, int fit_linear, int add_lower, double* lo
         hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(kBlock), 0, stream,
                            ev_part.as<double>(), nb, ev_part.as<double>() + 512);
         HIPC(hipGetLastError());
-        HIPC(hipMemcpyAsync(&total, ev_part.as<double>() + 512, sizeof(double),
-                            hipMemcpyDeviceToHost, stream));
+        SPFM_TRY(download(&total, ev_part.as<double>() + 512, 1));
     }
-    if (y_pred_out)
-        HIPC(hipMemcpyAsync(y_pred_out, ev_pred.p, sizeof(double) * (size_t)ev_n,
-                            hipMemcpyDeviceToHost, stream));
-    rc = sync();
-    if (rc) return rc;
+    if (y_pred_out) SPFM_TRY(download(y_pred_out, ev_pred.p, (size_t)ev_n));
+    SPFM_TRY(sync());
     if (loss_sum_out) *loss_sum_out = total;
     return SPFM_OK;
 }
+
+extern "C" {
+
+int spfm_objective_terms(spfm_handle h, int order_idx, int degree, double* out8) {
+    SPFM_GUARD(h);
+    return h->objective_terms(order_idx, degree, out8);
+}
+
+int spfm_set_eval_csr(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
+                      const int32_t* indices, const double* data, const double* y) {
+    SPFM_GUARD(h);
+    return h->set_eval_csr(n, d, indptr, indices, data, y);
+}
+
+int spfm_eval_loss(spfm_handle h, int degree, int fit_linear, int add_lower_deg2,
+                   double* loss_sum, double* y_pred_out) {
+    SPFM_GUARD(h);
+    return h->eval_loss(degree, fit_linear, add_lower_deg2, loss_sum, y_pred_out);
+}
+
+}  // extern "C"

@@ -164,9 +164,8 @@ int spfm_engine::pbcd_epoch(int order_idx, int degree, double beta, double gamma
         double* Pt_epoch = Pt.as<double>() + (size_t)order_idx * k * d;
         rc = snapshot_state(Pt_epoch, (size_t)k * d, snapP);
         if (rc) return rc;
-        rc = dtype == SPFM_F32
-                 ? pbcd_prb_dispatch<float>(kind_of(degree), order_idx, beta, gamma, eta)
-                 : pbcd_prb_dispatch<double>(kind_of(degree), order_idx, beta, gamma, eta);
+        rc = SPFM_DISPATCH(dtype, return pbcd_prb_dispatch<T>(kind_of(degree), order_idx, beta,
+                           gamma, eta));
         if (rc == kNotResident) {  // nothing launched but the epoch's set-up kernels
             mark_not_resident("persistent pbcd pass");
             return pbcd_epoch(order_idx, degree, beta, gamma, eta, viol);
@@ -187,8 +186,8 @@ int spfm_engine::pbcd_epoch(int order_idx, int degree, double beta, double gamma
     const std::string key = fkey("pbcd", {beta, gamma, eta},
                                  {order_idx, degree, loss, reg, sched_version});
     rc = run_cached(key, [&]() {
-        return dtype == SPFM_F32 ? pbcd_dispatch<float>(kind_of(degree), order_idx, beta, gamma, eta)
-                                 : pbcd_dispatch<double>(kind_of(degree), order_idx, beta, gamma, eta);
+        return SPFM_DISPATCH(dtype, return pbcd_dispatch<T>(kind_of(degree), order_idx, beta,
+                             gamma, eta));
     });
     if (rc) return rc;
     return epoch_epilogue(viol);
@@ -230,8 +229,7 @@ int spfm_engine::host_sums_pbcd(int b, double* out) {
     int rc = allreduce(part.as<double>(), np);
     if (rc) return rc;
     host_stage.resize(np);
-    HIPC(hipMemcpyAsync(host_stage.data(), part.p, sizeof(double) * np, hipMemcpyDeviceToHost,
-                        stream));
+    SPFM_TRY(download(host_stage.data(), part.p, np));
     rc = sync();
     if (rc) return rc;
     for (int q = 0; q < nc; ++q)  // the column's kPbW partial vectors in fixed order
@@ -252,12 +250,9 @@ int spfm_engine::host_apply_pbcd(int b, const double* p_new, const double* p_old
     double* Po = Pt.as<double>() + (size_t)host_order * k * d;
     host_stage.assign((size_t)4 * nc, 0.0);
     for (int q = 0; q < nc; ++q) host_stage[(size_t)4 * q + 2] = 1.0;  // shrink factor f = 1
-    HIPC(hipMemcpyAsync(delta.p, p_new, sizeof(double) * (size_t)nc * k, hipMemcpyHostToDevice,
-                        stream));
-    HIPC(hipMemcpyAsync(pold.p, p_old, sizeof(double) * (size_t)nc * k, hipMemcpyHostToDevice,
-                        stream));
-    HIPC(hipMemcpyAsync(pb_scal.p, host_stage.data(), sizeof(double) * 4 * (size_t)nc,
-                        hipMemcpyHostToDevice, stream));
+    SPFM_TRY(upload_to(delta.p, p_new, (size_t)nc * k));
+    SPFM_TRY(upload_to(pold.p, p_old, (size_t)nc * k));
+    SPFM_TRY(upload_to(pb_scal.p, host_stage.data(), 4 * (size_t)nc));
     hipLaunchKernelGGL((pbcd_sync_kernel<T, M, L, C>), dim3(nc * kPbW), dim3(kBlock), 0, stream,
                        d_desc.as<ColDesc>() + c0, cidx.as<int32_t>(), cval.as<T>(), A.as<T>(),
                        yy.as<T>(), lams.as<double>(), k, Po, delta.as<double>(),

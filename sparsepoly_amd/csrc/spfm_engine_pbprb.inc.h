@@ -80,14 +80,11 @@ int spfm_engine::ensure_pb_stream(int NG) {
             const char* bad = validate_pb_stream(G, NG, gsp, src, meta, tab);
             if (bad) FAIL(SPFM_ERR_RUNTIME, std::string("internal: pbcd entry stream: ") + bad);
         }
-        HIPC(hipMemcpyAsync(pb_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync(pb_sp.p, gsp.data(), sizeof(int32_t) * gsp.size(),
-                            hipMemcpyHostToDevice, stream));
+        SPFM_TRY(upload_to(pb_tab.p, tab.data(), tab.size()));
+        SPFM_TRY(upload_to(pb_sp.p, gsp.data(), gsp.size()));
         if (nnz > 0) {
-            HIPC(hipMemcpyAsync(d_src.p, src.data(), sizeof(int32_t) * (size_t)nnz,
-                                hipMemcpyHostToDevice, stream));
-            HIPC(hipMemcpyAsync(pb_meta.p, meta.data(), (size_t)nnz, hipMemcpyHostToDevice,
-                                stream));
+            SPFM_TRY(upload_to(d_src.p, src.data(), (size_t)nnz));
+            SPFM_TRY(upload_to(pb_meta.p, meta.data(), (size_t)nnz));
         }
         HIPC(hipStreamSynchronize(stream));  // the host staging vectors die here
     }
@@ -138,7 +135,7 @@ int spfm_engine::ensure_pb_relax(int NG) {
     std::vector<PrbConf<T>> hcf(ncf ? ncf : 1);
     {
         std::vector<T> hv((size_t)(nnz > 0 ? nnz : 1));
-        HIPC(hipMemcpyAsync(hv.data(), cval.p, sizeof(T) * (size_t)nnz, hipMemcpyDeviceToHost, stream));
+        SPFM_TRY(download(hv.data(), cval.p, (size_t)nnz));
         HIPC(hipStreamSynchronize(stream));
         for (size_t c = 0; c < ncf; ++c) {
             hcf[c].row = cf_row[c];
@@ -166,20 +163,15 @@ int spfm_engine::ensure_pb_relax(int NG) {
     HIPC(prb_abort.alloc(sizeof(unsigned) * 4));
     HIPC(prb_viol.alloc(sizeof(double) * (size_t)d));
     HIPC(hipMemsetAsync(prb_abort.p, 0, sizeof(unsigned) * 4, stream));
-    HIPC(hipMemcpyAsync(pbr_bptr.p, pbr_batch_ptr.data(), sizeof(int32_t) * pbr_batch_ptr.size(),
-                        hipMemcpyHostToDevice, stream));
-    HIPC(hipMemcpyAsync(pbr_sp.p, gsp.data(), sizeof(int32_t) * gsp.size(), hipMemcpyHostToDevice,
-                        stream));
-    HIPC(hipMemcpyAsync(pbr_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, stream));
-    HIPC(hipMemcpyAsync(pbr_cfptr.p, cf_ptr.data(), sizeof(int32_t) * cf_ptr.size(),
-                        hipMemcpyHostToDevice, stream));
-    HIPC(hipMemcpyAsync(pbr_cf.p, hcf.data(), sizeof(PrbConf<T>) * hcf.size(), hipMemcpyHostToDevice,
-                        stream));
-    HIPC(hipMemcpyAsync(pbr_clist.p, clist.data(), sizeof(int16_t) * clist.size(),
-                        hipMemcpyHostToDevice, stream));
+    SPFM_TRY(upload_to(pbr_bptr.p, pbr_batch_ptr.data(), pbr_batch_ptr.size()));
+    SPFM_TRY(upload_to(pbr_sp.p, gsp.data(), gsp.size()));
+    SPFM_TRY(upload_to(pbr_tab.p, tab.data(), tab.size()));
+    SPFM_TRY(upload_to(pbr_cfptr.p, cf_ptr.data(), cf_ptr.size()));
+    SPFM_TRY(upload_to(pbr_cf.p, hcf.data(), hcf.size()));
+    SPFM_TRY(upload_to(pbr_clist.p, clist.data(), clist.size()));
     if (ne > 0) {
-        HIPC(hipMemcpyAsync(d_src.p, src.data(), sizeof(int32_t) * ne, hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync(pbr_meta.p, meta.data(), ne, hipMemcpyHostToDevice, stream));
+        SPFM_TRY(upload_to(d_src.p, src.data(), ne));
+        SPFM_TRY(upload_to(pbr_meta.p, meta.data(), ne));
         hipLaunchKernelGGL((prb_gather_kernel<T>), dim3(cdiv((int64_t)ne, 256)), dim3(256), 0, stream,
                            (int64_t)ne, d_src.as<int32_t>(), cidx.as<int32_t>(), cval.as<T>(),
                            pbr_erow.as<int32_t>(), pbr_eval.as<T>());
@@ -280,7 +272,7 @@ int spfm_engine::pbcd_prb_l(int order_idx, double beta, double gamma, double eta
     if (pb_dbg & 8) HIPC(hipMemsetAsync(pb_dbgbuf.p, 0, sizeof(unsigned) * (16 + 4096), stream));
     if (pb_dbg & 8) {
         unsigned init[16] = {0, 0, 0, 0xFFFFFFFFu, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        HIPC(hipMemcpyAsync(pb_dbgbuf.p, init, sizeof init, hipMemcpyHostToDevice, stream));
+        SPFM_TRY(upload_to(pb_dbgbuf.p, init, 16));
     }
     a.dbg_out = pb_dbgbuf.as<unsigned>();
     const int ncache = top_degree > 0 ? top_degree + 1 : 1;

@@ -46,8 +46,8 @@ int spfm_engine::cd_linear_epoch(double alpha, double* viol) {
         const char* what = wide ? "wide persistent cd_linear pass" : "persistent cd_linear pass";
         rc = snapshot_state(w.as<double>(), (size_t)d, snapW);
         if (rc) return rc;
-        if (wide) rc = dtype == SPFM_F32 ? lin_wide<float>(alpha) : lin_wide<double>(alpha);
-        else rc = dtype == SPFM_F32 ? lin_prb_loss<float>(alpha) : lin_prb_loss<double>(alpha);
+        if (wide) rc = SPFM_DISPATCH(dtype, return lin_wide<T>(alpha));
+        else rc = SPFM_DISPATCH(dtype, return lin_prb_loss<T>(alpha));
         if (rc == kNotResident) {  // nothing was launched: the multi-kernel engine takes over
             mark_not_resident(what);
             return cd_linear_epoch(alpha, viol);
@@ -67,7 +67,7 @@ int spfm_engine::cd_linear_epoch(double alpha, double* viol) {
     }
     const std::string key = fkey("lin", {alpha}, {loss, sched_version});
     rc = run_cached(key, [&]() {
-        return dtype == SPFM_F32 ? lin_body<float>(alpha) : lin_body<double>(alpha);
+        return SPFM_DISPATCH(dtype, return lin_body<T>(alpha));
     });
     if (rc) return rc;
     return epoch_epilogue(viol);
@@ -231,14 +231,12 @@ int spfm_engine::pcd_epoch(int order_idx, int degree, double beta, double gamma,
     if (rc) return rc;
     pt_valid = false;
     if (n_comp > 0)
-        HIPC(hipMemcpyAsync(comp_order.p, ic, sizeof(int32_t) * (size_t)n_comp,
-                            hipMemcpyHostToDevice, stream));
+        SPFM_TRY(upload_to(comp_order.p, ic, (size_t)n_comp));
     HIPC(hipMemsetAsync(ctl.p, 0, sizeof(Ctl), stream));
     const std::string key = fkey("pcd", {beta, gamma, eta},
                                  {order_idx, degree, loss, reg, sched_version});
     const int M = kind_of(degree);
-    rc = dtype == SPFM_F32 ? pcd_precompute_all_dispatch<float>(M, order_idx)
-                           : pcd_precompute_all_dispatch<double>(M, order_idx);
+    rc = SPFM_DISPATCH(dtype, return pcd_precompute_all_dispatch<T>(M, order_idx));
     if (rc) return rc;
     bool use_prb = prb_usable();
     bool use_wide = wide_usable() && M == 2;
@@ -251,11 +249,9 @@ int spfm_engine::pcd_epoch(int order_idx, int degree, double beta, double gamma,
     for (int pass = 0; pass < n_comp; ++pass) {
         rc = SPFM_OK;
         if (use_wide) {
-            rc = dtype == SPFM_F32 ? pcd_pass_wide<float>(order_idx, beta, gamma, eta)
-                                   : pcd_pass_wide<double>(order_idx, beta, gamma, eta);
+            rc = SPFM_DISPATCH(dtype, return pcd_pass_wide<T>(order_idx, beta, gamma, eta));
         } else if (use_prb) {
-            rc = dtype == SPFM_F32 ? pcd_prb_dispatch<float>(M, order_idx, beta, gamma, eta)
-                                   : pcd_prb_dispatch<double>(M, order_idx, beta, gamma, eta);
+            rc = SPFM_DISPATCH(dtype, return pcd_prb_dispatch<T>(M, order_idx, beta, gamma, eta));
         }
         if (rc == kNotResident) {
             // the pass was not launched (its helper kernels only picked the component and
@@ -268,9 +264,8 @@ int spfm_engine::pcd_epoch(int order_idx, int degree, double beta, double gamma,
         }
         if (!use_wide && !use_prb) {
             rc = run_cached(key, [&]() {
-                return dtype == SPFM_F32
-                           ? pcd_pass_dispatch<float>(M, order_idx, beta, gamma, eta)
-                           : pcd_pass_dispatch<double>(M, order_idx, beta, gamma, eta);
+                return SPFM_DISPATCH(dtype, return pcd_pass_dispatch<T>(M, order_idx, beta, gamma,
+                                     eta));
             });
         }
         if (rc) return rc;
@@ -305,16 +300,14 @@ int spfm_engine::host_epoch_begin(int order_idx, int degree) {
         if (rc) return rc;
         pt_valid = false;
         HIPC(hipMemsetAsync(ctl.p, 0, sizeof(Ctl), stream));
-        rc = dtype == SPFM_F32 ? pcd_precompute_all_dispatch<float>(M, order_idx)
-                               : pcd_precompute_all_dispatch<double>(M, order_idx);
+        rc = SPFM_DISPATCH(dtype, return pcd_precompute_all_dispatch<T>(M, order_idx));
         if (rc) return rc;
         pt_valid = false;
     } else {
         rc = ensure_pt();
         if (rc) return rc;
         p_valid = false;
-        rc = dtype == SPFM_F32 ? host_pbcd_precompute<float>(M, order_idx)
-                               : host_pbcd_precompute<double>(M, order_idx);
+        rc = SPFM_DISPATCH(dtype, return host_pbcd_precompute<T>(M, order_idx));
         if (rc) return rc;
     }
     host_order = order_idx;
@@ -330,7 +323,7 @@ int spfm_engine::host_pass_begin(int s) {  // pcd: the component of the followin
     std::memset(&hc, 0, sizeof hc);
     hc.s = s;
     hc.lam = h_lams[(size_t)s];
-    HIPC(hipMemcpyAsync(ctl.p, &hc, sizeof hc, hipMemcpyHostToDevice, stream));
+    SPFM_TRY(upload_to(ctl.p, &hc, 1));
     return sync();
 }
 
@@ -346,8 +339,7 @@ int spfm_engine::host_sums_pcd(int b, double* out) {
     HIPC(hipGetLastError());
     int rc = allreduce(part.as<double>(), (size_t)2 * nc);
     if (rc) return rc;
-    HIPC(hipMemcpyAsync(out, part.p, sizeof(double) * 2 * (size_t)nc, hipMemcpyDeviceToHost,
-                        stream));
+    SPFM_TRY(download(out, part.p, 2 * (size_t)nc));
     return sync();
 }
 
@@ -356,8 +348,7 @@ int spfm_engine::host_apply_pcd(int b, const double* p_new) {
     const int c0 = batch_ptr[b], nc = batch_ptr[b + 1] - c0;
     if (nc == 0) return SPFM_OK;
     double* Po = P.as<double>() + (size_t)host_order * k * d;
-    HIPC(hipMemcpyAsync(delta.p, p_new, sizeof(double) * (size_t)nc, hipMemcpyHostToDevice,
-                        stream));
+    SPFM_TRY(upload_to(delta.p, p_new, (size_t)nc));
     hipLaunchKernelGGL(host_apply_pcd_kernel, dim3(cdiv(nc, 64)), dim3(64), 0, stream,
                        ctl.as<Ctl>(), d_desc.as<ColDesc>() + c0, nc, Po, d, pold.as<double>(),
                        delta.as<double>(), viol_col.as<double>());
@@ -374,10 +365,8 @@ int spfm_engine::host_step(bool sums, int b, double* out, const double* p_new, c
     if (rc) return rc;
     if ((sums && !out) || (!sums && !p_new)) FAIL(SPFM_ERR_INVALID, "host step: NULL buffer");
     if (solver == SPFM_SOLVER_PCD)
-        return dtype == SPFM_F32 ? host_step_pcd_t<float>(sums, b, out, p_new)
-                                 : host_step_pcd_t<double>(sums, b, out, p_new);
-    return dtype == SPFM_F32 ? host_step_pbcd_t<float>(sums, b, out, p_new, p_old)
-                             : host_step_pbcd_t<double>(sums, b, out, p_new, p_old);
+        return SPFM_DISPATCH(dtype, return host_step_pcd_t<T>(sums, b, out, p_new));
+    return SPFM_DISPATCH(dtype, return host_step_pbcd_t<T>(sums, b, out, p_new, p_old));
 }
 
 template <typename T>
@@ -408,18 +397,15 @@ int spfm_engine::host_epoch_end(double* viol) {
 int spfm_engine::debug_stream_probe(int64_t* bytes_out) {
     if (!have_schedule || !prb_usable())
         FAIL(SPFM_ERR_INVALID, "stream probe: needs a schedule the 64-column persistent pass can run");
-    int rc = dtype == SPFM_F32 ? ensure_prb<float>() : ensure_prb<double>();
+    int rc = SPFM_DISPATCH(dtype, return ensure_prb<T>());
     if (rc) return rc;
     DevBuf sink;
     if (sink.alloc(sizeof(double) * (size_t)prb_G * kPrbThreads) != hipSuccess)
         FAIL(SPFM_ERR_RUNTIME, "stream probe: allocation failed");
     const PrbArgs a = prb_args();
-    if (dtype == SPFM_F32)
-        hipLaunchKernelGGL((prb_stream_probe_kernel<float>), dim3(prb_G), dim3(kPrbThreads), 0,
-                           stream, a, prb_eval.as<float>(), sink.as<double>());
-    else
-        hipLaunchKernelGGL((prb_stream_probe_kernel<double>), dim3(prb_G), dim3(kPrbThreads), 0,
-                           stream, a, prb_eval.as<double>(), sink.as<double>());
+    SPFM_DISPATCH(dtype, hipLaunchKernelGGL((prb_stream_probe_kernel<T>), dim3(prb_G),
+                                            dim3(kPrbThreads), 0, stream, a, prb_eval.as<T>(),
+                                            sink.as<double>()));
     if (hipStreamSynchronize(stream) != hipSuccess)
         FAIL(SPFM_ERR_RUNTIME, "stream probe kernel failed");
     // requested bytes: per entry a 4-byte row id and a value; per (workgroup, step) the slot
@@ -435,7 +421,7 @@ int spfm_engine::debug_write_probe(int bytes, int64_t* bytes_out) {
     if (!have_schedule || !prb_usable())
         FAIL(SPFM_ERR_INVALID, "write probe: needs a schedule the 64-column persistent pass can run");
     if (bytes != 4 && bytes != 8 && bytes != 16) FAIL(SPFM_ERR_INVALID, "write probe: 4, 8 or 16 bytes");
-    int rc = dtype == SPFM_F32 ? ensure_prb<float>() : ensure_prb<double>();
+    int rc = SPFM_DISPATCH(dtype, return ensure_prb<T>());
     if (rc) return rc;
     DevBuf recs;
     if (recs.alloc((size_t)16 * (size_t)(n > 0 ? n : 1)) != hipSuccess)

@@ -207,18 +207,15 @@ int spfm_engine::build_prb_stream(int nb_) {
                               prb_long, sp, src, lmask, nullptr);
         prb_has_long = 0;
         for (uint32_t m : lmask) prb_has_long |= (m != 0u);
-        HIPC(hipMemcpyAsync(prb_lmask.p, lmask.data(), sizeof(uint32_t) * lmask.size(),
-                            hipMemcpyHostToDevice, stream));
+        SPFM_TRY(upload_to(prb_lmask.p, lmask.data(), lmask.size()));
     }
     HIPC(prb_erow.alloc(sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
     HIPC(prb_eval.alloc(sizeof(T) * (size_t)(nnz > 0 ? nnz : 1)));
     if (!stream_device_used)
-        HIPC(hipMemcpyAsync(prb_sp.p, sp.data(), sizeof(int32_t) * sp.size(),
-                            hipMemcpyHostToDevice, stream));
+        SPFM_TRY(upload_to(prb_sp.p, sp.data(), sp.size()));
     if (nnz > 0) {
         if (!stream_device_used)
-            HIPC(hipMemcpyAsync(d_src.p, src.data(), sizeof(int32_t) * (size_t)nnz,
-                                hipMemcpyHostToDevice, stream));
+            SPFM_TRY(upload_to(d_src.p, src.data(), (size_t)nnz));
         hipLaunchKernelGGL((prb_gather_kernel<T>), dim3(cdiv(nnz, 256)), dim3(256), 0, stream,
                            nnz, d_src.as<int32_t>(), cidx.as<int32_t>(), cval.as<T>(),
                            prb_erow.as<int32_t>(), prb_eval.as<T>());
@@ -247,15 +244,14 @@ int spfm_engine::ensure_relax() {
     // the strict one (ensure_prb), or by the host builder
     DevBuf d_src;
     HIPC(r_bptr.alloc(sizeof(int32_t) * r_batch_ptr.size()));
-    HIPC(hipMemcpyAsync(r_bptr.p, r_batch_ptr.data(), sizeof(int32_t) * r_batch_ptr.size(),
-                        hipMemcpyHostToDevice, stream));
+    SPFM_TRY(upload_to(r_bptr.p, r_batch_ptr.data(), r_batch_ptr.size()));
     const size_t nsp_r = (size_t)prb_G * nbr * 65 + 1;
     bool dev_stream = false;
     size_t ne = 0;
     if (stream_device && nnz >= (1 << 20)) {
         DevBuf d_skip;
         HIPC(d_skip.alloc((size_t)nnz));
-        HIPC(hipMemcpyAsync(d_skip.p, skip.data(), (size_t)nnz, hipMemcpyHostToDevice, stream));
+        SPFM_TRY(upload_to(d_skip.p, skip.data(), (size_t)nnz));
         HIPC(d_src.alloc(sizeof(int32_t) * (size_t)nnz));
         HIPC(r_sp.alloc(sizeof(int32_t) * nsp_r));
         HIPC(r_lmask.alloc(sizeof(uint32_t) * (size_t)prb_G * nbr * 2));
@@ -288,8 +284,7 @@ int spfm_engine::ensure_relax() {
         // (on the handle's own stream: a copy on the null stream would create that stream,
         // which then holds one of the process's few hardware queues for good -- and
         // concurrent fits, one stream each, end up two to a queue)
-        HIPC(hipMemcpyAsync(hv.data(), cval.p, sizeof(T) * (size_t)nnz, hipMemcpyDeviceToHost,
-                            stream));
+        SPFM_TRY(download(hv.data(), cval.p, (size_t)nnz));
         HIPC(hipStreamSynchronize(stream));
         for (size_t c = 0; c < ncf; ++c) {
             hcf[c].row = cf_row[c];
@@ -310,21 +305,15 @@ int spfm_engine::ensure_relax() {
     HIPC(r_clist.alloc(sizeof(int16_t) * clist.size() + 16));
     HIPC(r_cslab.alloc(sizeof(double) * 2 * 64 * 8));
     if (!dev_stream) {
-        HIPC(hipMemcpyAsync(r_sp.p, sp.data(), sizeof(int32_t) * sp.size(), hipMemcpyHostToDevice,
-                            stream));
-        HIPC(hipMemcpyAsync(r_lmask.p, lmask.data(), sizeof(uint32_t) * lmask.size(),
-                            hipMemcpyHostToDevice, stream));
+        SPFM_TRY(upload_to(r_sp.p, sp.data(), sp.size()));
+        SPFM_TRY(upload_to(r_lmask.p, lmask.data(), lmask.size()));
     }
-    HIPC(hipMemcpyAsync(r_cfptr.p, cf_ptr.data(), sizeof(int32_t) * cf_ptr.size(),
-                        hipMemcpyHostToDevice, stream));
-    HIPC(hipMemcpyAsync(r_cf.p, hcf.data(), sizeof(PrbConf<T>) * hcf.size(),
-                        hipMemcpyHostToDevice, stream));
-    HIPC(hipMemcpyAsync(r_clist.p, clist.data(), sizeof(int16_t) * clist.size(),
-                        hipMemcpyHostToDevice, stream));
+    SPFM_TRY(upload_to(r_cfptr.p, cf_ptr.data(), cf_ptr.size()));
+    SPFM_TRY(upload_to(r_cf.p, hcf.data(), hcf.size()));
+    SPFM_TRY(upload_to(r_clist.p, clist.data(), clist.size()));
     if (ne > 0) {
         if (!dev_stream)
-            HIPC(hipMemcpyAsync(d_src.p, src.data(), sizeof(int32_t) * ne, hipMemcpyHostToDevice,
-                                stream));
+            SPFM_TRY(upload_to(d_src.p, src.data(), ne));
         hipLaunchKernelGGL((prb_gather_kernel<T>), dim3(cdiv((int64_t)ne, 256)), dim3(256), 0,
                            stream, (int64_t)ne, d_src.as<int32_t>(), cidx.as<int32_t>(),
                            cval.as<T>(), r_erow.as<int32_t>(), r_eval.as<T>());

@@ -93,8 +93,7 @@ int spfm_engine::psgd_epoch_tl(int degree, double alpha, double beta, double gam
         HIPC(sg_sched.alloc(sizeof(PsgdBatch) * (size_t)nbat));
         HIPC(sg_idx.alloc(sizeof(int) * 4));
         if (sg_sched.p != old) clear_graphs();
-        HIPC(hipMemcpyAsync(sg_sched.p, h_sched.data(), sizeof(PsgdBatch) * (size_t)nbat,
-                            hipMemcpyHostToDevice, stream));
+        SPFM_TRY(upload_to(sg_sched.p, h_sched.data(), (size_t)nbat));
         HIPC(hipMemsetAsync(sg_idx.p, 0, sizeof(int) * 4, stream));  // idx[0..1], idx[2] = failed
         const size_t np = (size_t)n_orders * k * d;
         if (mich) {  // snapshot for the (rare) eager redo
@@ -153,8 +152,7 @@ int spfm_engine::psgd_epoch_tl(int degree, double alpha, double beta, double gam
         HIPC(hipGetLastError());
         int failed = 0;
         if (mich)
-            HIPC(hipMemcpyAsync(&failed, sg_idx.as<int>() + 2, sizeof(int),
-                                hipMemcpyDeviceToHost, stream));
+            SPFM_TRY(download(&failed, sg_idx.as<int>() + 2, 1));
         HIPC(hipStreamSynchronize(stream));  // h_sched may be rewritten by the next epoch
         if (!failed) {
             *it += nbat;
@@ -225,8 +223,7 @@ int spfm_engine::psgd_epoch_tl(int degree, double alpha, double beta, double gam
                 }
                 hipLaunchKernelGGL(psgd_mich_check_kernel, dim3(1), dim3(kBlock), 0, stream,
                                    ms);
-                HIPC(hipMemcpyAsync(h_done, sg_done.p, sizeof(int), hipMemcpyDeviceToHost,
-                                    stream));
+                SPFM_TRY(download(h_done, sg_done.p, 1));
                 HIPC(hipStreamSynchronize(stream));
                 if (*h_done) break;
                 if (guard > d) FAIL(SPFM_ERR_RUNTIME, "psgd: prox support search did not settle");
@@ -298,22 +295,14 @@ int spfm_engine::psgd_epoch(int degree, double alpha, double beta, double gamma,
         indices_samples = local.data();
     }
     if (n > 0) {
-        HIPC(hipMemcpyAsync(sg_samples.p, indices_samples, sizeof(int32_t) * (size_t)n,
-                            hipMemcpyHostToDevice, stream));
+        SPFM_TRY(upload_to(sg_samples.p, indices_samples, (size_t)n));
         HIPC(hipStreamSynchronize(stream));  // caller may reuse indices_samples
     }
-#define SPFM_PSGD_GO(T, L)                                                                    \
-rc = psgd_epoch_tl<T, L>(degree, alpha, beta, gamma, eta0, lr, power_t, batch_size,        \
-                         fit_linear, it)
-    if (dtype == SPFM_F32) {
-        if (k <= 16) SPFM_PSGD_GO(float, 16);
-        else if (k <= 32) SPFM_PSGD_GO(float, 32);
-        else SPFM_PSGD_GO(float, 64);
-    } else {
-        if (k <= 16) SPFM_PSGD_GO(double, 16);
-        else if (k <= 32) SPFM_PSGD_GO(double, 32);
-        else SPFM_PSGD_GO(double, 64);
-    }
+#define SPFM_PSGD_GO(L)                                                                     \
+    psgd_epoch_tl<T, L>(degree, alpha, beta, gamma, eta0, lr, power_t, batch_size, fit_linear, it)
+    rc = SPFM_DISPATCH(dtype, return k <= 16   ? SPFM_PSGD_GO(16)
+                                     : k <= 32 ? SPFM_PSGD_GO(32)
+                                               : SPFM_PSGD_GO(64));
 #undef SPFM_PSGD_GO
     if (rc) return rc;
     hipLaunchKernelGGL(reduce_partial_kernel, dim3(256), dim3(kBlock), 0, stream,
@@ -325,7 +314,7 @@ rc = psgd_epoch_tl<T, L>(degree, alpha, beta, gamma, eta0, lr, power_t, batch_si
         rc = allreduce(scalar.as<double>(), 1);
         if (rc) return rc;
     }
-    HIPC(hipMemcpyAsync(h_scalar, scalar.p, sizeof(double), hipMemcpyDeviceToHost, stream));
+    SPFM_TRY(download(h_scalar, scalar.p, 1));
     HIPC(hipStreamSynchronize(stream));
     prof_collect();
     if (sum_loss) *sum_loss = h_scalar[0];

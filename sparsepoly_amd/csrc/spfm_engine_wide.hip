@@ -56,8 +56,7 @@ int spfm_engine::ensure_wide() {
     HIPC(prb_viol.alloc(sizeof(double) * (size_t)d));
     HIPC(prb_cn.alloc(sizeof(double) * (size_t)d));
     HIPC(hipMemsetAsync(prb_abort.p, 0, sizeof(unsigned) * 4, stream));
-    HIPC(hipMemcpyAsync(w_wbase.p, wbase.data(), sizeof(int32_t) * wbase.size(),
-                        hipMemcpyHostToDevice, stream));
+    SPFM_TRY(upload_to(w_wbase.p, wbase.data(), wbase.size()));
     // the stream: on the device (spfm_ingest.hip device_wide_stream: the host builder's tables
     // exactly, tests/test_hip_stream.py) or by the host threads
     wide_stream_device_used = 0;
@@ -73,12 +72,10 @@ int spfm_engine::ensure_wide() {
         std::vector<int32_t> wb2, wsp, src;
         std::vector<uint8_t> hz;
         build_wide_stream(n, h_cptr.data(), h_cidx.data(), order, batch_ptr, G, wb2, wsp, src, hz);
-        HIPC(hipMemcpyAsync(w_wsp.p, wsp.data(), sizeof(int32_t) * wsp.size(),
-                            hipMemcpyHostToDevice, stream));
+        SPFM_TRY(upload_to(w_wsp.p, wsp.data(), wsp.size()));
         if (nnz > 0) {
-            HIPC(hipMemcpyAsync(d_src.p, src.data(), sizeof(int32_t) * (size_t)nnz,
-                                hipMemcpyHostToDevice, stream));
-            HIPC(hipMemcpyAsync(d_hz.p, hz.data(), (size_t)nnz, hipMemcpyHostToDevice, stream));
+            SPFM_TRY(upload_to(d_src.p, src.data(), (size_t)nnz));
+            SPFM_TRY(upload_to(d_hz.p, hz.data(), (size_t)nnz));
         }
         HIPC(hipStreamSynchronize(stream));  // the host staging vectors die here
     }
