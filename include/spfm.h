@@ -61,6 +61,7 @@ typedef struct spfm_engine* spfm_handle;
 /* coordinate schedules (spfm_set_schedule) */
 #define SPFM_SCHED_EXACT 0   /* keep the given order; batch = maximal run of row-disjoint columns */
 #define SPFM_SCHED_COLORED 1 /* first-fit colouring of the column conflict graph; order is permuted */
+#define SPFM_SCHED_COLORED_RLF 2 /* RLF colouring: fewer classes, longer set-up; order is permuted */
 
 #define SPFM_MAX_DEGREE 6
 
@@ -147,7 +148,16 @@ int spfm_predict_csr(spfm_handle h, int64_t n, const int64_t* indptr, const int3
  *     NULL to use the local data (single process).  Multi-GPU: pass the GLOBAL
  *     structure so that all ranks derive the identical schedule.
  *   order_out[d]: the order actually used (== indices_feature for EXACT).
- *   n_batches_out: number of dependent steps per sweep. */
+ *   n_batches_out: number of dependent steps per sweep.
+ * SPFM_SCHED_COLORED_RLF is accepted wherever SPFM_SCHED_COLORED is and yields the same product
+ * under the same class caps, with fewer classes (hence fewer dependent steps per sweep) for a
+ * longer set-up.  It builds one class at a time as a maximal independent set: the first member
+ * maximises the sum, over its rows, of the uncoloured columns on the row; every later member
+ * maximises the sum, over its rows, of the candidates that already left the class on that row (a
+ * candidate leaves when it shares a row with a member); ties go to the column that comes first
+ * in indices_feature.  Integer keys: the device form ("colour_device", the same size threshold
+ * as the first fit; SPFM_RLF_DEVICE=1 in the environment lifts the threshold, for tests) equals
+ * the host form exactly.  Opt-in: SPFM_SCHED_COLORED is unchanged. */
 int spfm_set_schedule(spfm_handle h, int mode, const int32_t* indices_feature,
                       const int64_t* conflict_indptr, const int32_t* conflict_indices,
                       int64_t conflict_n_rows, int32_t* order_out, int32_t* n_batches_out);

@@ -78,7 +78,7 @@ LOSSES = {"squared": 0, "squared_hinge": 1, "logistic": 2}
 REGULARIZERS = {"l1": 0, "l21": 1, "squaredl12": 2, "squaredl21": 3, "omegati": 4, "omegacs": 5}
 SOLVERS = {"pcd": 0, "pbcd": 1, "psgd": 2}
 LEARNING_RATE = {"constant": 0, "optimal": 1, "pegasos": 2, "invscaling": 3}
-SCHEDULES = {"exact": 0, "colored": 1}
+SCHEDULES = {"exact": 0, "colored": 1, "colored_rlf": 2}
 GRAM_KINDS = {"anova": 0, "poly": 1, "all-subsets": 2}  # SPFM_GRAM_*
 GRAM_MAX_DEGREE = 64  # SPFM_GRAM_MAX_DEGREE
 

@@ -40,6 +40,8 @@ void schedule_exact(int64_t, int32_t, const int64_t*, const int32_t*, const int3
                     std::vector<int32_t>&);
 void schedule_colored(int64_t, int32_t, const int64_t*, const int32_t*, const int32_t*, int,
                       std::vector<int32_t>&, std::vector<int32_t>&);
+void schedule_rlf(int64_t, int32_t, const int64_t*, const int32_t*, const int32_t*, int,
+                  std::vector<int32_t>&, std::vector<int32_t>&);
 bool csr_to_csc(int64_t, int32_t, const int64_t*, const int32_t*, std::vector<int64_t>&,
                 std::vector<int32_t>&, std::vector<int64_t>&);
 int schedule_threads();
@@ -84,6 +86,10 @@ hipError_t device_wide_stream(int64_t, int32_t, int64_t, int, int, const int32_t
 // spfm_colour.hip: the first-fit colouring on the device (same result as schedule_colored)
 hipError_t device_first_fit(int64_t, int32_t, int64_t, const int64_t*, const int32_t*, const int64_t*,
                             const int32_t*, int, int32_t*, int*, int*, hipStream_t);
+// ... and the RLF colouring (same result as schedule_rlf)
+hipError_t device_rlf(int64_t, int32_t, int64_t, const int64_t*, const int32_t*, const int64_t*,
+                      const int32_t*, int, std::vector<int32_t>&, std::vector<int32_t>&, int*,
+                      hipStream_t);
 }  // namespace spfm
 
 using namespace spfm;
@@ -659,7 +665,7 @@ struct spfm_engine {
     bool stream_device = true;   // the 64-column pass's entry stream built on the device
     int stream_device_used = 0;
     int pb_stream_device_used = 0, wide_stream_device_used = 0;  // the pbcd / wide entry streams
-    int colour_columns(int64_t rows, const int64_t* cp, const int32_t* ci, bool own,
+    int colour_columns(int mode, int64_t rows, const int64_t* cp, const int32_t* ci, bool own,
                        const int32_t* jf, int max_batch);
 
     int set_schedule(int mode, const int32_t* indices_feature, const int64_t* cf_indptr,

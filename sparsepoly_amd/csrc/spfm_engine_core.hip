@@ -513,9 +513,30 @@ int spfm_engine::alloc_work() {
     return SPFM_OK;
 }
 
-int spfm_engine::colour_columns(int64_t rows, const int64_t* cp, const int32_t* ci, bool own,
-                   const int32_t* jf, int max_batch) {
+int spfm_engine::colour_columns(int mode, int64_t rows, const int64_t* cp, const int32_t* ci,
+                   bool own, const int32_t* jf, int max_batch) {
     colour_device_used = 0;
+    if (mode == SPFM_SCHED_COLORED_RLF) {
+        // the device form sits behind the first-fit form's size threshold (below it the host loop
+        // is faster than the launches); SPFM_RLF_DEVICE=1 in the environment lifts the threshold
+        // so that small problems can exercise the kernels (tests/test_hip_colour_rlf.py)
+        const char* env = std::getenv("SPFM_RLF_DEVICE");
+        const bool any_size = env && env[0] == '1';
+        if (own && colour_device && (any_size || (d >= 4096 && nnz >= (1 << 20))) &&
+            nnz < ((int64_t)1 << 31) && rptr.p && cptr.p) {
+            int failed = 0;
+            const hipError_t e = device_rlf(n, d, nnz, cptr.as<int64_t>(), cidx.as<int32_t>(),
+                                            rptr.as<int64_t>(), jf, std::max(1, max_batch), order,
+                                            batch_ptr, &failed, stream);
+            if (e == hipSuccess && !failed) {
+                colour_device_used = 1;
+                return SPFM_OK;
+            }
+            (void)hipGetLastError();
+        }
+        schedule_rlf(rows, d, cp, ci, jf, std::max(1, max_batch), order, batch_ptr);
+        return SPFM_OK;
+    }
     if (own && colour_device && d >= 4096 && nnz >= (1 << 20) && nnz < ((int64_t)1 << 31) &&
         (int64_t)d / std::max(1, max_batch) < 3500 && rptr.p && cptr.p) {
         std::vector<int32_t> col((size_t)d);
@@ -566,8 +587,8 @@ int spfm_engine::set_schedule(int mode, const int32_t* indices_feature, const in
     if (mode == SPFM_SCHED_EXACT) {
         order.assign(indices_feature, indices_feature + d);
         schedule_exact(rows, d, cp, ci, indices_feature, max_batch, batch_ptr);
-    } else if (mode == SPFM_SCHED_COLORED) {
-        colour_columns(rows, cp, ci, !cf_indptr, indices_feature, max_batch);
+    } else if (mode == SPFM_SCHED_COLORED || mode == SPFM_SCHED_COLORED_RLF) {
+        colour_columns(mode, rows, cp, ci, !cf_indptr, indices_feature, max_batch);
         if (pers && max_batch > 64 && batch_ptr.size() > 1) {
             // A wide step costs about twice a 64-column step (two fabric hops, 7.0 vs 3.2 us
             // on one GPU): classes of moderate width are cheaper as more, narrower steps.
@@ -601,7 +622,7 @@ int spfm_engine::set_schedule(int mode, const int32_t* indices_feature, const in
             const bool rows_fit = dtype == SPFM_F32 && prb_lds && lds_lr <= (size_t)lds_max;
             const double limit = rows_fit ? (double)wide_min_cols : 0.72 * (double)wide_min_cols;
             if (widest > 64 && mean_cols < limit)
-                colour_columns(rows, cp, ci, !cf_indptr, indices_feature, 64);
+                colour_columns(mode, rows, cp, ci, !cf_indptr, indices_feature, 64);
         }
     } else {
         FAIL(SPFM_ERR_INVALID, "set_schedule: unknown mode");
@@ -1135,6 +1156,8 @@ int spfm_schedule_build(int mode, int64_t n_rows, int32_t d, const int64_t* indp
         schedule_exact(n_rows, d, indptr, indices, indices_feature, max_batch, bp);
     } else if (mode == SPFM_SCHED_COLORED) {
         schedule_colored(n_rows, d, indptr, indices, indices_feature, max_batch, order, bp);
+    } else if (mode == SPFM_SCHED_COLORED_RLF) {
+        schedule_rlf(n_rows, d, indptr, indices, indices_feature, max_batch, order, bp);
     } else {
         return SPFM_ERR_INVALID;
     }

@@ -436,6 +436,84 @@ void schedule_colored_parallel(int64_t n_rows, int32_t d, const int64_t* cptr, c
     if (batch_ptr.size() == 1) batch_ptr.push_back(0);
 }
 
+// COLORED_RLF: "recursive largest first" on the implicit conflict graph -- one class at a time, as
+// a maximal independent set (at most max_batch columns).  All keys are integer sums of per-row
+// counters, so the device form (spfm_colour.hip, device_rlf) reproduces this result exactly; this
+// single-threaded loop is the definition.
+//   urow[i]  uncoloured columns on row i (over the whole colouring)
+//   wrow[i]  per class: columns on row i that were candidates of the class and left it because
+//            they share a row with a member
+// One class: cand = the uncoloured columns, wrow = 0.  The first member maximises
+// sum_{i in rows(j)} urow[i], every later one sum_{i in rows(j)} wrow[i] over cand; ties go to
+// the column that comes first in `order` (the visiting order).  A member v leaves cand, and so
+// does every candidate u that shares a row with v -- each such u adds 1 to wrow on all its rows.
+// The class closes at max_batch members or when cand is empty.  The keys count row incidences,
+// not distinct neighbours: no adjacency is ever built.  Classes are emitted in the order they
+// were built, their columns in visiting order (as schedule_colored orders a class).
+// Cost: cand shrinks geometrically with every member, so a class reads a small multiple of the
+// uncoloured entries; the work follows the compacted `cand`, never d.
+void schedule_rlf(int64_t n_rows, int32_t d, const int64_t* cptr, const int32_t* cidx,
+                  const int32_t* order, int max_batch, std::vector<int32_t>& out_order,
+                  std::vector<int32_t>& batch_ptr) {
+    std::vector<int32_t> urow((size_t)n_rows, 0), wrow((size_t)n_rows, 0), mark((size_t)n_rows, 0);
+    for (int64_t ii = 0; ii < cptr[d]; ++ii) urow[(size_t)cidx[ii]]++;
+    std::vector<char> coloured((size_t)d, 0);  // by visiting position
+    std::vector<int32_t> cand, members;
+    cand.reserve((size_t)d);
+    out_order.clear();
+    out_order.reserve((size_t)d);
+    batch_ptr.assign(1, 0);
+    int32_t n_done = 0, stamp = 0;
+    while (n_done < d) {
+        cand.clear();
+        for (int32_t pos = 0; pos < d; ++pos)
+            if (!coloured[(size_t)pos]) cand.push_back(pos);
+        std::fill(wrow.begin(), wrow.end(), 0);
+        members.clear();
+        while (!cand.empty() && (int)members.size() < max_batch) {
+            const int32_t* cnt = members.empty() ? urow.data() : wrow.data();
+            int64_t best_key = -1;
+            int32_t best = -1;
+            for (const int32_t pos : cand) {  // ascending positions: the first maximum wins
+                const int32_t j = order[pos];
+                int64_t key = 0;
+                for (int64_t ii = cptr[j]; ii < cptr[j + 1]; ++ii) key += cnt[(size_t)cidx[ii]];
+                if (key > best_key) {
+                    best_key = key;
+                    best = pos;
+                }
+            }
+            ++stamp;
+            const int32_t v = order[best];
+            for (int64_t ii = cptr[v]; ii < cptr[v + 1]; ++ii) {
+                mark[(size_t)cidx[ii]] = stamp;
+                urow[(size_t)cidx[ii]]--;
+            }
+            coloured[(size_t)best] = 1;
+            members.push_back(best);
+            size_t kept = 0;
+            for (const int32_t pos : cand) {
+                if (pos == best) continue;
+                const int32_t u = order[pos];
+                bool hit = false;
+                for (int64_t ii = cptr[u]; ii < cptr[u + 1] && !hit; ++ii)
+                    hit = mark[(size_t)cidx[ii]] == stamp;
+                if (!hit) {
+                    cand[kept++] = pos;
+                    continue;
+                }
+                for (int64_t ii = cptr[u]; ii < cptr[u + 1]; ++ii) wrow[(size_t)cidx[ii]]++;
+            }
+            cand.resize(kept);
+        }
+        std::sort(members.begin(), members.end());
+        for (const int32_t pos : members) out_order.push_back(order[pos]);
+        n_done += (int32_t)members.size();
+        batch_ptr.push_back(n_done);
+    }
+    if (batch_ptr.size() == 1) batch_ptr.push_back(0);
+}
+
 // threads for the parallel colouring: SPFM_THREADS, else min(hardware, 16); 1 = sequential
 int schedule_threads() {
     if (const char* e = std::getenv("SPFM_THREADS")) {

@@ -20,6 +20,7 @@ from sklearn.utils import check_random_state
 from sklearn.utils.validation import NotFittedError, check_array
 
 from .base import BaseSparsePoly, SparsePolyClassifierMixin, SparsePolyRegressorMixin
+from . import _capi
 from .engine import HipEngine, canonical_csc
 from .loss import CLASSIFICATION_LOSSES, REGRESSION_LOSSES
 from .interactions import InteractionMixin
@@ -93,8 +94,9 @@ class _BaseSparseAllSubsets(ObjectiveMixin, InteractionMixin, BaseSparsePoly, me
         if self.solver not in ("pcd", "pbcd"):
             msg = f"Solver {self.solver} is not supported."
             raise ValueError(msg)
-        if not isinstance(self.schedule, Schedule) and self.schedule not in ("exact", "colored"):
-            raise ValueError("schedule must be 'exact', 'colored' or a Schedule object.")
+        if not isinstance(self.schedule, Schedule) and self.schedule not in _capi.SCHEDULES:
+            raise ValueError("schedule must be 'exact', 'colored', 'colored_rlf' or a Schedule "
+                             "object.")
         if isinstance(self.schedule, Schedule) and self.shuffle:
             raise ValueError("a fixed Schedule cannot be combined with shuffle=True.")
         beta = self.beta * n_samples if self.mean else self.beta

@@ -21,6 +21,9 @@ Additional keywords (after the reference's, so positional use is unchanged):
                colour classes are visited one after another -- the same algorithm
                run in the permuted order ``feature_order_`` (the reference's epoch
                functions take any order, pcd.py:86-87).
+               'colored_rlf': as 'colored', with the classes built by an RLF colouring
+               (one maximal independent set at a time): fewer classes, hence fewer
+               dependent steps per sweep, for a longer set-up.
 ``precision``  'f32' (default) stores X, the ANOVA caches and y_pred in float32
                (reductions, prox and parameters stay float64); 'f64' stores them
                in float64.
@@ -44,6 +47,7 @@ from sklearn.utils import check_random_state
 from sklearn.utils.validation import NotFittedError, check_array
 
 from .base import BaseSparsePoly, SparsePolyClassifierMixin, SparsePolyRegressorMixin
+from . import _capi
 from . import engine as _engine_mod
 from .engine import HipEngine, canonical_csc
 from .schedule import Schedule
@@ -197,7 +201,7 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, BaseSpar
         if isinstance(self.schedule, Schedule):
             order = engine.install_schedule(self.schedule, conflict_csc)
             self.schedule_ = self.schedule
-        elif conflict_csc is None and self.schedule == "colored" and \
+        elif conflict_csc is None and self.schedule in ("colored", "colored_rlf") and \
                 getattr(self, "_struct_key", None) is not None:
             # a colouring is a function of the matrix structure and the visiting order (and of
             # what decides the step width): concurrent fits on one data set
@@ -436,8 +440,9 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, BaseSpar
         if self.solver == "psgd":
             if not (self.warm_start and hasattr(self, "it_")):
                 self.it_ = 1  # :411-412
-        if not isinstance(self.schedule, Schedule) and self.schedule not in ("exact", "colored"):
-            raise ValueError("schedule must be 'exact', 'colored' or a Schedule object.")
+        if not isinstance(self.schedule, Schedule) and self.schedule not in _capi.SCHEDULES:
+            raise ValueError("schedule must be 'exact', 'colored', 'colored_rlf' or a Schedule "
+                             "object.")
         if isinstance(self.schedule, Schedule) and self.shuffle:
             raise ValueError("a fixed Schedule cannot be combined with shuffle=True.")
 
@@ -446,7 +451,8 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, BaseSpar
         csr_direct = sp.isspmatrix_csr(X) and X.has_canonical_format and not self.distributed
         Xc = None if csr_direct else canonical_csc(X)
         self._struct_key = None
-        if self.schedule == "colored" and not self.distributed and not self.shuffle:
+        if self.schedule in ("colored", "colored_rlf") and not self.distributed and \
+                not self.shuffle:
             self._struct_key = _engine_mod.structure_key(X if csr_direct else Xc)
         conflict_csc = None
         # warm_start keeps the device session: same data => no re-upload,
