@@ -593,6 +593,64 @@ int spfm_interaction_values(spfm_handle h, int order_idx, int64_t L, const int32
 int spfm_interaction_block(spfm_handle h, int order_idx, int64_t nJ, const int32_t* J,
                            int64_t nJ2, const int32_t* J2, double* out);
 
+/* -- third-order interaction weights of the live parameters ----------------------------------
+ * Which feature TRIPLES the fitted model kept.  For the block P_o = P[order_idx] (k x d),
+ *   T[a, j, l] = sum_s lams_s p_sa p_sj p_sl,   only a < j < l counts;
+ * T[a, j, l] is the coefficient of x_a x_j x_l when P_o is the degree-3 block of a factorization
+ * machine or the block of an all-subsets model.  T has d^3 / 6 entries and is NEVER formed: the
+ * pair entries' compaction and packed images are reused, and for every smallest member a (the
+ * "pivot") the 64 x 64 tiles of T[a, :, :] -- the pair product with the second operand scaled by
+ * p_.a -- are formed in registers (f64 matrix instructions) and consumed there.  A work unit is
+ * (pair tile, block of 64 pivots).  Device scratch is that of the pair entries (the same
+ * buffers, freed by the same three things): O(d_a k + min(units, 2^18) + units / 4096 + K), and
+ * units / 4096 stays below the pair-tile count under the work guard below.  The cost is
+ * d_a^3 k / 3 flops per pass.
+ * Semantics are those of the pair entries word for word: parameters only (no data, no
+ * spfm_configure), the LIVE image in either layout, read-only, f64 arithmetic for either storage
+ * precision, ids of the block as stored, every rank answers locally.
+ *
+ * Deterministic: in every entry, on every call and for every launch partition and tile budget
+ *   T[a, j, l] = sum_s A[j][s] * (B[l][s] * A[a][s]),  A = the packed block, B = diag(lams) A,
+ * with the smallest id as the pivot, the product in brackets rounded on its own and the sum the
+ * same chain of matrix-instruction steps over s = 0, 4, 8, ...; sums over triples are reduced in
+ * a fixed unit order without float atomics.
+ *
+ * Options: the pair entries' keys, none of its own.  "interaction_tile_budget" counts units per
+ * launch here (0 = default, 2^18), "interaction_launches" the unit launches of the last pass,
+ * "interaction_features" restricts stats / topk / list to the features [0, n),
+ * "interaction_scratch_kib" and "interaction_release" cover the shared scratch.
+ *
+ * Work guard: with more than SPFM_INTERACTION3_MAX_ACTIVE active features in view, stats / topk /
+ * list return SPFM_ERR_UNSUPPORTED before any product pass; the message names d_a and points to
+ * "interaction_features".  At the cap and k = 30 a pass is about 3.5e14 flops; at the 28 TFLOP/s
+ * the PAIR pass measured that would be roughly 12 s.  That figure is an extrapolation: nobody
+ * has measured a triple pass at the cap.
+ *
+ * spfm_interaction3_stats: counts2 = {triples with |T| > tol, active features d_a},
+ *   sums3 = {sum T^2, sum |T|, max |T|} over a < j < l.  tol >= 0; tol = 0 counts T != 0.
+ * spfm_interaction3_topk: the K triples of largest |T| among T != 0, ordered by |T| descending,
+ *   then i, j, l ascending; i[K] < j[K] < l[K], vals[K] (signed); *n_out = triples written (< K
+ *   when fewer exist).  Exact: the pair entries' radix select on the f64 patterns of |T|, then one
+ *   pass that emits the candidates.  More than max(2^20, 2K) triples tied with the K-th magnitude
+ *   -> SPFM_ERR_UNSUPPORTED.
+ * spfm_interaction3_list: every triple with |T| > tol as (i, j, l, vals), sorted by (i, j, l);
+ *   *n_out = their number.  If it exceeds `capacity` the call fails (SPFM_ERR_INVALID, the count
+ *   is in *n_out and in the message) and writes nothing to i / j / l / vals.
+ * spfm_interaction3_values: vals[q] = T[i[q], j[q], l[q]] for L given triples, the three ids in
+ *   any order (sorted on the device; the smallest is the pivot); any two equal ids give 0.
+ *   Components are summed in order s = 0..k-1.
+ * Errors: no parameters, bad order_idx, id out of range, negative tol / K / capacity ->
+ * SPFM_ERR_INVALID. */
+#define SPFM_INTERACTION3_MAX_ACTIVE (1 << 15)
+int spfm_interaction3_stats(spfm_handle h, int order_idx, double tol, int64_t* counts2,
+                            double* sums3);
+int spfm_interaction3_topk(spfm_handle h, int order_idx, int64_t K, int32_t* i, int32_t* j,
+                           int32_t* l, double* vals, int64_t* n_out);
+int spfm_interaction3_list(spfm_handle h, int order_idx, double tol, int64_t capacity, int32_t* i,
+                           int32_t* j, int32_t* l, double* vals, int64_t* n_out);
+int spfm_interaction3_values(spfm_handle h, int order_idx, int64_t L, const int32_t* i,
+                             const int32_t* j, const int32_t* l, double* vals);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,8 +99,11 @@ SYMBOLS = [
     "spfm_objective_terms", "spfm_set_eval_csr", "spfm_eval_loss",
     "spfm_interaction_stats", "spfm_interaction_topk", "spfm_interaction_list",
     "spfm_interaction_values", "spfm_interaction_block",
+    "spfm_interaction3_stats", "spfm_interaction3_topk", "spfm_interaction3_list",
+    "spfm_interaction3_values",
 ]
 INTERACTION_BLOCK_MAX_BYTES = 1 << 30  # SPFM_INTERACTION_BLOCK_MAX_BYTES
+INTERACTION3_MAX_ACTIVE = 1 << 15  # SPFM_INTERACTION3_MAX_ACTIVE
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -189,6 +192,11 @@ def load():
     L.spfm_interaction_list.argtypes = [_h, C.c_int, C.c_double, C.c_int64, _ip, _ip, _dp, _lp]
     L.spfm_interaction_values.argtypes = [_h, C.c_int, C.c_int64, _ip, _ip, _dp]
     L.spfm_interaction_block.argtypes = [_h, C.c_int, C.c_int64, _ip, C.c_int64, _ip, _dp]
+    L.spfm_interaction3_stats.argtypes = [_h, C.c_int, C.c_double, _lp, _dp]
+    L.spfm_interaction3_topk.argtypes = [_h, C.c_int, C.c_int64, _ip, _ip, _ip, _dp, _lp]
+    L.spfm_interaction3_list.argtypes = [_h, C.c_int, C.c_double, C.c_int64, _ip, _ip, _ip, _dp,
+                                         _lp]
+    L.spfm_interaction3_values.argtypes = [_h, C.c_int, C.c_int64, _ip, _ip, _ip, _dp]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in ("spfm_destroy", "spfm_last_error", "spfm_build_tag"):

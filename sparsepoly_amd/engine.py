@@ -532,6 +532,59 @@ class HipEngine(object):
             out.ctypes.data_as(_capi._dp)))
         return out
 
+    # ------------------------- third-order weights T[a, j, l] = sum_s lams_s p_sa p_sj p_sl (spfm.h)
+    def interaction3_stats(self, order_idx, tol=0.0, n_features=None):
+        """``spfm_interaction3_stats``: dict ``nnz`` (triples a < j < l with ``|T| > tol``),
+        ``active_features``, ``sum_sq``, ``sum_abs``, ``max_abs`` of the LIVE block
+        (``n_features``: of its first features only)."""
+        with self._interaction_features(n_features):
+            cnt = np.zeros(2, dtype=np.int64)
+            sums = np.zeros(3)
+            self._check(self._lib.spfm_interaction3_stats(
+                self._h, int(order_idx), float(tol), cnt.ctypes.data_as(_capi._lp),
+                sums.ctypes.data_as(_capi._dp)))
+            return dict(nnz=int(cnt[0]), active_features=int(cnt[1]), sum_sq=float(sums[0]),
+                        sum_abs=float(sums[1]), max_abs=float(sums[2]))
+
+    def _interaction3_out(self, call, size):
+        """Runs ``call(i, j, l, vals, n_out)`` on arrays of ``size`` -> the ``n_out`` first."""
+        arrs = [np.zeros(max(size, 1), dtype=np.int32) for _ in range(3)]
+        vals = np.zeros(max(size, 1))
+        n = C.c_int64()
+        self._check(call(*[a.ctypes.data_as(_capi._ip) for a in arrs],
+                         vals.ctypes.data_as(_capi._dp), C.byref(n)))
+        return tuple(a[:n.value].copy() for a in arrs) + (vals[:n.value].copy(),)
+
+    def interaction3_topk(self, order_idx, K, n_features=None):
+        """``spfm_interaction3_topk``: ``(i, j, l, vals)`` of the K largest ``|T|`` among
+        ``T != 0`` (``i < j < l``), by ``|T|`` descending, then ``i``, ``j``, ``l``."""
+        K = int(K)
+        with self._interaction_features(n_features):
+            return self._interaction3_out(
+                lambda *out: self._lib.spfm_interaction3_topk(self._h, int(order_idx), K, *out), K)
+
+    def interaction3_list(self, order_idx, tol, capacity, n_features=None):
+        """``spfm_interaction3_list``: ``(i, j, l, vals)`` of every triple with ``|T| > tol``,
+        sorted by ``(i, j, l)``.  ``ValueError`` naming the count when it exceeds ``capacity``."""
+        capacity = int(capacity)
+        with self._interaction_features(n_features):
+            return self._interaction3_out(
+                lambda *out: self._lib.spfm_interaction3_list(
+                    self._h, int(order_idx), float(tol), capacity, *out), capacity)
+
+    def interaction3_values(self, order_idx, i, j, l):
+        """``spfm_interaction3_values``: ``T[i[q], j[q], l[q]]``, the three ids in any order (0
+        where two of them are equal)."""
+        ia, ip = _capi.i32(i)
+        ja, jp = _capi.i32(j)
+        la, lp = _capi.i32(l)
+        if ia.ndim != 1 or ia.shape != ja.shape or ia.shape != la.shape:
+            raise ValueError("i, j and l must be 1-d arrays of one length")
+        vals = np.zeros(ia.shape[0])
+        self._check(self._lib.spfm_interaction3_values(
+            self._h, int(order_idx), ia.shape[0], ip, jp, lp, vals.ctypes.data_as(_capi._dp)))
+        return vals
+
     # -------------------------------------------------------------- schedule
     def set_schedule(self, mode, indices_feature, conflict_csc=None):
         """Fix the coordinate order for the next epochs; returns the order used.

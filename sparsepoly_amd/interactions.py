@@ -12,6 +12,13 @@ the product in registers.  There is no CPU path: without the library or a GPU th
 ``InteractionMixin`` gives the estimators ``interaction_stats``, ``top_interactions``,
 ``interactions``, ``interaction_block`` and ``interaction_values``; ``support_recovery`` and
 ``estimation_error`` restate the notebook's metrics without a d x d array.
+
+Third order: ``T[a, j, l] = sum_s lams_s p_sa p_sj p_sl`` over ``a < j < l`` is the coefficient of
+``x_a x_j x_l`` for the degree-3 block of a factorization machine (``P_[0]`` for ``degree=3``, the
+explicit lower block of a higher degree) and for an all-subsets model.  ``triple_stats``,
+``top_triples``, ``triples`` and ``triple_values`` (``spfm_interaction3_*``, DESIGN.md section
+14a) never store ``T`` either; ``support_recovery3`` is ``support_recovery`` for a true support
+of triples.
 """
 import contextlib
 
@@ -22,6 +29,9 @@ from sklearn.utils.validation import NotFittedError
 _NO_DEGREE2 = ("%s: the model has no degree-2 block (degree=%d without fit_lower='explicit'); "
                "pairwise interaction weights are defined for degree=2, for the explicit lower "
                "block of a higher degree, and for all-subsets models.")
+_NO_DEGREE3 = ("%s: the model has no degree-3 block (degree=%d%s); third-order interaction weights "
+               "are defined for degree=3, for the explicit lower block of a higher degree "
+               "(fit_lower='explicit'), and for all-subsets models.")
 
 
 class InteractionMixin(object):
@@ -54,10 +64,27 @@ class InteractionMixin(object):
             n_dummy = max(0, degree - (2 if self.fit_linear else 1))
         return degree - 2, n_dummy  # order degree - deg holds degree deg
 
+    def _interaction3_block_spec(self, what):
+        """(order index of the degree-3 block, number of augmented dummy columns)"""
+        if not hasattr(self, "P_"):
+            raise NotFittedError("Estimator not fitted.")
+        degree = getattr(self, "degree", None)
+        if degree is None:  # all-subsets: one block, never augmented
+            return 0, 0
+        explicit = self.fit_lower == "explicit"
+        if degree < 3 or (degree > 3 and not explicit):
+            raise ValueError(_NO_DEGREE3 % (
+                what, degree, "" if degree < 3 else " without fit_lower='explicit'"))
+        n_dummy = 0
+        if self.fit_lower == "augment":
+            n_dummy = max(0, degree - (2 if self.fit_linear else 1))
+        return degree - 3, n_dummy  # order degree - deg holds degree deg
+
     @contextlib.contextmanager
-    def _interaction_session(self, what, include_augmented):
+    def _interaction_session(self, what, include_augmented, order=2):
         """-> (engine, order index, number of features in view)"""
-        order_idx, n_dummy = self._interaction_block_spec(what)
+        spec = self._interaction_block_spec if order == 2 else self._interaction3_block_spec
+        order_idx, n_dummy = spec(what)
         live = getattr(self, "_live", None)
         if live is None:
             cached = getattr(self, "_device_session", None)
@@ -139,6 +166,40 @@ class InteractionMixin(object):
             return (eng.interaction_stats(o, 0.0, n_features=dv),
                     eng.interaction_values(o, rows, cols))
 
+    # ---------------------------------------------------------------- third order
+    def triple_stats(self, tol=0.0, include_augmented=False):
+        """dict ``nnz`` (triples ``a < j < l`` with ``|T| > tol``; ``tol = 0``: ``T != 0``),
+        ``active_features``, ``sum_sq``, ``sum_abs``, ``max_abs`` of the third-order weights."""
+        with self._interaction_session("triple_stats()", include_augmented, 3) as (eng, o, dv):
+            return eng.interaction3_stats(o, tol, n_features=dv)
+
+    def top_triples(self, K, include_augmented=False):
+        """``(i, j, l, vals)`` of the ``K`` triples of largest ``|T|`` among ``T != 0``
+        (``i < j < l``), ordered by ``|T|`` descending, then ``i``, ``j``, ``l``; fewer than ``K``
+        when fewer exist."""
+        with self._interaction_session("top_triples()", include_augmented, 3) as (eng, o, dv):
+            return eng.interaction3_topk(o, K, n_features=dv)
+
+    def triples(self, tol=0.0, max_triples=10_000_000, include_augmented=False):
+        """Every triple with ``|T| > tol`` as arrays ``(i, j, l, vals)`` with ``i < j < l``,
+        sorted by ``(i, j, l)``.  ``ValueError`` naming the count when it exceeds
+        ``max_triples``."""
+        with self._interaction_session("triples()", include_augmented, 3) as (eng, o, dv):
+            nnz = eng.interaction3_stats(o, tol, n_features=dv)["nnz"]
+            if nnz > max_triples:
+                raise ValueError("triples(): %d triples have |T| > %g, more than max_triples=%d"
+                                 % (nnz, tol, max_triples))
+            return eng.interaction3_list(o, tol, nnz, n_features=dv)
+
+    def triple_values(self, i, j, l, include_augmented=False):
+        """``T[i[q], j[q], l[q]]`` for given triples (any order of the three ids; 0 where two of
+        them are equal)."""
+        with self._interaction_session("triple_values()", include_augmented, 3) as (eng, o, dv):
+            i = self._interaction_ids(i, dv, "i")
+            j = self._interaction_ids(j, dv, "j")
+            l = self._interaction_ids(l, dv, "l")
+            return eng.interaction3_values(o, i, j, l)
+
 
 # ------------------------------------------------------------------ the notebook's metrics
 def _true_support(W_true):
@@ -177,6 +238,30 @@ def support_recovery(est, W_true, include_augmented=False):
     recall = 0.0 if tp + fn == 0 else tp / (tp + fn)
     fscore = 0.0 if precision + recall == 0 else 2 * precision * recall / (precision + recall)
     return dict(fscore=fscore, pssr=(fp + fn) == 0, nnz=int(nnz), tp=tp, fp=fp, fn=fn)
+
+
+def support_recovery3(est, support, include_augmented=False):
+    """``support_recovery`` at third order: ``support = (i, j, l)`` are three id arrays naming the
+    true triples (any order inside a triple; repeats of a triple count once, a triple with two
+    equal ids is refused).  Same dict: ``fscore``, ``pssr``, ``nnz`` (selected triples), ``tp``,
+    ``fp``, ``fn``, with the same zero-division rules.  One ``triple_stats(0)`` call plus one
+    ``triple_values`` call on the true support; no d x d x d array is formed."""
+    i, j, l = (np.asarray(a) for a in support)
+    if not (i.ndim == j.ndim == l.ndim == 1 and i.shape == j.shape == l.shape):
+        raise ValueError("support must be three 1-d id arrays of one length")
+    t = np.sort(np.stack([i, j, l], axis=1).astype(np.int64).reshape(-1, 3), axis=1)
+    if t.size and ((t[:, 0] == t[:, 1]) | (t[:, 1] == t[:, 2])).any():
+        raise ValueError("support: the three ids of a triple must differ")
+    t = np.unique(t, axis=0) if t.size else t
+    nnz = int(est.triple_stats(0.0, include_augmented=include_augmented)["nnz"])
+    te = est.triple_values(t[:, 0], t[:, 1], t[:, 2], include_augmented=include_augmented)
+    tp = int(np.count_nonzero(te))
+    fp = nnz - tp
+    fn = int(t.shape[0]) - tp
+    precision = 0.0 if tp + fp == 0 else tp / (tp + fp)
+    recall = 0.0 if tp + fn == 0 else tp / (tp + fn)
+    fscore = 0.0 if precision + recall == 0 else 2 * precision * recall / (precision + recall)
+    return dict(fscore=fscore, pssr=(fp + fn) == 0, nnz=nnz, tp=tp, fp=fp, fn=fn)
 
 
 def estimation_error(est, W_true, scaling=True, include_augmented=False):
