@@ -3,9 +3,9 @@
 // parameters, schedule, predict, communicators, recovery, C ABI; pcd: multi-kernel pcd /
 // cd_linear and the epoch drivers; prb: persistent 64-column passes, one translation unit per
 // storage type; wide: wide persistent passes; pbcd: multi-kernel pbcd; pbprb: persistent pbcd
-// pass, one unit per storage type; psgd; gram, objective, interactions, interactions3: the
-// read-only feature units).  Every unit owns the extern "C" block of its entries.  See DESIGN.md for the execution
-// model.
+// pass, one unit per storage type; psgd; gram, objective, interactions (pairs and triples): the
+// read-only feature units).  Every unit owns the extern "C" block of its entries.  See DESIGN.md
+// for the execution model.
 #pragma once
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -35,8 +35,7 @@
 #include "spfm_psgd.hip.h"   // PsgdBatch
 
 namespace spfm {
-struct IntArgs;   // spfm_interactions.hip.h
-struct Int3Args;  // spfm_interactions3.hip.h
+struct IntArgs;  // spfm_interactions.hip.h
 void schedule_exact(int64_t, int32_t, const int64_t*, const int32_t*, const int32_t*, int,
                     std::vector<int32_t>&);
 void schedule_colored(int64_t, int32_t, const int64_t*, const int32_t*, const int32_t*, int,
@@ -94,6 +93,7 @@ hipError_t device_rlf(int64_t, int32_t, int64_t, const int64_t*, const int32_t*,
 }  // namespace spfm
 
 using namespace spfm;
+struct IntPass;  // spfm_engine_interactions.hip: what a pass over pairs or triples is
 
 typedef struct ncclComm* ncclComm_t;
 
@@ -991,12 +991,7 @@ struct spfm_engine {
     int interaction_view(const char* what, int order_idx, BlockView* v);
     int interaction_prepare(const char* what, int order_idx);
     IntArgs interaction_args();
-    template <int MODE>
-    int interaction_tiles(IntArgs a);
-    template <int MODE>
-    int interaction_tiles(IntArgs a, int64_t t0, int64_t t1);
     void interaction_release();  // frees the scratch (set_params, option "interaction_release")
-    int interaction_emit(double tol, unsigned long long thr_key, int64_t cap, int64_t* n_found);
     int interaction_stats(int order_idx, double tol, int64_t* counts2, double* sums3);
     int interaction_topk(int order_idx, int64_t K, int32_t* rows, int32_t* cols, double* vals,
                          int64_t* n_out);
@@ -1007,18 +1002,12 @@ struct spfm_engine {
     int interaction_block(int order_idx, int64_t nJ, const int32_t* J, int64_t nJ2,
                           const int32_t* J2, double* out);
 
-    // ------------------------------- third-order weights (spfm_engine_interactions3.hip)
+    // ------------------------------- third-order weights (same unit)
     // T[a, j, l] = sum_s lams_s p_sa p_sj p_sl over a < j < l, on the compaction, the packed images
     // and the scratch of the pair passes above (freed by the same three things); nothing of size
     // d_a^3 or d_a^2 is allocated.  A unit is (pair tile, pivot block); "interaction_tile_budget"
     // and "interaction_launches" count in units here.
     int interaction3_prepare(const char* what, int order_idx);  // + the work guard
-    template <int MODE>
-    int interaction3_units(Int3Args a);
-    template <int MODE>
-    int interaction3_units(Int3Args a, int64_t u0, int64_t u1);
-    int interaction3_emit(double tol, unsigned long long thr_key, int64_t cap, int64_t* n_found);
-    int interaction3_unpack(const uint64_t* keys, size_t n, int32_t* i, int32_t* j, int32_t* l);
     int interaction3_stats(int order_idx, double tol, int64_t* counts2, double* sums3);
     int interaction3_topk(int order_idx, int64_t K, int32_t* i, int32_t* j, int32_t* l,
                           double* vals, int64_t* n_out);
@@ -1026,6 +1015,21 @@ struct spfm_engine {
                           int32_t* l, double* vals, int64_t* n_out);
     int interaction3_values(int order_idx, int64_t L, const int32_t* i, const int32_t* j,
                             const int32_t* l, double* vals);
+
+    // ------------------------------- the driver both orders go through: stats, select and list of
+    // one compaction, written against an IntPass (what a pass over pairs or triples is)
+    int interaction_run(const IntPass& ps, int mode, IntArgs a);  // a whole pass
+    int interaction_run(const IntPass& ps, int mode, IntArgs a, int64_t u0, int64_t u1);
+    int interaction_emit(const IntPass& ps, double tol, unsigned long long thr_key, int64_t cap,
+                         int64_t* n_found);
+    int interaction_pass_stats(const IntPass& ps, double tol, int64_t* counts2, double* sums3);
+    int interaction_pass_topk(const IntPass& ps, int64_t K, int32_t* const* ids, double* vals,
+                              int64_t* n_out);
+    int interaction_pass_list(const IntPass& ps, double tol, int64_t capacity, int32_t* const* ids,
+                              double* vals, int64_t* n_out);
+    // IntPass::unpack: sorted keys -> the caller's id arrays (pairs: 2, triples: 3)
+    int interaction_unpack(const uint64_t* keys, size_t n, int32_t* const* ids);
+    int interaction3_unpack(const uint64_t* keys, size_t n, int32_t* const* ids);
 
     // diagnostics that need kernels of one translation unit
     int debug_stream_probe(int64_t* bytes_out);  // spfm_engine_pcd.hip

@@ -138,6 +138,118 @@ __device__ __forceinline__ void int_rec_block_reduce(IntRec& a, IntRec* red /*[4
         for (int w = 1; w < kBlock / kWave; ++w) int_rec_combine(a, red[w]);
 }
 
+// ---- the pieces int_tile_kernel and int3_tile_kernel (spfm_interactions3.hip.h) are made of ----
+
+// Chunk staging: components [kc0, kc0 + kend) of the 64 rows at Ag / Bg -> sA / sB (row stride
+// kIntLd, zeros up to kIntKC), between two barriers
+__device__ __forceinline__ void int_stage_chunk(const double* __restrict__ Ag,
+                                                const double* __restrict__ Bg, int kp, int kc0,
+                                                int kend, double* sA, double* sB) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < kIntTile * kIntKC / kBlock; ++i) {
+        const int idx = tid + i * kBlock, r = idx / kIntKC, c = idx % kIntKC;
+        const bool in = c < kend;
+        sA[r * kIntLd + c] = in ? Ag[(size_t)r * kp + kc0 + c] : 0.0;
+        sB[r * kIntLd + c] = in ? Bg[(size_t)r * kp + kc0 + c] : 0.0;
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ void int_acc_zero(int_v4d (&acc)[2][2]) {
+#pragma unroll
+    for (int ra = 0; ra < 2; ++ra)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) acc[ra][cb] = (int_v4d){0.0, 0.0, 0.0, 0.0};
+}
+
+// MFMA chunk step: the staged chunk into the wave's 32 x 32 quadrant (wave = 2 * wr + wc), four
+// accumulators.  Operand maps of v_mfma_f64_16x16x4_f64: lane l holds A[row l & 15][k = l >> 4]
+// and B[k = l >> 4][col l & 15].  PIVOT: the B fragment is scaled by pp[kk], the lane's component
+// of the pivot (one f64 multiply per fragment element); the pair form has no multiply.
+template <bool PIVOT>
+__device__ __forceinline__ void int_mfma_chunk(const double* sA, const double* sB, int kend,
+                                               const double* __restrict__ pp,
+                                               int_v4d (&acc)[2][2]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wr = wave >> 1, wc = wave & 1, l15 = lane & 15, l4 = lane >> 4;
+    const double* pa = sA + (wr * 32 + l15) * kIntLd + l4;
+    const double* pb = sB + (wc * 32 + l15) * kIntLd + l4;
+    for (int kk = 0; kk < kend; kk += 4) {
+        const double a0 = pa[kk], a1 = pa[16 * kIntLd + kk];
+        double b0 = pb[kk], b1 = pb[16 * kIntLd + kk];
+        if constexpr (PIVOT) {
+            const double ps = pp[kk];
+            b0 *= ps;
+            b1 *= ps;
+        }
+        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+    }
+}
+
+template <int MODE>
+__device__ __forceinline__ void int_hist_clear(unsigned* sHist) {
+    if constexpr (MODE == INT_HIST) {
+        for (int b = threadIdx.x; b < kIntHistBins; b += kBlock) sHist[b] = 0u;
+    }
+}
+
+// Per-value epilogue: the value w, its magnitude m (0 where the kernel's mask leaves the value
+// out) and key(), the key to emit (called for the values that are stored only).  Wave-uniform
+// control flow: every lane of the wave calls it for every value.
+template <int MODE, typename KeyFn>
+__device__ __forceinline__ void int_consume(const IntArgs& a, double w, double m, KeyFn key,
+                                            IntRec& mine, unsigned* sHist) {
+    if constexpr (MODE == INT_STATS) {
+        mine.cnt += (m > a.tol) ? 1 : 0;
+        mine.sumsq += m * m;
+        mine.sumabs += m;
+        mine.maxabs = fmax(mine.maxabs, m);
+    } else if constexpr (MODE == INT_HIST) {
+        const unsigned long long pat = (unsigned long long)__double_as_longlong(m);
+        if (m > 0.0 && (a.prefix_shift >= 64 || (pat >> a.prefix_shift) == a.prefix))
+            atomicAdd(&sHist[(unsigned)(pat >> a.bin_shift) & a.bin_mask], 1u);
+    } else {
+        const int lane = threadIdx.x & 63;
+        const unsigned long long pat = (unsigned long long)__double_as_longlong(m);
+        const bool take = m > a.tol && pat >= a.thr_key;
+        const unsigned long long mask = __ballot(take);
+        if (mask != 0ull) {  // wave-uniform
+            const int leader = __ffsll((long long)mask) - 1;
+            unsigned long long slot = 0ull;
+            if (lane == leader) slot = atomicAdd(a.counter, (unsigned long long)__popcll(mask));
+            slot = __shfl(slot, leader, kWave);
+            if (take) {
+                slot += (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
+                if (slot < a.cap) {
+                    a.keys[slot] = key();
+                    a.vals[slot] = w;
+                }
+            }
+        }
+    }
+}
+
+// Closing step of workgroup `unit`: its record (lanes, then waves in order), or its histogram
+template <int MODE>
+__device__ __forceinline__ void int_finish(const IntArgs& a, long long unit, IntRec& mine,
+                                           IntRec* red, const unsigned* sHist) {
+    if constexpr (MODE == INT_STATS) {
+        int_rec_block_reduce(mine, red);
+        if (threadIdx.x == 0) a.rec[unit - a.rec_base] = mine;
+    } else if constexpr (MODE == INT_HIST) {
+        __syncthreads();
+        for (int b = threadIdx.x; b < kIntHistBins; b += kBlock) {
+            const unsigned c = sHist[b];
+            if (c) atomicAdd(&a.hist[b], (unsigned long long)c);
+        }
+    }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void int_tile_kernel(IntArgs a) {
     __shared__ double sA[kIntTile * kIntLd];
@@ -155,45 +267,19 @@ __global__ __launch_bounds__(kBlock) void int_tile_kernel(IntArgs a) {
     while (ti > 0 && ti * T - ti * (ti - 1) / 2 > t) --ti;
     const long long tj = ti + (t - (ti * T - ti * (ti - 1) / 2));
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wr = wave >> 1, wc = wave & 1;
     const int l15 = lane & 15, l4 = lane >> 4;
 
-    if constexpr (MODE == INT_HIST) {
-        for (int b = tid; b < kIntHistBins; b += kBlock) sHist[b] = 0u;
-    }
-
+    int_hist_clear<MODE>(sHist);
     int_v4d acc[2][2];
-#pragma unroll
-    for (int ra = 0; ra < 2; ++ra)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[ra][cb] = (int_v4d){0.0, 0.0, 0.0, 0.0};
-
+    int_acc_zero(acc);
     const double* Ag = a.A + (size_t)ti * kIntTile * a.kp;
     const double* Bg = a.B + (size_t)tj * kIntTile * a.kp;
     for (int kc0 = 0; kc0 < a.kp; kc0 += kIntKC) {
         const int kend = (a.kp - kc0 < kIntKC) ? a.kp - kc0 : kIntKC;  // multiple of 4
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < kIntTile * kIntKC / kBlock; ++i) {
-            const int idx = tid + i * kBlock, r = idx / kIntKC, c = idx % kIntKC;
-            const bool in = c < kend;
-            sA[r * kIntLd + c] = in ? Ag[(size_t)r * a.kp + kc0 + c] : 0.0;
-            sB[r * kIntLd + c] = in ? Bg[(size_t)r * a.kp + kc0 + c] : 0.0;
-        }
-        __syncthreads();
-        // operand maps of v_mfma_f64_16x16x4_f64: lane l holds A[row l & 15][k = l >> 4] and
-        // B[k = l >> 4][col l & 15]
-        const double* pa = sA + (wr * 32 + l15) * kIntLd + l4;
-        const double* pb = sB + (wc * 32 + l15) * kIntLd + l4;
-        for (int kk = 0; kk < kend; kk += 4) {
-            const double a0 = pa[kk], a1 = pa[16 * kIntLd + kk];
-            const double b0 = pb[kk], b1 = pb[16 * kIntLd + kk];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
+        int_stage_chunk(Ag, Bg, a.kp, kc0, kend, sA, sB);
+        int_mfma_chunk<false>(sA, sB, kend, nullptr, acc);
     }
 
     // C/D map of the f64 form: register r of lane l is row (l >> 4) + 4 r, column l & 15
@@ -210,46 +296,15 @@ __global__ __launch_bounds__(kBlock) void int_tile_kernel(IntArgs a) {
                 const long long gj = tj * kIntTile + wc * 32 + cb * 16 + l15;
                 const double w = acc[ra][cb][r];
                 const double m = (gi < gj) ? fabs(w) : 0.0;  // diagonal tile: j < j' only
-                if constexpr (MODE == INT_STATS) {
-                    mine.cnt += (m > a.tol) ? 1 : 0;
-                    mine.sumsq += m * m;
-                    mine.sumabs += m;
-                    mine.maxabs = fmax(mine.maxabs, m);
-                } else if constexpr (MODE == INT_HIST) {
-                    const unsigned long long key = (unsigned long long)__double_as_longlong(m);
-                    if (m > 0.0 && (a.prefix_shift >= 64 || (key >> a.prefix_shift) == a.prefix))
-                        atomicAdd(&sHist[(unsigned)(key >> a.bin_shift) & a.bin_mask], 1u);
-                } else {
-                    const unsigned long long key = (unsigned long long)__double_as_longlong(m);
-                    const bool take = m > a.tol && key >= a.thr_key;
-                    const unsigned long long mask = __ballot(take);
-                    if (mask != 0ull) {  // wave-uniform
-                        const int leader = __ffsll((long long)mask) - 1;
-                        unsigned long long slot = 0ull;
-                        if (lane == leader)
-                            slot = atomicAdd(a.counter, (unsigned long long)__popcll(mask));
-                        slot = __shfl(slot, leader, kWave);
-                        if (take) {
-                            slot += (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
-                            if (slot < a.cap) {
-                                a.keys[slot] = ((unsigned long long)(unsigned)a.ids[gi] << 32) |
-                                               (unsigned long long)(unsigned)a.ids[gj];
-                                a.vals[slot] = w;
-                            }
-                        }
-                    }
-                }
+                int_consume<MODE>(
+                    a, w, m,
+                    [&] {
+                        return ((unsigned long long)(unsigned)a.ids[gi] << 32) |
+                               (unsigned long long)(unsigned)a.ids[gj];
+                    },
+                    mine, sHist);
             }
-    if constexpr (MODE == INT_STATS) {
-        int_rec_block_reduce(mine, red);
-        if (tid == 0) a.rec[t - a.rec_base] = mine;
-    } else if constexpr (MODE == INT_HIST) {
-        __syncthreads();
-        for (int b = tid; b < kIntHistBins; b += kBlock) {
-            const unsigned c = sHist[b];
-            if (c) atomicAdd(&a.hist[b], (unsigned long long)c);
-        }
-    }
+    int_finish<MODE>(a, t, mine, red, sHist);
 }
 
 // out[b] = the records [b * kIntRun, min(n, (b + 1) * kIntRun)) combined in a fixed order

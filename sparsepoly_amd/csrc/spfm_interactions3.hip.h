@@ -77,14 +77,11 @@ __global__ __launch_bounds__(kBlock) void int3_tile_kernel(Int3Args a3) {
     long long p1 = (ta == tj) ? p0 + kIntTile - 1 : p0 + kIntTile;
     if (p1 > a3.da) p1 = a3.da;
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wr = wave >> 1, wc = wave & 1;
     const int l15 = lane & 15, l4 = lane >> 4;
 
-    if constexpr (MODE == INT_HIST) {
-        for (int b = tid; b < kIntHistBins; b += kBlock) sHist[b] = 0u;
-    }
-
+    int_hist_clear<MODE>(sHist);
     IntRec mine;
     mine.cnt = 0;
     mine.sumsq = mine.sumabs = mine.maxabs = 0.0;
@@ -92,39 +89,18 @@ __global__ __launch_bounds__(kBlock) void int3_tile_kernel(Int3Args a3) {
     const double* Ag = a.A + (size_t)tj * kIntTile * a.kp;
     const double* Bg = a.B + (size_t)tl * kIntTile * a.kp;
     const bool restage = a.kp > kIntKC;  // more than one chunk: the tiles cannot stay in LDS
+    // kp is k >= 1 padded to a multiple of 4: every pivot has a chunk.  Said here so that the
+    // accumulators go from the last MFMA straight into the epilogue, with no second way in
+    __builtin_assume(a.kp > 0);
     for (long long piv = p0; piv < p1; ++piv) {
         int_v4d acc[2][2];
-#pragma unroll
-        for (int ra = 0; ra < 2; ++ra)
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) acc[ra][cb] = (int_v4d){0.0, 0.0, 0.0, 0.0};
+        int_acc_zero(acc);
         const double* pp = a.A + (size_t)piv * a.kp + l4;  // the lane's components of the pivot
         for (int kc0 = 0; kc0 < a.kp; kc0 += kIntKC) {
             const int kend = (a.kp - kc0 < kIntKC) ? a.kp - kc0 : kIntKC;  // multiple of 4
-            if (restage || piv == p0) {  // workgroup-uniform
-                __syncthreads();
-#pragma unroll
-                for (int i = 0; i < kIntTile * kIntKC / kBlock; ++i) {
-                    const int idx = tid + i * kBlock, r = idx / kIntKC, c = idx % kIntKC;
-                    const bool in = c < kend;
-                    sA[r * kIntLd + c] = in ? Ag[(size_t)r * a.kp + kc0 + c] : 0.0;
-                    sB[r * kIntLd + c] = in ? Bg[(size_t)r * a.kp + kc0 + c] : 0.0;
-                }
-                __syncthreads();
-            }
-            // operand maps as int_tile_kernel: lane l holds A[row l & 15][k = l >> 4] and
-            // B[k = l >> 4][col l & 15]; the pivot scales B at the lane's component
-            const double* pa = sA + (wr * 32 + l15) * kIntLd + l4;
-            const double* pb = sB + (wc * 32 + l15) * kIntLd + l4;
-            for (int kk = 0; kk < kend; kk += 4) {
-                const double ps = pp[kc0 + kk];
-                const double a0 = pa[kk], a1 = pa[16 * kIntLd + kk];
-                const double b0 = pb[kk] * ps, b1 = pb[16 * kIntLd + kk] * ps;
-                acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-            }
+            if (restage || piv == p0)  // workgroup-uniform
+                int_stage_chunk(Ag, Bg, a.kp, kc0, kend, sA, sB);
+            int_mfma_chunk<true>(sA, sB, kend, pp + kc0, acc);
         }
 
         // C/D map of the f64 form: register r of lane l is row (l >> 4) + 4 r, column l & 15
@@ -138,49 +114,16 @@ __global__ __launch_bounds__(kBlock) void int3_tile_kernel(Int3Args a3) {
                     const long long gl = tl * kIntTile + wc * 32 + cb * 16 + l15;
                     const double w = acc[ra][cb][r];
                     const double m = (piv < gj && gj < gl) ? fabs(w) : 0.0;  // a < j < l only
-                    if constexpr (MODE == INT_STATS) {
-                        mine.cnt += (m > a.tol) ? 1 : 0;
-                        mine.sumsq += m * m;
-                        mine.sumabs += m;
-                        mine.maxabs = fmax(mine.maxabs, m);
-                    } else if constexpr (MODE == INT_HIST) {
-                        const unsigned long long key = (unsigned long long)__double_as_longlong(m);
-                        if (m > 0.0 &&
-                            (a.prefix_shift >= 64 || (key >> a.prefix_shift) == a.prefix))
-                            atomicAdd(&sHist[(unsigned)(key >> a.bin_shift) & a.bin_mask], 1u);
-                    } else {
-                        const unsigned long long key = (unsigned long long)__double_as_longlong(m);
-                        const bool take = m > a.tol && key >= a.thr_key;
-                        const unsigned long long mask = __ballot(take);
-                        if (mask != 0ull) {  // wave-uniform
-                            const int leader = __ffsll((long long)mask) - 1;
-                            unsigned long long slot = 0ull;
-                            if (lane == leader)
-                                slot = atomicAdd(a.counter, (unsigned long long)__popcll(mask));
-                            slot = __shfl(slot, leader, kWave);
-                            if (take) {
-                                slot += (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
-                                if (slot < a.cap) {
-                                    a.keys[slot] = ((unsigned long long)piv << (2 * kInt3IdBits)) |
-                                                   ((unsigned long long)gj << kInt3IdBits) |
-                                                   (unsigned long long)gl;
-                                    a.vals[slot] = w;
-                                }
-                            }
-                        }
-                    }
+                    int_consume<MODE>(
+                        a, w, m,
+                        [&] {
+                            return ((unsigned long long)piv << (2 * kInt3IdBits)) |
+                                   ((unsigned long long)gj << kInt3IdBits) | (unsigned long long)gl;
+                        },
+                        mine, sHist);
                 }
     }
-    if constexpr (MODE == INT_STATS) {
-        int_rec_block_reduce(mine, red);
-        if (tid == 0) a.rec[u - a.rec_base] = mine;
-    } else if constexpr (MODE == INT_HIST) {
-        __syncthreads();
-        for (int b = tid; b < kIntHistBins; b += kBlock) {
-            const unsigned c = sHist[b];
-            if (c) atomicAdd(&a.hist[b], (unsigned long long)c);
-        }
-    }
+    int_finish<MODE>(a, u, mine, red, sHist);
 }
 
 // T at L triples: one thread per triple, the three ids in any order (sorted here, the smallest is

@@ -455,55 +455,49 @@ class HipEngine(object):
         """Free the device scratch the interaction calls keep between calls."""
         self.set_option("interaction_release", 1)
 
+    def _interaction_stats_dict(self, entry, order_idx, tol):
+        """The stats dictionary of ``spfm_interaction_stats`` / ``spfm_interaction3_stats``."""
+        cnt = np.zeros(2, dtype=np.int64)
+        sums = np.zeros(3)
+        self._check(entry(self._h, int(order_idx), float(tol), cnt.ctypes.data_as(_capi._lp),
+                          sums.ctypes.data_as(_capi._dp)))
+        return dict(nnz=int(cnt[0]), active_features=int(cnt[1]), sum_sq=float(sums[0]),
+                    sum_abs=float(sums[1]), max_abs=float(sums[2]))
+
+    def _interaction_out(self, call, n_ids, size):
+        """Runs ``call(ids_0, .., ids_{n_ids - 1}, vals, n_out)`` on arrays of ``size`` -> the
+        ``n_out`` first of each."""
+        arrs = [np.zeros(max(size, 1), dtype=np.int32) for _ in range(n_ids)]
+        vals = np.zeros(max(size, 1))
+        n = C.c_int64()
+        self._check(call(*[a.ctypes.data_as(_capi._ip) for a in arrs],
+                         vals.ctypes.data_as(_capi._dp), C.byref(n)))
+        return tuple(a[:n.value].copy() for a in arrs) + (vals[:n.value].copy(),)
+
     def interaction_stats(self, order_idx, tol=0.0, n_features=None):
         """``spfm_interaction_stats``: dict ``nnz`` (pairs j < j' with ``|W| > tol``),
         ``active_features``, ``sum_sq``, ``sum_abs``, ``max_abs`` of the LIVE block
         (``n_features``: of its first features only)."""
         with self._interaction_features(n_features):
-            return self._interaction_stats(order_idx, tol)
-
-    def _interaction_stats(self, order_idx, tol):
-        cnt = np.zeros(2, dtype=np.int64)
-        sums = np.zeros(3)
-        self._check(self._lib.spfm_interaction_stats(
-            self._h, int(order_idx), float(tol), cnt.ctypes.data_as(_capi._lp),
-            sums.ctypes.data_as(_capi._dp)))
-        return dict(nnz=int(cnt[0]), active_features=int(cnt[1]), sum_sq=float(sums[0]),
-                    sum_abs=float(sums[1]), max_abs=float(sums[2]))
+            return self._interaction_stats_dict(self._lib.spfm_interaction_stats, order_idx, tol)
 
     def interaction_topk(self, order_idx, K, n_features=None):
         """``spfm_interaction_topk``: ``(rows, cols, vals)`` of the K largest ``|W|`` among
         ``W != 0``, by ``|W|`` descending, then row, then column."""
-        with self._interaction_features(n_features):
-            return self._interaction_topk(order_idx, K)
-
-    def _interaction_topk(self, order_idx, K):
         K = int(K)
-        rows = np.zeros(max(K, 1), dtype=np.int32)
-        cols = np.zeros(max(K, 1), dtype=np.int32)
-        vals = np.zeros(max(K, 1))
-        n = C.c_int64()
-        self._check(self._lib.spfm_interaction_topk(
-            self._h, int(order_idx), K, rows.ctypes.data_as(_capi._ip),
-            cols.ctypes.data_as(_capi._ip), vals.ctypes.data_as(_capi._dp), C.byref(n)))
-        return rows[:n.value].copy(), cols[:n.value].copy(), vals[:n.value].copy()
+        with self._interaction_features(n_features):
+            return self._interaction_out(
+                lambda *out: self._lib.spfm_interaction_topk(self._h, int(order_idx), K, *out),
+                2, K)
 
     def interaction_list(self, order_idx, tol, capacity, n_features=None):
         """``spfm_interaction_list``: ``(rows, cols, vals)`` of every pair with ``|W| > tol``,
         sorted by (row, col).  ``ValueError`` naming the count when it exceeds ``capacity``."""
-        with self._interaction_features(n_features):
-            return self._interaction_list(order_idx, tol, capacity)
-
-    def _interaction_list(self, order_idx, tol, capacity):
         capacity = int(capacity)
-        rows = np.zeros(max(capacity, 1), dtype=np.int32)
-        cols = np.zeros(max(capacity, 1), dtype=np.int32)
-        vals = np.zeros(max(capacity, 1))
-        n = C.c_int64()
-        self._check(self._lib.spfm_interaction_list(
-            self._h, int(order_idx), float(tol), capacity, rows.ctypes.data_as(_capi._ip),
-            cols.ctypes.data_as(_capi._ip), vals.ctypes.data_as(_capi._dp), C.byref(n)))
-        return rows[:n.value].copy(), cols[:n.value].copy(), vals[:n.value].copy()
+        with self._interaction_features(n_features):
+            return self._interaction_out(
+                lambda *out: self._lib.spfm_interaction_list(
+                    self._h, int(order_idx), float(tol), capacity, *out), 2, capacity)
 
     def interaction_values(self, order_idx, rows, cols):
         """``spfm_interaction_values``: ``W[rows[q], cols[q]]`` (0 where the two ids are equal)."""
@@ -538,39 +532,25 @@ class HipEngine(object):
         ``active_features``, ``sum_sq``, ``sum_abs``, ``max_abs`` of the LIVE block
         (``n_features``: of its first features only)."""
         with self._interaction_features(n_features):
-            cnt = np.zeros(2, dtype=np.int64)
-            sums = np.zeros(3)
-            self._check(self._lib.spfm_interaction3_stats(
-                self._h, int(order_idx), float(tol), cnt.ctypes.data_as(_capi._lp),
-                sums.ctypes.data_as(_capi._dp)))
-            return dict(nnz=int(cnt[0]), active_features=int(cnt[1]), sum_sq=float(sums[0]),
-                        sum_abs=float(sums[1]), max_abs=float(sums[2]))
-
-    def _interaction3_out(self, call, size):
-        """Runs ``call(i, j, l, vals, n_out)`` on arrays of ``size`` -> the ``n_out`` first."""
-        arrs = [np.zeros(max(size, 1), dtype=np.int32) for _ in range(3)]
-        vals = np.zeros(max(size, 1))
-        n = C.c_int64()
-        self._check(call(*[a.ctypes.data_as(_capi._ip) for a in arrs],
-                         vals.ctypes.data_as(_capi._dp), C.byref(n)))
-        return tuple(a[:n.value].copy() for a in arrs) + (vals[:n.value].copy(),)
+            return self._interaction_stats_dict(self._lib.spfm_interaction3_stats, order_idx, tol)
 
     def interaction3_topk(self, order_idx, K, n_features=None):
         """``spfm_interaction3_topk``: ``(i, j, l, vals)`` of the K largest ``|T|`` among
         ``T != 0`` (``i < j < l``), by ``|T|`` descending, then ``i``, ``j``, ``l``."""
         K = int(K)
         with self._interaction_features(n_features):
-            return self._interaction3_out(
-                lambda *out: self._lib.spfm_interaction3_topk(self._h, int(order_idx), K, *out), K)
+            return self._interaction_out(
+                lambda *out: self._lib.spfm_interaction3_topk(self._h, int(order_idx), K, *out),
+                3, K)
 
     def interaction3_list(self, order_idx, tol, capacity, n_features=None):
         """``spfm_interaction3_list``: ``(i, j, l, vals)`` of every triple with ``|T| > tol``,
         sorted by ``(i, j, l)``.  ``ValueError`` naming the count when it exceeds ``capacity``."""
         capacity = int(capacity)
         with self._interaction_features(n_features):
-            return self._interaction3_out(
+            return self._interaction_out(
                 lambda *out: self._lib.spfm_interaction3_list(
-                    self._h, int(order_idx), float(tol), capacity, *out), capacity)
+                    self._h, int(order_idx), float(tol), capacity, *out), 3, capacity)
 
     def interaction3_values(self, order_idx, i, j, l):
         """``spfm_interaction3_values``: ``T[i[q], j[q], l[q]]``, the three ids in any order (0

@@ -49,42 +49,34 @@ class InteractionMixin(object):
     locally."""
 
     # ---------------------------------------------------------------- which block
-    def _interaction_block_spec(self, what):
-        """(order index of the degree-2 block, number of augmented dummy columns)"""
+    def _block_spec(self, what, deg):
+        """(order index of the degree-``deg`` block, number of augmented dummy columns)"""
         if not hasattr(self, "P_"):
             raise NotFittedError("Estimator not fitted.")
         degree = getattr(self, "degree", None)
         if degree is None:  # all-subsets: one block, never augmented
             return 0, 0
         explicit = self.fit_lower == "explicit"
-        if degree != 2 and not (explicit and degree >= 3):
-            raise ValueError(_NO_DEGREE2 % (what, degree))
-        n_dummy = 0
-        if self.fit_lower == "augment":
-            n_dummy = max(0, degree - (2 if self.fit_linear else 1))
-        return degree - 2, n_dummy  # order degree - deg holds degree deg
-
-    def _interaction3_block_spec(self, what):
-        """(order index of the degree-3 block, number of augmented dummy columns)"""
-        if not hasattr(self, "P_"):
-            raise NotFittedError("Estimator not fitted.")
-        degree = getattr(self, "degree", None)
-        if degree is None:  # all-subsets: one block, never augmented
-            return 0, 0
-        explicit = self.fit_lower == "explicit"
-        if degree < 3 or (degree > 3 and not explicit):
+        if degree < deg or (degree > deg and not explicit):
+            if deg == 2:
+                raise ValueError(_NO_DEGREE2 % (what, degree))
             raise ValueError(_NO_DEGREE3 % (
                 what, degree, "" if degree < 3 else " without fit_lower='explicit'"))
         n_dummy = 0
         if self.fit_lower == "augment":
             n_dummy = max(0, degree - (2 if self.fit_linear else 1))
-        return degree - 3, n_dummy  # order degree - deg holds degree deg
+        return degree - deg, n_dummy  # order degree - deg holds degree deg
+
+    def _interaction_block_spec(self, what):
+        return self._block_spec(what, 2)
+
+    def _interaction3_block_spec(self, what):
+        return self._block_spec(what, 3)
 
     @contextlib.contextmanager
     def _interaction_session(self, what, include_augmented, order=2):
         """-> (engine, order index, number of features in view)"""
-        spec = self._interaction_block_spec if order == 2 else self._interaction3_block_spec
-        order_idx, n_dummy = spec(what)
+        order_idx, n_dummy = self._block_spec(what, order)
         live = getattr(self, "_live", None)
         if live is None:
             cached = getattr(self, "_device_session", None)
@@ -220,6 +212,19 @@ def _true_support(W_true):
             np.asarray(vals, dtype=np.double)[order])
 
 
+def _support_metrics(nnz, tp, n_true):
+    """The support metrics from ``nnz`` selected, ``tp`` of them true and ``n_true`` true ones.
+    Zero divisions as in the notebook: precision is 0 when nothing is selected, the F-score is 0
+    when precision + recall is 0; an empty true support gives recall 0."""
+    nnz, tp = int(nnz), int(tp)
+    fp = nnz - tp
+    fn = int(n_true) - tp
+    precision = 0.0 if tp + fp == 0 else tp / (tp + fp)
+    recall = 0.0 if tp + fn == 0 else tp / (tp + fn)
+    fscore = 0.0 if precision + recall == 0 else 2 * precision * recall / (precision + recall)
+    return dict(fscore=fscore, pssr=(fp + fn) == 0, nnz=nnz, tp=tp, fp=fp, fn=fn)
+
+
 def support_recovery(est, W_true, include_augmented=False):
     """The notebook's support metrics of ``est`` against a symmetric true matrix ``W_true``
     (dense or scipy-sparse), over pairs ``j < j'``: dict ``fscore``, ``pssr`` (the supports are
@@ -230,14 +235,7 @@ def support_recovery(est, W_true, include_augmented=False):
     notebook does not meet, gives recall 0.  No d x d array is formed."""
     rows, cols, _ = _true_support(W_true)
     stats, we = est._interaction_support_query(rows, cols, include_augmented)
-    nnz = stats["nnz"]
-    tp = int(np.count_nonzero(we))
-    fp = int(nnz) - tp
-    fn = int(rows.shape[0]) - tp
-    precision = 0.0 if tp + fp == 0 else tp / (tp + fp)
-    recall = 0.0 if tp + fn == 0 else tp / (tp + fn)
-    fscore = 0.0 if precision + recall == 0 else 2 * precision * recall / (precision + recall)
-    return dict(fscore=fscore, pssr=(fp + fn) == 0, nnz=int(nnz), tp=tp, fp=fp, fn=fn)
+    return _support_metrics(stats["nnz"], int(np.count_nonzero(we)), rows.shape[0])
 
 
 def support_recovery3(est, support, include_augmented=False):
@@ -253,15 +251,9 @@ def support_recovery3(est, support, include_augmented=False):
     if t.size and ((t[:, 0] == t[:, 1]) | (t[:, 1] == t[:, 2])).any():
         raise ValueError("support: the three ids of a triple must differ")
     t = np.unique(t, axis=0) if t.size else t
-    nnz = int(est.triple_stats(0.0, include_augmented=include_augmented)["nnz"])
+    nnz = est.triple_stats(0.0, include_augmented=include_augmented)["nnz"]
     te = est.triple_values(t[:, 0], t[:, 1], t[:, 2], include_augmented=include_augmented)
-    tp = int(np.count_nonzero(te))
-    fp = nnz - tp
-    fn = int(t.shape[0]) - tp
-    precision = 0.0 if tp + fp == 0 else tp / (tp + fp)
-    recall = 0.0 if tp + fn == 0 else tp / (tp + fn)
-    fscore = 0.0 if precision + recall == 0 else 2 * precision * recall / (precision + recall)
-    return dict(fscore=fscore, pssr=(fp + fn) == 0, nnz=nnz, tp=tp, fp=fp, fn=fn)
+    return _support_metrics(nnz, int(np.count_nonzero(te)), t.shape[0])
 
 
 def estimation_error(est, W_true, scaling=True, include_augmented=False):

@@ -1,17 +1,18 @@
-// Stand-alone check of the pure-host helpers of the triple passes
-// (sparsepoly_amd/csrc/spfm_interactions3_host.h): key unpacking, the bin choice of a radix-select
-// level and the candidate order of top-K.  Meant to be built with a host sanitizer:
+// Stand-alone check of the pure-host helpers of the pair and triple passes
+// (sparsepoly_amd/csrc/spfm_interactions_host.h): the pair key split, the triple key unpacking,
+// the bin choice of a radix-select level and the candidate order of top-K.  Meant to be built
+// with a host sanitizer:
 //
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
-//       tools/check_interactions3_host.cpp -o check_interactions3_host && \
-//       ./check_interactions3_host
+//       tools/check_interactions_host.cpp -o check_interactions_host && \
+//       ./check_interactions_host
 //
 // Prints "ok" and returns 0, or reports the first failed check.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 
-#include "../sparsepoly_amd/csrc/spfm_interactions3_host.h"
+#include "../sparsepoly_amd/csrc/spfm_interactions_host.h"
 
 #define CHECK(cond)                                                     \
     do {                                                                \
@@ -28,7 +29,24 @@ static uint64_t pack(uint64_t a, uint64_t j, uint64_t l) {
 }
 
 int main() {
-    // keys: feature ids beyond 2^21 come out of the lookup, ids beyond d_a are refused
+    // pair keys: both halves keep their 32 bits, at and above 2^31 - 1 too
+    {
+        const uint32_t edge[] = {0u, 1u, 0x7ffffffeu, 0x7fffffffu, 0x80000000u, 0xffffffffu};
+        for (uint32_t r : edge)
+            for (uint32_t c : edge) {
+                int32_t row = 5, col = 5;
+                int_split_key(((uint64_t)r << 32) | (uint64_t)c, &row, &col);
+                CHECK((uint32_t)row == r && (uint32_t)col == c);
+            }
+        int32_t row = 0, col = 0;
+        int_split_key(((uint64_t)0x7fffffffu << 32) | 0x7fffffffu, &row, &col);
+        CHECK(row == INT32_MAX && col == INT32_MAX);
+        int_split_key(((uint64_t)(unsigned)3000000000u << 32) | 7u, &row, &col);
+        CHECK(row == (int32_t)3000000000u && col == 7);  // no bit of one half reaches the other
+        // the key orders pairs by (row, col)
+        CHECK((((uint64_t)1 << 32) | 0xffffffffu) < (((uint64_t)2 << 32) | 0u));
+    }
+    // triple keys: feature ids beyond 2^21 come out of the lookup, ids beyond d_a are refused
     {
         const int64_t da = (1 << 15) + 1;
         std::vector<int32_t> ids((size_t)da);
@@ -52,17 +70,17 @@ int main() {
     {
         std::vector<uint64_t> h(4096, 0);
         int64_t tail = -1, above = -1;
-        CHECK(int3_select_bin(h.data(), 4096, 0, 5, &tail, &above) == -1 && tail == 0 && above == 0);
+        CHECK(int_select_bin(h.data(), 4096, 0, 5, &tail, &above) == -1 && tail == 0 && above == 0);
         h[10] = 3;
         h[7] = 4;
         h[0] = 100;
-        CHECK(int3_select_bin(h.data(), 4096, 0, 3, &tail, &above) == 10 && tail == 3 && above == 0);
-        CHECK(int3_select_bin(h.data(), 4096, 0, 4, &tail, &above) == 7 && tail == 7 && above == 3);
-        CHECK(int3_select_bin(h.data(), 4096, 2, 10, &tail, &above) == 0 && tail == 109 &&
+        CHECK(int_select_bin(h.data(), 4096, 0, 3, &tail, &above) == 10 && tail == 3 && above == 0);
+        CHECK(int_select_bin(h.data(), 4096, 0, 4, &tail, &above) == 7 && tail == 7 && above == 3);
+        CHECK(int_select_bin(h.data(), 4096, 2, 10, &tail, &above) == 0 && tail == 109 &&
               above == 9);
-        CHECK(int3_select_bin(h.data(), 4096, 0, 108, &tail, &above) == -1 && tail == 107);
-        CHECK(int3_select_bin(h.data(), 16, 0, 5, &tail, &above) == 7 && tail == 7);  // last level
-        CHECK(int3_select_bin(h.data(), 0, 1, 5, &tail, &above) == -1 && tail == 1);
+        CHECK(int_select_bin(h.data(), 4096, 0, 108, &tail, &above) == -1 && tail == 107);
+        CHECK(int_select_bin(h.data(), 16, 0, 5, &tail, &above) == 7 && tail == 7);  // last level
+        CHECK(int_select_bin(h.data(), 0, 1, 5, &tail, &above) == -1 && tail == 1);
     }
     // candidate order against a full sort, with ties
     {
@@ -84,7 +102,7 @@ int main() {
             for (int64_t K : {(int64_t)0, (int64_t)1, (int64_t)17, (int64_t)n, (int64_t)n + 5,
                               (int64_t)-3}) {
                 std::vector<int64_t> idx;
-                const int64_t nk = int3_order_candidates(keys, vals, K, idx);
+                const int64_t nk = int_order_candidates(keys, vals, K, idx);
                 CHECK(nk == std::max<int64_t>(0, std::min<int64_t>(K, (int64_t)n)));
                 CHECK(idx.size() == n);
                 for (int64_t q = 0; q < nk; ++q) CHECK(idx[(size_t)q] == full[(size_t)q]);
