@@ -651,6 +651,67 @@ int spfm_interaction3_list(spfm_handle h, int order_idx, double tol, int64_t cap
 int spfm_interaction3_values(spfm_handle h, int order_idx, int64_t L, const int32_t* i,
                              const int32_t* j, const int32_t* l, double* vals);
 
+/* -- candidate ranking ------------------------------------------------------------------------
+ * Given context rows X (n_ctx x d) and candidate rows Z (n_cand x d), both CSR over the handle's d
+ * features: score[b, c] = _get_output(x_b + z_c), the value spfm_predict_csr gives for the summed
+ * row with the same (degree, fit_linear, add_lower_deg2), and the K best candidates of every
+ * context.  The columns with a stored entry in X and those with a stored entry in Z must be
+ * DISJOINT (the field structure of a recommender: user / context fields against item fields).
+ * Then the ANOVA kernel splits, a^m(x + z) = sum_t a^t(x) a^(m-t)(z), and so does the all-subsets
+ * product:
+ *   score[b, c] = rowconst[b] + colconst[c] + sum_r U[b, r] V[c, r],
+ * R = k (degree - 1) columns (+ k with add_lower_deg2; k for degree = -1), rowconst / colconst the
+ * model's output on x_b / z_c alone (0 for degree = -1).  Both towers cost one pass over their
+ * own non-zeros; the product is formed in 64 x 64 tiles in registers (f64 matrix instructions)
+ * and consumed there.  Nothing of size n_ctx * n_cand exists on the device: contexts go through in
+ * slabs of rows, candidates in strips of tiles (spfm_rank_set_partition), and only
+ * spfm_rank_scores stores its result (one slab at a time, at most 256 MiB).
+ * Parameters only (spfm_set_params; no data, no spfm_configure), read-only as the interaction
+ * entries, f64 arithmetic for either storage precision.  The candidate towers describe the
+ * parameters at the time of spfm_rank_set_candidates; they and the scratch stay allocated until
+ * spfm_set_params, spfm_destroy or spfm_rank_release (spfm_rank_info reads the size).
+ *
+ * Deterministic: a score is the same chain of matrix-instruction steps over r = 0, 4, 8, ...,
+ * then + (rowconst + colconst), in both entries, on every call and for every slab height and
+ * strip width; the selection uses integer counters only.
+ *
+ * spfm_rank_set_candidates: builds V and colconst from Z (n_cand >= 1; indptr[n_cand+1] int64
+ *   starting at 0, indices int32 in [0,d), data).  degree 2..SPFM_MAX_DEGREE or -1 (all-subsets;
+ *   fit_linear is ignored then); add_lower_deg2 needs P[1].
+ * spfm_rank_scores: out (n_ctx x n_cand, row-major).  Above SPFM_RANK_SCORES_MAX_BYTES of output
+ *   it is refused (SPFM_ERR_INVALID).  Every check precedes the first write to out.
+ * spfm_rank_topk: per context row the *k_out = min(K, n_cand) largest scores, ordered by score
+ *   descending, then candidate index ascending: idx_out / val_out (n_ctx x *k_out, row-major).
+ *   Exact.  1 <= K <= SPFM_RANK_MAX_K, a larger K -> SPFM_ERR_UNSUPPORTED (never an approximate
+ *   answer).  Scores are taken to be finite: a NaN or infinite score never ranks, and a slot that
+ *   no finite score fills holds index -1 and NaN.  idx_out / val_out are written only once
+ *   nothing can fail any more.
+ * spfm_rank_set_partition: context rows per slab and candidates per strip of the following
+ *   calls, each rounded up to 64; 0 = the library's default (4096 rows; a strip width chosen from
+ *   the shape).  row_slab in [0, 2^20], cand_strip in [0, 65536].  No result bit depends on either:
+ *   they exist so that a small problem can be made to run as many slabs and strips.
+ * spfm_rank_info: out4 = {device scratch held in bytes (candidate towers included), device time
+ *   in microseconds (HIP events) of the kernels of the last spfm_rank_scores / spfm_rank_topk call
+ *   without its copies, row_slab, cand_strip as set}.
+ * spfm_rank_release: frees the scratch and forgets the candidates.
+ * These three are entries of their own, not keys of spfm_set_option.
+ * Errors: no parameters / no candidates, indptr not starting at 0 or decreasing, column id out of
+ * range, a column stored on both sides (checked with a d-byte flag pass; the message names the
+ * column), K < 1 -> SPFM_ERR_INVALID. */
+#define SPFM_RANK_MAX_K 128
+#define SPFM_RANK_SCORES_MAX_BYTES (1LL << 30)
+int spfm_rank_set_candidates(spfm_handle h, int degree, int fit_linear, int add_lower_deg2,
+                             int64_t n_cand, const int64_t* indptr, const int32_t* indices,
+                             const double* data);
+int spfm_rank_scores(spfm_handle h, int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
+                     const double* data, double* out);
+int spfm_rank_topk(spfm_handle h, int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
+                   const double* data, int64_t K, int32_t* idx_out, double* val_out,
+                   int64_t* k_out);
+int spfm_rank_set_partition(spfm_handle h, int64_t row_slab, int64_t cand_strip);
+int spfm_rank_info(spfm_handle h, int64_t* out4);
+int spfm_rank_release(spfm_handle h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,9 +101,13 @@ SYMBOLS = [
     "spfm_interaction_values", "spfm_interaction_block",
     "spfm_interaction3_stats", "spfm_interaction3_topk", "spfm_interaction3_list",
     "spfm_interaction3_values",
+    "spfm_rank_set_candidates", "spfm_rank_scores", "spfm_rank_topk",
+    "spfm_rank_set_partition", "spfm_rank_info", "spfm_rank_release",
 ]
 INTERACTION_BLOCK_MAX_BYTES = 1 << 30  # SPFM_INTERACTION_BLOCK_MAX_BYTES
 INTERACTION3_MAX_ACTIVE = 1 << 15  # SPFM_INTERACTION3_MAX_ACTIVE
+RANK_MAX_K = 128  # SPFM_RANK_MAX_K
+RANK_SCORES_MAX_BYTES = 1 << 30  # SPFM_RANK_SCORES_MAX_BYTES
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -197,6 +201,12 @@ def load():
     L.spfm_interaction3_list.argtypes = [_h, C.c_int, C.c_double, C.c_int64, _ip, _ip, _ip, _dp,
                                          _lp]
     L.spfm_interaction3_values.argtypes = [_h, C.c_int, C.c_int64, _ip, _ip, _ip, _dp]
+    L.spfm_rank_set_candidates.argtypes = [_h, C.c_int, C.c_int, C.c_int, C.c_int64, _lp, _ip, _dp]
+    L.spfm_rank_scores.argtypes = [_h, C.c_int64, _lp, _ip, _dp, _dp]
+    L.spfm_rank_topk.argtypes = [_h, C.c_int64, _lp, _ip, _dp, C.c_int64, _ip, _dp, _lp]
+    L.spfm_rank_set_partition.argtypes = [_h, C.c_int64, C.c_int64]
+    L.spfm_rank_info.argtypes = [_h, _lp]
+    L.spfm_rank_release.argtypes = [_h]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in ("spfm_destroy", "spfm_last_error", "spfm_build_tag"):

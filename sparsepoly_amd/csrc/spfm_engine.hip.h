@@ -3,8 +3,8 @@
 // parameters, schedule, predict, communicators, recovery, C ABI; pcd: multi-kernel pcd /
 // cd_linear and the epoch drivers; prb: persistent 64-column passes, one translation unit per
 // storage type; wide: wide persistent passes; pbcd: multi-kernel pbcd; pbprb: persistent pbcd
-// pass, one unit per storage type; psgd; gram, objective, interactions (pairs and triples): the
-// read-only feature units).  Every unit owns the extern "C" block of its entries.  See DESIGN.md
+// pass, one unit per storage type; psgd; gram, objective, interactions (pairs and triples), rank:
+// the read-only feature units).  Every unit owns the extern "C" block of its entries.  See DESIGN.md
 // for the execution model.
 #pragma once
 #include <dlfcn.h>
@@ -1030,6 +1030,44 @@ struct spfm_engine {
     // IntPass::unpack: sorted keys -> the caller's id arrays (pairs: 2, triples: 3)
     int interaction_unpack(const uint64_t* keys, size_t n, int32_t* const* ids);
     int interaction3_unpack(const uint64_t* keys, size_t n, int32_t* const* ids);
+
+    // ------------------------------- candidate ranking (spfm_engine_rank.hip)
+    // score[b, c] = _get_output(x_b + z_c) for disjoint supports = rowconst + colconst + U V^T
+    // (DESIGN.md section 15).  The candidate towers (rk_V, rk_cc) are built once by
+    // rank_set_candidates and kept; contexts go through in slabs of rows.  Nothing is of size
+    // n_ctx * n_cand.  Freed by spfm_set_params, spfm_destroy or spfm_rank_release.
+    DevBuf rk_V, rk_cc;                    // candidate towers (padded rows, rk_Rp), constants
+    DevBuf rk_U, rk_rc;                    // context towers of one slab
+    DevBuf rk_xp, rk_xi, rk_xv;            // CSR staging (contexts or candidates)
+    DevBuf rk_lv, rk_li, rk_ov, rk_oi;     // per-strip lists, merged lists of one slab
+    DevBuf rk_dense;                       // dense scores of one slab
+    std::vector<uint8_t> rk_zflag;         // columns with a stored candidate entry
+    bool rk_have = false;
+    int64_t rk_C = 0;
+    int rk_R = 0, rk_Rp = 0, rk_degree = 0, rk_lin = 0, rk_lower = 0;
+    int rk_row_slab = 0;    // spfm_rank_set_partition: context rows per slab (0 = default)
+    int rk_cand_strip = 0;  // ... and candidates per strip (0 = default)
+    int rk_device_us = 0;   // spfm_rank_info: kernels of the last scores / topk call
+    size_t rank_scratch_bytes() const {
+        return rk_V.bytes + rk_cc.bytes + rk_U.bytes + rk_rc.bytes + rk_xp.bytes + rk_xi.bytes +
+               rk_xv.bytes + rk_lv.bytes + rk_li.bytes + rk_ov.bytes + rk_oi.bytes + rk_dense.bytes;
+    }
+    void rank_release();  // frees the scratch and forgets the candidates
+    int rank_check_csr(const char* what, int64_t rows, const int64_t* indptr,
+                       const int32_t* indices, const double* data);
+    template <int M>
+    void rank_launch_tower(int64_t row0, int64_t rows, int order_idx, bool lin, int side, int col0,
+                           double* img, double* cst);
+    int rank_towers(int64_t row0, int64_t rows, int side, double* img, double* cst);
+    int rank_set_candidates(int degree, int fit_linear, int add_lower, int64_t n_cand,
+                            const int64_t* indptr, const int32_t* indices, const double* data);
+    int rank_contexts(const char* what, int64_t n_ctx, const int64_t* indptr,
+                      const int32_t* indices, const double* data);
+    int rank_scores(int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
+                    const double* data, double* out);
+    int rank_topk(int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
+                  const double* data, int64_t K, int32_t* idx_out, double* val_out,
+                  int64_t* k_out);
 
     // diagnostics that need kernels of one translation unit
     int debug_stream_probe(int64_t* bytes_out);  // spfm_engine_pcd.hip

@@ -1,0 +1,348 @@
+// spfm_engine_rank.hip -- spfm_rank_set_candidates / _scores / _topk (include/spfm.h): the
+// scores of every (context row, candidate row) pair under the handle's parameters and the K best
+// candidates of every context row.  score = rowconst + colconst + U V^T (spfm_rank.hip.h); the
+// candidate towers are built once and kept, contexts go through in slabs of rows, the product
+// is consumed tile by tile.  Read-only like the interaction unit: scratch of its own, the live
+// parameter image is read through its strides and no validity flag changes.  See DESIGN.md
+// section 15.
+#include "spfm_engine.hip.h"
+#include "spfm_rank.hip.h"
+
+#include <algorithm>
+
+static_assert(kRankMaxK == SPFM_RANK_MAX_K, "header and device agree on the cap");
+
+namespace {
+constexpr int64_t kRankSlabDefault = 4096;          // context rows per slab
+constexpr int64_t kRankDenseSlabBytes = 256ll << 20;  // device image of one dense slab
+int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+
+// device time of the kernels of one call (towers, tiles, merge; not the copies): one event pair,
+// read after each slab's sync (spfm_rank_info)
+struct RankTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    double ms = 0.0;
+    RankTimer() {
+        if (hipEventCreate(&e0) != hipSuccess) e0 = nullptr;
+        if (hipEventCreate(&e1) != hipSuccess) e1 = nullptr;
+    }
+    ~RankTimer() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    void begin(hipStream_t s) {
+        if (e0 && e1) (void)hipEventRecord(e0, s);
+    }
+    void end(hipStream_t s) {
+        if (e0 && e1) (void)hipEventRecord(e1, s);
+    }
+    void collect() {  // after a sync
+        float t = 0.f;
+        if (e0 && e1 && hipEventElapsedTime(&t, e0, e1) == hipSuccess) ms += t;
+    }
+};
+}  // namespace
+
+void spfm_engine::rank_release() {
+    for (DevBuf* b : {&rk_V, &rk_cc, &rk_U, &rk_rc, &rk_xp, &rk_xi, &rk_xv, &rk_lv, &rk_li, &rk_ov,
+                      &rk_oi, &rk_dense})
+        b->release();
+    rk_zflag.clear();
+    rk_have = false;
+    rk_C = 0;
+}
+
+// indptr starts at 0 and does not decrease, column ids in [0, d)
+int spfm_engine::rank_check_csr(const char* what, int64_t rows, const int64_t* indptr,
+                                const int32_t* indices, const double* data) {
+    if (rows < 0 || !indptr) FAIL(SPFM_ERR_INVALID, std::string(what) + ": bad arguments");
+    if (indptr[0] != 0) FAIL(SPFM_ERR_INVALID, std::string(what) + ": indptr[0] must be 0");
+    for (int64_t i = 0; i < rows; ++i)
+        if (indptr[i + 1] < indptr[i])
+            FAIL(SPFM_ERR_INVALID, std::string(what) + ": indptr is not monotone");
+    const int64_t nz = indptr[rows];
+    if (nz > 0 && (!indices || !data)) FAIL(SPFM_ERR_INVALID, std::string(what) + ": NULL array");
+    for (int64_t ii = 0; ii < nz; ++ii)
+        if (indices[ii] < 0 || indices[ii] >= d)
+            FAIL(SPFM_ERR_INVALID, std::string(what) + ": column index out of range");
+    return SPFM_OK;
+}
+
+template <int M>
+void spfm_engine::rank_launch_tower(int64_t row0, int64_t rows, int order_idx, bool lin, int side,
+                                    int col0, double* img, double* cst) {
+    const BlockView v = live_block(order_idx);
+    hipLaunchKernelGGL((tower_kernel<double, M>), dim3(cdiv(rows * kWave, kBlock)), dim3(kBlock), 0,
+                       stream, row0, rows, k, rk_xp.as<int64_t>(), rk_xi.as<int32_t>(),
+                       rk_xv.as<double>(), v.base, v.ss, v.sj, lams.as<double>(),
+                       lin ? w.as<double>() : (const double*)nullptr, side, rk_Rp, col0, img, cst);
+}
+
+// the towers of rows [row0, row0 + rows) of the staged CSR matrix into img / cst (cleared here)
+int spfm_engine::rank_towers(int64_t row0, int64_t rows, int side, double* img, double* cst) {
+    const int64_t pad = round_up(rows, kIntTile);
+    HIPC(hipMemsetAsync(img, 0, sizeof(double) * (size_t)pad * rk_Rp, stream));
+    HIPC(hipMemsetAsync(cst, 0, sizeof(double) * (size_t)pad, stream));
+    const bool lin = rk_lin != 0;
+    switch (kind_of(rk_degree)) {
+        case 0: rank_launch_tower<0>(row0, rows, 0, false, side, 0, img, cst); break;
+        case 2: rank_launch_tower<2>(row0, rows, 0, lin, side, 0, img, cst); break;
+        case 3: rank_launch_tower<3>(row0, rows, 0, lin, side, 0, img, cst); break;
+        case 4: rank_launch_tower<4>(row0, rows, 0, lin, side, 0, img, cst); break;
+        case 5: rank_launch_tower<5>(row0, rows, 0, lin, side, 0, img, cst); break;
+        case 6: rank_launch_tower<6>(row0, rows, 0, lin, side, 0, img, cst); break;
+        default: FAIL(SPFM_ERR_UNSUPPORTED, "rank: degree outside 2..6 and -1");
+    }
+    if (rk_lower)  // the order-2 term on P[1]
+        rank_launch_tower<2>(row0, rows, 1, false, side, k * (rk_degree - 1), img, cst);
+    HIPC(hipGetLastError());
+    return SPFM_OK;
+}
+
+int spfm_engine::rank_set_candidates(int degree, int fit_linear, int add_lower, int64_t n_cand,
+                                     const int64_t* indptr, const int32_t* indices,
+                                     const double* data) {
+    if (!have_params) FAIL(SPFM_ERR_INVALID, "rank_set_candidates: no parameters set");
+    if (degree != -1 && (degree < 2 || degree > SPFM_MAX_DEGREE))
+        FAIL(SPFM_ERR_UNSUPPORTED, "rank_set_candidates: degree outside 2..6 and -1");
+    if (add_lower && (n_orders < 2 || degree < 3))
+        FAIL(SPFM_ERR_INVALID, "rank_set_candidates: add_lower_deg2 needs P_[1] and degree >= 3");
+    if (n_cand < 1) FAIL(SPFM_ERR_INVALID, "rank_set_candidates: n_cand must be >= 1");
+    if (n_cand > INT32_MAX - kIntTile)
+        FAIL(SPFM_ERR_UNSUPPORTED, "rank_set_candidates: more than 2^31 - 65 candidates");
+    SPFM_TRY(rank_check_csr("rank_set_candidates", n_cand, indptr, indices, data));
+    const int64_t R = (degree == -1 ? (int64_t)k : (int64_t)k * (degree - 1)) + (add_lower ? k : 0);
+    const int64_t Rp = round_up(R, 4), pad = round_up(n_cand, kIntTile);
+    rank_release();
+    rk_degree = degree;
+    rk_lin = (degree != -1 && fit_linear) ? 1 : 0;
+    rk_lower = add_lower ? 1 : 0;
+    rk_R = (int)R;
+    rk_Rp = (int)Rp;
+    const int64_t nz = indptr[n_cand];
+    std::vector<uint8_t> flag((size_t)d, 0);
+    for (int64_t ii = 0; ii < nz; ++ii) flag[(size_t)indices[ii]] = 1;
+    std::vector<double> hv;
+    SPFM_TRY(stage_csr_rows<double>(rk_xp, rk_xi, rk_xv, hv, indptr, indices, data, 0, n_cand));
+    HIPC(rk_V.alloc(sizeof(double) * (size_t)pad * Rp));
+    HIPC(rk_cc.alloc(sizeof(double) * (size_t)pad));
+    SPFM_TRY(rank_towers(0, n_cand, RANK_CAND, rk_V.as<double>(), rk_cc.as<double>()));
+    SPFM_TRY(sync());
+    rk_zflag.swap(flag);
+    rk_C = n_cand;
+    rk_have = true;
+    return SPFM_OK;
+}
+
+// checks of a context matrix (before any device work), then its CSR image on the device
+int spfm_engine::rank_contexts(const char* what, int64_t n_ctx, const int64_t* indptr,
+                               const int32_t* indices, const double* data) {
+    if (!have_params) FAIL(SPFM_ERR_INVALID, std::string(what) + ": no parameters set");
+    if (!rk_have) FAIL(SPFM_ERR_INVALID, std::string(what) + ": call spfm_rank_set_candidates first");
+    SPFM_TRY(rank_check_csr(what, n_ctx, indptr, indices, data));
+    const int64_t nz = indptr[n_ctx];
+    for (int64_t ii = 0; ii < nz; ++ii)
+        if (rk_zflag[(size_t)indices[ii]]) {
+            char buf[160];
+            snprintf(buf, sizeof buf,
+                     "%s: column %d has stored entries in the contexts and in the candidates "
+                     "(their column sets must be disjoint)", what, (int)indices[ii]);
+            FAIL(SPFM_ERR_INVALID, buf);
+        }
+    if (n_ctx == 0) return SPFM_OK;
+    std::vector<double> hv;
+    SPFM_TRY(stage_csr_rows<double>(rk_xp, rk_xi, rk_xv, hv, indptr, indices, data, 0, n_ctx));
+    return sync();  // the caller's arrays are not read after this
+}
+
+static RankArgs rank_args(const spfm_engine* h, int64_t nrow) {
+    RankArgs a;
+    memset(&a, 0, sizeof a);
+    a.U = h->rk_U.as<double>();
+    a.V = h->rk_V.as<double>();
+    a.rc = h->rk_rc.as<double>();
+    a.cc = h->rk_cc.as<double>();
+    a.Rp = h->rk_Rp;
+    a.nrow = (int)nrow;
+    a.C = (int)h->rk_C;
+    a.rows_pad = (int)round_up(nrow, kIntTile);
+    return a;
+}
+
+int spfm_engine::rank_scores(int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
+                             const double* data, double* out) {
+    SPFM_TRY(rank_contexts("rank_scores", n_ctx, indptr, indices, data));
+    if ((double)n_ctx * (double)rk_C * 8.0 > (double)SPFM_RANK_SCORES_MAX_BYTES) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "rank_scores: %lld x %lld doubles exceed the budget of %lld bytes",
+                 (long long)n_ctx, (long long)rk_C, (long long)SPFM_RANK_SCORES_MAX_BYTES);
+        FAIL(SPFM_ERR_INVALID, buf);
+    }
+    if (n_ctx == 0) return SPFM_OK;
+    if (!out) FAIL(SPFM_ERR_INVALID, "rank_scores: out is NULL");
+    int64_t slab = round_up(rk_row_slab > 0 ? rk_row_slab : kRankSlabDefault, kIntTile);
+    const int64_t fit = kRankDenseSlabBytes / (8 * rk_C) / kIntTile * kIntTile;
+    slab = std::min(slab, std::max<int64_t>(fit, kIntTile));
+    slab = std::min(slab, round_up(n_ctx, kIntTile));
+    const int Tc = (int)cdiv(rk_C, kIntTile);
+    int64_t strip = rk_cand_strip > 0 ? rk_cand_strip : 8192;
+    const int strip_tiles = (int)std::min<int64_t>(cdiv(strip, kIntTile), Tc);
+    HIPC(rk_U.alloc(sizeof(double) * (size_t)slab * rk_Rp));
+    HIPC(rk_rc.alloc(sizeof(double) * (size_t)slab));
+    HIPC(rk_dense.alloc(sizeof(double) * (size_t)slab * (size_t)rk_C));
+    const size_t lds = rank_lds_bytes(RANK_DENSE, 0);
+    RankTimer timer;
+    rk_device_us = 0;
+    for (int64_t r0 = 0; r0 < n_ctx; r0 += slab) {
+        const int64_t nrow = std::min(slab, n_ctx - r0);
+        timer.begin(stream);
+        SPFM_TRY(rank_towers(r0, nrow, RANK_CTX, rk_U.as<double>(), rk_rc.as<double>()));
+        RankArgs a = rank_args(this, nrow);
+        a.strip_tiles = strip_tiles;
+        a.n_strips = (int)cdiv(Tc, strip_tiles);
+        a.dense = rk_dense.as<double>();
+        hipLaunchKernelGGL((rank_tile_kernel<RANK_DENSE>),
+                           dim3((unsigned)a.n_strips, (unsigned)(a.rows_pad / kIntTile)),
+                           dim3(kBlock), lds, stream, a);
+        HIPC(hipGetLastError());
+        timer.end(stream);
+        SPFM_TRY(download(out + (size_t)r0 * rk_C, rk_dense.p, (size_t)nrow * rk_C));
+        SPFM_TRY(sync());
+        timer.collect();
+    }
+    rk_device_us = (int)std::min(timer.ms * 1e3, 2e9);
+    return SPFM_OK;
+}
+
+int spfm_engine::rank_topk(int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
+                           const double* data, int64_t K, int32_t* idx_out, double* val_out,
+                           int64_t* k_out) {
+    if (!k_out) FAIL(SPFM_ERR_INVALID, "rank_topk: k_out is NULL");
+    *k_out = 0;
+    if (K < 1) FAIL(SPFM_ERR_INVALID, "rank_topk: K must be >= 1");
+    if (K > SPFM_RANK_MAX_K) {
+        char buf[96];
+        snprintf(buf, sizeof buf, "rank_topk: K must be <= SPFM_RANK_MAX_K = %d",
+                 (int)SPFM_RANK_MAX_K);
+        FAIL(SPFM_ERR_UNSUPPORTED, buf);
+    }
+    SPFM_TRY(rank_contexts("rank_topk", n_ctx, indptr, indices, data));
+    const int Ko = (int)std::min<int64_t>(K, rk_C);
+    if (n_ctx > 0 && (!idx_out || !val_out)) FAIL(SPFM_ERR_INVALID, "rank_topk: NULL output");
+    if (n_ctx == 0) {
+        *k_out = Ko;
+        return SPFM_OK;
+    }
+    const int64_t slab = std::min(
+        round_up(rk_row_slab > 0 ? rk_row_slab : kRankSlabDefault, kIntTile),
+        round_up(n_ctx, kIntTile));
+    const int row_tiles = (int)(slab / kIntTile);
+    const int Tc = (int)cdiv(rk_C, kIntTile);
+    // strip width: the option, else about 512 workgroups per slab, 16 .. 1024 tiles (a longer
+    // strip has fewer survivors per candidate: about K ln(strip / K) per row and strip)
+    int64_t strip_tiles = rk_cand_strip > 0
+                              ? cdiv(rk_cand_strip, kIntTile)
+                              : std::min<int64_t>(1024, std::max<int64_t>(16, (int64_t)Tc * row_tiles / 512));
+    strip_tiles = std::min<int64_t>(strip_tiles, std::min<int64_t>(Tc, kRankMaxStrip / kIntTile));
+    const int n_strips = (int)cdiv(Tc, strip_tiles);
+    const int cap = kRankCap;
+    const size_t lds = rank_lds_bytes(RANK_SELECT, cap);
+    HIPC(hipFuncSetAttribute((const void*)rank_tile_kernel<RANK_SELECT>,
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPC(rk_U.alloc(sizeof(double) * (size_t)slab * rk_Rp));
+    HIPC(rk_rc.alloc(sizeof(double) * (size_t)slab));
+    const size_t ln = (size_t)n_strips * (size_t)slab * Ko;
+    HIPC(rk_lv.alloc(sizeof(double) * ln));
+    HIPC(rk_li.alloc(sizeof(int32_t) * ln));
+    HIPC(rk_ov.alloc(sizeof(double) * (size_t)slab * Ko));
+    HIPC(rk_oi.alloc(sizeof(int32_t) * (size_t)slab * Ko));
+    // the caller's arrays are written only once nothing can fail
+    std::vector<int32_t> hi((size_t)n_ctx * Ko);
+    std::vector<double> hv((size_t)n_ctx * Ko);
+    RankTimer timer;
+    rk_device_us = 0;
+    for (int64_t r0 = 0; r0 < n_ctx; r0 += slab) {
+        const int64_t nrow = std::min(slab, n_ctx - r0);
+        timer.begin(stream);
+        SPFM_TRY(rank_towers(r0, nrow, RANK_CTX, rk_U.as<double>(), rk_rc.as<double>()));
+        RankArgs a = rank_args(this, nrow);
+        a.strip_tiles = (int)strip_tiles;
+        a.n_strips = n_strips;
+        a.K = Ko;
+        a.cap = cap;
+        a.lval = rk_lv.as<double>();
+        a.lidx = rk_li.as<int32_t>();
+        a.oval = rk_ov.as<double>();
+        a.oidx = rk_oi.as<int32_t>();
+        // slots no finite score fills: index -1, NaN
+        HIPC(hipMemsetAsync(rk_ov.p, 0xFF, sizeof(double) * (size_t)nrow * Ko, stream));
+        HIPC(hipMemsetAsync(rk_oi.p, 0xFF, sizeof(int32_t) * (size_t)nrow * Ko, stream));
+        hipLaunchKernelGGL((rank_tile_kernel<RANK_SELECT>),
+                           dim3((unsigned)n_strips, (unsigned)(a.rows_pad / kIntTile)),
+                           dim3(kBlock), lds, stream, a);
+        hipLaunchKernelGGL((rank_tile_kernel<RANK_MERGE>), dim3(cdiv(nrow * kWave, kBlock)),
+                           dim3(kBlock), 0, stream, a);
+        HIPC(hipGetLastError());
+        timer.end(stream);
+        SPFM_TRY(download(hv.data() + (size_t)r0 * Ko, rk_ov.p, (size_t)nrow * Ko));
+        SPFM_TRY(download(hi.data() + (size_t)r0 * Ko, rk_oi.p, (size_t)nrow * Ko));
+        SPFM_TRY(sync());
+        timer.collect();
+    }
+    rk_device_us = (int)std::min(timer.ms * 1e3, 2e9);
+    std::copy(hi.begin(), hi.end(), idx_out);
+    std::copy(hv.begin(), hv.end(), val_out);
+    *k_out = Ko;
+    return SPFM_OK;
+}
+
+extern "C" {
+
+int spfm_rank_set_candidates(spfm_handle h, int degree, int fit_linear, int add_lower_deg2,
+                             int64_t n_cand, const int64_t* indptr, const int32_t* indices,
+                             const double* data) {
+    SPFM_GUARD(h);
+    return h->rank_set_candidates(degree, fit_linear, add_lower_deg2, n_cand, indptr, indices,
+                                  data);
+}
+
+int spfm_rank_scores(spfm_handle h, int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
+                     const double* data, double* out) {
+    SPFM_GUARD(h);
+    return h->rank_scores(n_ctx, indptr, indices, data, out);
+}
+
+int spfm_rank_topk(spfm_handle h, int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
+                   const double* data, int64_t K, int32_t* idx_out, double* val_out,
+                   int64_t* k_out) {
+    SPFM_GUARD(h);
+    return h->rank_topk(n_ctx, indptr, indices, data, K, idx_out, val_out, k_out);
+}
+
+int spfm_rank_set_partition(spfm_handle h, int64_t row_slab, int64_t cand_strip) {
+    if (!h) return SPFM_ERR_INVALID;
+    if (row_slab < 0 || row_slab > (1 << 20) || cand_strip < 0 || cand_strip > kRankMaxStrip) {
+        h->err = "rank_set_partition: row_slab must be in [0, 2^20], cand_strip in [0, 65536]";
+        return SPFM_ERR_INVALID;
+    }
+    h->rk_row_slab = (int)row_slab;
+    h->rk_cand_strip = (int)cand_strip;
+    return SPFM_OK;
+}
+
+int spfm_rank_info(spfm_handle h, int64_t* out4) {
+    if (!h || !out4) return SPFM_ERR_INVALID;
+    out4[0] = (int64_t)h->rank_scratch_bytes();
+    out4[1] = h->rk_device_us;
+    out4[2] = h->rk_row_slab;
+    out4[3] = h->rk_cand_strip;
+    return SPFM_OK;
+}
+
+int spfm_rank_release(spfm_handle h) {
+    SPFM_GUARD(h);
+    h->rank_release();
+    return SPFM_OK;
+}
+
+}  // extern "C"

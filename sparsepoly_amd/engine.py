@@ -327,6 +327,7 @@ class HipEngine(object):
             raise ValueError("w / lams shapes do not match P")
         self._check(self._lib.spfm_set_params(self._h, n_orders, k, d, Pp, wp, lp))
         self.n_orders, self.k, self.d = n_orders, k, d
+        self.n_candidates = None  # the library forgets the candidate towers with the parameters
 
     def get_params(self, P=None, w=None, skip_P=False):
         """Copy the live device state into P (n_orders, k, d) and w (d), in place when
@@ -525,6 +526,85 @@ class HipEngine(object):
             self._h, int(order_idx), ja.shape[0], jp, j2a.shape[0], j2p,
             out.ctypes.data_as(_capi._dp)))
         return out
+
+    # ------------------------- candidate ranking: scores and top-K of (context, candidate) pairs
+    def _rank_csr(self, X, what):
+        """Canonical CSR (sorted, duplicates summed) of the handle's width -> (matrix, pointers)"""
+        Xr = sp.csr_matrix(X, dtype=np.float64)
+        if not Xr.has_canonical_format:
+            Xr = Xr.copy()
+            Xr.sum_duplicates()
+            Xr.sort_indices()
+        if self.d is None:
+            raise ValueError("%s: set_params first" % what)
+        if Xr.shape[1] != self.d:
+            raise ValueError("%s: the matrix has %d features, the model has %d"
+                             % (what, Xr.shape[1], self.d))
+        return Xr, (_capi.i64(Xr.indptr), _capi.i32(Xr.indices), _capi.f64(Xr.data))
+
+    def rank_set_candidates(self, Z, degree, fit_linear, add_lower_deg2):
+        """``spfm_rank_set_candidates``: build and keep the candidate towers of ``Z`` (C, d) under
+        the handle's parameters.  ``degree`` -1: all-subsets."""
+        Zr, (ia, ja, da) = self._rank_csr(Z, "rank_set_candidates")
+        self._check(self._lib.spfm_rank_set_candidates(
+            self._h, int(degree), int(bool(fit_linear)), int(bool(add_lower_deg2)), Zr.shape[0],
+            ia[1], ja[1], da[1]))
+        self.n_candidates = Zr.shape[0]
+
+    def rank_scores(self, X):
+        """``spfm_rank_scores``: the dense (B, C) scores of the contexts ``X`` against the resident
+        candidates; refused above ``SPFM_RANK_SCORES_MAX_BYTES`` of result."""
+        Xr, (ia, ja, da) = self._rank_csr(X, "rank_scores")
+        C_ = getattr(self, "n_candidates", None)
+        if C_ is None:
+            raise ValueError("rank_scores: call rank_set_candidates first")
+        if Xr.shape[0] * C_ * 8 > _capi.RANK_SCORES_MAX_BYTES:
+            raise ValueError("rank_scores: %d x %d doubles exceed the budget of %d bytes"
+                             % (Xr.shape[0], C_, _capi.RANK_SCORES_MAX_BYTES))
+        out = np.zeros((Xr.shape[0], C_))
+        self._check(self._lib.spfm_rank_scores(self._h, Xr.shape[0], ia[1], ja[1], da[1],
+                                               out.ctypes.data_as(_capi._dp)))
+        return out
+
+    def rank_topk(self, X, K):
+        """``spfm_rank_topk``: ``(idx, scores)`` of shape (B, min(K, C)), per row by score
+        descending, then candidate index ascending.  ``K`` above ``SPFM_RANK_MAX_K``: ValueError."""
+        K = int(K)
+        if K > _capi.RANK_MAX_K:
+            raise ValueError("rank_topk: K = %d exceeds SPFM_RANK_MAX_K = %d (never answered "
+                             "approximately)" % (K, _capi.RANK_MAX_K))
+        Xr, (ia, ja, da) = self._rank_csr(X, "rank_topk")
+        C_ = getattr(self, "n_candidates", None)
+        if C_ is None:
+            raise ValueError("rank_topk: call rank_set_candidates first")
+        ko = max(min(K, C_), 1)
+        idx = np.zeros((Xr.shape[0], ko), dtype=np.int32)
+        val = np.zeros((Xr.shape[0], ko))
+        k_out = C.c_int64()
+        self._check(self._lib.spfm_rank_topk(
+            self._h, Xr.shape[0], ia[1], ja[1], da[1], K, idx.ctypes.data_as(_capi._ip),
+            val.ctypes.data_as(_capi._dp), C.byref(k_out)))
+        assert k_out.value == ko
+        return idx, val
+
+    def rank_set_partition(self, row_slab=0, cand_strip=0):
+        """``spfm_rank_set_partition``: context rows per slab and candidates per strip of the
+        following ranking calls (0: the library's default).  No result bit depends on them."""
+        self._check(self._lib.spfm_rank_set_partition(self._h, int(row_slab), int(cand_strip)))
+
+    def rank_info(self):
+        """``spfm_rank_info``: dict ``scratch_kib`` (device memory the ranking calls hold),
+        ``device_ms`` (kernels of the last ``rank_scores`` / ``rank_topk``), ``row_slab``,
+        ``cand_strip``."""
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.spfm_rank_info(self._h, out.ctypes.data_as(_capi._lp)))
+        return dict(scratch_kib=int((out[0] + 1023) // 1024), device_ms=out[1] / 1e3,
+                    row_slab=int(out[2]), cand_strip=int(out[3]))
+
+    def rank_release(self):
+        """``spfm_rank_release``: free the ranking scratch and forget the candidates."""
+        self._check(self._lib.spfm_rank_release(self._h))
+        self.n_candidates = None
 
     # ------------------------- third-order weights T[a, j, l] = sum_s lams_s p_sa p_sj p_sl (spfm.h)
     def interaction3_stats(self, order_idx, tol=0.0, n_features=None):

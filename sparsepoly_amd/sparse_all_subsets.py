@@ -24,12 +24,13 @@ from . import _capi
 from .engine import HipEngine, canonical_csc
 from .loss import CLASSIFICATION_LOSSES, REGRESSION_LOSSES
 from .interactions import InteractionMixin
+from .ranking import RankingMixin
 from .monitor import ObjectiveMixin, callback_needs_params
 from .regularizer import L1, L21, OmegaCS, OmegaTI
 from .schedule import Schedule
 
 
-class _BaseSparseAllSubsets(ObjectiveMixin, InteractionMixin, BaseSparsePoly, metaclass=ABCMeta):
+class _BaseSparseAllSubsets(ObjectiveMixin, InteractionMixin, RankingMixin, BaseSparsePoly, metaclass=ABCMeta):
     # sparse_all_subsets.py:33-38
     _REGULARIZERS = {"l1": L1, "l21": L21, "omegacs": OmegaCS, "omegati": OmegaTI}
 

@@ -54,6 +54,7 @@ from .schedule import Schedule
 from .loss import CLASSIFICATION_LOSSES, REGRESSION_LOSSES
 from .regularizer import REGULARIZATION
 from .interactions import InteractionMixin
+from .ranking import RankingMixin
 from .monitor import ObjectiveMixin, callback_needs_params
 
 MAX_DEGREE = 6  # include/spfm.h SPFM_MAX_DEGREE
@@ -96,7 +97,7 @@ def _fingerprint(Xc, y):
     return (Xc.shape, int(Xc.nnz), fin())
 
 
-class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, BaseSparsePoly, metaclass=ABCMeta):
+class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingMixin, BaseSparsePoly, metaclass=ABCMeta):
     _REGULARIZERS = REGULARIZATION
 
     @abstractmethod
