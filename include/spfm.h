@@ -712,6 +712,66 @@ int spfm_rank_set_partition(spfm_handle h, int64_t row_slab, int64_t cand_strip)
 int spfm_rank_info(spfm_handle h, int64_t* out4);
 int spfm_rank_release(spfm_handle h);
 
+/* -- per-row feature attributions -------------------------------------------------------------
+ * Why a row got its prediction.  The model is a sum of blocks, block q being
+ *   sum_s lams_s sum_{t=0..6} coef[q][s][t] A^t(p_s, x),   p_s = P[order_idx[q]][s],
+ * A^t the ANOVA kernel of order t, plus w.x when fit_linear.  A plain block of degree M has
+ * coef[s][M] = 1 and zeros elsewhere; the table lets a caller fold columns that are constant in
+ * every row (the dummy columns of fit_lower='augment') into lower orders instead of storing
+ * them.  Only t = 1..degree[q] is read: column 0 is a constant of the model and belongs to the
+ * caller's base value.
+ * Every monomial of A^t is a product over t entries of the row.  Against the baseline x = 0 its
+ * Shapley value splits it equally among those entries, so for the stored entry (i, j)
+ *   phi_ij   = w_j x_ij + x_ij sum_q sum_s lams_s p_sj sum_t (coef[q][s][t] / t) g_{t-1}
+ *   df/dx_ij = w_j      +      sum_q sum_s lams_s p_sj sum_t  coef[q][s][t]      g_{t-1}
+ * with g_0 = 1, g_t = A^t(p_s, x_i) - p_sj x_ij g_{t-1}, which is A^t of the row without entry j.
+ * Exact, not sampled; sum_j phi_ij = f(x_i) - f(0).  The gradient is that of a stored entry with
+ * the sparsity pattern held fixed.  The input is CSR over the handle's d features (indptr[n+1]
+ * int64 starting at 0, indices int32 in [0,d), data); a column stored twice in a row is treated
+ * as two features with the same parameters, so canonical input is the caller's business.
+ * Parameters only (spfm_set_params; no data, no spfm_configure), read-only as spfm_predict_csr,
+ * values read in the handle's precision, all arithmetic in f64.  Rows go through in slabs bounded
+ * by a count of stored entries; the scratch holds one slab (at most 256 MiB unless a single row
+ * is larger) and stays allocated until spfm_set_params or spfm_destroy.
+ *
+ * Deterministic: an entry's value is the linear term, then the blocks in the caller's order,
+ * each a sum over the components in index order formed by one lane; a row sum adds lane l's
+ * entries l, l + 64, ... in order and then the lanes by a fixed butterfly; the selection compares
+ * integers.  No result bit depends on the slab size or the launch shape.
+ *
+ * spfm_explain_csr: mode SPFM_EXPLAIN_ATTRIBUTION or SPFM_EXPLAIN_GRADIENT; out_vals (nnz, in
+ *   the order of data; slab by slab, so after an error its contents are unspecified) and
+ *   out_rowsum (n; NULL: not computed), out_rowsum[i] = sum_j out_vals[i, j].
+ * spfm_explain_topk_csr: the attributions of every row largest by magnitude: per row its
+ *   min(K, n_i) entries ordered by |phi| descending, then column ascending (then position), in
+ *   idx / val (n x K, row-major; val holds phi with its sign); the remaining slots hold column -1
+ *   and value 0.  Exact.  1 <= K <= SPFM_EXPLAIN_MAX_K, a larger K -> SPFM_ERR_UNSUPPORTED (never
+ *   an approximate answer).  The values stay on the device; only n x K come back.
+ * spfm_explain_set_partition: stored entries per slab of the following calls, in [0, 2^23];
+ *   0 = the default, 2^23.  A slab always holds at least one whole row.  No result bit depends
+ *   on it: it exists so that a small problem can be made to run as many slabs.
+ * spfm_explain_info: out4 = {device scratch held in bytes, device time in microseconds (HIP
+ *   events) of the kernels of the last spfm_explain_* call without its copies, slab_nnz as set,
+ *   slabs of the last call}.
+ * The last two are entries of their own, not keys of spfm_set_option.
+ * Errors: no parameters, order_idx outside the parameters, indptr not starting at 0 or
+ * decreasing, column id out of range, K < 1 -> SPFM_ERR_INVALID; degree outside
+ * 2..SPFM_MAX_DEGREE, K above the cap -> SPFM_ERR_UNSUPPORTED.  Every check precedes the first
+ * write to an output; n = 0 is valid and writes nothing. */
+#define SPFM_EXPLAIN_MAX_K 64
+#define SPFM_EXPLAIN_ATTRIBUTION 0
+#define SPFM_EXPLAIN_GRADIENT 1
+int spfm_explain_csr(spfm_handle h, int64_t n, const int64_t* indptr, const int32_t* indices,
+                     const double* data, int n_blocks, const int32_t* order_idx,
+                     const int32_t* degree, const double* coef /* n_blocks x k x 7 */,
+                     int fit_linear, int mode, double* out_vals, double* out_rowsum);
+int spfm_explain_topk_csr(spfm_handle h, int64_t n, const int64_t* indptr, const int32_t* indices,
+                          const double* data, int n_blocks, const int32_t* order_idx,
+                          const int32_t* degree, const double* coef /* n_blocks x k x 7 */,
+                          int fit_linear, int K, int32_t* idx, double* val);
+int spfm_explain_set_partition(spfm_handle h, int64_t slab_nnz);
+int spfm_explain_info(spfm_handle h, int64_t* out4);
+
 #ifdef __cplusplus
 }
 #endif

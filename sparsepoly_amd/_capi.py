@@ -103,11 +103,15 @@ SYMBOLS = [
     "spfm_interaction3_values",
     "spfm_rank_set_candidates", "spfm_rank_scores", "spfm_rank_topk",
     "spfm_rank_set_partition", "spfm_rank_info", "spfm_rank_release",
+    "spfm_explain_csr", "spfm_explain_topk_csr", "spfm_explain_set_partition",
+    "spfm_explain_info",
 ]
 INTERACTION_BLOCK_MAX_BYTES = 1 << 30  # SPFM_INTERACTION_BLOCK_MAX_BYTES
 INTERACTION3_MAX_ACTIVE = 1 << 15  # SPFM_INTERACTION3_MAX_ACTIVE
 RANK_MAX_K = 128  # SPFM_RANK_MAX_K
 RANK_SCORES_MAX_BYTES = 1 << 30  # SPFM_RANK_SCORES_MAX_BYTES
+EXPLAIN_MAX_K = 64  # SPFM_EXPLAIN_MAX_K
+EXPLAIN_MODES = {"attribution": 0, "gradient": 1}  # SPFM_EXPLAIN_ATTRIBUTION / _GRADIENT
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -207,6 +211,11 @@ def load():
     L.spfm_rank_set_partition.argtypes = [_h, C.c_int64, C.c_int64]
     L.spfm_rank_info.argtypes = [_h, _lp]
     L.spfm_rank_release.argtypes = [_h]
+    _explain = [_h, C.c_int64, _lp, _ip, _dp, C.c_int, _ip, _ip, _dp, C.c_int]
+    L.spfm_explain_csr.argtypes = _explain + [C.c_int, _dp, _dp]
+    L.spfm_explain_topk_csr.argtypes = _explain + [C.c_int, _ip, _dp]
+    L.spfm_explain_set_partition.argtypes = [_h, C.c_int64]
+    L.spfm_explain_info.argtypes = [_h, _lp]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in ("spfm_destroy", "spfm_last_error", "spfm_build_tag"):

@@ -3,8 +3,8 @@
 // parameters, schedule, predict, communicators, recovery, C ABI; pcd: multi-kernel pcd /
 // cd_linear and the epoch drivers; prb: persistent 64-column passes, one translation unit per
 // storage type; wide: wide persistent passes; pbcd: multi-kernel pbcd; pbprb: persistent pbcd
-// pass, one unit per storage type; psgd; gram, objective, interactions (pairs and triples), rank:
-// the read-only feature units).  Every unit owns the extern "C" block of its entries.  See DESIGN.md
+// pass, one unit per storage type; psgd; gram, objective, interactions (pairs and triples), rank,
+// explain: the read-only feature units).  Every unit owns the extern "C" block of its entries.  See DESIGN.md
 // for the execution model.
 #pragma once
 #include <dlfcn.h>
@@ -188,6 +188,31 @@ struct DevBuf {
                       : [&] { using T = double; __VA_ARGS__; }())
 
 static inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
+
+// device time of the kernels of one call (not its copies): one event pair, read after each
+// slab's sync (spfm_rank_info, spfm_explain_info)
+struct DeviceTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    double ms = 0.0;
+    DeviceTimer() {
+        if (hipEventCreate(&e0) != hipSuccess) e0 = nullptr;
+        if (hipEventCreate(&e1) != hipSuccess) e1 = nullptr;
+    }
+    ~DeviceTimer() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    void begin(hipStream_t s) {
+        if (e0 && e1) (void)hipEventRecord(e0, s);
+    }
+    void end(hipStream_t s) {
+        if (e0 && e1) (void)hipEventRecord(e1, s);
+    }
+    void collect() {  // after a sync
+        float t = 0.f;
+        if (e0 && e1 && hipEventElapsedTime(&t, e0, e1) == hipSuccess) ms += t;
+    }
+};
 
 // Entry streams of the persistent passes, shared by the handles that share one data image
 // (spfm_share_data): whoever needs a stream first builds it (under the lock: co-tenant fits of
@@ -1068,6 +1093,48 @@ struct spfm_engine {
     int rank_topk(int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
                   const double* data, int64_t K, int32_t* idx_out, double* val_out,
                   int64_t* k_out);
+
+    // ------------------------------- per-row attributions (spfm_engine_explain.hip)
+    // phi_ij (exact Shapley values against a zero baseline) or df/dx_ij on the stored entries of a
+    // CSR matrix, their row sums and the per-row top-K.  Read-only like
+    // predict; rows go through in slabs bounded by stored entries, the scratch below holds one slab
+    // and is kept until spfm_set_params or spfm_destroy.
+    DevBuf ex_rp, ex_ri, ex_rv;   // CSR image of one slab (values in the handle's precision)
+    DevBuf ex_out, ex_rs;         // its values and row sums
+    DevBuf ex_coef;               // the blocks' coefficient tables (n_blocks x k x 7)
+    DevBuf ex_ti, ex_tv;          // its top-K lists
+    int64_t ex_slab_nnz = 0;      // spfm_explain_set_partition: stored entries per slab (0 = default)
+    int64_t ex_slabs = 0;         // spfm_explain_info: slabs of the last call ...
+    int ex_device_us = 0;         // ... and its kernels' device time
+    size_t explain_scratch_bytes() const {
+        return ex_rp.bytes + ex_ri.bytes + ex_rv.bytes + ex_out.bytes + ex_rs.bytes +
+               ex_coef.bytes + ex_ti.bytes + ex_tv.bytes;
+    }
+    void explain_release();
+    struct ExplainCall {  // the arguments of spfm_explain_csr / spfm_explain_topk_csr
+        int64_t n;
+        const int64_t* indptr;
+        const int32_t* indices;
+        const double* data;
+        int n_blocks;
+        const int32_t* order_idx;
+        const int32_t* degree;
+        const double* coef;
+        int fit_linear, mode;
+        double *out_vals, *out_rowsum;  // values: either may be NULL
+        bool topk;                      // the top-K entry: K, idx, val (else K = 0)
+        int K;
+        int32_t* idx;
+        double* val;
+    };
+    int explain_check(const char* what, const ExplainCall& c);
+    template <typename T, int M>
+    void explain_launch_block(int64_t rows, int64_t e0, const double* Pt_o, const double* coef_o,
+                              int mode);
+    template <typename T>
+    int explain_slab(const ExplainCall& c, int64_t r0, int64_t r1);
+    template <typename T>
+    int explain_run(const char* what, const ExplainCall& c);
 
     // diagnostics that need kernels of one translation unit
     int debug_stream_probe(int64_t* bytes_out);  // spfm_engine_pcd.hip

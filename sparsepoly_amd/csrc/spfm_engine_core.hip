@@ -413,6 +413,7 @@ int spfm_engine::set_params(int n_orders_, int k_, int32_t d_, const double* P_,
         if (std::fabs(lams_[s]) != 1.0) FAIL(SPFM_ERR_INVALID, "Lambdas must be +1 or -1.");
     interaction_release();  // scratch of the interaction passes (sized by the old block)
     rank_release();         // candidate towers of the old parameters
+    explain_release();      // slab scratch of the attribution entries
     if (n_orders_ != n_orders || k_ != k) {
         configured = false;
         clear_graphs();

@@ -17,30 +17,6 @@ constexpr int64_t kRankSlabDefault = 4096;          // context rows per slab
 constexpr int64_t kRankDenseSlabBytes = 256ll << 20;  // device image of one dense slab
 int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
-// device time of the kernels of one call (towers, tiles, merge; not the copies): one event pair,
-// read after each slab's sync (spfm_rank_info)
-struct RankTimer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    double ms = 0.0;
-    RankTimer() {
-        if (hipEventCreate(&e0) != hipSuccess) e0 = nullptr;
-        if (hipEventCreate(&e1) != hipSuccess) e1 = nullptr;
-    }
-    ~RankTimer() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    void begin(hipStream_t s) {
-        if (e0 && e1) (void)hipEventRecord(e0, s);
-    }
-    void end(hipStream_t s) {
-        if (e0 && e1) (void)hipEventRecord(e1, s);
-    }
-    void collect() {  // after a sync
-        float t = 0.f;
-        if (e0 && e1 && hipEventElapsedTime(&t, e0, e1) == hipSuccess) ms += t;
-    }
-};
 }  // namespace
 
 void spfm_engine::rank_release() {
@@ -191,7 +167,7 @@ int spfm_engine::rank_scores(int64_t n_ctx, const int64_t* indptr, const int32_t
     HIPC(rk_rc.alloc(sizeof(double) * (size_t)slab));
     HIPC(rk_dense.alloc(sizeof(double) * (size_t)slab * (size_t)rk_C));
     const size_t lds = rank_lds_bytes(RANK_DENSE, 0);
-    RankTimer timer;
+    DeviceTimer timer;
     rk_device_us = 0;
     for (int64_t r0 = 0; r0 < n_ctx; r0 += slab) {
         const int64_t nrow = std::min(slab, n_ctx - r0);
@@ -259,7 +235,7 @@ int spfm_engine::rank_topk(int64_t n_ctx, const int64_t* indptr, const int32_t* 
     // the caller's arrays are written only once nothing can fail
     std::vector<int32_t> hi((size_t)n_ctx * Ko);
     std::vector<double> hv((size_t)n_ctx * Ko);
-    RankTimer timer;
+    DeviceTimer timer;
     rk_device_us = 0;
     for (int64_t r0 = 0; r0 < n_ctx; r0 += slab) {
         const int64_t nrow = std::min(slab, n_ctx - r0);

@@ -606,6 +606,66 @@ class HipEngine(object):
         self._check(self._lib.spfm_rank_release(self._h))
         self.n_candidates = None
 
+    # ------------------------- per-row attributions: values, gradients, row sums, top-K (spfm.h)
+    def _explain_args(self, X, blocks, coef, fit_linear, what):
+        """-> (canonical CSR, the ten leading arguments of the two entries, what keeps them alive)"""
+        Xr, (ia, ja, da) = self._rank_csr(X, what)
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.shape != (len(blocks), self.k, 7):
+            raise ValueError("%s: coef must be (n_blocks, n_components, 7), got %r"
+                             % (what, coef.shape))
+        oa, op = _capi.i32(np.array([b[0] for b in blocks], dtype=np.int32))
+        ga, gp = _capi.i32(np.array([b[1] for b in blocks], dtype=np.int32))
+        ca, cp = _capi.f64(coef)
+        args = (self._h, Xr.shape[0], ia[1], ja[1], da[1], len(blocks), op, gp, cp,
+                int(bool(fit_linear)))
+        return Xr, args, (ia, ja, da, oa, ga, ca)
+
+    def explain(self, X, blocks, coef, fit_linear, mode="attribution", rowsum=True):
+        """``spfm_explain_csr``: ``(vals, rowsum)`` for the canonical CSR form of ``X``: per stored
+        entry (in the order of its ``data``) the attribution ``phi_ij`` or, with
+        ``mode='gradient'``, ``df/dx_ij``; per row their sum (``None`` without ``rowsum``).
+        ``blocks``: ``(order_idx, degree)`` pairs, ``coef`` (n_blocks, k, 7) their tables."""
+        if mode not in _capi.EXPLAIN_MODES:
+            raise ValueError("explain: mode must be 'attribution' or 'gradient', got %r" % (mode,))
+        Xr, args, keep = self._explain_args(X, blocks, coef, fit_linear, "explain")
+        vals = np.zeros(Xr.nnz)
+        rs = np.zeros(Xr.shape[0]) if rowsum else None
+        self._check(self._lib.spfm_explain_csr(
+            *args, _capi.EXPLAIN_MODES[mode], vals.ctypes.data_as(_capi._dp),
+            rs.ctypes.data_as(_capi._dp) if rowsum else None))
+        return vals, rs
+
+    def explain_topk(self, X, blocks, coef, fit_linear, K):
+        """``spfm_explain_topk_csr``: ``(cols, vals)`` of shape (n, K): per row its attributions
+        largest by magnitude, by ``|phi|`` descending, then column ascending; rows with fewer
+        than K stored entries are padded with column -1 and value 0.  ``K`` above
+        ``SPFM_EXPLAIN_MAX_K``: ValueError."""
+        K = int(K)
+        if K > _capi.EXPLAIN_MAX_K:
+            raise ValueError("explain_topk: K = %d exceeds SPFM_EXPLAIN_MAX_K = %d (never answered "
+                             "approximately)" % (K, _capi.EXPLAIN_MAX_K))
+        Xr, args, keep = self._explain_args(X, blocks, coef, fit_linear, "explain_topk")
+        idx = np.full((Xr.shape[0], max(K, 1)), -1, dtype=np.int32)
+        val = np.zeros((Xr.shape[0], max(K, 1)))
+        self._check(self._lib.spfm_explain_topk_csr(
+            *args, K, idx.ctypes.data_as(_capi._ip), val.ctypes.data_as(_capi._dp)))
+        return idx, val
+
+    def explain_set_partition(self, slab_nnz=0):
+        """``spfm_explain_set_partition``: stored entries per slab of the following explain calls
+        (0: the library's default).  No result bit depends on it."""
+        self._check(self._lib.spfm_explain_set_partition(self._h, int(slab_nnz)))
+
+    def explain_info(self):
+        """``spfm_explain_info``: dict ``scratch_kib`` (device memory the explain calls hold),
+        ``device_ms`` (kernels of the last ``explain`` / ``explain_topk``), ``slab_nnz`` as set,
+        ``slabs`` of the last call."""
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.spfm_explain_info(self._h, out.ctypes.data_as(_capi._lp)))
+        return dict(scratch_kib=int((out[0] + 1023) // 1024), device_ms=out[1] / 1e3,
+                    slab_nnz=int(out[2]), slabs=int(out[3]))
+
     # ------------------------- third-order weights T[a, j, l] = sum_s lams_s p_sa p_sj p_sl (spfm.h)
     def interaction3_stats(self, order_idx, tol=0.0, n_features=None):
         """``spfm_interaction3_stats``: dict ``nnz`` (triples a < j < l with ``|T| > tol``),

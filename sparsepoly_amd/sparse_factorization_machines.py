@@ -55,6 +55,7 @@ from .loss import CLASSIFICATION_LOSSES, REGRESSION_LOSSES
 from .regularizer import REGULARIZATION
 from .interactions import InteractionMixin
 from .ranking import RankingMixin
+from .explain import ExplainMixin
 from .monitor import ObjectiveMixin, callback_needs_params
 
 MAX_DEGREE = 6  # include/spfm.h SPFM_MAX_DEGREE
@@ -97,7 +98,8 @@ def _fingerprint(Xc, y):
     return (Xc.shape, int(Xc.nnz), fin())
 
 
-class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingMixin, BaseSparsePoly, metaclass=ABCMeta):
+class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingMixin, ExplainMixin,
+                                      BaseSparsePoly, metaclass=ABCMeta):
     _REGULARIZERS = REGULARIZATION
 
     @abstractmethod
