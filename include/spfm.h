@@ -772,6 +772,64 @@ int spfm_explain_topk_csr(spfm_handle h, int64_t n, const int64_t* indptr, const
 int spfm_explain_set_partition(spfm_handle h, int64_t slab_nnz);
 int spfm_explain_info(spfm_handle h, int64_t* out4);
 
+/* ---- model banks: F fitted models scored in one pass over the rows of X.
+ * A bank is F models of one kind -- all of degree 2..SPFM_MAX_DEGREE or all all-subsets (-1),
+ * the same blocks, the same use of a linear term, the same d columns -- that may differ in their
+ * component counts k_f.  Their parameters are stacked along the component axis, feature-major:
+ *   koff (F + 1): 0 = koff[0] < koff[1] < ... ; model f owns the stacked components
+ *                 koff[f] .. koff[f+1] - 1, S = koff[F]
+ *   Pt_bank (n_blocks x d x S): block q's P of every model, transposed and side by side
+ *   lams_bank (S), w_bank (d x F; NULL = the models have no linear term)
+ *   degree (n_blocks): the blocks in _get_output's order: {M} or {3, 2}; {-1} = all-subsets
+ * spfm_bank_set copies the image to the device, where it stays until spfm_bank_release, the next
+ * spfm_bank_set or spfm_destroy; it needs neither data nor spfm_set_params and changes neither.
+ * The four passes take a CSR matrix over the bank's d columns (indptr[n+1] int64 starting at 0,
+ * indices int32 in [0,d), data; values read in the handle's precision, all arithmetic in f64; a
+ * column stored twice in a row is two features, canonical input is the caller's business) and
+ * run it through in slabs bounded by a count of stored entries:
+ * spfm_bank_scores: out (n x F) row-major, out[i][f] = what spfm_predict_csr gives for model f.
+ * spfm_bank_argmax: per row the index of the largest score (ties: the lowest index), that score
+ *   and the second largest (-inf when F = 1): idx, best, runner (n each).  No score leaves the device.
+ * spfm_bank_losses: out[f] = sum_i loss(score_if, y_i) (per_model = 0, y (n)) or
+ *   sum_i loss(score_if, y[i][f]) (per_model = 1, y (n x F) row-major); loss one of SPFM_LOSS_*.
+ *   F doubles leave the device.
+ * spfm_bank_mean: out[i] = sum_f weights[f] score_if, added in model order; weights NULL = 1/F.
+ * Deterministic: model f's score is (B_0 + lin) + B_1, every B_q the sum of f's own component
+ * terms one after the other in f's component order, lin the sum over the row's entries in stored
+ * order.  No bit of it depends on the other members, on f's position, on the slab size or the
+ * launch shape.  A loss sum adds the 256 rows of a block by a fixed tree and the blocks in a
+ * fixed order: the same from run to run for one slab size.
+ * spfm_bank_set_partition: stored entries per slab of the following calls, in [0, 2^23]; 0 = the
+ *   default, 2^23.  A slab always holds at least one whole row.
+ * spfm_bank_info: out4 = {slabs of the last pass, launches of bank_predict_kernel in it, bytes of
+ *   the resident image, S}.
+ * Errors: NULL arrays (with n > 0 for the outputs), F < 1, koff not starting at 0 or not
+ * increasing, n_blocks outside 1..2, d < 1, a matrix whose d differs from the bank's, indptr not
+ * starting at 0 or decreasing, column id out of range, an unknown loss, no bank set
+ * -> SPFM_ERR_INVALID; F above SPFM_BANK_MAX_MODELS, S above SPFM_BANK_MAX_COMPONENTS (the
+ * message names the cap; never answered approximately, never split), a degree outside
+ * 2..SPFM_MAX_DEGREE and -1 -> SPFM_ERR_UNSUPPORTED.  Every check precedes the first write to an
+ * output; n = 0 is valid (the loss sums are 0). */
+#define SPFM_BANK_MAX_MODELS 64
+#define SPFM_BANK_MAX_COMPONENTS 4096
+int spfm_bank_set(spfm_handle h, int32_t d, int F, const int32_t* koff, int n_blocks,
+                  const int32_t* degree, const double* Pt_bank, const double* lams_bank,
+                  const double* w_bank);
+int spfm_bank_scores(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
+                     const int32_t* indices, const double* data, double* out);
+int spfm_bank_argmax(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
+                     const int32_t* indices, const double* data, int32_t* idx, double* best,
+                     double* runner);
+int spfm_bank_losses(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
+                     const int32_t* indices, const double* data, int loss, const double* y,
+                     int per_model, double* out);
+int spfm_bank_mean(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
+                   const int32_t* indices, const double* data, const double* weights,
+                   double* out);
+int spfm_bank_set_partition(spfm_handle h, int64_t slab_nnz);
+int spfm_bank_info(spfm_handle h, int64_t* out4);
+int spfm_bank_release(spfm_handle h);
+
 #ifdef __cplusplus
 }
 #endif

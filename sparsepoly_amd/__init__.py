@@ -2,6 +2,7 @@
 factorization machines; drop-in for the pcd / pbcd path of neonnnnn/sparsepoly
 (reference ``sparsepoly/__init__.py:1-19`` exports the same estimator and
 regularizer names)."""
+from .bank import ModelBank
 from .regularizer import L1, L21, OmegaCS, OmegaTI, SquaredL12, SquaredL21
 from .sparse_all_subsets import SparseAllSubsetsClassifier, SparseAllSubsetsRegressor
 from .sparse_factorization_machines import (
@@ -12,6 +13,7 @@ from .sparse_factorization_machines import (
 __all__ = [
     "L1",
     "L21",
+    "ModelBank",
     "OmegaCS",
     "OmegaTI",
     "SquaredL12",

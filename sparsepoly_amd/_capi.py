@@ -105,6 +105,8 @@ SYMBOLS = [
     "spfm_rank_set_partition", "spfm_rank_info", "spfm_rank_release",
     "spfm_explain_csr", "spfm_explain_topk_csr", "spfm_explain_set_partition",
     "spfm_explain_info",
+    "spfm_bank_set", "spfm_bank_scores", "spfm_bank_argmax", "spfm_bank_losses", "spfm_bank_mean",
+    "spfm_bank_set_partition", "spfm_bank_info", "spfm_bank_release",
 ]
 INTERACTION_BLOCK_MAX_BYTES = 1 << 30  # SPFM_INTERACTION_BLOCK_MAX_BYTES
 INTERACTION3_MAX_ACTIVE = 1 << 15  # SPFM_INTERACTION3_MAX_ACTIVE
@@ -112,6 +114,8 @@ RANK_MAX_K = 128  # SPFM_RANK_MAX_K
 RANK_SCORES_MAX_BYTES = 1 << 30  # SPFM_RANK_SCORES_MAX_BYTES
 EXPLAIN_MAX_K = 64  # SPFM_EXPLAIN_MAX_K
 EXPLAIN_MODES = {"attribution": 0, "gradient": 1}  # SPFM_EXPLAIN_ATTRIBUTION / _GRADIENT
+BANK_MAX_MODELS = 64  # SPFM_BANK_MAX_MODELS
+BANK_MAX_COMPONENTS = 4096  # SPFM_BANK_MAX_COMPONENTS (stacked)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -216,6 +220,15 @@ def load():
     L.spfm_explain_topk_csr.argtypes = _explain + [C.c_int, _ip, _dp]
     L.spfm_explain_set_partition.argtypes = [_h, C.c_int64]
     L.spfm_explain_info.argtypes = [_h, _lp]
+    L.spfm_bank_set.argtypes = [_h, C.c_int32, C.c_int, _ip, C.c_int, _ip, _dp, _dp, _dp]
+    _bank = [_h, C.c_int64, C.c_int32, _lp, _ip, _dp]
+    L.spfm_bank_scores.argtypes = _bank + [_dp]
+    L.spfm_bank_argmax.argtypes = _bank + [_ip, _dp, _dp]
+    L.spfm_bank_losses.argtypes = _bank + [C.c_int, _dp, C.c_int, _dp]
+    L.spfm_bank_mean.argtypes = _bank + [_dp, _dp]
+    L.spfm_bank_set_partition.argtypes = [_h, C.c_int64]
+    L.spfm_bank_info.argtypes = [_h, _lp]
+    L.spfm_bank_release.argtypes = [_h]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in ("spfm_destroy", "spfm_last_error", "spfm_build_tag"):

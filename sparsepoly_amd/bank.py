@@ -1,0 +1,205 @@
+"""Score many fitted models in one pass over the rows of ``X``, on the device.
+
+A regularisation path (``fit_path``), a cross-validation grid or the per-class members of a
+one-vs-rest classifier are F fitted models over the same features.  Their own
+``decision_function`` calls upload ``X`` F times and fetch, per stored entry, F short rows of
+parameters.  A ``ModelBank`` stacks the models along the component axis into one resident image
+(``spfm_bank_*``, ``include/spfm.h``): ``X`` goes up once per call, a stored
+entry costs one contiguous read of ``sum_f k_f`` doubles, and what users reduce the (n, F) scores
+to -- the best model per row, a loss per model, a weighted mean -- is formed on the device, so
+only that leaves it.  There is no CPU path: without the library or a GPU the device calls raise.
+
+The members are all factorization machines of one ``degree``, ``fit_lower`` and ``fit_linear``,
+or all all-subsets models, over the same features; they may differ in ``n_components``.  The score
+of a member does not depend on the other members or on its position: column f of a bank equals
+the one-model bank of that member bit for bit.
+
+``restate_bank_scores`` is the plain NumPy restatement, a test aid that never touches the device.
+"""
+import numpy as np
+import scipy.sparse as sp
+
+from . import _capi
+from . import engine as _engine
+from .ranking import _canonical, _restate_output, _spec
+from .sparse_factorization_machines import _fit_device
+
+
+def _members(estimators):
+    """The checked members of a bank: ``(ests, specs, kind)`` with ``specs`` the ``_spec`` of each
+    and ``kind = (degree or -1, fit_linear, add_lower_deg2, d')``.  Every argument error is raised
+    here, before a handle exists."""
+    ests = list(estimators)
+    if not ests:
+        raise ValueError("a ModelBank needs at least one fitted estimator")
+    specs = [_spec(e) for e in ests]  # NotFittedError for an unfitted member
+
+    def key(e, s):
+        return (s[0], s[1], s[2], getattr(e, "fit_lower", None), s[3].shape[0], s[3].shape[2])
+
+    names = ("degree", "fit_linear", "the order-2 block", "fit_lower", "the number of blocks",
+             "the number of features")
+    first = key(ests[0], specs[0])
+    for i, (e, s) in enumerate(zip(ests, specs)):
+        if (s[0] == -1) != (first[0] == -1):
+            raise ValueError("member %d: factorization machines and all-subsets models cannot "
+                             "share a bank" % i)
+        for name, a, b in zip(names, key(e, s), first):
+            if a != b:
+                raise ValueError("member %d disagrees with member 0 on %s (%r against %r): the "
+                                 "members of a bank share degree, fit_lower, fit_linear and the "
+                                 "features" % (i, name, a, b))
+    if len(ests) > _capi.BANK_MAX_MODELS:
+        raise ValueError("%d models exceed the cap of %d (SPFM_BANK_MAX_MODELS); a larger bank is "
+                         "refused, never split silently" % (len(ests), _capi.BANK_MAX_MODELS))
+    S = sum(s[3].shape[1] for s in specs)
+    if S > _capi.BANK_MAX_COMPONENTS:
+        raise ValueError("%d stacked components exceed the cap of %d "
+                         "(SPFM_BANK_MAX_COMPONENTS); a larger bank is refused, never split "
+                         "silently" % (S, _capi.BANK_MAX_COMPONENTS))
+    return ests, specs, (first[0], first[1], first[2], first[5])
+
+
+def _prepare(est, X, d_model):
+    """``X`` as the members see it: check_array, ``_augment``, canonical CSR -- a copy, the
+    caller's arrays are never changed"""
+    Xc = _canonical(X)
+    aug = getattr(est, "_augment", None)
+    Xa = Xc if aug is None else sp.csr_matrix(aug(Xc))
+    if Xa.shape[1] != d_model:
+        raise ValueError("X has %d features, the models were fitted on %d"
+                         % (Xc.shape[1], d_model - (Xa.shape[1] - Xc.shape[1])))
+    if Xa is not Xc:
+        Xa.sort_indices()
+    return Xa
+
+
+class ModelBank(object):
+    """F fitted estimators resident on one device handle as a stacked image.  ``device`` and
+    ``precision`` default to the first member's.  ``close()`` (or leaving the ``with`` block)
+    releases the handle.  Not picklable."""
+
+    def __init__(self, estimators, device=None, precision=None):
+        self._engine = None
+        self.estimators, specs, (degree, lin, lower, d_model) = _members(estimators)
+        first = self.estimators[0]
+        if precision is None:
+            precision = first.precision
+        if precision not in _capi.DTYPES:
+            raise ValueError("precision must be 'f32' or 'f64'")
+        self._d_model = d_model
+        self.n_models = len(specs)
+        blocks = [(0, degree)] + ([(1, 2)] if lower else [])
+        ks = [s[3].shape[1] for s in specs]
+        self.koff = np.concatenate([[0], np.cumsum(ks)]).astype(np.int32)
+        # feature-major, stacked: block q of every member transposed and side by side
+        Pt = np.empty((len(blocks), d_model, int(self.koff[-1])))
+        for q, (o, _) in enumerate(blocks):
+            for f, s in enumerate(specs):
+                Pt[q, :, self.koff[f]:self.koff[f + 1]] = s[3][o].T
+        lams = np.concatenate([s[5] for s in specs])
+        w = np.stack([s[4] for s in specs], axis=1) if lin else None
+        engine = _engine.HipEngine(device=_fit_device(first) if device is None else device,
+                                   precision=precision)
+        try:
+            engine.bank_set(self.koff, [m for _, m in blocks], Pt, lams, w)
+        except Exception:
+            engine.close()
+            raise
+        self._engine = engine
+
+    def _X(self, X):
+        if self._engine is None:
+            raise ValueError("this ModelBank is closed")
+        return _prepare(self.estimators[0], X, self._d_model)
+
+    def decision_function(self, X):
+        """float64 (n, F): column f is member f's ``decision_function(X)`` (regressors:
+        ``predict``)."""
+        return self._engine.bank_scores(self._X(X))
+
+    def argmax(self, X):
+        """``(index int32, best, runner_up)``, (n,) each: per row the member with the largest
+        score (ties go to the lowest index), that score and the second largest (``-inf`` for a
+        one-member bank).  The scores stay on the device."""
+        return self._engine.bank_argmax(self._X(X))
+
+    def losses(self, X, y, loss=None, mean=False):
+        """(F,) ``sum_i loss(score_if, y_i)`` for a shared target ``y`` (n,), or
+        ``sum_i loss(score_if, y_if)`` for per-member targets ``y`` (n, F); ``mean``: divided by
+        n.  ``loss`` defaults to the members' common ``loss``.  Classifier members take their
+        targets already as -1 / +1.  F doubles leave the device."""
+        if loss is None:
+            found = {getattr(e, "loss", None) for e in self.estimators}
+            if len(found) != 1:
+                raise ValueError("the members have different losses (%s): say which one with "
+                                 "loss=" % ", ".join(sorted(map(str, found))))
+            loss = found.pop()
+        if loss not in _capi.LOSSES:
+            raise ValueError("loss must be one of %s, got %r" % (sorted(_capi.LOSSES), loss))
+        Xa = self._X(X)
+        y = np.asarray(y, dtype=np.double)
+        n = Xa.shape[0]
+        if y.shape not in ((n,), (n, self.n_models)):
+            raise ValueError("y must be (%d,) or (%d, %d), got %r"
+                             % (n, n, self.n_models, y.shape))
+        out = self._engine.bank_losses(Xa, y, loss)
+        return out / n if mean else out
+
+    def mean(self, X, weights=None):
+        """(n,) ``sum_f weights[f] score_if``, the weights applied in member order; default
+        ``1 / F``."""
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.double)
+            if weights.shape != (self.n_models,):
+                raise ValueError("weights must be (%d,), got %r"
+                                 % (self.n_models, weights.shape))
+        return self._engine.bank_mean(self._X(X), weights)
+
+    def set_partition(self, slab_nnz=0):
+        """Stored entries per slab of the following calls (0: the default).  No bit of a score,
+        an argmax or a mean depends on it; a loss sum is reproducible for one slab size."""
+        self._engine.bank_set_partition(slab_nnz)
+
+    def info(self):
+        """dict: ``slabs`` and ``launches`` of the last call, ``resident_bytes`` of the image,
+        ``S`` its stacked components, ``n_models``."""
+        return dict(self._engine.bank_info(), n_models=self.n_models)
+
+    def close(self):
+        if self._engine is not None:
+            self._engine.close()
+            self._engine = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __reduce__(self):
+        raise TypeError("a ModelBank holds a device handle and cannot be pickled")
+
+
+# ------------------------------------------------------------------ NumPy restatement (test aid)
+def restate_bank_scores(estimators, X, wide=False):
+    """Test aid, NumPy only, never touches the device: the (n, F) scores, column f what
+    ``_get_output`` of member f computes on the dense rows of the checked, augmented, canonical
+    ``X`` -- each column from that member's parameters alone.  ``wide``: in ``np.longdouble``.
+    Dense (n, k, d) intermediates: small shapes only."""
+    ests, specs, (degree, lin, lower, d_model) = _members(estimators)
+    dtype = np.longdouble if wide else np.double
+    Xa = _prepare(ests[0], X, d_model)
+    V = np.asarray(Xa.todense(), dtype=dtype)
+    used = np.flatnonzero((V != 0).any(axis=0))  # the other columns add exact zeros
+    out = np.zeros((V.shape[0], len(ests)), dtype=dtype)
+    for f, (_, _, _, P, w, lams) in enumerate(specs):
+        out[:, f] = _restate_output(V[:, used], degree, lin, lower, P[:, :, used], w[used], lams,
+                                    dtype)
+    return out

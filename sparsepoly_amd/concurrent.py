@@ -35,7 +35,8 @@ def visible_devices():
         return [0]
 
 
-def fit_concurrently(estimators, X, y, max_concurrent=None, devices=None, share_data=True):
+def fit_concurrently(estimators, X, y, max_concurrent=None, devices=None, share_data=True, *,
+                     targets=None):
     """Fit every estimator of ``estimators`` on ``(X, y)``, up to ``max_concurrent`` at a time
     PER DEVICE (default: four, two when all of them use ``solver='pbcd'``).  ``X`` / ``y`` may be
     one data set for all of them or sequences with one entry per estimator (cross-validation
@@ -48,8 +49,10 @@ def fit_concurrently(estimators, X, y, max_concurrent=None, devices=None, share_
 
     One data set for all: the fits of a device share ONE device image of the matrix and its entry
     streams (``share_data``; ``spfm_share_data``), and the first fit to reach the colouring
-    computes it for everybody.  Returns the list of fitted estimators (the same objects); the
-    first exception raised by a fit is re-raised after all fits have ended."""
+    computes it for everybody.  ``targets`` (keyword only): one target per estimator over the ONE
+    ``X`` -- the per-class targets of a one-vs-rest fit, say; ``y`` is not used then, and the image
+    and the schedule are shared as for one ``y``.  Returns the list of fitted estimators (the same
+    objects); the first exception raised by a fit is re-raised after all fits have ended."""
     ests = list(estimators)
     if not ests:
         return ests
@@ -59,6 +62,13 @@ def fit_concurrently(estimators, X, y, max_concurrent=None, devices=None, share_
     if int(max_concurrent) < 1:
         raise ValueError("max_concurrent must be >= 1.")
     per_fit_data = isinstance(X, (list, tuple))
+    if targets is not None:
+        if per_fit_data:
+            raise ValueError("targets= gives one target per estimator over a single X; with a "
+                             "list X pass the targets as the list y.")
+        targets = list(targets)
+        if len(targets) != len(ests):
+            raise ValueError("targets must hold one entry per estimator.")
     if per_fit_data:
         if not isinstance(y, (list, tuple)) or len(X) != len(ests) or len(y) != len(ests):
             raise ValueError("X and y must hold one entry per estimator.")
@@ -96,7 +106,10 @@ def fit_concurrently(estimators, X, y, max_concurrent=None, devices=None, share_
                         return
                     i, est = todo.pop()
                 try:
-                    est.fit(X[i] if per_fit_data else X, y[i] if per_fit_data else y)
+                    if targets is not None:
+                        est.fit(X, targets[i])
+                    else:
+                        est.fit(X[i] if per_fit_data else X, y[i] if per_fit_data else y)
                 except BaseException as exc:  # re-raised by the caller's thread
                     with lock:
                         errors.append(exc)

@@ -1,0 +1,181 @@
+// spfm_bank.hip.h -- a bank of F fitted models evaluated in one pass over the rows of X, and the
+// per-row reductions fused behind it (argmax, loss sums, weighted mean).  Part of the gfx950
+// device code; see DESIGN.md section 17.
+//
+// Layout.  The models share the kind (degree M or all-subsets), fit_lower, fit_linear and the
+// column count d; they may differ in their component counts k_f.  Their parameters are stacked
+// along the component axis, feature-major: per block Pt[d][S] with S = sum_f k_f, lams[S],
+// w[d][F], and koff[F + 1] (model f owns the stacked components koff[f] .. koff[f+1] - 1).  One
+// stored entry (i, j) then costs ONE contiguous read of S doubles for all models, and the row's
+// indices and values are read once.
+//
+// Work split.  One wavefront per row.  The row's entries are staged in LDS, kBankStage at a time;
+// the lanes run over the stacked components in chunks of 64, each lane the DP of
+// anova_predict_kernel (a[t] += a[t-1] p x, entries in stored order) for its component.  A row of
+// at most kBankStage entries is staged once for all chunks; a longer row is swept tile by tile
+// for every chunk.  During the first chunk's sweep lane f < F also forms model f's linear term.
+//
+// Summation order (what the error bound of tests/test_hip_bank.py is derived from).  For model f
+//   B_q  = ((0 + t_0) + t_1) + ... + t_{k_f - 1},  t_c = a_M(component c of f) * lams_c,
+// the terms of block q added ONE AFTER THE OTHER IN THE MODEL'S OWN COMPONENT ORDER by lane f:
+// after each chunk the 64 terms go through LDS and lane f adds those of them that are its own,
+// in index order, to its running sum.  No butterfly, no atomics: where a chunk boundary falls
+// inside a model changes nothing, a chunk that straddles two models feeds two lanes.
+//   lin  = ((0 + x_1 w_1f) + x_2 w_2f) + ...   in stored order (as linear_predict_kernel)
+//   score_f = (B_0 + lin) + B_1                (lin only with fit_linear, B_1 only with a second block)
+// Every operand is model f's own, so the value depends neither on the other members nor on f's
+// position, nor on the slab or the grid.
+#pragma once
+#include "spfm_common.hip.h"
+
+namespace spfm {
+
+constexpr int kBankStage = 128;            // entries of a row a wave stages at a time
+constexpr int kBankMaxModels = 64;         // one model per lane of the wave that owns the row
+constexpr int kBankMaxComponents = 4096;   // stacked components: 64 chunk sweeps per row at most
+
+enum { BANK_SCORES = 0, BANK_ARGMAX = 1, BANK_LOSSES = 2, BANK_MEAN = 3 };
+
+// LDS written by some lanes of a wave, read by others of the same wave (as explain_wave_sync)
+__device__ __forceinline__ void bank_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// One block of the bank on the rows of one slab: out[row][f] = B + lin (first) or += B.
+// rptr holds the slab's rows with the matrix's own offsets, ridx / rval its entries from e0 on.
+template <typename T, int M>
+__global__ __launch_bounds__(kBlock) void bank_predict_kernel(
+    int64_t rows, int64_t e0, int S, int F, const int64_t* __restrict__ rptr,
+    const int32_t* __restrict__ ridx, const T* __restrict__ rval,
+    const double* __restrict__ Pt /* d x S */, const double* __restrict__ lams /* S */,
+    const int32_t* __restrict__ koff /* F + 1 */, const double* __restrict__ wb /* d x F or NULL */,
+    int first, double* __restrict__ out /* rows x F */) {
+    __shared__ int32_t sh_j[kBlock / kWave][kBankStage];
+    __shared__ double sh_x[kBlock / kWave][kBankStage];
+    __shared__ double sh_t[kBlock / kWave][kWave];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * (kBlock / kWave) + wave;
+    if (row >= rows) return;  // (waves are independent: no workgroup barrier below)
+    const int64_t b = rptr[row] - e0;
+    const int n_i = (int)(rptr[row + 1] - rptr[row]);
+    const int ntile = (n_i + kBankStage - 1) / kBankStage;
+    const int lo = lane < F ? koff[lane] : 0, hi = lane < F ? koff[lane + 1] : 0;
+    int32_t* const js = sh_j[wave];
+    double* const xs = sh_x[wave];
+    double* const ts = sh_t[wave];
+    double acc = 0.0, lin = 0.0;
+    for (int c0 = 0; c0 < S; c0 += kWave) {
+        const int s = c0 + lane;
+        const bool active = s < S;
+        double a[M + 1];
+        a[0] = 1.0;
+#pragma unroll
+        for (int t = 1; t <= M; ++t) a[t] = 0.0;
+        for (int tile = 0; tile < ntile; ++tile) {
+            const int len = min(kBankStage, n_i - tile * kBankStage);
+            if (ntile > 1 || c0 == 0) {  // a short row stays staged for every chunk
+                bank_wave_sync();        // the previous tile has been read
+                for (int u = lane; u < len; u += kWave) {
+                    const int64_t ii = b + (int64_t)tile * kBankStage + u;
+                    js[u] = ridx[ii];
+                    xs[u] = (double)rval[ii];
+                }
+                bank_wave_sync();
+            }
+            if (c0 == 0 && wb != nullptr && lane < F)
+                for (int u = 0; u < len; ++u) lin += xs[u] * wb[(size_t)js[u] * F + lane];
+            if (active) {
+                for (int u = 0; u < len; ++u) {
+                    if constexpr (M == 0) {  // all-subsets kernel, as anova_predict_kernel
+                        a[0] *= 1 + xs[u] * Pt[(size_t)js[u] * S + s];
+                    } else {
+                        const double px = Pt[(size_t)js[u] * S + s] * xs[u];
+#pragma unroll
+                        for (int t = M; t >= 1; --t) a[t] += a[t - 1] * px;
+                    }
+                }
+            }
+        }
+        bank_wave_sync();  // the previous chunk's terms have been read
+        ts[lane] = active ? a[M] * lams[s] : 0.0;
+        bank_wave_sync();
+        const int s0 = max(lo, c0), s1 = min(hi, c0 + kWave);
+        for (int c = s0; c < s1; ++c) acc += ts[c - c0];
+    }
+    if (lane < F) {
+        double* o = out + (size_t)row * F + lane;
+        if (first)
+            *o = (wb != nullptr) ? acc + lin : acc;
+        else
+            *o += acc;
+    }
+}
+
+// per row: index of the largest score (ties: the lowest index), that score, the runner-up
+static __global__ __launch_bounds__(kBlock) void bank_argmax_kernel(
+    int64_t rows, int F, const double* __restrict__ sc, int32_t* __restrict__ idx,
+    double* __restrict__ best, double* __restrict__ runner) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= rows) return;
+    const double* r = sc + (size_t)i * F;
+    double bv = r[0], rv = -INFINITY;
+    int bi = 0;
+    for (int f = 1; f < F; ++f) {
+        const double v = r[f];
+        if (v > bv) {
+            rv = bv;
+            bv = v;
+            bi = f;
+        } else if (v > rv) {
+            rv = v;
+        }
+    }
+    idx[i] = bi;
+    best[i] = bv;
+    runner[i] = rv;
+}
+
+// per row: ((0 + wt_0 s_0) + wt_1 s_1) + ... in model order
+static __global__ __launch_bounds__(kBlock) void bank_mean_kernel(
+    int64_t rows, int F, const double* __restrict__ sc, const double* __restrict__ wt,
+    double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= rows) return;
+    const double* r = sc + (size_t)i * F;
+    double a = 0.0;
+    for (int f = 0; f < F; ++f) a += wt[f] * r[f];
+    out[i] = a;
+}
+
+// partial[block][f] = sum over the block's 256 rows of loss(score_if, y_if): one row per thread,
+// block_sum2 (butterfly, then the four waves in order).  y[i * ys_row + f * ys_f]: shared target
+// (1, 0) or per-model targets (F, 1).  Finished by bank_loss_finish_kernel.
+static __global__ __launch_bounds__(kBlock) void bank_loss_partial_kernel(
+    int64_t rows, int F, const double* __restrict__ sc, const double* __restrict__ y, int ys_row,
+    int ys_f, int loss, double* __restrict__ partial) {
+    __shared__ double red[16];
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    for (int f = 0; f < F; ++f) {
+        double a = 0.0, b = 0.0;
+        if (i < rows)
+            a = loss_dev(loss, sc[(size_t)i * F + f], y[(size_t)i * ys_row + (size_t)f * ys_f]);
+        block_sum2(a, b, red);
+        if (threadIdx.x == 0) partial[(size_t)blockIdx.x * F + f] = a;
+    }
+}
+
+// out[f] = sum of partial[0..P)[f]: workgroup f, thread t adds the partials t, t + 256, ... in
+// order, then block_sum2 (fixed order => reproducible for one partition of the rows)
+static __global__ __launch_bounds__(kBlock) void bank_loss_finish_kernel(
+    int64_t P, int F, const double* __restrict__ partial, double* __restrict__ out) {
+    __shared__ double red[16];
+    const int f = blockIdx.x;
+    double a = 0.0, b = 0.0;
+    for (int64_t p = threadIdx.x; p < P; p += kBlock) a += partial[(size_t)p * F + f];
+    block_sum2(a, b, red);
+    if (threadIdx.x == 0) out[f] = a;
+}
+
+}  // namespace spfm

@@ -4,7 +4,7 @@
 // cd_linear and the epoch drivers; prb: persistent 64-column passes, one translation unit per
 // storage type; wide: wide persistent passes; pbcd: multi-kernel pbcd; pbprb: persistent pbcd
 // pass, one unit per storage type; psgd; gram, objective, interactions (pairs and triples), rank,
-// explain: the read-only feature units).  Every unit owns the extern "C" block of its entries.  See DESIGN.md
+// explain, bank: the read-only feature units).  Every unit owns the extern "C" block of its entries.  See DESIGN.md
 // for the execution model.
 #pragma once
 #include <dlfcn.h>
@@ -1135,6 +1135,50 @@ struct spfm_engine {
     int explain_slab(const ExplainCall& c, int64_t r0, int64_t r1);
     template <typename T>
     int explain_run(const char* what, const ExplainCall& c);
+
+    // ------------------------------- model banks (spfm_engine_bank.hip)
+    // F fitted models stacked along the component axis, resident until spfm_bank_release, the next
+    // spfm_bank_set or spfm_destroy (independent of spfm_set_params: the bank brings its own
+    // parameters).  One pass over the rows of a CSR matrix gives every model's score; the argmax,
+    // the loss sums and the weighted mean are formed on the device behind it (DESIGN.md section
+    // 17).  Rows go through in slabs bounded by stored entries; the scratch holds one slab.
+    DevBuf bk_pt, bk_lams, bk_w, bk_koff;  // the image: blocks x d x S, S, d x F, F + 1
+    DevBuf bk_rp, bk_ri, bk_rv;            // CSR image of one slab (values in the handle's precision)
+    DevBuf bk_sc;                          // its scores (rows x F)
+    DevBuf bk_y, bk_wt, bk_part, bk_fin;   // targets of one slab, mean weights, loss partials, sums
+    DevBuf bk_oi, bk_o0, bk_o1;            // per-row results of one slab
+    bool bk_have = false, bk_lin = false;
+    int bk_F = 0, bk_S = 0, bk_d = 0, bk_blocks = 0, bk_degree[2] = {0, 0};
+    int64_t bk_slab_nnz = 0;               // spfm_bank_set_partition: stored entries per slab (0 = default)
+    int64_t bk_slabs = 0, bk_launches = 0;  // spfm_bank_info: of the last call
+    size_t bank_image_bytes() const {
+        return bk_have ? bk_pt.bytes + bk_lams.bytes + bk_w.bytes + bk_koff.bytes : 0;
+    }
+    void bank_release();
+    int bank_set(int32_t d_, int F, const int32_t* koff, int n_blocks, const int32_t* degree,
+                 const double* Pt_bank, const double* lams_bank, const double* w_bank);
+    struct BankCall {  // the arguments of spfm_bank_scores / _argmax / _losses / _mean
+        int what;  // BANK_SCORES ...
+        int64_t n;
+        int32_t d;
+        const int64_t* indptr;
+        const int32_t* indices;
+        const double* data;
+        double* out;         // scores (n x F), best (n), loss sums (F) or mean (n)
+        int32_t* idx;        // argmax
+        double* runner;      // argmax
+        int loss;            // losses
+        const double* y;     // losses: (n) or (n x F)
+        int per_model;       // losses
+        const double* wt;    // mean: (F) or NULL = 1 / F
+    };
+    int bank_check(const char* what, const BankCall& c);
+    template <typename T, int M>
+    void bank_launch_block(int64_t rows, int64_t e0, int q, int first);
+    template <typename T>
+    int bank_slab(const BankCall& c, int64_t r0, int64_t r1, int64_t part0);
+    template <typename T>
+    int bank_run(const char* what, const BankCall& c);
 
     // diagnostics that need kernels of one translation unit
     int debug_stream_probe(int64_t* bytes_out);  // spfm_engine_pcd.hip

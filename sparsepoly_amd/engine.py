@@ -666,6 +666,109 @@ class HipEngine(object):
         return dict(scratch_kib=int((out[0] + 1023) // 1024), device_ms=out[1] / 1e3,
                     slab_nnz=int(out[2]), slabs=int(out[3]))
 
+    # ------------------------- model banks: F models scored in one pass over the rows (spfm.h)
+    def bank_set(self, koff, degrees, Pt_bank, lams_bank, w_bank=None):
+        """``spfm_bank_set``: make the stacked image resident.  ``Pt_bank`` (n_blocks, d, S),
+        ``lams_bank`` (S), ``w_bank`` (d, F) or ``None`` (no linear term), ``koff`` (F + 1),
+        ``degrees`` the blocks' degrees (-1: all-subsets)."""
+        Pt_bank = np.ascontiguousarray(Pt_bank, dtype=np.float64)
+        if Pt_bank.ndim != 3:
+            raise ValueError("bank_set: Pt_bank must be (n_blocks, n_features, S)")
+        nb, d, S = Pt_bank.shape
+        ka, kp = _capi.i32(koff)
+        ga, gp = _capi.i32(degrees)
+        la, lp = _capi.f64(lams_bank)
+        F = ka.shape[0] - 1
+        if ga.shape[0] != nb or la.shape[0] != S or F < 0 or (F >= 1 and ka[-1] != S):
+            raise ValueError("bank_set: koff / degrees / lams_bank do not match Pt_bank")
+        wp = None
+        if w_bank is not None:
+            wa, wp = _capi.f64(w_bank)
+            if wa.shape != (d, F):
+                raise ValueError("bank_set: w_bank must be (n_features, F)")
+        self._check(self._lib.spfm_bank_set(self._h, d, F, kp, nb, gp,
+                                            Pt_bank.ctypes.data_as(_capi._dp), lp, wp))
+        self.bank_shape = (F, S, d)
+
+    def _bank_args(self, X, what):
+        """-> (rows, the six leading arguments of the four passes, what keeps them alive)"""
+        if getattr(self, "bank_shape", None) is None:
+            raise ValueError("%s: call bank_set first" % what)
+        Xr = sp.csr_matrix(X, dtype=np.float64)
+        if not Xr.has_canonical_format:
+            Xr = Xr.copy()
+            Xr.sum_duplicates()
+            Xr.sort_indices()
+        keep = (_capi.i64(Xr.indptr), _capi.i32(Xr.indices), _capi.f64(Xr.data))
+        return Xr.shape[0], (self._h, Xr.shape[0], Xr.shape[1], keep[0][1], keep[1][1],
+                             keep[2][1]), keep
+
+    def bank_scores(self, X):
+        """``spfm_bank_scores``: float64 (n, F), every model's ``decision_function``."""
+        n, args, keep = self._bank_args(X, "bank_scores")
+        out = np.zeros((n, self.bank_shape[0]))
+        self._check(self._lib.spfm_bank_scores(*args, out.ctypes.data_as(_capi._dp)))
+        return out
+
+    def bank_argmax(self, X):
+        """``spfm_bank_argmax``: ``(index int32, best, runner_up)``, (n,) each; ties go to the
+        lowest index, the runner-up of a one-model bank is ``-inf``."""
+        n, args, keep = self._bank_args(X, "bank_argmax")
+        idx, best, runner = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n)
+        self._check(self._lib.spfm_bank_argmax(
+            *args, idx.ctypes.data_as(_capi._ip), best.ctypes.data_as(_capi._dp),
+            runner.ctypes.data_as(_capi._dp)))
+        return idx, best, runner
+
+    def bank_losses(self, X, y, loss):
+        """``spfm_bank_losses``: (F,) sums of ``loss(score_if, y_i)`` (``y`` (n,)) or of
+        ``loss(score_if, y_if)`` (``y`` (n, F))."""
+        if loss not in _capi.LOSSES:
+            raise ValueError("bank_losses: loss must be one of %s, got %r"
+                             % (sorted(_capi.LOSSES), loss))
+        n, args, keep = self._bank_args(X, "bank_losses")
+        ya, yp = _capi.f64(y)
+        F = self.bank_shape[0]
+        if ya.shape not in ((n,), (n, F)):
+            raise ValueError("bank_losses: y must be (%d,) or (%d, %d), got %r"
+                             % (n, n, F, ya.shape))
+        out = np.zeros(F)
+        self._check(self._lib.spfm_bank_losses(*args, _capi.LOSSES[loss], yp, int(ya.ndim == 2),
+                                               out.ctypes.data_as(_capi._dp)))
+        return out
+
+    def bank_mean(self, X, weights=None):
+        """``spfm_bank_mean``: (n,) ``sum_f weights[f] score_if``, added in model order;
+        ``weights`` ``None``: ``1 / F``."""
+        n, args, keep = self._bank_args(X, "bank_mean")
+        wp = None
+        if weights is not None:
+            wa, wp = _capi.f64(weights)
+            if wa.shape != (self.bank_shape[0],):
+                raise ValueError("bank_mean: weights must be (%d,), got %r"
+                                 % (self.bank_shape[0], wa.shape))
+        out = np.zeros(n)
+        self._check(self._lib.spfm_bank_mean(*args, wp, out.ctypes.data_as(_capi._dp)))
+        return out
+
+    def bank_set_partition(self, slab_nnz=0):
+        """``spfm_bank_set_partition``: stored entries per slab of the following bank passes
+        (0: the library's default).  No bit of a score depends on it."""
+        self._check(self._lib.spfm_bank_set_partition(self._h, int(slab_nnz)))
+
+    def bank_info(self):
+        """``spfm_bank_info``: dict ``slabs`` and ``launches`` (of ``bank_predict_kernel``) of the
+        last pass, ``resident_bytes`` of the image, ``S`` its stacked components."""
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.spfm_bank_info(self._h, out.ctypes.data_as(_capi._lp)))
+        return dict(slabs=int(out[0]), launches=int(out[1]), resident_bytes=int(out[2]),
+                    S=int(out[3]))
+
+    def bank_release(self):
+        """``spfm_bank_release``: free the image and the scratch of the bank passes."""
+        self._check(self._lib.spfm_bank_release(self._h))
+        self.bank_shape = None
+
     # ------------------------- third-order weights T[a, j, l] = sum_s lams_s p_sa p_sj p_sl (spfm.h)
     def interaction3_stats(self, order_idx, tol=0.0, n_features=None):
         """``spfm_interaction3_stats``: dict ``nnz`` (triples a < j < l with ``|T| > tol``),
