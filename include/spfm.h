@@ -712,6 +712,44 @@ int spfm_rank_set_partition(spfm_handle h, int64_t row_slab, int64_t cand_strip)
 int spfm_rank_info(spfm_handle h, int64_t* out4);
 int spfm_rank_release(spfm_handle h);
 
+/* -- candidate ranking: lists left out, exact ranks of held-out candidates ------------------
+ * Both entries take per-row lists of candidates as CSR patterns over the resident candidates:
+ * ptr[n_ctx+1] int64 starting at 0 and not decreasing, ids int32 in [0, n_cand), strictly ascending
+ * within a row (sorted, no duplicate).  E_b (eptr, eidx) are the candidates LEFT OUT for context
+ * row b -- what the user already has --; eptr == NULL: nothing is left out.  T_b (tptr, tidx) are
+ * the TARGETS of row b, the held-out candidates whose rank is asked for; a row may have none, at
+ * most SPFM_RANK_MAX_TARGETS.  T_b and E_b must be disjoint.  score[b, c] below is the value
+ * spfm_rank_scores writes for the pair, bit for bit, and beats((v, c), (s, t)) = v > s ||
+ * (v == s && c < t) is the order of spfm_rank_topk.
+ *
+ * spfm_rank_topk_excl: spfm_rank_topk over the candidates outside E_b.  *k_out = min(K, n_cand) as
+ *   before; a row with fewer admissible candidates ends in slots of index -1 and NaN.  With
+ *   eptr == NULL it is spfm_rank_topk, bit for bit.
+ * spfm_rank_eval: for every target, in the order of tidx,
+ *     rank_out  = #{ c not in E_b, c != t : beats((score[b, c], c), (score[b, t], t)) }   (0-based;
+ *                 the row's other targets count like any other candidate)
+ *     score_out = score[b, t]
+ *   and per row n_eff_out[b] = n_cand - |E_b|.  Any of the three may be NULL.  A candidate whose
+ *   score is not finite never beats anything; a target whose own score is not finite gets rank -1.
+ *   Exact: the target's score comes from the same chain of matrix-instruction steps as every other
+ *   score, the counts are integers, and no result depends on the slab height or the strip width.
+ *   Nothing of size n_ctx * n_cand is stored.
+ * Slabs, strips, spfm_rank_info (device time of the last call's kernels; the scratch includes the
+ * lists, scores and counts of the last call) and spfm_rank_release work as above.
+ * Errors, all found before the first write to an output: a row with more than
+ * SPFM_RANK_MAX_TARGETS targets -> SPFM_ERR_UNSUPPORTED (the message names the cap; a row is never
+ * truncated); pointers not starting at 0 or decreasing, an id out of range, an unsorted list or a
+ * duplicate, a target that is also left out, no candidates set, and the errors of spfm_rank_topk
+ * -> SPFM_ERR_INVALID. */
+#define SPFM_RANK_MAX_TARGETS 64
+int spfm_rank_topk_excl(spfm_handle h, int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
+                        const double* data, const int64_t* eptr, const int32_t* eidx, int64_t K,
+                        int32_t* idx_out, double* val_out, int64_t* k_out);
+int spfm_rank_eval(spfm_handle h, int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
+                   const double* data, const int64_t* tptr, const int32_t* tidx,
+                   const int64_t* eptr, const int32_t* eidx,
+                   int32_t* rank_out, double* score_out, int32_t* n_eff_out);
+
 /* -- per-row feature attributions -------------------------------------------------------------
  * Why a row got its prediction.  The model is a sum of blocks, block q being
  *   sum_s lams_s sum_{t=0..6} coef[q][s][t] A^t(p_s, x),   p_s = P[order_idx[q]][s],

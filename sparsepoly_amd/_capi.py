@@ -103,6 +103,7 @@ SYMBOLS = [
     "spfm_interaction3_values",
     "spfm_rank_set_candidates", "spfm_rank_scores", "spfm_rank_topk",
     "spfm_rank_set_partition", "spfm_rank_info", "spfm_rank_release",
+    "spfm_rank_topk_excl", "spfm_rank_eval",
     "spfm_explain_csr", "spfm_explain_topk_csr", "spfm_explain_set_partition",
     "spfm_explain_info",
     "spfm_bank_set", "spfm_bank_scores", "spfm_bank_argmax", "spfm_bank_losses", "spfm_bank_mean",
@@ -112,6 +113,7 @@ INTERACTION_BLOCK_MAX_BYTES = 1 << 30  # SPFM_INTERACTION_BLOCK_MAX_BYTES
 INTERACTION3_MAX_ACTIVE = 1 << 15  # SPFM_INTERACTION3_MAX_ACTIVE
 RANK_MAX_K = 128  # SPFM_RANK_MAX_K
 RANK_SCORES_MAX_BYTES = 1 << 30  # SPFM_RANK_SCORES_MAX_BYTES
+RANK_MAX_TARGETS = 64  # SPFM_RANK_MAX_TARGETS
 EXPLAIN_MAX_K = 64  # SPFM_EXPLAIN_MAX_K
 EXPLAIN_MODES = {"attribution": 0, "gradient": 1}  # SPFM_EXPLAIN_ATTRIBUTION / _GRADIENT
 BANK_MAX_MODELS = 64  # SPFM_BANK_MAX_MODELS
@@ -215,6 +217,9 @@ def load():
     L.spfm_rank_set_partition.argtypes = [_h, C.c_int64, C.c_int64]
     L.spfm_rank_info.argtypes = [_h, _lp]
     L.spfm_rank_release.argtypes = [_h]
+    L.spfm_rank_topk_excl.argtypes = [_h, C.c_int64, _lp, _ip, _dp, _lp, _ip, C.c_int64, _ip, _dp,
+                                      _lp]
+    L.spfm_rank_eval.argtypes = [_h, C.c_int64, _lp, _ip, _dp, _lp, _ip, _lp, _ip, _ip, _dp, _ip]
     _explain = [_h, C.c_int64, _lp, _ip, _dp, C.c_int, _ip, _ip, _dp, C.c_int]
     L.spfm_explain_csr.argtypes = _explain + [C.c_int, _dp, _dp]
     L.spfm_explain_topk_csr.argtypes = _explain + [C.c_int, _ip, _dp]

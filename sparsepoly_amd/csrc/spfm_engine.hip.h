@@ -1066,6 +1066,9 @@ struct spfm_engine {
     DevBuf rk_xp, rk_xi, rk_xv;            // CSR staging (contexts or candidates)
     DevBuf rk_lv, rk_li, rk_ov, rk_oi;     // per-strip lists, merged lists of one slab
     DevBuf rk_dense;                       // dense scores of one slab
+    DevBuf rk_ep, rk_ei;                   // excluded candidates of the call's rows (CSR pattern)
+    DevBuf rk_tp, rk_ti, rk_ts, rk_tr;     // rank_eval: targets, their scores and counts
+    DevBuf rk_pairs;                       // ... (row tile, candidate tile) pairs with a target
     std::vector<uint8_t> rk_zflag;         // columns with a stored candidate entry
     bool rk_have = false;
     int64_t rk_C = 0;
@@ -1075,7 +1078,9 @@ struct spfm_engine {
     int rk_device_us = 0;   // spfm_rank_info: kernels of the last scores / topk call
     size_t rank_scratch_bytes() const {
         return rk_V.bytes + rk_cc.bytes + rk_U.bytes + rk_rc.bytes + rk_xp.bytes + rk_xi.bytes +
-               rk_xv.bytes + rk_lv.bytes + rk_li.bytes + rk_ov.bytes + rk_oi.bytes + rk_dense.bytes;
+               rk_xv.bytes + rk_lv.bytes + rk_li.bytes + rk_ov.bytes + rk_oi.bytes + rk_dense.bytes +
+               rk_ep.bytes + rk_ei.bytes + rk_tp.bytes + rk_ti.bytes + rk_ts.bytes + rk_tr.bytes +
+               rk_pairs.bytes;
     }
     void rank_release();  // frees the scratch and forgets the candidates
     int rank_check_csr(const char* what, int64_t rows, const int64_t* indptr,
@@ -1090,9 +1095,15 @@ struct spfm_engine {
                       const int32_t* indices, const double* data);
     int rank_scores(int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
                     const double* data, double* out);
+    // (eptr NULL: nothing excluded, the selection spfm_rank_topk has always launched)
     int rank_topk(int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
-                  const double* data, int64_t K, int32_t* idx_out, double* val_out,
-                  int64_t* k_out);
+                  const double* data, const int64_t* eptr, const int32_t* eidx, int64_t K,
+                  int32_t* idx_out, double* val_out, int64_t* k_out);
+    int rank_check_pattern(const char* what, const char* name, int64_t rows, const int64_t* ptr,
+                           const int32_t* idx);
+    int rank_eval(int64_t n_ctx, const int64_t* indptr, const int32_t* indices, const double* data,
+                  const int64_t* tptr, const int32_t* tidx, const int64_t* eptr,
+                  const int32_t* eidx, int32_t* rank_out, double* score_out, int32_t* n_eff_out);
 
     // ------------------------------- per-row attributions (spfm_engine_explain.hip)
     // phi_ij (exact Shapley values against a zero baseline) or df/dx_ij on the stored entries of a

@@ -1,27 +1,39 @@
-// spfm_engine_rank.hip -- spfm_rank_set_candidates / _scores / _topk (include/spfm.h): the
-// scores of every (context row, candidate row) pair under the handle's parameters and the K best
-// candidates of every context row.  score = rowconst + colconst + U V^T (spfm_rank.hip.h); the
-// candidate towers are built once and kept, contexts go through in slabs of rows, the product
-// is consumed tile by tile.  Read-only like the interaction unit: scratch of its own, the live
-// parameter image is read through its strides and no validity flag changes.  See DESIGN.md
-// section 15.
+// spfm_engine_rank.hip -- spfm_rank_set_candidates / _scores / _topk / _topk_excl / _eval
+// (include/spfm.h): the scores of every (context row, candidate row) pair under the handle's
+// parameters, the K best candidates of every context row (with or without a per-row list of
+// candidates left out) and the exact ranks of held-out candidates.  score = rowconst + colconst +
+// U V^T (spfm_rank.hip.h, spfm_rankeval.hip.h); the candidate towers are built once and kept,
+// contexts go through in slabs of rows, the product is consumed tile by tile.  Read-only like the
+// interaction unit: scratch of its own, the live parameter image is read through its strides and
+// no validity flag changes.  See DESIGN.md sections 15 and 15a.
 #include "spfm_engine.hip.h"
-#include "spfm_rank.hip.h"
+#include "spfm_rankeval.hip.h"
 
 #include <algorithm>
 
 static_assert(kRankMaxK == SPFM_RANK_MAX_K, "header and device agree on the cap");
+static_assert(kRankMaxTargets == SPFM_RANK_MAX_TARGETS, "header and device agree on the cap");
 
 namespace {
 constexpr int64_t kRankSlabDefault = 4096;          // context rows per slab
 constexpr int64_t kRankDenseSlabBytes = 256ll << 20;  // device image of one dense slab
 int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
+// strip width of the selection and of the count pass, in tiles: the option, else about 512
+// workgroups per slab, 16 .. 1024 tiles (a longer strip has fewer survivors per candidate: about
+// K ln(strip / K) per row and strip)
+int64_t rank_strip_tiles(int cand_strip, int Tc, int row_tiles) {
+    int64_t t = std::min<int64_t>(1024, std::max<int64_t>(16, (int64_t)Tc * row_tiles / 512));
+    if (cand_strip > 0) t = cdiv(cand_strip, kIntTile);
+    return std::min<int64_t>(t, std::min<int64_t>(Tc, kRankMaxStrip / kIntTile));
+}
+
 }  // namespace
 
 void spfm_engine::rank_release() {
     for (DevBuf* b : {&rk_V, &rk_cc, &rk_U, &rk_rc, &rk_xp, &rk_xi, &rk_xv, &rk_lv, &rk_li, &rk_ov,
-                      &rk_oi, &rk_dense})
+                      &rk_oi, &rk_dense, &rk_ep, &rk_ei, &rk_tp, &rk_ti, &rk_ts, &rk_tr,
+                      &rk_pairs})
         b->release();
     rk_zflag.clear();
     rk_have = false;
@@ -190,9 +202,29 @@ int spfm_engine::rank_scores(int64_t n_ctx, const int64_t* indptr, const int32_t
     return SPFM_OK;
 }
 
+// a per-row list of candidates: pointers start at 0 and do not decrease, ids in [0, C) and
+// strictly ascending within a row
+int spfm_engine::rank_check_pattern(const char* what, const char* name, int64_t rows,
+                                    const int64_t* ptr, const int32_t* idx) {
+    const std::string w = std::string(what) + ": " + name;
+    if (rows < 0 || !ptr) FAIL(SPFM_ERR_INVALID, w + ": bad arguments");
+    if (ptr[0] != 0) FAIL(SPFM_ERR_INVALID, w + ": the pointers must start at 0");
+    for (int64_t i = 0; i < rows; ++i)
+        if (ptr[i + 1] < ptr[i]) FAIL(SPFM_ERR_INVALID, w + ": the pointers decrease");
+    if (ptr[rows] > 0 && !idx) FAIL(SPFM_ERR_INVALID, w + ": NULL array");
+    for (int64_t i = 0; i < rows; ++i)
+        for (int64_t ii = ptr[i]; ii < ptr[i + 1]; ++ii) {
+            if (idx[ii] < 0 || idx[ii] >= rk_C)
+                FAIL(SPFM_ERR_INVALID, w + ": candidate id out of range");
+            if (ii > ptr[i] && idx[ii] <= idx[ii - 1])
+                FAIL(SPFM_ERR_INVALID, w + ": the ids of a row must be ascending without duplicates");
+        }
+    return SPFM_OK;
+}
+
 int spfm_engine::rank_topk(int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
-                           const double* data, int64_t K, int32_t* idx_out, double* val_out,
-                           int64_t* k_out) {
+                           const double* data, const int64_t* eptr, const int32_t* eidx, int64_t K,
+                           int32_t* idx_out, double* val_out, int64_t* k_out) {
     if (!k_out) FAIL(SPFM_ERR_INVALID, "rank_topk: k_out is NULL");
     *k_out = 0;
     if (K < 1) FAIL(SPFM_ERR_INVALID, "rank_topk: K must be >= 1");
@@ -201,6 +233,10 @@ int spfm_engine::rank_topk(int64_t n_ctx, const int64_t* indptr, const int32_t* 
         snprintf(buf, sizeof buf, "rank_topk: K must be <= SPFM_RANK_MAX_K = %d",
                  (int)SPFM_RANK_MAX_K);
         FAIL(SPFM_ERR_UNSUPPORTED, buf);
+    }
+    if (eptr) {
+        if (!rk_have) FAIL(SPFM_ERR_INVALID, "rank_topk: call spfm_rank_set_candidates first");
+        SPFM_TRY(rank_check_pattern("rank_topk", "excluded", n_ctx, eptr, eidx));
     }
     SPFM_TRY(rank_contexts("rank_topk", n_ctx, indptr, indices, data));
     const int Ko = (int)std::min<int64_t>(K, rk_C);
@@ -214,17 +250,19 @@ int spfm_engine::rank_topk(int64_t n_ctx, const int64_t* indptr, const int32_t* 
         round_up(n_ctx, kIntTile));
     const int row_tiles = (int)(slab / kIntTile);
     const int Tc = (int)cdiv(rk_C, kIntTile);
-    // strip width: the option, else about 512 workgroups per slab, 16 .. 1024 tiles (a longer
-    // strip has fewer survivors per candidate: about K ln(strip / K) per row and strip)
-    int64_t strip_tiles = rk_cand_strip > 0
-                              ? cdiv(rk_cand_strip, kIntTile)
-                              : std::min<int64_t>(1024, std::max<int64_t>(16, (int64_t)Tc * row_tiles / 512));
-    strip_tiles = std::min<int64_t>(strip_tiles, std::min<int64_t>(Tc, kRankMaxStrip / kIntTile));
+    const int64_t strip_tiles = rank_strip_tiles(rk_cand_strip, Tc, row_tiles);
     const int n_strips = (int)cdiv(Tc, strip_tiles);
     const int cap = kRankCap;
-    const size_t lds = rank_lds_bytes(RANK_SELECT, cap);
-    HIPC(hipFuncSetAttribute((const void*)rank_tile_kernel<RANK_SELECT>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const size_t lds = rank_lds_bytes(RANK_SELECT, cap, eptr != nullptr);
+    if (eptr) {
+        HIPC(hipFuncSetAttribute((const void*)rank_tile_kernel<RANK_SELECT, true>,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        SPFM_TRY(upload(rk_ep, eptr, (size_t)n_ctx + 1));
+        SPFM_TRY(upload(rk_ei, eidx, (size_t)eptr[n_ctx]));
+    } else {
+        HIPC(hipFuncSetAttribute((const void*)rank_tile_kernel<RANK_SELECT>,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
     HIPC(rk_U.alloc(sizeof(double) * (size_t)slab * rk_Rp));
     HIPC(rk_rc.alloc(sizeof(double) * (size_t)slab));
     const size_t ln = (size_t)n_strips * (size_t)slab * Ko;
@@ -253,9 +291,15 @@ int spfm_engine::rank_topk(int64_t n_ctx, const int64_t* indptr, const int32_t* 
         // slots no finite score fills: index -1, NaN
         HIPC(hipMemsetAsync(rk_ov.p, 0xFF, sizeof(double) * (size_t)nrow * Ko, stream));
         HIPC(hipMemsetAsync(rk_oi.p, 0xFF, sizeof(int32_t) * (size_t)nrow * Ko, stream));
-        hipLaunchKernelGGL((rank_tile_kernel<RANK_SELECT>),
-                           dim3((unsigned)n_strips, (unsigned)(a.rows_pad / kIntTile)),
-                           dim3(kBlock), lds, stream, a);
+        a.eptr = rk_ep.as<int64_t>();
+        a.eidx = rk_ei.as<int32_t>();
+        a.row0 = r0;
+        const dim3 grid((unsigned)n_strips, (unsigned)(a.rows_pad / kIntTile));
+        if (eptr)
+            hipLaunchKernelGGL((rank_tile_kernel<RANK_SELECT, true>), grid, dim3(kBlock), lds,
+                               stream, a);
+        else
+            hipLaunchKernelGGL((rank_tile_kernel<RANK_SELECT>), grid, dim3(kBlock), lds, stream, a);
         hipLaunchKernelGGL((rank_tile_kernel<RANK_MERGE>), dim3(cdiv(nrow * kWave, kBlock)),
                            dim3(kBlock), 0, stream, a);
         HIPC(hipGetLastError());
@@ -269,6 +313,128 @@ int spfm_engine::rank_topk(int64_t n_ctx, const int64_t* indptr, const int32_t* 
     std::copy(hi.begin(), hi.end(), idx_out);
     std::copy(hv.begin(), hv.end(), val_out);
     *k_out = Ko;
+    return SPFM_OK;
+}
+
+int spfm_engine::rank_eval(int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
+                           const double* data, const int64_t* tptr, const int32_t* tidx,
+                           const int64_t* eptr, const int32_t* eidx, int32_t* rank_out,
+                           double* score_out, int32_t* n_eff_out) {
+    if (!have_params) FAIL(SPFM_ERR_INVALID, "rank_eval: no parameters set");
+    if (!rk_have) FAIL(SPFM_ERR_INVALID, "rank_eval: call spfm_rank_set_candidates first");
+    SPFM_TRY(rank_check_pattern("rank_eval", "targets", n_ctx, tptr, tidx));
+    if (eptr) SPFM_TRY(rank_check_pattern("rank_eval", "excluded", n_ctx, eptr, eidx));
+    int tcap = 1;
+    for (int64_t i = 0; i < n_ctx; ++i) {
+        const int64_t nt = tptr[i + 1] - tptr[i];
+        if (nt > SPFM_RANK_MAX_TARGETS) {
+            char buf[160];
+            snprintf(buf, sizeof buf,
+                     "rank_eval: row %lld has %lld targets, more than SPFM_RANK_MAX_TARGETS = %d",
+                     (long long)i, (long long)nt, (int)SPFM_RANK_MAX_TARGETS);
+            FAIL(SPFM_ERR_UNSUPPORTED, buf);
+        }
+        tcap = std::max(tcap, (int)nt);
+        if (!eptr) continue;
+        for (int64_t it = tptr[i], ie = eptr[i]; it < tptr[i + 1] && ie < eptr[i + 1];) {
+            if (tidx[it] == eidx[ie]) {
+                char buf[160];
+                snprintf(buf, sizeof buf, "rank_eval: candidate %d is a target of row %lld and "
+                         "excluded from it", (int)tidx[it], (long long)i);
+                FAIL(SPFM_ERR_INVALID, buf);
+            }
+            if (tidx[it] < eidx[ie])
+                ++it;
+            else
+                ++ie;
+        }
+    }
+    SPFM_TRY(rank_contexts("rank_eval", n_ctx, indptr, indices, data));
+    const int64_t nt = tptr[n_ctx];
+    std::vector<int32_t> hr((size_t)nt, 0);
+    std::vector<double> hs((size_t)nt, 0.0);
+    rk_device_us = 0;
+    if (nt > 0) {
+        const int64_t slab = std::min(
+            round_up(rk_row_slab > 0 ? rk_row_slab : kRankSlabDefault, kIntTile),
+            round_up(n_ctx, kIntTile));
+        const int Tc = (int)cdiv(rk_C, kIntTile);
+        const int64_t strip_tiles = rank_strip_tiles(rk_cand_strip, Tc, (int)(slab / kIntTile));
+        const int n_strips = (int)cdiv(Tc, strip_tiles);
+        const size_t lds = rank_count_lds_bytes(tcap);
+        HIPC(hipFuncSetAttribute(eptr ? (const void*)rank_count_kernel<true>
+                                      : (const void*)rank_count_kernel<false>,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPC(rk_U.alloc(sizeof(double) * (size_t)slab * rk_Rp));
+        HIPC(rk_rc.alloc(sizeof(double) * (size_t)slab));
+        SPFM_TRY(upload(rk_tp, tptr, (size_t)n_ctx + 1));
+        SPFM_TRY(upload(rk_ti, tidx, (size_t)nt));
+        if (eptr) {
+            SPFM_TRY(upload(rk_ep, eptr, (size_t)n_ctx + 1));
+            SPFM_TRY(upload(rk_ei, eidx, (size_t)eptr[n_ctx]));
+        }
+        HIPC(rk_ts.alloc(sizeof(double) * (size_t)nt));
+        HIPC(rk_tr.alloc(sizeof(int32_t) * (size_t)nt));
+        HIPC(hipMemsetAsync(rk_ts.p, 0, sizeof(double) * (size_t)nt, stream));
+        HIPC(hipMemsetAsync(rk_tr.p, 0, sizeof(int32_t) * (size_t)nt, stream));
+        std::vector<int64_t> keys;
+        std::vector<int2> pairs;
+        DeviceTimer timer;
+        for (int64_t r0 = 0; r0 < n_ctx; r0 += slab) {
+            const int64_t nrow = std::min(slab, n_ctx - r0);
+            if (tptr[r0 + nrow] == tptr[r0]) continue;  // no target in the slab
+            // the (row tile, candidate tile) pairs of the slab that hold a target
+            keys.clear();
+            for (int64_t i = 0; i < nrow; ++i)
+                for (int64_t ii = tptr[r0 + i]; ii < tptr[r0 + i + 1]; ++ii)
+                    keys.push_back((i / kIntTile) * Tc + tidx[ii] / kIntTile);
+            std::sort(keys.begin(), keys.end());
+            keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+            pairs.resize(keys.size());
+            for (size_t q = 0; q < keys.size(); ++q)
+                pairs[q] = make_int2((int)(keys[q] / Tc), (int)(keys[q] % Tc));
+            SPFM_TRY(upload(rk_pairs, pairs.data(), pairs.size()));
+            timer.begin(stream);
+            SPFM_TRY(rank_towers(r0, nrow, RANK_CTX, rk_U.as<double>(), rk_rc.as<double>()));
+            RankEvalArgs e;
+            memset(&e, 0, sizeof e);
+            e.r = rank_args(this, nrow);
+            e.r.strip_tiles = (int)strip_tiles;
+            e.r.n_strips = n_strips;
+            e.r.eptr = rk_ep.as<int64_t>();
+            e.r.eidx = rk_ei.as<int32_t>();
+            e.r.row0 = r0;
+            e.tptr = rk_tp.as<int64_t>();
+            e.tidx = rk_ti.as<int32_t>();
+            e.pairs = rk_pairs.as<int2>();
+            e.tscore = rk_ts.as<double>();
+            e.trank = rk_tr.as<int32_t>();
+            e.tcap = tcap;
+            hipLaunchKernelGGL(rank_tscore_kernel, dim3((unsigned)pairs.size()), dim3(kBlock), 0,
+                               stream, e);
+            const dim3 grid((unsigned)n_strips, (unsigned)(e.r.rows_pad / kIntTile));
+            if (eptr)
+                hipLaunchKernelGGL(rank_count_kernel<true>, grid, dim3(kBlock), lds, stream, e);
+            else
+                hipLaunchKernelGGL(rank_count_kernel<false>, grid, dim3(kBlock), lds, stream, e);
+            HIPC(hipGetLastError());
+            timer.end(stream);
+            SPFM_TRY(sync());  // `pairs` and the context towers are rewritten by the next slab
+            timer.collect();
+        }
+        SPFM_TRY(download(hs.data(), rk_ts.p, (size_t)nt));
+        SPFM_TRY(download(hr.data(), rk_tr.p, (size_t)nt));
+        SPFM_TRY(sync());
+        rk_device_us = (int)std::min(timer.ms * 1e3, 2e9);
+        for (int64_t ii = 0; ii < nt; ++ii)
+            if (!std::isfinite(hs[(size_t)ii])) hr[(size_t)ii] = -1;
+    }
+    // the caller's arrays are written only once nothing can fail
+    if (rank_out) std::copy(hr.begin(), hr.end(), rank_out);
+    if (score_out) std::copy(hs.begin(), hs.end(), score_out);
+    if (n_eff_out)
+        for (int64_t i = 0; i < n_ctx; ++i)
+            n_eff_out[i] = (int32_t)(rk_C - (eptr ? eptr[i + 1] - eptr[i] : 0));
     return SPFM_OK;
 }
 
@@ -292,7 +458,25 @@ int spfm_rank_topk(spfm_handle h, int64_t n_ctx, const int64_t* indptr, const in
                    const double* data, int64_t K, int32_t* idx_out, double* val_out,
                    int64_t* k_out) {
     SPFM_GUARD(h);
-    return h->rank_topk(n_ctx, indptr, indices, data, K, idx_out, val_out, k_out);
+    return h->rank_topk(n_ctx, indptr, indices, data, nullptr, nullptr, K, idx_out, val_out,
+                        k_out);
+}
+
+int spfm_rank_topk_excl(spfm_handle h, int64_t n_ctx, const int64_t* indptr,
+                        const int32_t* indices, const double* data, const int64_t* eptr,
+                        const int32_t* eidx, int64_t K, int32_t* idx_out, double* val_out,
+                        int64_t* k_out) {
+    SPFM_GUARD(h);
+    return h->rank_topk(n_ctx, indptr, indices, data, eptr, eidx, K, idx_out, val_out, k_out);
+}
+
+int spfm_rank_eval(spfm_handle h, int64_t n_ctx, const int64_t* indptr, const int32_t* indices,
+                   const double* data, const int64_t* tptr, const int32_t* tidx,
+                   const int64_t* eptr, const int32_t* eidx, int32_t* rank_out, double* score_out,
+                   int32_t* n_eff_out) {
+    SPFM_GUARD(h);
+    return h->rank_eval(n_ctx, indptr, indices, data, tptr, tidx, eptr, eidx, rank_out, score_out,
+                        n_eff_out);
 }
 
 int spfm_rank_set_partition(spfm_handle h, int64_t row_slab, int64_t cand_strip) {

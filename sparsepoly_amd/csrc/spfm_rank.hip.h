@@ -39,6 +39,12 @@
 //                   strip's list plus, by binary search, the entries of every other list that beat
 //                   it; ranks below K are written.
 //    No float atomics; the LDS counters are integers.  Non-finite scores never enter a list.
+//    EXCL (spfm_rank_topk_excl): per context row an ascending list of
+//    candidates that are left out.  Before a tile is staged, wave 0 (lane = row of the tile)
+//    turns each row's list into one 64-bit mask of the tile's columns (rank_mask_step: a cursor per
+//    row, kept across the tiles of the strip, found by binary search where the strip starts); the
+//    masks sit in LDS (512 B) and a score survives only if its bit is clear.  EXCL = false is the
+//    code without any of this.
 #pragma once
 #include "spfm_interactions.hip.h"
 
@@ -64,14 +70,18 @@ struct RankArgs {
     int32_t* lidx;
     double* oval;       // RANK_MERGE (nrow, K)
     int32_t* oidx;
+    const int64_t* eptr;  // EXCL: excluded candidates of every context row of the call (CSR
+    const int32_t* eidx;  //       pattern, ascending per row), row `row0 + r` for slab row r
+    int64_t row0;
 };
 
 // dynamic LDS of rank_tile_kernel<MODE>
-static inline size_t rank_lds_bytes(int mode, int cap) {
+static inline size_t rank_lds_bytes(int mode, int cap, bool excl = false) {
     size_t b = sizeof(double) * 2 * kIntTile * kIntLd;
     if (mode == RANK_SELECT)
         b += (size_t)kIntTile * cap * (sizeof(double) + sizeof(uint16_t)) +
-             kIntTile * (sizeof(double) + 2 * sizeof(int));
+             kIntTile * (sizeof(double) + 2 * sizeof(int)) +
+             (excl ? kIntTile * sizeof(unsigned long long) : 0);
     return mode == RANK_MERGE ? 0 : b;
 }
 
@@ -120,6 +130,33 @@ __global__ __launch_bounds__(kBlock) void tower_kernel(
 // (value descending, candidate ascending)
 __device__ __forceinline__ bool rank_beats(double va, unsigned ca, double vb, unsigned cb) {
     return va > vb || (va == vb && ca < cb);
+}
+
+// first position in [lo, hi) of the ascending list idx whose id is >= key
+__device__ __forceinline__ int64_t rank_lower_bound(const int32_t* __restrict__ idx, int64_t lo,
+                                                    int64_t hi, int key) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (idx[mid] < key)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// The ids of the ascending list idx[cur, end) that fall into the tile [col0, col0 + 64), as a
+// mask; cur moves past them.  idx[cur] >= col0 on entry (the tiles are visited in ascending order)
+__device__ __forceinline__ unsigned long long rank_mask_step(const int32_t* __restrict__ idx,
+                                                             int64_t& cur, int64_t end, int col0) {
+    unsigned long long m = 0ull;
+    while (cur < end) {
+        const int c = idx[cur] - col0;
+        if (c >= kIntTile) break;
+        m |= 1ull << c;
+        ++cur;
+    }
+    return m;
 }
 
 // One wave: the n entries of a row's buffer -> its min(n, K) best, sorted, at the front
@@ -197,8 +234,9 @@ __device__ __forceinline__ void rank_merge_body(const RankArgs& a) {
     }
 }
 
-template <int MODE>
+template <int MODE, bool EXCL = false>
 __global__ __launch_bounds__(kBlock) void rank_tile_kernel(RankArgs a) {
+    static_assert(!EXCL || MODE == RANK_SELECT, "only the selection takes an exclusion list");
     if constexpr (MODE == RANK_MERGE) {
         rank_merge_body<MODE>(a);
         return;
@@ -211,6 +249,8 @@ __global__ __launch_bounds__(kBlock) void rank_tile_kernel(RankArgs a) {
         uint16_t* bidx = reinterpret_cast<uint16_t*>(thr + kIntTile);  // [64][cap]
         int* cnt = reinterpret_cast<int*>(bidx + (size_t)kIntTile * a.cap);  // [64]
         int* add = cnt + kIntTile;                              // [64] survivors of the tile
+        [[maybe_unused]] unsigned long long* emask =
+            reinterpret_cast<unsigned long long*>(add + kIntTile);  // [64] EXCL
 
         const int strip = blockIdx.x, ti = blockIdx.y;
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -236,8 +276,23 @@ __global__ __launch_bounds__(kBlock) void rank_tile_kernel(RankArgs a) {
             for (int r = 0; r < 4; ++r)
                 rcv[ra][r] = a.rc[(size_t)ti * kIntTile + wr * 32 + ra * 16 + l4 + 4 * r];
 
+        // EXCL, wave 0: the row's cursor into eidx, at the strip's first candidate
+        [[maybe_unused]] int64_t ecur = 0, eend = 0;
+        if constexpr (EXCL) {
+            if (wave == 0 && ti * kIntTile + lane < a.nrow) {
+                const int64_t row = a.row0 + ti * kIntTile + lane;
+                eend = a.eptr[row + 1];
+                ecur = rank_lower_bound(a.eidx, a.eptr[row], eend, c0);
+            }
+        }
+
         const double* Ug = a.U + (size_t)ti * kIntTile * a.Rp;
         for (int tj = t0; tj < t1; ++tj) {
+            if constexpr (EXCL) {
+                __syncthreads();  // the last tile's masks have been read
+                if (wave == 0) emask[lane] = rank_mask_step(a.eidx, ecur, eend, tj * kIntTile);
+                // (published by the barriers of the staging step)
+            }
             int_v4d acc[2][2];
             int_acc_zero(acc);
             const double* Vg = a.V + (size_t)tj * kIntTile * a.Rp;
@@ -245,6 +300,13 @@ __global__ __launch_bounds__(kBlock) void rank_tile_kernel(RankArgs a) {
                 const int kend = (a.Rp - kc0 < kIntKC) ? a.Rp - kc0 : kIntKC;  // multiple of 4
                 int_stage_chunk(Ug, Vg, a.Rp, kc0, kend, sA, sB);
                 int_mfma_chunk<false>(sA, sB, kend, nullptr, acc);
+            }
+            [[maybe_unused]] unsigned long long em[2][4];  // EXCL: the masks of the lane's eight rows
+            if constexpr (EXCL) {
+#pragma unroll
+                for (int ra = 0; ra < 2; ++ra)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) em[ra][r] = emask[wr * 32 + ra * 16 + l4 + 4 * r];
             }
             // pass 0: count the survivors (RANK_SELECT); pass 1: store / append
 #pragma unroll
@@ -260,7 +322,9 @@ __global__ __launch_bounds__(kBlock) void rank_tile_kernel(RankArgs a) {
                             const int rl = wr * 32 + ra * 16 + l4 + 4 * r;
                             const int row = ti * kIntTile + rl;
                             const double v = acc[ra][cb][r] + (rcv[ra][r] + ccv);
-                            const bool in = row < a.nrow && col < a.C;
+                            bool in = row < a.nrow && col < a.C;
+                            if constexpr (EXCL)
+                                in = in && !((em[ra][r] >> (wc * 32 + cb * 16 + l15)) & 1ull);
                             if constexpr (MODE == RANK_DENSE) {
                                 if (in) a.dense[(size_t)row * a.C + col] = v;
                             } else {

@@ -566,9 +566,18 @@ class HipEngine(object):
                                                out.ctypes.data_as(_capi._dp)))
         return out
 
-    def rank_topk(self, X, K):
+    @staticmethod
+    def _rank_pattern(pattern):
+        """``(indptr, indices)`` of per-row candidate lists -> their int64 / int32 holders.  The
+        arrays go to the library as they are; it checks them."""
+        ptr, idx = pattern
+        return _capi.i64(ptr), _capi.i32(idx)
+
+    def rank_topk(self, X, K, exclude=None):
         """``spfm_rank_topk``: ``(idx, scores)`` of shape (B, min(K, C)), per row by score
-        descending, then candidate index ascending.  ``K`` above ``SPFM_RANK_MAX_K``: ValueError."""
+        descending, then candidate index ascending.  ``K`` above ``SPFM_RANK_MAX_K``: ValueError.
+        ``exclude``: ``(indptr, indices)``, per row the ascending candidate ids that are left out
+        (``spfm_rank_topk_excl``); a row with fewer than K admissible candidates ends in -1 / NaN."""
         K = int(K)
         if K > _capi.RANK_MAX_K:
             raise ValueError("rank_topk: K = %d exceeds SPFM_RANK_MAX_K = %d (never answered "
@@ -581,11 +590,37 @@ class HipEngine(object):
         idx = np.zeros((Xr.shape[0], ko), dtype=np.int32)
         val = np.zeros((Xr.shape[0], ko))
         k_out = C.c_int64()
-        self._check(self._lib.spfm_rank_topk(
-            self._h, Xr.shape[0], ia[1], ja[1], da[1], K, idx.ctypes.data_as(_capi._ip),
-            val.ctypes.data_as(_capi._dp), C.byref(k_out)))
+        if exclude is None:
+            self._check(self._lib.spfm_rank_topk(
+                self._h, Xr.shape[0], ia[1], ja[1], da[1], K, idx.ctypes.data_as(_capi._ip),
+                val.ctypes.data_as(_capi._dp), C.byref(k_out)))
+        else:
+            ep, ei = self._rank_pattern(exclude)
+            self._check(self._lib.spfm_rank_topk_excl(
+                self._h, Xr.shape[0], ia[1], ja[1], da[1], ep[1], ei[1], K,
+                idx.ctypes.data_as(_capi._ip), val.ctypes.data_as(_capi._dp), C.byref(k_out)))
         assert k_out.value == ko
         return idx, val
+
+    def rank_eval(self, X, targets, exclude=None):
+        """``spfm_rank_eval``: ``(ranks, scores, n_eff)``.  ``targets`` and ``exclude`` are
+        ``(indptr, indices)`` pairs, per context row ascending candidate ids; ``ranks`` (int32) and
+        ``scores`` are aligned with the targets' ``indices``: the 0-based rank of each target among
+        the candidates that are not excluded, and its score; ``n_eff`` (B,) = C minus the row's
+        excluded candidates.  A target with a score that is not finite has rank -1."""
+        Xr, (ia, ja, da) = self._rank_csr(X, "rank_eval")
+        if getattr(self, "n_candidates", None) is None:
+            raise ValueError("rank_eval: call rank_set_candidates first")
+        tp, ti = self._rank_pattern(targets)
+        ep, ei = self._rank_pattern(exclude) if exclude is not None else ((None, None),) * 2
+        ranks = np.zeros(ti[0].shape[0], dtype=np.int32)
+        scores = np.zeros(ti[0].shape[0])
+        n_eff = np.zeros(Xr.shape[0], dtype=np.int32)
+        self._check(self._lib.spfm_rank_eval(
+            self._h, Xr.shape[0], ia[1], ja[1], da[1], tp[1], ti[1], ep[1], ei[1],
+            ranks.ctypes.data_as(_capi._ip), scores.ctypes.data_as(_capi._dp),
+            n_eff.ctypes.data_as(_capi._ip)))
+        return ranks, scores, n_eff
 
     def rank_set_partition(self, row_slab=0, cand_strip=0):
         """``spfm_rank_set_partition``: context rows per slab and candidates per strip of the
@@ -594,8 +629,8 @@ class HipEngine(object):
 
     def rank_info(self):
         """``spfm_rank_info``: dict ``scratch_kib`` (device memory the ranking calls hold),
-        ``device_ms`` (kernels of the last ``rank_scores`` / ``rank_topk``), ``row_slab``,
-        ``cand_strip``."""
+        ``device_ms`` (kernels of the last ``rank_scores`` / ``rank_topk`` / ``rank_eval``),
+        ``row_slab``, ``cand_strip``."""
         out = np.zeros(4, dtype=np.int64)
         self._check(self._lib.spfm_rank_info(self._h, out.ctypes.data_as(_capi._lp)))
         return dict(scratch_kib=int((out[0] + 1023) // 1024), device_ms=out[1] / 1e3,

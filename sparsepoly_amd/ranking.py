@@ -14,7 +14,13 @@ is a rank-R product of two "towers" plus a constant per row and per column
 unless the dense matrix is asked for.  There is no CPU path: without the library or a GPU the
 device calls raise.
 
-``RankingMixin`` gives the estimators ``ranker``, ``candidate_scores`` and ``top_candidates``.
+Two further consumers of the same score tiles: ``top_k(..., exclude=E)``
+leaves out, per context row, the candidates that row already has, and ``ranks`` / ``evaluate``
+give the exact rank of held-out candidates against the whole catalogue and the usual metrics of
+it (``metrics_from_ranks``: plain NumPy on the ranks, no device).
+
+``RankingMixin`` gives the estimators ``ranker``, ``candidate_scores``, ``top_candidates`` and
+``rank_metrics``.
 ``restate_scores`` is the plain NumPy restatement, a test aid that never touches the device.
 """
 import numpy as np
@@ -104,10 +110,125 @@ def _check_K(K):
     return int(K)
 
 
+def _pattern(M, B, C, what):
+    """The pattern of a (B, C) matrix of per-row candidate lists as canonical CSR (a copy with
+    sorted indices, duplicates merged, every stored entry 1)"""
+    if not sp.issparse(M):
+        M = sp.csr_matrix(np.asarray(M))
+    if M.shape != (B, C):
+        raise ValueError("%s has shape %r, expected (%d contexts, %d candidates)"
+                         % (what, tuple(M.shape), B, C))
+    M = M.tocsr()
+    if M.indices.size and (M.indices.min() < 0 or M.indices.max() >= C):
+        raise ValueError("%s: candidate id out of range [0, %d)" % (what, C))
+    out = sp.csr_matrix((np.ones(M.indices.shape[0]), M.indices.copy(), M.indptr.copy()),
+                        shape=(B, C))
+    out.sum_duplicates()
+    out.sort_indices()
+    out.data[:] = 1.0
+    return out
+
+
+def check_rank_lists(B, C, targets, exclude=None):
+    """The input checks of ``Ranker.ranks`` / ``evaluate`` / ``top_k(exclude=...)``; needs no
+    device.  ``targets`` and ``exclude`` are (B, C) matrices (scipy sparse or array-like) of which
+    only the pattern is read.  Returns their canonical CSR patterns ``(T, E)`` (``None`` for a
+    ``None``): indices sorted, duplicates merged.  ``ValueError`` for a wrong shape, a candidate id
+    outside ``[0, C)``, a target that is also excluded and a row with more than
+    ``SPFM_RANK_MAX_TARGETS`` targets (such a row is never truncated)."""
+    T = None if targets is None else _pattern(targets, B, C, "targets")
+    E = None if exclude is None else _pattern(exclude, B, C, "exclude")
+    if T is not None:
+        most = int(np.diff(T.indptr).max(initial=0))
+        if most > _capi.RANK_MAX_TARGETS:
+            row = int(np.argmax(np.diff(T.indptr)))
+            raise ValueError("row %d has %d targets, more than the cap of %d "
+                             "(SPFM_RANK_MAX_TARGETS); a row is never truncated"
+                             % (row, most, _capi.RANK_MAX_TARGETS))
+    if T is not None and E is not None:
+        both = T.multiply(E).tocoo()
+        if both.nnz:
+            raise ValueError("candidate %d is a target of row %d and excluded from it "
+                             "(%d such pairs): targets and exclude must be disjoint"
+                             % (int(both.col[0]), int(both.row[0]), both.nnz))
+    return T, E
+
+
+def _check_ks(ks):
+    ks = tuple(ks)
+    for k in ks:
+        if int(k) != k or k < 1:
+            raise ValueError("ks must hold integers >= 1, got %r" % (k,))
+    return tuple(int(k) for k in ks)
+
+
+def metrics_from_ranks(tptr, ranks, n_eff, ks=(10,)):
+    """Ranking metrics from exact ranks; NumPy only.  ``tptr`` (B + 1): the targets of row b are
+    ``ranks[tptr[b]:tptr[b + 1]]``, 0-based among the row's ``n_eff[b]`` admissible candidates
+    (targets included); a rank of -1 (a score that is not finite) counts as a miss.  Per row with
+    ``n`` targets and per ``k`` in ``ks``:
+
+    * ``recall@k`` = #{rank < k} / n, ``hit@k`` = 1 if any rank < k else 0;
+    * ``ndcg@k`` = sum over the ranks < k of 1 / log2(rank + 2), over the same sum for ranks
+      0 .. min(n, k) - 1;
+    * ``mrr`` = 1 / (smallest rank + 1), 0 when every target is a miss;
+    * ``auc`` = 1 - sum_i (r_(i) - i) / (n (n_eff - n)) with the ranks sorted ascending: the share
+      of (target, other candidate) pairs the model orders correctly; a miss loses all its pairs;
+      NaN when ``n_eff == n``.
+
+    Returns a dict: each name -> its mean over the rows that have a target (``auc``: over those
+    where it is defined; NaN when there is no such row), ``n_rows_scored`` -> their number,
+    ``per_row`` -> a dict of the (B,) arrays (NaN for a row without targets) and ``n_targets``."""
+    ks = _check_ks(ks)
+    tptr = np.asarray(tptr, dtype=np.int64)
+    ranks = np.asarray(ranks, dtype=np.int64)
+    n_eff = np.asarray(n_eff, dtype=np.int64)
+    B = tptr.shape[0] - 1
+    if n_eff.shape != (B,) or ranks.shape != (int(tptr[-1]),):
+        raise ValueError("tptr, ranks and n_eff do not fit together")
+    n = np.diff(tptr)
+    rows = np.repeat(np.arange(B), n)
+    have = n > 0
+    nf = np.where(have, n, 1).astype(np.double)
+    valid = ranks >= 0
+
+    def per_row_sum(w):
+        return np.bincount(rows, weights=w, minlength=B)
+
+    def blank(a):
+        return np.where(have, a, np.nan)
+
+    per = {"n_targets": n}
+    gain = 1.0 / np.log2(np.where(valid, ranks, 0) + 2.0)
+    ideal = np.concatenate([[0.0], np.cumsum(1.0 / np.log2(np.arange(max(ks)) + 2.0))])
+    for k in ks:
+        hit = valid & (ranks < k)
+        per["recall@%d" % k] = blank(per_row_sum(hit) / nf)
+        per["hit@%d" % k] = blank((per_row_sum(hit) > 0).astype(np.double))
+        per["ndcg@%d" % k] = blank(per_row_sum(np.where(hit, gain, 0.0))
+                                   / ideal[np.maximum(np.minimum(n, k), 1)])
+    best = np.full(B, np.iinfo(np.int64).max)
+    np.minimum.at(best, rows[valid], ranks[valid])
+    found = best < np.iinfo(np.int64).max
+    per["mrr"] = blank(np.where(found, 1.0 / (np.where(found, best, 0) + 1.0), 0.0))
+    # sum_i (r_(i) - i): the ranks count the row's other targets too; a miss is beaten by all
+    nv = per_row_sum(valid)
+    lost = per_row_sum(np.where(valid, ranks, 0)) - nv * (nv - 1) / 2 + (n - nv) * (n_eff - n)
+    pairs = (n * (n_eff - n)).astype(np.double)
+    per["auc"] = np.where(pairs > 0, 1.0 - lost / np.where(pairs > 0, pairs, 1.0), np.nan)
+    out = {"n_rows_scored": int(have.sum()), "per_row": per}
+    for name, a in per.items():
+        if name != "n_targets":
+            ok = have & ~np.isnan(a)
+            out[name] = float(a[ok].mean()) if ok.any() else float("nan")
+    return out
+
+
 class Ranker(object):
     """The candidates ``Z`` resident on a device handle of its own (made from ``P_``, ``w_``,
-    ``lams_`` as ``predict`` makes one).  ``scores(X)`` / ``top_k(X, K)`` for any number of context
-    batches; ``close()`` (or leaving the ``with`` block) releases the handle.  Not picklable."""
+    ``lams_`` as ``predict`` makes one).  ``scores(X)`` / ``top_k(X, K)`` / ``ranks(X, targets)`` /
+    ``evaluate(X, targets)`` for any number of context batches; ``close()`` (or leaving the
+    ``with`` block) releases the handle.  Not picklable."""
 
     def __init__(self, est, Z):
         self._est = est
@@ -137,13 +258,45 @@ class Ranker(object):
         Xa = self._contexts(X)
         return self._engine.rank_scores(Xa)
 
-    def top_k(self, X, K):
+    def top_k(self, X, K, exclude=None):
         """``(idx, scores)``: int32 and float64 of shape (B, min(K, C)); per context row the
         largest scores, ordered by (score descending, candidate index ascending).  Exact and
-        deterministic.  ``1 <= K <= 128``."""
+        deterministic.  ``1 <= K <= 128``.  ``exclude``: a (B, C) matrix of which only the pattern
+        is read (a train-interaction matrix fits): the candidates stored in row b are left out for
+        context b; a row with fewer than K candidates left ends in index -1 / NaN."""
         K = _check_K(K)
         Xa = self._contexts(X)
-        return self._engine.rank_topk(Xa, K)
+        if exclude is None:
+            return self._engine.rank_topk(Xa, K)
+        _, E = check_rank_lists(Xa.shape[0], self.n_candidates, None, exclude)
+        return self._engine.rank_topk(Xa, K, exclude=(E.indptr, E.indices))
+
+    def _rank_eval(self, X, targets, exclude):
+        Xa = self._contexts(X)
+        T, E = check_rank_lists(Xa.shape[0], self.n_candidates, targets, exclude)
+        ranks, scores, n_eff = self._engine.rank_eval(
+            Xa, (T.indptr, T.indices), None if E is None else (E.indptr, E.indices))
+        return T, ranks, scores, n_eff
+
+    def ranks(self, X, targets, exclude=None):
+        """``(ranks, scores)``: int32 and float64 arrays with one entry per stored entry of
+        ``targets`` (B, C; pattern only), in the order of its canonical CSR form -- rows in order,
+        candidate ids ascending within a row, duplicates merged: the ``T`` of
+        ``check_rank_lists(B, C, targets)``.  ``ranks`` is the number of candidates outside
+        ``exclude`` that beat the target under (score descending, index ascending), 0-based, the
+        row's other targets counted like any candidate; ``scores`` equals ``scores(X)[b, t]`` bit
+        for bit.  Exact; at most 64 targets per row; -1 for a target whose score is not finite."""
+        _, ranks, scores, _ = self._rank_eval(X, targets, exclude)
+        return ranks, scores
+
+    def evaluate(self, X, targets, exclude=None, ks=(10,)):
+        """Full-catalogue metrics of the held-out ``targets`` with ``exclude`` left out:
+        ``metrics_from_ranks`` on the exact ranks -- ``recall@k``, ``ndcg@k``, ``hit@k`` per ``k``
+        in ``ks``, ``mrr``, ``auc`` (means over the rows that have a target), ``n_rows_scored``
+        and the per-row arrays under ``"per_row"``."""
+        ks = _check_ks(ks)
+        T, ranks, _, n_eff = self._rank_eval(X, targets, exclude)
+        return metrics_from_ranks(T.indptr, ranks, n_eff, ks)
 
     def close(self):
         if self._engine is not None:
@@ -185,6 +338,14 @@ class RankingMixin(object):
         _prepare(self, X, Z)
         with Ranker(self, Z) as r:
             return r.top_k(X, K)
+
+    def rank_metrics(self, X, Z, targets, exclude=None, ks=(10,)):
+        """One-shot ``ranker(Z).evaluate(X, targets, exclude, ks)``."""
+        _check_ks(ks)
+        Xa, Za = _prepare(self, X, Z)
+        check_rank_lists(Xa.shape[0], Za.shape[0], targets, exclude)
+        with Ranker(self, Z) as r:
+            return r.evaluate(X, targets, exclude, ks)
 
 
 # ------------------------------------------------------------------ NumPy restatement (test aid)
