@@ -593,6 +593,54 @@ int spfm_interaction_values(spfm_handle h, int order_idx, int64_t L, const int32
 int spfm_interaction_block(spfm_handle h, int order_idx, int64_t nJ, const int32_t* J,
                            int64_t nJ2, const int32_t* J2, double* out);
 
+/* -- per-feature views of the pairwise weights -----------------------------------------------
+ * For one feature, or for every feature: whom does it interact with, and how strongly?  Both
+ * entries walk the FULL square of W (both triangles, 2 d_a^2 k flops) on the pair entries'
+ * compaction and packed images: 64-row tiles of query features against strips of candidate
+ * partners, W formed in registers and consumed there, nothing of size d_a^2 stored.  The scratch
+ * is part of the pair entries' scratch (counted by "interaction_scratch_kib", freed by the same
+ * three things): O(slab * d_a / 64) row records for the degrees, O(slab * (k + strips * K)) for
+ * the partners.  "interaction_launches" reports the tile launches of the last pass.
+ * Semantics are those of the pair entries word for word: parameters only (no data, no
+ * spfm_configure), the LIVE image in either layout, read-only, f64 arithmetic for either storage
+ * precision, ids of the block as stored, every rank answers locally.  The view is theirs too:
+ * with "interaction_features" = n > 0 the features >= n are neither queries nor partners.
+ *
+ * Bits: every value of W seen or returned here is the tile chain's value, the bits that
+ * spfm_interaction_topk / _list give; W[j, j'] and W[j', j] are the same bits (lams is +-1).
+ *
+ * spfm_interaction_degrees: for every feature j of the block, over all j' != j in view:
+ *   degree[j] = number of j' with |W[j, j']| > tol (tol = 0 counts W != 0), sum_abs[j] =
+ *   sum |W[j, j']|, max_abs[j] = the largest |W[j, j']|, strongest[j] = the smallest j' attaining
+ *   it, -1 when max_abs[j] == 0.  Each array is [d]; any may be NULL.  A feature that is inactive
+ *   or out of view gets 0, 0.0, 0.0, -1.  sum_abs is reduced without float atomics in an order
+ *   that depends on d_a alone (per row: inside a 64-column tile, then the tiles); it is the same
+ *   bits on every call and for every cand_strip (columns a workgroup walks; 0 = default, else a
+ *   multiple of 64).
+ * spfm_interaction_partners: for query q, feature J[q] (J == NULL: all features of the view in id
+ *   order, nJ ignored; repeats allowed), the K partners j' in [cand_lo, cand_hi) and in view,
+ *   j' != J[q], admissible under `by`, ordered by key descending, then j' ascending -- exact.
+ *   cand_hi <= 0 = the end of the view.  ids / vals are [nJ][K] row-major, vals the SIGNED W;
+ *   n_out[q] partners are written, the rest of the row is -1 / 0.0.  An inactive query gets
+ *   n_out = 0.  row_slab = queries per slab, cand_strip = candidate columns per strip (0 =
+ *   default, as in spfm_rank_set_partition; cand_strip a multiple of 64, at most 65536); no result
+ *   bit depends on either.
+ * Errors: no parameters, bad order_idx, id out of range, tol < 0, K < 1, an empty
+ * [cand_lo, cand_hi), a bad `by`, cand_strip not a multiple of 64 -> SPFM_ERR_INVALID;
+ * K > SPFM_INTERACTION_MAX_K -> SPFM_ERR_UNSUPPORTED (never an approximate answer).  With fewer
+ * than 2 active features in view both succeed with the empty answers above. */
+#define SPFM_PARTNERS_ABS 0   /* key |W|, among W != 0 */
+#define SPFM_PARTNERS_POS 1   /* key  W,  among W > 0  */
+#define SPFM_PARTNERS_NEG 2   /* key -W,  among W < 0  */
+#define SPFM_INTERACTION_MAX_K 128
+int spfm_interaction_degrees(spfm_handle h, int order_idx, double tol, int64_t cand_strip,
+                             int64_t* degree, double* sum_abs, double* max_abs,
+                             int32_t* strongest);
+int spfm_interaction_partners(spfm_handle h, int order_idx, int64_t nJ, const int32_t* J,
+                              int64_t K, int32_t cand_lo, int32_t cand_hi, int by,
+                              int64_t row_slab, int64_t cand_strip, int32_t* ids, double* vals,
+                              int32_t* n_out);
+
 /* -- third-order interaction weights of the live parameters ----------------------------------
  * Which feature TRIPLES the fitted model kept.  For the block P_o = P[order_idx] (k x d),
  *   T[a, j, l] = sum_s lams_s p_sa p_sj p_sl,   only a < j < l counts;

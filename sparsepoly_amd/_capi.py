@@ -99,6 +99,7 @@ SYMBOLS = [
     "spfm_objective_terms", "spfm_set_eval_csr", "spfm_eval_loss",
     "spfm_interaction_stats", "spfm_interaction_topk", "spfm_interaction_list",
     "spfm_interaction_values", "spfm_interaction_block",
+    "spfm_interaction_degrees", "spfm_interaction_partners",
     "spfm_interaction3_stats", "spfm_interaction3_topk", "spfm_interaction3_list",
     "spfm_interaction3_values",
     "spfm_rank_set_candidates", "spfm_rank_scores", "spfm_rank_topk",
@@ -111,6 +112,8 @@ SYMBOLS = [
 ]
 INTERACTION_BLOCK_MAX_BYTES = 1 << 30  # SPFM_INTERACTION_BLOCK_MAX_BYTES
 INTERACTION3_MAX_ACTIVE = 1 << 15  # SPFM_INTERACTION3_MAX_ACTIVE
+INTERACTION_MAX_K = 128  # SPFM_INTERACTION_MAX_K
+PARTNERS_BY = {"abs": 0, "positive": 1, "negative": 2}  # SPFM_PARTNERS_ABS / _POS / _NEG
 RANK_MAX_K = 128  # SPFM_RANK_MAX_K
 RANK_SCORES_MAX_BYTES = 1 << 30  # SPFM_RANK_SCORES_MAX_BYTES
 RANK_MAX_TARGETS = 64  # SPFM_RANK_MAX_TARGETS
@@ -206,6 +209,10 @@ def load():
     L.spfm_interaction_list.argtypes = [_h, C.c_int, C.c_double, C.c_int64, _ip, _ip, _dp, _lp]
     L.spfm_interaction_values.argtypes = [_h, C.c_int, C.c_int64, _ip, _ip, _dp]
     L.spfm_interaction_block.argtypes = [_h, C.c_int, C.c_int64, _ip, C.c_int64, _ip, _dp]
+    L.spfm_interaction_degrees.argtypes = [_h, C.c_int, C.c_double, C.c_int64, _lp, _dp, _dp, _ip]
+    L.spfm_interaction_partners.argtypes = [_h, C.c_int, C.c_int64, _ip, C.c_int64, C.c_int32,
+                                            C.c_int32, C.c_int, C.c_int64, C.c_int64, _ip, _dp,
+                                            _ip]
     L.spfm_interaction3_stats.argtypes = [_h, C.c_int, C.c_double, _lp, _dp]
     L.spfm_interaction3_topk.argtypes = [_h, C.c_int, C.c_int64, _ip, _ip, _ip, _dp, _lp]
     L.spfm_interaction3_list.argtypes = [_h, C.c_int, C.c_double, C.c_int64, _ip, _ip, _ip, _dp,

@@ -1003,6 +1003,9 @@ struct spfm_engine {
     DevBuf int_rec, int_rec2;                             // per-tile records and their reduction
     DevBuf int_hist, int_cnt, int_keys, int_vals, int_keys2, int_vals2;  // select / list
     DevBuf int_io, int_out;                               // values / block
+    // per-feature views (spfm_engine_partners.hip): query image and ranks, per-tile row records
+    // and the degree answers, strip lists and merged lists of a slab
+    DevBuf int_pq, int_pqr, int_prec, int_pdeg, int_plv, int_pli, int_pov, int_poi, int_pon;
     int int_da = 0, int_kp = 0, int_T = 0;  // of the last compaction
     int int_tile_budget = 0;  // option "interaction_tile_budget": tiles per launch (0 = default)
     int int_dlim = 0;         // option "interaction_features": only features < this (0 = all)
@@ -1011,7 +1014,9 @@ struct spfm_engine {
         return int_flag.bytes + int_pos.bytes + int_ids.bytes + int_tot.bytes + int_tmp.bytes +
                int_A.bytes + int_B.bytes + int_rec.bytes + int_rec2.bytes + int_hist.bytes +
                int_cnt.bytes + int_keys.bytes + int_vals.bytes + int_keys2.bytes +
-               int_vals2.bytes + int_io.bytes + int_out.bytes;
+               int_vals2.bytes + int_io.bytes + int_out.bytes + int_pq.bytes + int_pqr.bytes +
+               int_prec.bytes + int_pdeg.bytes + int_plv.bytes + int_pli.bytes + int_pov.bytes +
+               int_poi.bytes + int_pon.bytes;
     }
     int interaction_view(const char* what, int order_idx, BlockView* v);
     int interaction_prepare(const char* what, int order_idx);
@@ -1026,6 +1031,14 @@ struct spfm_engine {
                            double* vals);
     int interaction_block(int order_idx, int64_t nJ, const int32_t* J, int64_t nJ2,
                           const int32_t* J2, double* out);
+
+    // per-feature views of W (spfm_engine_partners.hip): the full square,
+    // query rows in slabs against candidate strips; scratch O(slab * tiles + slab * strips * K)
+    int interaction_degrees(int order_idx, double tol, int64_t cand_strip, int64_t* degree,
+                            double* sum_abs, double* max_abs, int32_t* strongest);
+    int interaction_partners(int order_idx, int64_t nJ, const int32_t* J, int64_t K,
+                             int32_t cand_lo, int32_t cand_hi, int by, int64_t row_slab,
+                             int64_t cand_strip, int32_t* ids, double* vals, int32_t* n_out);
 
     // ------------------------------- third-order weights (same unit)
     // T[a, j, l] = sum_s lams_s p_sa p_sj p_sl over a < j < l, on the compaction, the packed images

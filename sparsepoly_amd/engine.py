@@ -527,6 +527,60 @@ class HipEngine(object):
             out.ctypes.data_as(_capi._dp)))
         return out
 
+    def interaction_degrees(self, order_idx, tol=0.0, n_features=None, cand_strip=0):
+        """``spfm_interaction_degrees``: dict of arrays over the features in view, ``degree``
+        (int64: partners ``j' != j`` with ``|W[j, j']| > tol``), ``sum_abs``, ``max_abs`` and
+        ``strongest`` (int32: the smallest partner attaining ``max_abs``, -1 when it is 0).
+        ``cand_strip`` (columns a workgroup walks) changes no result bit."""
+        d = self.d or 0  # (no parameters yet: the entry refuses)
+        n = d if n_features is None else min(int(n_features), d)
+        deg = np.zeros(d, dtype=np.int64)
+        sa, ma = np.zeros(d), np.zeros(d)
+        st = np.full(d, -1, dtype=np.int32)
+        with self._interaction_features(n_features):
+            self._check(self._lib.spfm_interaction_degrees(
+                self._h, int(order_idx), float(tol), int(cand_strip),
+                deg.ctypes.data_as(_capi._lp), sa.ctypes.data_as(_capi._dp),
+                ma.ctypes.data_as(_capi._dp), st.ctypes.data_as(_capi._ip)))
+        return dict(degree=deg[:n].copy(), sum_abs=sa[:n].copy(), max_abs=ma[:n].copy(),
+                    strongest=st[:n].copy())
+
+    def interaction_partners(self, order_idx, J, K, among=None, by="abs", n_features=None,
+                             row_slab=0, cand_strip=0):
+        """``spfm_interaction_partners``: ``(ids (nJ, K) int32, vals (nJ, K), counts (nJ,) int32)``,
+        the ``K`` strongest partners of every feature of ``J`` (None: every feature in view) among
+        the features ``among = (lo, hi)`` (None: the view), by key descending (``by``: ``"abs"``
+        ``|W|`` among ``W != 0``, ``"positive"`` ``W`` among ``W > 0``, ``"negative"`` ``-W`` among
+        ``W < 0``), then id ascending.  ``vals`` is the signed ``W``; rows are padded with
+        ``-1`` / ``0.0``.  ``row_slab`` / ``cand_strip`` change no result bit."""
+        if by not in _capi.PARTNERS_BY:
+            by_code = int(by) if isinstance(by, (int, np.integer)) else -1  # refused below
+        else:
+            by_code = _capi.PARTNERS_BY[by]
+        d = self.d or 0  # (no parameters yet: the entry refuses)
+        n = d if n_features is None else min(int(n_features), d)
+        if J is None:
+            nJ, jp = n, None
+        else:
+            ja, jp = _capi.i32(J)
+            if ja.ndim != 1:
+                raise ValueError("J must be a 1-d index array")
+            nJ = ja.shape[0]
+        K = int(K)
+        lo, hi = (0, 0) if among is None else (int(among[0]), int(among[1]))
+        if among is not None and hi <= 0:  # (0 means "the end of the view" to the C entry)
+            raise ValueError("interaction_partners: among=(%d, %d) is empty" % (lo, hi))
+        rows = nJ * K if 1 <= K <= _capi.INTERACTION_MAX_K else 0
+        ids = np.full(max(rows, 1), -1, dtype=np.int32)
+        vals = np.zeros(max(rows, 1))
+        cnt = np.zeros(max(nJ, 1), dtype=np.int32)
+        with self._interaction_features(n_features):
+            self._check(self._lib.spfm_interaction_partners(
+                self._h, int(order_idx), nJ, jp, K, lo, hi, by_code, int(row_slab),
+                int(cand_strip), ids.ctypes.data_as(_capi._ip), vals.ctypes.data_as(_capi._dp),
+                cnt.ctypes.data_as(_capi._ip)))
+        return ids[:rows].reshape(nJ, K), vals[:rows].reshape(nJ, K), cnt[:nJ]
+
     # ------------------------- candidate ranking: scores and top-K of (context, candidate) pairs
     def _rank_csr(self, X, what):
         """Canonical CSR (sorted, duplicates summed) of the handle's width -> (matrix, pointers)"""

@@ -13,6 +13,13 @@ the product in registers.  There is no CPU path: without the library or a GPU th
 ``interactions``, ``interaction_block`` and ``interaction_values``; ``support_recovery`` and
 ``estimation_error`` restate the notebook's metrics without a d x d array.
 
+Per feature: ``interaction_degrees`` gives every feature its number of partners, their total and
+largest weight and the strongest partner; ``top_partners`` gives the ``K`` strongest partners of
+every feature (or of some), optionally among a range of features; ``partner_graph`` is that table
+as a sparse kNN graph (``spfm_interaction_degrees`` / ``_partners``).  The
+full square of ``W`` is walked in registers and never stored.  ``restate_partners`` and
+``restate_degrees`` restate both on a dense ``W`` in NumPy, for tests.
+
 Third order: ``T[a, j, l] = sum_s lams_s p_sa p_sj p_sl`` over ``a < j < l`` is the coefficient of
 ``x_a x_j x_l`` for the degree-3 block of a factorization machine (``P_[0]`` for ``degree=3``, the
 explicit lower block of a higher degree) and for an all-subsets model.  ``triple_stats``,
@@ -29,6 +36,9 @@ from sklearn.utils.validation import NotFittedError
 _NO_DEGREE2 = ("%s: the model has no degree-2 block (degree=%d without fit_lower='explicit'); "
                "pairwise interaction weights are defined for degree=2, for the explicit lower "
                "block of a higher degree, and for all-subsets models.")
+_PARTNERS_BY = ("abs", "positive", "negative")
+_PARTNERS_MAX_K = 128  # SPFM_INTERACTION_MAX_K
+
 _NO_DEGREE3 = ("%s: the model has no degree-3 block (degree=%d%s); third-order interaction weights "
                "are defined for degree=3, for the explicit lower block of a higher degree "
                "(fit_lower='explicit'), and for all-subsets models.")
@@ -158,6 +168,38 @@ class InteractionMixin(object):
             return (eng.interaction_stats(o, 0.0, n_features=dv),
                     eng.interaction_values(o, rows, cols))
 
+    # ---------------------------------------------------------------- per feature
+    def _view_width(self, what, include_augmented):
+        """Features in view, from the stored block alone (no device work)"""
+        _, n_dummy = self._block_spec(what, 2)
+        d = np.shape(self.P_)[-1]
+        return d if include_augmented else d - n_dummy
+
+    def interaction_degrees(self, tol=0.0, include_augmented=False):
+        """Per feature ``j`` in view, over its partners ``j' != j``: dict of arrays ``degree``
+        (int64, partners with ``|W[j, j']| > tol``; ``tol = 0``: ``W != 0``), ``sum_abs``,
+        ``max_abs`` and ``strongest`` (int32, the smallest partner attaining ``max_abs``; -1 when
+        ``max_abs`` is 0).  The read-out of a feature-selecting regularizer: how many partners a
+        feature kept and how much weight they carry."""
+        if not float(tol) >= 0.0:
+            raise ValueError("interaction_degrees(): tol must be >= 0")
+        with self._interaction_session("interaction_degrees()", include_augmented) as (eng, o, dv):
+            return eng.interaction_degrees(o, tol, n_features=dv)
+
+    def top_partners(self, K, features=None, among=None, by="abs", include_augmented=False):
+        """``(ids (nJ, K) int32, vals (nJ, K), counts (nJ,))``: for every feature of ``features``
+        (None: every feature in view; repeats allowed) its ``K`` strongest partners ``j' != j``,
+        by key descending, then id ascending -- exactly.  ``among=(lo, hi)`` keeps the partners in
+        ``[lo, hi)`` only (the item field of a recommender, say).  ``by``: ``"abs"`` orders by
+        ``|W|`` among ``W != 0``, ``"positive"`` by ``W`` among ``W > 0``, ``"negative"`` by ``-W``
+        among ``W < 0``.  ``vals`` is the signed ``W``; a row with fewer than ``K`` admissible
+        partners (``counts`` of them) is padded with ``-1`` / ``0.0``.  Argument errors are raised
+        before any device work."""
+        dv = self._view_width("top_partners()", include_augmented)
+        features, among = _check_partner_args("top_partners()", K, features, among, by, dv)
+        with self._interaction_session("top_partners()", include_augmented) as (eng, o, dv):
+            return eng.interaction_partners(o, features, int(K), among=among, by=by, n_features=dv)
+
     # ---------------------------------------------------------------- third order
     def triple_stats(self, tol=0.0, include_augmented=False):
         """dict ``nnz`` (triples ``a < j < l`` with ``|T| > tol``; ``tol = 0``: ``T != 0``),
@@ -191,6 +233,95 @@ class InteractionMixin(object):
             j = self._interaction_ids(j, dv, "j")
             l = self._interaction_ids(l, dv, "l")
             return eng.interaction3_values(o, i, j, l)
+
+
+# ------------------------------------------------------------------ per-feature views
+def _check_partner_args(what, K, features, among, by, d_view):
+    """The argument errors of ``top_partners`` -> (features as int32 or None, among or None)"""
+    if int(K) != K or not 1 <= int(K) <= _PARTNERS_MAX_K:
+        raise ValueError("%s: K must be an integer in [1, %d]" % (what, _PARTNERS_MAX_K))
+    if by not in _PARTNERS_BY:
+        raise ValueError("%s: by must be one of %s" % (what, ", ".join(map(repr, _PARTNERS_BY))))
+    if features is not None:
+        features = InteractionMixin._interaction_ids(features, d_view, "features")
+    if among is not None:
+        if len(among) != 2 or int(among[0]) != among[0] or int(among[1]) != among[1]:
+            raise ValueError("%s: among must be a pair of integers (lo, hi)" % what)
+        lo, hi = int(among[0]), int(among[1])
+        if lo < 0 or hi > d_view:
+            raise ValueError("%s: among=(%d, %d) outside [0, %d]" % (what, lo, hi, d_view))
+        if lo >= hi:
+            raise ValueError("%s: among=(%d, %d) is empty" % (what, lo, hi))
+        among = (lo, hi)
+    return features, among
+
+
+def partner_graph(est, K, features=None, among=None, by="abs", include_augmented=False):
+    """``est.top_partners`` as a ``scipy.sparse.csr_matrix`` of shape ``(d_view, d_view)`` with at
+    most ``K`` stored entries per row: row ``j`` holds the signed weights of the ``K`` strongest
+    partners of feature ``j`` (the kNN graph of the features, or a similar-items table with
+    ``among`` set to the item field).  Rows outside ``features`` are empty; a repeated feature
+    counts once."""
+    dv = est._view_width("partner_graph()", include_augmented)
+    features, among = _check_partner_args("partner_graph()", K, features, among, by, dv)
+    if features is not None:
+        features = np.unique(features)
+    ids, vals, counts = est.top_partners(K, features=features, among=among, by=by,
+                                         include_augmented=include_augmented)
+    rows = np.arange(dv, dtype=np.int64) if features is None else features.astype(np.int64)
+    indptr = np.zeros(dv + 1, dtype=np.int64)
+    indptr[rows + 1] = counts
+    np.cumsum(indptr, out=indptr)
+    keep = np.arange(ids.shape[1])[None, :] < np.asarray(counts)[:, None]
+    return sp.csr_matrix((vals[keep], ids[keep], indptr), shape=(dv, dv))
+
+
+def _dense_w(P_block, lams):
+    P = np.asarray(P_block, dtype=np.double)
+    if P.ndim != 2:
+        raise ValueError("P_block must be a (k, d) array")
+    lams = np.asarray(lams, dtype=np.double)
+    return P.T @ (lams[:, None] * P)
+
+
+def restate_partners(P_block, lams, K, features=None, among=None, by="abs", W=None):
+    """``top_partners`` restated on the dense ``W = P_block^T diag(lams) P_block`` (or a given
+    symmetric ``W``) in NumPy: a test aid, quadratic in ``d``.  Same outputs, same order (key
+    descending, then id ascending), same padding."""
+    W = _dense_w(P_block, lams) if W is None else np.asarray(W, dtype=np.double)
+    d = W.shape[0]
+    features, among = _check_partner_args("restate_partners()", K, features, among, by, d)
+    J = np.arange(d) if features is None else features
+    lo, hi = (0, d) if among is None else among
+    K = int(K)
+    ids = np.full((len(J), K), -1, dtype=np.int32)
+    vals = np.zeros((len(J), K))
+    counts = np.zeros(len(J), dtype=np.int32)
+    cand = np.arange(lo, hi)
+    for q, j in enumerate(J):
+        w = W[j, lo:hi]
+        key = np.abs(w) if by == "abs" else (w if by == "positive" else -w)
+        ok = (key > 0) & (cand != j)
+        c, kk, ww = cand[ok], key[ok], w[ok]
+        order = np.lexsort((c, -kk))[:K]
+        n = order.shape[0]
+        ids[q, :n], vals[q, :n], counts[q] = c[order], ww[order], n
+    return ids, vals, counts
+
+
+def restate_degrees(P_block, lams, tol=0.0, W=None):
+    """``interaction_degrees`` restated on the dense ``W`` in NumPy: a test aid.  ``sum_abs`` is
+    NumPy's row sum (equal to the device's for integer-valued blocks, otherwise up to the
+    summation order)."""
+    W = _dense_w(P_block, lams) if W is None else np.asarray(W, dtype=np.double)
+    if not float(tol) >= 0.0:
+        raise ValueError("restate_degrees(): tol must be >= 0")
+    M = np.abs(W).copy()
+    np.fill_diagonal(M, 0.0)
+    mx = M.max(axis=1) if M.shape[0] else np.zeros(0)
+    strongest = np.where(mx > 0, M.argmax(axis=1), -1).astype(np.int32)  # first = smallest id
+    return dict(degree=(M > tol).sum(axis=1).astype(np.int64), sum_abs=M.sum(axis=1), max_abs=mx,
+                strongest=strongest)
 
 
 # ------------------------------------------------------------------ the notebook's metrics
