@@ -82,6 +82,11 @@ __device__ __forceinline__ double ld_agent(const double* p) {
     return __longlong_as_double((long long)u);
 }
 
+// load of a table nobody writes during the launch, through the constant address space
+__device__ __forceinline__ int32_t prb_const_load(const int32_t* p) {
+    return *(const __attribute__((address_space(4))) int32_t*)p;
+}
+
 // ---- tagged-granule exchange ----------------------------------------------------
 // A partial sum travels as ONE naturally aligned 8-byte word: the double with its two
 // lowest mantissa bits replaced by a step tag (relative perturbation <= 2^-51, applied
@@ -322,6 +327,70 @@ __device__ __forceinline__ void prb_load_entries(const PrbArgs& a, const T* __re
     }
 }
 
+// Rows of a block into LDS and back (LR 1 / 2 of pcd_prb_kernel and lin_prb_kernel; AS = 0: no
+// A values).  The loads of kPrbFillU trips are issued back to back before the first is used, so
+// a wave pays one memory latency per kPrbFillU trips instead of one per trip (15 625 rows over 512
+// threads are 31 trips).  Trips beyond the block re-read its last row and store nothing.
+constexpr int kPrbThreads = 512;  // pcd_prb_kernel / lin_prb_kernel: 8 waves
+constexpr int kPrbFillU = 8;
+template <typename T, int AS, int LR>
+__device__ __forceinline__ void prb_fill_lds(const T* __restrict__ A,
+                                             const typename Vec2<T>::type* __restrict__ yy2,
+                                             int row0, int nr, int tid, T* lds_a, T* lds_r,
+                                             unsigned char* lds_s) {
+    for (int base = tid; base < nr; base += kPrbThreads * kPrbFillU) {
+        typename Vec2<T>::type yv[kPrbFillU];
+        T ar[kPrbFillU][AS > 0 ? AS : 1];
+#pragma unroll
+        for (int u = 0; u < kPrbFillU; ++u) {
+            const size_t i = (size_t)(row0 + min(base + u * kPrbThreads, nr - 1));
+            yv[u] = yy2[i];
+#pragma unroll
+            for (int t = 0; t < AS; ++t) ar[u][t] = A[i * AS + t];
+        }
+#pragma unroll
+        for (int u = 0; u < kPrbFillU; ++u) {
+            const int il = base + u * kPrbThreads;
+            if (il < nr) {
+#pragma unroll
+                for (int t = 0; t < AS; ++t) lds_a[il * AS + t] = ar[u][t];
+                if constexpr (LR == 1) {
+                    lds_r[il] = (T)((double)yv[u].x - (double)yv[u].y);
+                } else {
+                    lds_r[il] = yv[u].x;
+                    lds_s[il] = yv[u].y > (T)0 ? 1 : 0;
+                }
+            }
+        }
+    }
+}
+template <typename T, int AS, int LR>
+__device__ __forceinline__ void prb_writeback_lds(T* __restrict__ A, T* __restrict__ yy, int row0,
+                                                  int nr, int tid, const T* lds_a,
+                                                  const T* lds_r) {
+    for (int base = tid; base < nr; base += kPrbThreads * kPrbFillU) {
+        T yt[kPrbFillU];
+        if constexpr (LR == 1) {  // yhat = r + y: the targets of all trips first
+#pragma unroll
+            for (int u = 0; u < kPrbFillU; ++u)
+                yt[u] = yy[2 * (size_t)(row0 + min(base + u * kPrbThreads, nr - 1)) + 1];
+        }
+#pragma unroll
+        for (int u = 0; u < kPrbFillU; ++u) {
+            const int il = base + u * kPrbThreads;
+            if (il < nr) {
+                const size_t i = (size_t)(row0 + il);
+#pragma unroll
+                for (int t = 0; t < AS; ++t) A[i * AS + t] = lds_a[il * AS + t];
+                if constexpr (LR == 1)
+                    yy[2 * i] = (T)((double)lds_r[il] + (double)yt[u]);
+                else
+                    yy[2 * i] = lds_r[il];
+            }
+        }
+    }
+}
+
 // Workgroup = 8 wavefronts: wave 0 is the CONTROL wave (chain), waves 1..4 are WORKERS
 // (256 threads = 64 slots x 4 lanes) that own the entries, waves 5..7 are HELPERS.  All
 // eight take part in the granule sweep, an eighth of the workgroups each, so that at
@@ -333,7 +402,6 @@ __device__ __forceinline__ void prb_load_entries(const PrbArgs& a, const T* __re
 // b-1 from slot bounds loaded during step b-2), so phase 1 starts with the row gathers;
 // the workers issue the next step's streaming loads while the control wave waits for
 // the other workgroups.
-constexpr int kPrbThreads = 512;
 constexpr int kPrbParts = 8;  // waves that sweep = parts of the workgroup range
 constexpr int kPrbLdsFixed = 2560;  // doubles of fixed LDS (control data, part sums, long slots)
 
@@ -459,17 +527,7 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
     unsigned char* lds_s = reinterpret_cast<unsigned char*>(lds_r + a.rows_per);  // y > 0
     if constexpr (LDSR) {
         const int nr = min(a.rows_per, a.n_rows - row0);
-        for (int il = tid; il < nr; il += kPrbThreads) {
-            const typename Vec2<T>::type yv = yy2[(size_t)(row0 + il)];
-#pragma unroll
-            for (int t = 0; t < AS; ++t) lds_a[il * AS + t] = A[(size_t)(row0 + il) * AS + t];
-            if constexpr (LR == 1) {
-                lds_r[il] = (T)((double)yv.x - (double)yv.y);
-            } else {
-                lds_r[il] = yv.x;
-                lds_s[il] = yv.y > (T)0 ? 1 : 0;
-            }
-        }
+        prb_fill_lds<T, AS, LR>(A, yy2, row0, nr, tid, lds_a, lds_r, lds_s);
         __syncthreads();
     }
     PrbEntries<T> cur, nxt;
@@ -537,9 +595,14 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
         }                                   \
     }
 
+    // boundary b + 4 of step b, read a step ahead (behind B4, in the shadow of the scatter) and
+    // through the constant address space -- the table is written before the launch and by nobody
+    // during it -- i.e. as a scalar load: as a vector load at the top of the step it stood,
+    // with its s_waitcnt vmcnt(0), in front of every step's gather
+    int c4n = (4 <= a.nb) ? prb_const_load(a.bptr + 4) : c3;
     for (int b = 0; b < a.nb; ++b) {
         const int ncols = c1 - c0;
-        const int c4 = (b + 4 <= a.nb) ? a.bptr[b + 4] : c3;  // used two steps from now
+        const int c4 = c4n;  // used two steps from now; loaded during the previous step
         // Drain vmcnt here, where it is free (this step's entries are needed at once and
         // everything else was issued a step ago).  It is a real S_WAITCNT (not inline asm), so
         // the compiler's wait-count bookkeeping knows that nothing is pending from the previous
@@ -978,6 +1041,7 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
             PRB_STAMP(4)
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // B4: deltas in LDS
+        c4n = (b + 5 <= a.nb) ? prb_const_load(a.bptr + b + 5) : c4;
         PRB_STAMP(5)
         PRB_WSTAMP(5)  // waiting for the control wave's chain
         // ---- phase 3 (workers): scatter-update of the own rows (pcd.py:124-133)
@@ -1107,15 +1171,7 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
     if constexpr (LDSR) {  // write the row block back (LR == 1: yhat = r + y)
         __syncthreads();
         const int nr = min(a.rows_per, a.n_rows - row0);
-        for (int il = tid; il < nr; il += kPrbThreads) {
-            const size_t i = (size_t)(row0 + il);
-#pragma unroll
-            for (int t = 0; t < AS; ++t) A[i * AS + t] = lds_a[il * AS + t];
-            if constexpr (LR == 1)
-                yy[2 * i] = (T)((double)lds_r[il] + (double)yy[2 * i + 1]);
-            else
-                yy[2 * i] = lds_r[il];
-        }
+        prb_writeback_lds<T, AS, LR>(A, yy, row0, nr, tid, lds_a, lds_r);
     }
     if (STAMP && a.stamps != nullptr && (tid == 0 || tid == 64)) {
 #pragma unroll
@@ -1169,15 +1225,7 @@ __global__ __launch_bounds__(kPrbThreads) void lin_prb_kernel(
     unsigned char* lds_s = reinterpret_cast<unsigned char*>(lds_r + a.rows_per);  // y > 0
     if constexpr (LR != 0) {
         const int nr = min(a.rows_per, a.n_rows - row0);
-        for (int il = tid; il < nr; il += kPrbThreads) {
-            const typename Vec2<T>::type yv = yy2[(size_t)(row0 + il)];
-            if constexpr (LR == 1) {
-                lds_r[il] = (T)((double)yv.x - (double)yv.y);
-            } else {
-                lds_r[il] = yv.x;
-                lds_s[il] = yv.y > (T)0 ? 1 : 0;
-            }
-        }
+        prb_fill_lds<T, 0, LR>(nullptr, yy2, row0, nr, tid, nullptr, lds_r, lds_s);
         __syncthreads();
     }
     // (yhat, y) of a row as the loss sees them
@@ -1231,7 +1279,8 @@ __global__ __launch_bounds__(kPrbThreads) void lin_prb_kernel(
     }
     for (int b = 0; b < a.nb; ++b) {
         const int ncols = c1 - c0;
-        const int c4 = (b + 4 <= a.nb) ? a.bptr[b + 4] : c3;
+        // (a scalar load, see pcd_prb_kernel: as a vector load its wait stood in front of the step)
+        const int c4 = (b + 4 <= a.nb) ? prb_const_load(a.bptr + b + 4) : c3;
         double yh[PRB_PF];
         double wl = 0.0, cnl = 0.0;
         int jl = 0;
@@ -1488,13 +1537,7 @@ __global__ __launch_bounds__(kPrbThreads) void lin_prb_kernel(
     if constexpr (LR != 0) {  // write the row block back (LR == 1: yhat = r + y)
         __syncthreads();
         const int nr = min(a.rows_per, a.n_rows - row0);
-        for (int il = tid; il < nr; il += kPrbThreads) {
-            const size_t i = (size_t)(row0 + il);
-            if constexpr (LR == 1)
-                yy[2 * i] = (T)((double)lds_r[il] + (double)yy[2 * i + 1]);
-            else
-                yy[2 * i] = lds_r[il];
-        }
+        prb_writeback_lds<T, 0, LR>(nullptr, yy, row0, nr, tid, nullptr, lds_r);
     }
 }
 
