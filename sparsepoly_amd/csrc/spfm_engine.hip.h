@@ -188,6 +188,31 @@ struct DevBuf {
                       : [&] { using T = double; __VA_ARGS__; }())
 
 static inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
+static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+
+// Lists of one slab of a streaming top-K selection (spfm_select.hip.h): the sorted per-strip
+// lists (values, ids) and the merged ones
+struct SelBufs {
+    DevBuf lv, li, ov, oi;
+    hipError_t alloc(int n_strips, int64_t slab, int K) {
+        const size_t on = (size_t)slab * K, ln = (size_t)n_strips * on;
+        hipError_t e = lv.alloc(sizeof(double) * ln);
+        if (e == hipSuccess) e = li.alloc(sizeof(int32_t) * ln);
+        if (e == hipSuccess) e = ov.alloc(sizeof(double) * on);
+        if (e == hipSuccess) e = oi.alloc(sizeof(int32_t) * on);
+        return e;
+    }
+    // the merged slots of nrow rows before a slab: id -1, every value byte `vbyte`
+    hipError_t clear(int64_t nrow, int K, int vbyte, hipStream_t s) {
+        hipError_t e = hipMemsetAsync(ov.p, vbyte, sizeof(double) * (size_t)nrow * K, s);
+        if (e == hipSuccess) e = hipMemsetAsync(oi.p, 0xFF, sizeof(int32_t) * (size_t)nrow * K, s);
+        return e;
+    }
+    size_t bytes() const { return lv.bytes + li.bytes + ov.bytes + oi.bytes; }
+    void release() {
+        for (DevBuf* b : {&lv, &li, &ov, &oi}) b->release();
+    }
+};
 
 // device time of the kernels of one call (not its copies): one event pair, read after each
 // slab's sync (spfm_rank_info, spfm_explain_info)
@@ -1005,7 +1030,8 @@ struct spfm_engine {
     DevBuf int_io, int_out;                               // values / block
     // per-feature views (spfm_engine_partners.hip): query image and ranks, per-tile row records
     // and the degree answers, strip lists and merged lists of a slab
-    DevBuf int_pq, int_pqr, int_prec, int_pdeg, int_plv, int_pli, int_pov, int_poi, int_pon;
+    DevBuf int_pq, int_pqr, int_prec, int_pdeg, int_pon;
+    SelBufs int_psel;
     int int_da = 0, int_kp = 0, int_T = 0;  // of the last compaction
     int int_tile_budget = 0;  // option "interaction_tile_budget": tiles per launch (0 = default)
     int int_dlim = 0;         // option "interaction_features": only features < this (0 = all)
@@ -1015,8 +1041,7 @@ struct spfm_engine {
                int_A.bytes + int_B.bytes + int_rec.bytes + int_rec2.bytes + int_hist.bytes +
                int_cnt.bytes + int_keys.bytes + int_vals.bytes + int_keys2.bytes +
                int_vals2.bytes + int_io.bytes + int_out.bytes + int_pq.bytes + int_pqr.bytes +
-               int_prec.bytes + int_pdeg.bytes + int_plv.bytes + int_pli.bytes + int_pov.bytes +
-               int_poi.bytes + int_pon.bytes;
+               int_prec.bytes + int_pdeg.bytes + int_psel.bytes() + int_pon.bytes;
     }
     int interaction_view(const char* what, int order_idx, BlockView* v);
     int interaction_prepare(const char* what, int order_idx);
@@ -1077,7 +1102,7 @@ struct spfm_engine {
     DevBuf rk_V, rk_cc;                    // candidate towers (padded rows, rk_Rp), constants
     DevBuf rk_U, rk_rc;                    // context towers of one slab
     DevBuf rk_xp, rk_xi, rk_xv;            // CSR staging (contexts or candidates)
-    DevBuf rk_lv, rk_li, rk_ov, rk_oi;     // per-strip lists, merged lists of one slab
+    SelBufs rk_sel;                        // per-strip lists, merged lists of one slab
     DevBuf rk_dense;                       // dense scores of one slab
     DevBuf rk_ep, rk_ei;                   // excluded candidates of the call's rows (CSR pattern)
     DevBuf rk_tp, rk_ti, rk_ts, rk_tr;     // rank_eval: targets, their scores and counts
@@ -1091,7 +1116,7 @@ struct spfm_engine {
     int rk_device_us = 0;   // spfm_rank_info: kernels of the last scores / topk call
     size_t rank_scratch_bytes() const {
         return rk_V.bytes + rk_cc.bytes + rk_U.bytes + rk_rc.bytes + rk_xp.bytes + rk_xi.bytes +
-               rk_xv.bytes + rk_lv.bytes + rk_li.bytes + rk_ov.bytes + rk_oi.bytes + rk_dense.bytes +
+               rk_xv.bytes + rk_sel.bytes() + rk_dense.bytes +
                rk_ep.bytes + rk_ei.bytes + rk_tp.bytes + rk_ti.bytes + rk_ts.bytes + rk_tr.bytes +
                rk_pairs.bytes;
     }

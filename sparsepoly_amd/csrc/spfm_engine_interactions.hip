@@ -109,8 +109,9 @@ void spfm_engine::interaction_release() {
     for (DevBuf* b : {&int_flag, &int_pos, &int_ids, &int_tot, &int_tmp, &int_A, &int_B, &int_rec,
                       &int_rec2, &int_hist, &int_cnt, &int_keys, &int_vals, &int_keys2,
                       &int_vals2, &int_io, &int_out, &int_pq, &int_pqr, &int_prec, &int_pdeg,
-                      &int_plv, &int_pli, &int_pov, &int_poi, &int_pon})
+                      &int_pon})
         b->release();
+    int_psel.release();
 }
 
 // What a pass is; the driver below reads these and interprets none of them.

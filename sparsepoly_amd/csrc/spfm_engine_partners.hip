@@ -16,10 +16,8 @@ static_assert(PART_ABS == SPFM_PARTNERS_ABS && PART_POS == SPFM_PARTNERS_POS &&
               "header and device agree on the modes");
 
 namespace {
-constexpr int64_t kPartSlabDefault = 4096;         // query rows per slab of the selection
 constexpr int64_t kPartRecBytes = 256ll << 20;     // row records of one degree slab
 constexpr int64_t kPartDegreeStrip = 16;           // tiles per strip of the degree pass
-int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 }  // namespace
 
 int spfm_engine::interaction_degrees(int order_idx, double tol, int64_t cand_strip,
@@ -50,7 +48,7 @@ int spfm_engine::interaction_degrees(int order_idx, double tol, int64_t cand_str
         out.sum = reinterpret_cast<double*>(out.cnt + pad);
         out.mx = out.sum + pad;
         out.arg = reinterpret_cast<int32_t*>(out.mx + pad);
-        const size_t lds = part_lds_bytes(PART_DEGREE, 0);
+        const size_t lds = part_degree_lds_bytes();
         for (int64_t r0 = 0; r0 < pad; r0 += slab) {
             const int64_t rows_pad = std::min(slab, pad - r0);
             const int64_t nrow = std::min<int64_t>(rows_pad, da - r0);
@@ -122,7 +120,7 @@ int spfm_engine::interaction_partners(int order_idx, int64_t nJ, const int32_t* 
         FAIL(SPFM_ERR_INVALID, "interaction_partners: by must be SPFM_PARTNERS_ABS, _POS or _NEG");
     if (row_slab < 0 || row_slab > (1 << 20))
         FAIL(SPFM_ERR_INVALID, "interaction_partners: row_slab must be in [0, 2^20]");
-    if (cand_strip < 0 || cand_strip % kIntTile != 0 || cand_strip > kPartMaxStrip)
+    if (cand_strip < 0 || cand_strip % kIntTile != 0 || cand_strip > kSelMaxStrip)
         FAIL(SPFM_ERR_INVALID,
              "interaction_partners: cand_strip must be 0 or a multiple of 64, at most 65536");
     const int dlim = (int_dlim > 0 && int_dlim < d) ? int_dlim : d;
@@ -153,25 +151,15 @@ int spfm_engine::interaction_partners(int order_idx, int64_t nJ, const int32_t* 
         r_hi = (int)(std::lower_bound(ids.begin(), ids.end(), hi) - ids.begin());
     }
     if (r_lo < r_hi) {
-        const int t_lo = r_lo / kIntTile, t_hi = (int)cdiv(r_hi, kIntTile), Tc = t_hi - t_lo;
-        const int64_t slab = std::min(round_up(row_slab > 0 ? row_slab : kPartSlabDefault, kIntTile),
-                                      round_up(nq, kIntTile));
-        // strip width as in the ranking unit: about 512 workgroups per slab, 16 .. 1024 tiles
-        int64_t st = std::min<int64_t>(1024, std::max<int64_t>(16, (int64_t)Tc * (slab / kIntTile) / 512));
-        if (cand_strip > 0) st = cand_strip / kIntTile;
-        st = std::min<int64_t>(st, Tc);
-        const int n_strips = (int)cdiv(Tc, st);
+        const int t_lo = r_lo / kIntTile, t_hi = (int)cdiv(r_hi, kIntTile);
+        const SelPlan plan = sel_plan(row_slab, cand_strip, nq, t_hi - t_lo);
+        const int64_t slab = plan.slab;
         const int Ki = (int)K;
-        const size_t lds = part_lds_bytes(PART_SELECT, kPartCap);
         HIPC(hipFuncSetAttribute((const void*)part_tile_kernel<PART_SELECT>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
         HIPC(int_pq.alloc(sizeof(double) * (size_t)slab * int_kp));
         HIPC(int_pqr.alloc(sizeof(int32_t) * (size_t)slab));
-        const size_t ln = (size_t)n_strips * (size_t)slab * Ki;
-        HIPC(int_plv.alloc(sizeof(double) * ln));
-        HIPC(int_pli.alloc(sizeof(int32_t) * ln));
-        HIPC(int_pov.alloc(sizeof(double) * (size_t)slab * Ki));
-        HIPC(int_poi.alloc(sizeof(int32_t) * (size_t)slab * Ki));
+        HIPC(int_psel.alloc(plan.n_strips, slab, Ki));
         HIPC(int_pon.alloc(sizeof(int32_t) * (size_t)slab));
         if (J) SPFM_TRY(upload(int_io, J, (size_t)nq));
         for (int64_t r0 = 0; r0 < nq; r0 += slab) {
@@ -196,28 +184,22 @@ int spfm_engine::interaction_partners(int order_idx, int64_t nJ, const int32_t* 
             a.r_hi = r_hi;
             a.t_lo = t_lo;
             a.t_hi = t_hi;
-            a.strip_tiles = (int)st;
-            a.n_strips = n_strips;
-            a.K = Ki;
-            a.cap = kPartCap;
+            a.strip_tiles = plan.strip_tiles;
+            a.n_strips = plan.n_strips;
             a.by = by;
-            a.lval = int_plv.as<double>();
-            a.lidx = int_pli.as<int32_t>();
-            a.oval = int_pov.as<double>();
-            a.oidx = int_poi.as<int32_t>();
+            a.sel = {Ki, kSelCap, int_psel.lv.as<double>(), int_psel.li.as<int32_t>(),
+                     int_psel.ov.as<double>(), int_psel.oi.as<int32_t>()};
             a.ocnt = int_pon.as<int32_t>();
-            // slots no partner fills: id -1, value 0
-            HIPC(hipMemsetAsync(int_pov.p, 0, sizeof(double) * (size_t)nrow * Ki, stream));
-            HIPC(hipMemsetAsync(int_poi.p, 0xFF, sizeof(int32_t) * (size_t)nrow * Ki, stream));
+            HIPC(int_psel.clear(nrow, Ki, 0, stream));  // slots no partner fills: id -1, value 0
             hipLaunchKernelGGL((part_tile_kernel<PART_SELECT>),
-                               dim3((unsigned)n_strips, (unsigned)(rows_pad / kIntTile)),
-                               dim3(kBlock), lds, stream, a);
+                               dim3((unsigned)plan.n_strips, (unsigned)(rows_pad / kIntTile)),
+                               dim3(kBlock), plan.lds, stream, a);
             hipLaunchKernelGGL(part_merge_kernel, dim3(cdiv(nrow * kWave, kBlock)), dim3(kBlock), 0,
                                stream, a);
             HIPC(hipGetLastError());
             ++int_launches;
-            SPFM_TRY(download(hv.data() + (size_t)r0 * Ki, int_pov.p, (size_t)nrow * Ki));
-            SPFM_TRY(download(hi_.data() + (size_t)r0 * Ki, int_poi.p, (size_t)nrow * Ki));
+            SPFM_TRY(download(hv.data() + (size_t)r0 * Ki, int_psel.ov.p, (size_t)nrow * Ki));
+            SPFM_TRY(download(hi_.data() + (size_t)r0 * Ki, int_psel.oi.p, (size_t)nrow * Ki));
             SPFM_TRY(download(hn.data() + (size_t)r0, int_pon.p, (size_t)nrow));
             SPFM_TRY(sync());  // the slab's buffers are rewritten by the next one
         }

@@ -15,26 +15,14 @@ static_assert(kRankMaxK == SPFM_RANK_MAX_K, "header and device agree on the cap"
 static_assert(kRankMaxTargets == SPFM_RANK_MAX_TARGETS, "header and device agree on the cap");
 
 namespace {
-constexpr int64_t kRankSlabDefault = 4096;          // context rows per slab
 constexpr int64_t kRankDenseSlabBytes = 256ll << 20;  // device image of one dense slab
-int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
-// strip width of the selection and of the count pass, in tiles: the option, else about 512
-// workgroups per slab, 16 .. 1024 tiles (a longer strip has fewer survivors per candidate: about
-// K ln(strip / K) per row and strip)
-int64_t rank_strip_tiles(int cand_strip, int Tc, int row_tiles) {
-    int64_t t = std::min<int64_t>(1024, std::max<int64_t>(16, (int64_t)Tc * row_tiles / 512));
-    if (cand_strip > 0) t = cdiv(cand_strip, kIntTile);
-    return std::min<int64_t>(t, std::min<int64_t>(Tc, kRankMaxStrip / kIntTile));
-}
-
 }  // namespace
 
 void spfm_engine::rank_release() {
-    for (DevBuf* b : {&rk_V, &rk_cc, &rk_U, &rk_rc, &rk_xp, &rk_xi, &rk_xv, &rk_lv, &rk_li, &rk_ov,
-                      &rk_oi, &rk_dense, &rk_ep, &rk_ei, &rk_tp, &rk_ti, &rk_ts, &rk_tr,
-                      &rk_pairs})
+    for (DevBuf* b : {&rk_V, &rk_cc, &rk_U, &rk_rc, &rk_xp, &rk_xi, &rk_xv, &rk_dense, &rk_ep,
+                      &rk_ei, &rk_tp, &rk_ti, &rk_ts, &rk_tr, &rk_pairs})
         b->release();
+    rk_sel.release();
     rk_zflag.clear();
     rk_have = false;
     rk_C = 0;
@@ -143,9 +131,15 @@ int spfm_engine::rank_contexts(const char* what, int64_t n_ctx, const int64_t* i
     return sync();  // the caller's arrays are not read after this
 }
 
-static RankArgs rank_args(const spfm_engine* h, int64_t nrow) {
+// slab rows [r0, r0 + nrow) of the call against the candidates, in strips of strip_tiles tiles
+static RankArgs rank_args(const spfm_engine* h, int64_t r0, int64_t nrow, int strip_tiles) {
     RankArgs a;
     memset(&a, 0, sizeof a);
+    a.strip_tiles = strip_tiles;
+    a.n_strips = (int)cdiv(cdiv(h->rk_C, kIntTile), strip_tiles);
+    a.eptr = h->rk_ep.as<int64_t>();
+    a.eidx = h->rk_ei.as<int32_t>();
+    a.row0 = r0;
     a.U = h->rk_U.as<double>();
     a.V = h->rk_V.as<double>();
     a.rc = h->rk_rc.as<double>();
@@ -168,7 +162,7 @@ int spfm_engine::rank_scores(int64_t n_ctx, const int64_t* indptr, const int32_t
     }
     if (n_ctx == 0) return SPFM_OK;
     if (!out) FAIL(SPFM_ERR_INVALID, "rank_scores: out is NULL");
-    int64_t slab = round_up(rk_row_slab > 0 ? rk_row_slab : kRankSlabDefault, kIntTile);
+    int64_t slab = round_up(rk_row_slab > 0 ? rk_row_slab : kSelSlabDefault, kIntTile);
     const int64_t fit = kRankDenseSlabBytes / (8 * rk_C) / kIntTile * kIntTile;
     slab = std::min(slab, std::max<int64_t>(fit, kIntTile));
     slab = std::min(slab, round_up(n_ctx, kIntTile));
@@ -178,16 +172,14 @@ int spfm_engine::rank_scores(int64_t n_ctx, const int64_t* indptr, const int32_t
     HIPC(rk_U.alloc(sizeof(double) * (size_t)slab * rk_Rp));
     HIPC(rk_rc.alloc(sizeof(double) * (size_t)slab));
     HIPC(rk_dense.alloc(sizeof(double) * (size_t)slab * (size_t)rk_C));
-    const size_t lds = rank_lds_bytes(RANK_DENSE, 0);
+    const size_t lds = int_stage_lds_bytes();
     DeviceTimer timer;
     rk_device_us = 0;
     for (int64_t r0 = 0; r0 < n_ctx; r0 += slab) {
         const int64_t nrow = std::min(slab, n_ctx - r0);
         timer.begin(stream);
         SPFM_TRY(rank_towers(r0, nrow, RANK_CTX, rk_U.as<double>(), rk_rc.as<double>()));
-        RankArgs a = rank_args(this, nrow);
-        a.strip_tiles = strip_tiles;
-        a.n_strips = (int)cdiv(Tc, strip_tiles);
+        RankArgs a = rank_args(this, r0, nrow, strip_tiles);
         a.dense = rk_dense.as<double>();
         hipLaunchKernelGGL((rank_tile_kernel<RANK_DENSE>),
                            dim3((unsigned)a.n_strips, (unsigned)(a.rows_pad / kIntTile)),
@@ -245,31 +237,19 @@ int spfm_engine::rank_topk(int64_t n_ctx, const int64_t* indptr, const int32_t* 
         *k_out = Ko;
         return SPFM_OK;
     }
-    const int64_t slab = std::min(
-        round_up(rk_row_slab > 0 ? rk_row_slab : kRankSlabDefault, kIntTile),
-        round_up(n_ctx, kIntTile));
-    const int row_tiles = (int)(slab / kIntTile);
-    const int Tc = (int)cdiv(rk_C, kIntTile);
-    const int64_t strip_tiles = rank_strip_tiles(rk_cand_strip, Tc, row_tiles);
-    const int n_strips = (int)cdiv(Tc, strip_tiles);
-    const int cap = kRankCap;
-    const size_t lds = rank_lds_bytes(RANK_SELECT, cap, eptr != nullptr);
+    const SelPlan plan = sel_plan(rk_row_slab, rk_cand_strip, n_ctx, (int)cdiv(rk_C, kIntTile));
+    const int64_t slab = plan.slab;
+    const size_t lds = plan.lds + (eptr ? kRankExclLdsBytes : 0);
+    HIPC(hipFuncSetAttribute(eptr ? (const void*)rank_tile_kernel<RANK_SELECT, true>
+                                  : (const void*)rank_tile_kernel<RANK_SELECT>,
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (eptr) {
-        HIPC(hipFuncSetAttribute((const void*)rank_tile_kernel<RANK_SELECT, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         SPFM_TRY(upload(rk_ep, eptr, (size_t)n_ctx + 1));
         SPFM_TRY(upload(rk_ei, eidx, (size_t)eptr[n_ctx]));
-    } else {
-        HIPC(hipFuncSetAttribute((const void*)rank_tile_kernel<RANK_SELECT>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     HIPC(rk_U.alloc(sizeof(double) * (size_t)slab * rk_Rp));
     HIPC(rk_rc.alloc(sizeof(double) * (size_t)slab));
-    const size_t ln = (size_t)n_strips * (size_t)slab * Ko;
-    HIPC(rk_lv.alloc(sizeof(double) * ln));
-    HIPC(rk_li.alloc(sizeof(int32_t) * ln));
-    HIPC(rk_ov.alloc(sizeof(double) * (size_t)slab * Ko));
-    HIPC(rk_oi.alloc(sizeof(int32_t) * (size_t)slab * Ko));
+    HIPC(rk_sel.alloc(plan.n_strips, slab, Ko));
     // the caller's arrays are written only once nothing can fail
     std::vector<int32_t> hi((size_t)n_ctx * Ko);
     std::vector<double> hv((size_t)n_ctx * Ko);
@@ -279,33 +259,22 @@ int spfm_engine::rank_topk(int64_t n_ctx, const int64_t* indptr, const int32_t* 
         const int64_t nrow = std::min(slab, n_ctx - r0);
         timer.begin(stream);
         SPFM_TRY(rank_towers(r0, nrow, RANK_CTX, rk_U.as<double>(), rk_rc.as<double>()));
-        RankArgs a = rank_args(this, nrow);
-        a.strip_tiles = (int)strip_tiles;
-        a.n_strips = n_strips;
-        a.K = Ko;
-        a.cap = cap;
-        a.lval = rk_lv.as<double>();
-        a.lidx = rk_li.as<int32_t>();
-        a.oval = rk_ov.as<double>();
-        a.oidx = rk_oi.as<int32_t>();
-        // slots no finite score fills: index -1, NaN
-        HIPC(hipMemsetAsync(rk_ov.p, 0xFF, sizeof(double) * (size_t)nrow * Ko, stream));
-        HIPC(hipMemsetAsync(rk_oi.p, 0xFF, sizeof(int32_t) * (size_t)nrow * Ko, stream));
-        a.eptr = rk_ep.as<int64_t>();
-        a.eidx = rk_ei.as<int32_t>();
-        a.row0 = r0;
-        const dim3 grid((unsigned)n_strips, (unsigned)(a.rows_pad / kIntTile));
+        RankArgs a = rank_args(this, r0, nrow, plan.strip_tiles);
+        a.sel = {Ko, kSelCap, rk_sel.lv.as<double>(), rk_sel.li.as<int32_t>(),
+                 rk_sel.ov.as<double>(), rk_sel.oi.as<int32_t>()};
+        HIPC(rk_sel.clear(nrow, Ko, 0xFF, stream));  // slots no finite score fills: index -1, NaN
+        const dim3 grid((unsigned)a.n_strips, (unsigned)(a.rows_pad / kIntTile));
         if (eptr)
             hipLaunchKernelGGL((rank_tile_kernel<RANK_SELECT, true>), grid, dim3(kBlock), lds,
                                stream, a);
         else
             hipLaunchKernelGGL((rank_tile_kernel<RANK_SELECT>), grid, dim3(kBlock), lds, stream, a);
-        hipLaunchKernelGGL((rank_tile_kernel<RANK_MERGE>), dim3(cdiv(nrow * kWave, kBlock)),
-                           dim3(kBlock), 0, stream, a);
+        hipLaunchKernelGGL(rank_merge_kernel, dim3(cdiv(nrow * kWave, kBlock)), dim3(kBlock), 0,
+                           stream, a);
         HIPC(hipGetLastError());
         timer.end(stream);
-        SPFM_TRY(download(hv.data() + (size_t)r0 * Ko, rk_ov.p, (size_t)nrow * Ko));
-        SPFM_TRY(download(hi.data() + (size_t)r0 * Ko, rk_oi.p, (size_t)nrow * Ko));
+        SPFM_TRY(download(hv.data() + (size_t)r0 * Ko, rk_sel.ov.p, (size_t)nrow * Ko));
+        SPFM_TRY(download(hi.data() + (size_t)r0 * Ko, rk_sel.oi.p, (size_t)nrow * Ko));
         SPFM_TRY(sync());
         timer.collect();
     }
@@ -355,12 +324,9 @@ int spfm_engine::rank_eval(int64_t n_ctx, const int64_t* indptr, const int32_t* 
     std::vector<double> hs((size_t)nt, 0.0);
     rk_device_us = 0;
     if (nt > 0) {
-        const int64_t slab = std::min(
-            round_up(rk_row_slab > 0 ? rk_row_slab : kRankSlabDefault, kIntTile),
-            round_up(n_ctx, kIntTile));
         const int Tc = (int)cdiv(rk_C, kIntTile);
-        const int64_t strip_tiles = rank_strip_tiles(rk_cand_strip, Tc, (int)(slab / kIntTile));
-        const int n_strips = (int)cdiv(Tc, strip_tiles);
+        const SelPlan plan = sel_plan(rk_row_slab, rk_cand_strip, n_ctx, Tc);
+        const int64_t slab = plan.slab;
         const size_t lds = rank_count_lds_bytes(tcap);
         HIPC(hipFuncSetAttribute(eptr ? (const void*)rank_count_kernel<true>
                                       : (const void*)rank_count_kernel<false>,
@@ -398,12 +364,7 @@ int spfm_engine::rank_eval(int64_t n_ctx, const int64_t* indptr, const int32_t* 
             SPFM_TRY(rank_towers(r0, nrow, RANK_CTX, rk_U.as<double>(), rk_rc.as<double>()));
             RankEvalArgs e;
             memset(&e, 0, sizeof e);
-            e.r = rank_args(this, nrow);
-            e.r.strip_tiles = (int)strip_tiles;
-            e.r.n_strips = n_strips;
-            e.r.eptr = rk_ep.as<int64_t>();
-            e.r.eidx = rk_ei.as<int32_t>();
-            e.r.row0 = r0;
+            e.r = rank_args(this, r0, nrow, plan.strip_tiles);
             e.tptr = rk_tp.as<int64_t>();
             e.tidx = rk_ti.as<int32_t>();
             e.pairs = rk_pairs.as<int2>();
@@ -412,7 +373,7 @@ int spfm_engine::rank_eval(int64_t n_ctx, const int64_t* indptr, const int32_t* 
             e.tcap = tcap;
             hipLaunchKernelGGL(rank_tscore_kernel, dim3((unsigned)pairs.size()), dim3(kBlock), 0,
                                stream, e);
-            const dim3 grid((unsigned)n_strips, (unsigned)(e.r.rows_pad / kIntTile));
+            const dim3 grid((unsigned)e.r.n_strips, (unsigned)(e.r.rows_pad / kIntTile));
             if (eptr)
                 hipLaunchKernelGGL(rank_count_kernel<true>, grid, dim3(kBlock), lds, stream, e);
             else
@@ -481,7 +442,7 @@ int spfm_rank_eval(spfm_handle h, int64_t n_ctx, const int64_t* indptr, const in
 
 int spfm_rank_set_partition(spfm_handle h, int64_t row_slab, int64_t cand_strip) {
     if (!h) return SPFM_ERR_INVALID;
-    if (row_slab < 0 || row_slab > (1 << 20) || cand_strip < 0 || cand_strip > kRankMaxStrip) {
+    if (row_slab < 0 || row_slab > (1 << 20) || cand_strip < 0 || cand_strip > kSelMaxStrip) {
         h->err = "rank_set_partition: row_slab must be in [0, 2^20], cand_strip in [0, 65536]";
         return SPFM_ERR_INVALID;
     }

@@ -191,6 +191,21 @@ __device__ __forceinline__ void int_mfma_chunk(const double* sA, const double* s
     }
 }
 
+// One 64 x 64 tile of the pair form: the rows at Ag against the rows at Bg over kp components,
+// into the wave's quadrant
+__device__ __forceinline__ void int_tile_product(const double* Ag, const double* Bg, int kp,
+                                                 double* sA, double* sB, int_v4d (&acc)[2][2]) {
+    int_acc_zero(acc);
+    for (int kc0 = 0; kc0 < kp; kc0 += kIntKC) {
+        const int kend = (kp - kc0 < kIntKC) ? kp - kc0 : kIntKC;  // multiple of 4
+        int_stage_chunk(Ag, Bg, kp, kc0, kend, sA, sB);
+        int_mfma_chunk<false>(sA, sB, kend, nullptr, acc);
+    }
+}
+
+// LDS of the two staging tiles
+static inline size_t int_stage_lds_bytes() { return sizeof(double) * 2 * kIntTile * kIntLd; }
+
 template <int MODE>
 __device__ __forceinline__ void int_hist_clear(unsigned* sHist) {
     if constexpr (MODE == INT_HIST) {
@@ -273,14 +288,8 @@ __global__ __launch_bounds__(kBlock) void int_tile_kernel(IntArgs a) {
 
     int_hist_clear<MODE>(sHist);
     int_v4d acc[2][2];
-    int_acc_zero(acc);
-    const double* Ag = a.A + (size_t)ti * kIntTile * a.kp;
-    const double* Bg = a.B + (size_t)tj * kIntTile * a.kp;
-    for (int kc0 = 0; kc0 < a.kp; kc0 += kIntKC) {
-        const int kend = (a.kp - kc0 < kIntKC) ? a.kp - kc0 : kIntKC;  // multiple of 4
-        int_stage_chunk(Ag, Bg, a.kp, kc0, kend, sA, sB);
-        int_mfma_chunk<false>(sA, sB, kend, nullptr, acc);
-    }
+    int_tile_product(a.A + (size_t)ti * kIntTile * a.kp, a.B + (size_t)tj * kIntTile * a.kp, a.kp,
+                     sA, sB, acc);
 
     // C/D map of the f64 form: register r of lane l is row (l >> 4) + 4 r, column l & 15
     IntRec mine;

@@ -4,10 +4,9 @@
 // proximal CD core; see DESIGN.md section 14b.
 //
 // Both walk the full square of W, rows = query features, columns = candidate partners, on the
-// compacted images A / B of spfm_interactions.hip.h.  Staging, quadrants and the MFMA chain are
-// those of int_tile_kernel (int_stage_chunk / int_mfma_chunk, chunks of 32 components, s = 0, 4,
-// 8, ... in order), with the query rows as the A operand and the candidates as the B operand: a
-// value of W is the same bits here, in spfm_interaction_topk / _list and under every partition.
+// compacted images A / B of spfm_interactions.hip.h.  The tile product is int_tile_product, with
+// the query rows as the A operand and the candidates as the B operand: a value of W is the same
+// bits here, in spfm_interaction_topk / _list and under every partition.
 // Workgroup (strip, ti) owns the 64-row query tile ti against the candidate tiles of its strip, in
 // ascending order.  The diagonal is masked by comparing compact ranks.
 //
@@ -18,27 +17,19 @@
 //    here, so the strip width decides nothing but who computes a record.
 //    part_reduce_kernel: one wave per row; lane l combines the tiles l, l + 64, ... in order, then
 //    the lanes (xor shuffle tree).  The tree depends on the tile count alone.  No float atomics.
-// 2. part_tile_kernel<PART_SELECT>: rank_tile_kernel<RANK_SELECT>'s scheme (spfm_rank.hip.h) with
-//    the signed W in the buffer and the key derived from it (|W|, W or -W: an entry is admissible
-//    when its key is > 0, so `thr` starts at 0).  A candidate survives when its key is > thr
-//    (candidates come in ascending order: a tie with the K-th loses); rows that cannot take a
-//    tile's survivors are compacted first (part_compact: rank_compact on keys).  At the end of the
-//    strip every row's sorted list is written out.
-//    part_merge_kernel: one wave per query; an entry's final rank is its position in its own list
-//    plus, by binary search, the entries of every other list that beat it (key descending, id
-//    ascending: a total order, so no result bit depends on the partition).
+// 2. part_tile_kernel<PART_SELECT>: the streaming top-K selection of spfm_select.hip.h with the
+//    signed W in the buffer and the key derived from it (|W|, W or -W: an entry is admissible
+//    when its key is > 0, so the floor is 0).
+//    part_merge_kernel: sel_merge of the per-strip lists, one wave per query; compact ranks
+//    become feature ids and the row's count is written.
 #pragma once
-#include "spfm_interactions.hip.h"
-#include "spfm_rank.hip.h"
+#include "spfm_select.hip.h"
 
 namespace spfm {
 
-constexpr int kPartMaxK = 128;                  // SPFM_INTERACTION_MAX_K
-constexpr int kPartCap = kPartMaxK + kIntTile;  // buffer entries per row: K + one tile's worth
-constexpr int kPartMaxStrip = 65536;            // candidates per strip: 16-bit local ids
+constexpr int kPartMaxK = kSelMaxK;  // SPFM_INTERACTION_MAX_K
 enum { PART_DEGREE = 0, PART_SELECT = 1 };
 enum { PART_ABS = 0, PART_POS = 1, PART_NEG = 2 };
-static_assert(kPartCap <= 3 * kWave, "part_compact keeps three entries per lane");
 
 struct PartRec {
     double sum, mx;
@@ -55,14 +46,11 @@ struct PartArgs {
     int r_lo, r_hi;         // candidates: compact ranks [r_lo, r_hi)
     int t_lo, t_hi;         // the candidate tiles that hold them
     int strip_tiles, n_strips;
-    int K, cap, by;
+    int by;
     double tol;
     PartRec* rec;           // PART_DEGREE (rows_pad, t_hi - t_lo)
-    double* lval;           // PART_SELECT (n_strips, rows_pad, K): signed W
-    int32_t* lidx;          //             compact ranks, INT32_MAX = padding
-    double* oval;           // merge (nrow, K)
-    int32_t* oidx;
-    int32_t* ocnt;          // (nrow)
+    SelLists sel;           // PART_SELECT, merge: signed W and compact ranks
+    int32_t* ocnt;          // merge (nrow)
 };
 
 struct PartOut {  // of part_reduce_kernel, per compact rank
@@ -72,15 +60,9 @@ struct PartOut {  // of part_reduce_kernel, per compact rank
     int32_t* arg;  // feature id, -1 = none
 };
 
-// dynamic LDS of part_tile_kernel<MODE>
-static inline size_t part_lds_bytes(int mode, int cap) {
-    size_t b = sizeof(double) * 2 * kIntTile * kIntLd;
-    if (mode == PART_SELECT)
-        b += (size_t)kIntTile * cap * (sizeof(double) + sizeof(uint16_t)) +
-             kIntTile * (sizeof(double) + 2 * sizeof(int));
-    else
-        b += sizeof(PartRec) * 2 * kIntTile;
-    return b;
+// dynamic LDS of part_tile_kernel<PART_DEGREE> (PART_SELECT: SelPlan::lds)
+static inline size_t part_degree_lds_bytes() {
+    return int_stage_lds_bytes() + sizeof(PartRec) * 2 * kIntTile;
 }
 
 __device__ __forceinline__ double part_key(double w, int by) {
@@ -130,60 +112,13 @@ static __global__ __launch_bounds__(kBlock) void part_gather_kernel(
     if (s == 0) qrank[q] = r;
 }
 
-// One wave: the n entries of a row's buffer -> its min(n, K) best by key, sorted, at the front
-// (rank_compact of spfm_rank.hip.h with the key derived from the stored value)
-__device__ __forceinline__ void part_compact(double* bv, uint16_t* bc, int* cnt, double* thr, int K,
-                                             int by) {
-    const int lane = threadIdx.x & 63;
-    const int n = __builtin_amdgcn_readfirstlane(*cnt);  // wave-uniform
-    double w[3], v[3];
-    unsigned c[3];
-    int rk[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const int i = lane + q * kWave;
-        w[q] = i < n ? bv[i] : 0.0;
-        v[q] = part_key(w[q], by);
-        c[q] = i < n ? bc[i] : 0u;
-        rk[q] = 0;
-    }
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {  // entry p * 64 + l sits in lane l, slot p
-        const int m = n - p * kWave < kWave ? n - p * kWave : kWave;
-        for (int l = 0; l < m; ++l) {
-            const double vj = readlane_d(v[p], l);
-            const unsigned cj = (unsigned)__builtin_amdgcn_readlane((int)c[p], l);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) rk[q] += rank_beats(vj, cj, v[q], c[q]) ? 1 : 0;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();  // every entry is in registers before the moves
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const int i = lane + q * kWave;
-        if (i < n && rk[q] < K) {
-            bv[rk[q]] = w[q];
-            bc[rk[q]] = (uint16_t)c[q];
-            if (rk[q] == K - 1) *thr = v[q];
-        }
-    }
-    if (lane == 0) *cnt = n < K ? n : K;
-    __builtin_amdgcn_wave_barrier();
-}
-
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void part_tile_kernel(PartArgs a) {
     extern __shared__ double part_lds[];
     double* sA = part_lds;
     double* sB = sA + kIntTile * kIntLd;
-    // PART_SELECT
-    double* bval = sB + kIntTile * kIntLd;                  // [64][cap]
-    double* thr = bval + (size_t)kIntTile * a.cap;          // [64]
-    uint16_t* bidx = reinterpret_cast<uint16_t*>(thr + kIntTile);  // [64][cap]
-    int* cnt = reinterpret_cast<int*>(bidx + (size_t)kIntTile * a.cap);  // [64]
-    int* add = cnt + kIntTile;                              // [64] survivors of the tile
-    // PART_DEGREE
-    PartRec* sRec = reinterpret_cast<PartRec*>(sB + kIntTile * kIntLd);  // [2][64]
+    const SelLds s(sB + kIntTile * kIntLd, a.sel.cap);                   // PART_SELECT
+    PartRec* sRec = reinterpret_cast<PartRec*>(sB + kIntTile * kIntLd);  // PART_DEGREE [2][64]
 
     const int strip = blockIdx.x, ti = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -193,14 +128,9 @@ __global__ __launch_bounds__(kBlock) void part_tile_kernel(PartArgs a) {
     const int t1 = (t0 + a.strip_tiles < a.t_hi) ? t0 + a.strip_tiles : a.t_hi;
     const int c0 = t0 * kIntTile;  // first candidate of the strip
     const int Tc = a.t_hi - a.t_lo;
+    const auto key = [by = a.by](double w) { return part_key(w, by); };
 
-    if constexpr (MODE == PART_SELECT) {
-        if (threadIdx.x < kIntTile) {
-            thr[threadIdx.x] = 0.0;  // a key must be > 0
-            cnt[threadIdx.x] = 0;
-            add[threadIdx.x] = 0;
-        }
-    }
+    if constexpr (MODE == PART_SELECT) sel_init(s, 0.0);  // a key must be > 0
     // C/D map of the f64 form: register r of lane l is row (l >> 4) + 4 r, column l & 15.
     // The compact ranks of the lane's eight rows:
     int qr[2][4];
@@ -215,13 +145,7 @@ __global__ __launch_bounds__(kBlock) void part_tile_kernel(PartArgs a) {
     const double* Qg = a.Q + (size_t)ti * kIntTile * a.kp;
     for (int tj = t0; tj < t1; ++tj) {
         int_v4d acc[2][2];
-        int_acc_zero(acc);
-        const double* Bg = a.B + (size_t)tj * kIntTile * a.kp;
-        for (int kc0 = 0; kc0 < a.kp; kc0 += kIntKC) {
-            const int kend = (a.kp - kc0 < kIntKC) ? a.kp - kc0 : kIntKC;  // multiple of 4
-            int_stage_chunk(Qg, Bg, a.kp, kc0, kend, sA, sB);
-            int_mfma_chunk<false>(sA, sB, kend, nullptr, acc);
-        }
+        int_tile_product(Qg, a.B + (size_t)tj * kIntTile * a.kp, a.kp, sA, sB, acc);
         if constexpr (MODE == PART_DEGREE) {
             // (padding rows and columns are zero rows of the images: W = 0 there)
 #pragma unroll
@@ -254,63 +178,18 @@ __global__ __launch_bounds__(kBlock) void part_tile_kernel(PartArgs a) {
             }
             // (sRec is rewritten behind the barriers of the next tile's staging step)
         } else {
-            // pass 0: count the survivors; pass 1: append
-#pragma unroll
-            for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-                for (int cb = 0; cb < 2; ++cb) {
-                    const int col = tj * kIntTile + wc * 32 + cb * 16 + l15;
-                    const bool colin = col >= a.r_lo && col < a.r_hi;
-#pragma unroll
-                    for (int ra = 0; ra < 2; ++ra)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int rl = wr * 32 + ra * 16 + l4 + 4 * r;
-                            const double w = acc[ra][cb][r];
-                            const bool in = colin && col != qr[ra][r];
-                            if (in && part_key(w, a.by) > thr[rl]) {
-                                if (pass == 0) {
-                                    atomicAdd(&add[rl], 1);
-                                } else {
-                                    const int pos = atomicAdd(&cnt[rl], 1);  // < cap
-                                    bval[(size_t)rl * a.cap + pos] = w;
-                                    bidx[(size_t)rl * a.cap + pos] = (uint16_t)(col - c0);
-                                }
-                            }
-                        }
-                }
-                if (pass == 0) {
-                    // a row that cannot take its survivors is compacted first: thr rises, and
-                    // K + 64 <= cap entries always fit afterwards
-                    __syncthreads();
-                    for (int rl = wave; rl < kIntTile; rl += kBlock / kWave) {
-                        if (cnt[rl] + add[rl] > a.cap)
-                            part_compact(bval + (size_t)rl * a.cap, bidx + (size_t)rl * a.cap,
-                                         cnt + rl, thr + rl, a.K, a.by);
-                        __builtin_amdgcn_wave_barrier();
-                        if (lane == 0) add[rl] = 0;
-                    }
-                    __syncthreads();
-                }
-            }
-            // (the next tile reads thr / cnt / add behind the barriers of its staging step)
+            // admissible: in the candidate range and off the diagonal
+            sel_tile(s, a.sel.K, tj * kIntTile - c0,
+                     [&](int ra, int cb, int r, double& w) {
+                         const int col = tj * kIntTile + wc * 32 + cb * 16 + l15;
+                         w = acc[ra][cb][r];
+                         return col >= a.r_lo && col < a.r_hi && col != qr[ra][r];
+                     },
+                     key);
         }
     }
-    if constexpr (MODE == PART_SELECT) {
-        __syncthreads();
-        for (int rl = wave; rl < kIntTile; rl += kBlock / kWave) {
-            const int row = ti * kIntTile + rl;
-            if (row >= a.nrow) continue;  // wave-uniform
-            part_compact(bval + (size_t)rl * a.cap, bidx + (size_t)rl * a.cap, cnt + rl, thr + rl,
-                         a.K, a.by);
-            const int n = cnt[rl];
-            const size_t o = ((size_t)strip * a.rows_pad + row) * a.K;
-            for (int q = lane; q < a.K; q += kWave) {
-                a.lval[o + q] = q < n ? bval[(size_t)rl * a.cap + q] : 0.0;
-                a.lidx[o + q] = q < n ? c0 + (int)bidx[(size_t)rl * a.cap + q] : INT32_MAX;
-            }
-        }
-    }
+    if constexpr (MODE == PART_SELECT)
+        sel_write(s, a.sel, strip, ti * kIntTile, a.nrow, a.rows_pad, c0, 0.0, key);
 }
 
 // rows [0, nrow) of a degree slab: the records of the Tc tiles -> the row's answer at compact
@@ -338,44 +217,9 @@ static __global__ __launch_bounds__(kBlock) void part_reduce_kernel(
 
 // one wave per query row of the slab
 static __global__ __launch_bounds__(kBlock) void part_merge_kernel(PartArgs a) {
-    const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (row >= a.nrow) return;  // wave-uniform
-    const int K = a.K, N = a.n_strips * K;
-    const size_t sstride = (size_t)a.rows_pad * K;
-    const double* lv = a.lval + (size_t)row * K;
-    const int32_t* li = a.lidx + (size_t)row * K;
-    int found = 0;
-    for (int e = lane; e < N; e += kWave) {
-        const int i = e / K, q = e - i * K;
-        const double w = lv[i * sstride + q];
-        const int32_t c = li[i * sstride + q];
-        if (c == INT32_MAX) continue;  // padding of a short list
-        ++found;
-        const double v = part_key(w, a.by);
-        int rank = q;
-        for (int j = 0; j < a.n_strips; ++j) {
-            if (j == i) continue;
-            const double* jv = lv + j * sstride;
-            const int32_t* jc = li + j * sstride;
-            int lo = 0, hi = K;  // first entry of list j that does not beat (v, c)
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (rank_beats(part_key(jv[mid], a.by), (unsigned)jc[mid], v, (unsigned)c))
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
-            rank += lo;
-        }
-        if (rank < K) {
-            a.oval[(size_t)row * K + rank] = w;
-            a.oidx[(size_t)row * K + rank] = a.ids[c];
-        }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) found += __shfl_xor(found, m, kWave);
-    if (lane == 0) a.ocnt[row] = found < K ? found : K;
+    sel_merge(a.sel, a.n_strips, a.nrow, a.rows_pad,
+              [by = a.by](double w) { return part_key(w, by); },
+              [ids = a.ids](int32_t c) { return ids[c]; }, a.ocnt);
 }
 
 }  // namespace spfm

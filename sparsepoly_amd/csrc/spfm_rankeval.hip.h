@@ -4,8 +4,8 @@
 // Per context row b a list of targets T_b and a list of excluded candidates E_b (CSR patterns,
 // ascending, disjoint).  rank[b, t] = the number of candidates c outside E_b, c != t, whose
 // (score, id) beats (score[b, t], t) under rank_beats.  Two kernels, both consumers of the 64 x 64
-// score tiles of rank_tile_kernel (spfm_rank.hip.h): the same int_stage_chunk / int_mfma_chunk
-// chain and the same closing + (rowconst + colconst), hence the same bits for every pair.
+// score tiles of rank_tile_kernel (spfm_rank.hip.h): the same int_tile_product and the same
+// closing + (rowconst + colconst), hence the same bits for every pair.
 //
 // 1. rank_tscore_kernel: one workgroup per (row tile, candidate tile) pair that holds a target
 //    (a work list the host makes from the patterns).  Wave 0, lane = row, finds by binary search
@@ -22,7 +22,7 @@
 //    lands one past its own position.  At the end of the strip a wave per row forms the inclusive
 //    prefix sums of the buckets, the per-target counts of the strip, and adds them into the
 //    call's int32 array with integer atomics (they commute: no result depends on the strips).
-//    The exclusion masks are those of rank_tile_kernel<RANK_SELECT, true>.
+//    The exclusion masks are RankExcl's (spfm_rank.hip.h).
 //    A target whose score is not finite is sorted as -inf and gets rank -1 on the host; a
 //    candidate whose score is not finite is never counted.
 // No float atomics, no waiting between workgroups.
@@ -46,7 +46,7 @@ struct RankEvalArgs {
 
 // dynamic LDS of rank_count_kernel
 static inline size_t rank_count_lds_bytes(int tcap) {
-    return sizeof(double) * 2 * kIntTile * kIntLd +
+    return int_stage_lds_bytes() +
            (size_t)kIntTile * tcap * (sizeof(double) + sizeof(int32_t) + sizeof(uint8_t)) +
            (size_t)kIntTile * (tcap + 1) * sizeof(int) +
            kIntTile * (sizeof(unsigned long long) + sizeof(int));
@@ -84,14 +84,8 @@ static __global__ __launch_bounds__(kBlock) void rank_tscore_kernel(RankEvalArgs
             rcv[ra][r] = a.rc[(size_t)ti * kIntTile + wr * 32 + ra * 16 + l4 + 4 * r];
 
     int_v4d acc[2][2];
-    int_acc_zero(acc);
-    const double* Ug = a.U + (size_t)ti * kIntTile * a.Rp;
-    const double* Vg = a.V + (size_t)tj * kIntTile * a.Rp;
-    for (int kc0 = 0; kc0 < a.Rp; kc0 += kIntKC) {
-        const int kend = (a.Rp - kc0 < kIntKC) ? a.Rp - kc0 : kIntKC;  // multiple of 4
-        int_stage_chunk(Ug, Vg, a.Rp, kc0, kend, sA, sB);
-        int_mfma_chunk<false>(sA, sB, kend, nullptr, acc);
-    }
+    int_tile_product(a.U + (size_t)ti * kIntTile * a.Rp, a.V + (size_t)tj * kIntTile * a.Rp, a.Rp,
+                     sA, sB, acc);
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
         const int bit = wc * 32 + cb * 16 + l15;
@@ -118,8 +112,8 @@ __global__ __launch_bounds__(kBlock) void rank_count_kernel(RankEvalArgs e) {
     double* sA = rank_count_lds;
     double* sB = sA + kIntTile * kIntLd;
     double* tv = sB + kIntTile * kIntLd;                                         // [64][tcap]
-    unsigned long long* emask = reinterpret_cast<unsigned long long*>(tv + (size_t)kIntTile * tcap);
-    int32_t* tc = reinterpret_cast<int32_t*>(emask + kIntTile);                  // [64][tcap]
+    [[maybe_unused]] RankExcl ex{reinterpret_cast<unsigned long long*>(tv + (size_t)kIntTile * tcap)};
+    int32_t* tc = reinterpret_cast<int32_t*>(ex.mask + kIntTile);                // [64][tcap]
     int* hist = tc + (size_t)kIntTile * tcap;                                    // [64][tcap + 1]
     int* ntg = hist + (size_t)kIntTile * hld;                                    // [64]
     uint8_t* perm = reinterpret_cast<uint8_t*>(ntg + kIntTile);                  // [64][tcap]
@@ -179,37 +173,15 @@ __global__ __launch_bounds__(kBlock) void rank_count_kernel(RankEvalArgs e) {
             wkc[ra][r] = n ? (unsigned)tc[rl * tcap + n - 1] : 0u;
         }
 
-    [[maybe_unused]] int64_t ecur = 0, eend = 0;  // EXCL, wave 0: the row's cursor into eidx
-    if constexpr (EXCL) {
-        if (wave == 0 && ti * kIntTile + lane < a.nrow) {
-            const int64_t row = a.row0 + ti * kIntTile + lane;
-            eend = a.eptr[row + 1];
-            ecur = rank_lower_bound(a.eidx, a.eptr[row], eend, t0 * kIntTile);
-        }
-    }
+    if constexpr (EXCL) ex.open(a, ti, t0 * kIntTile);
 
     const double* Ug = a.U + (size_t)ti * kIntTile * a.Rp;
     for (int tj = t0; tj < t1; ++tj) {
-        if constexpr (EXCL) {
-            __syncthreads();  // the last tile's masks have been read
-            if (wave == 0) emask[lane] = rank_mask_step(a.eidx, ecur, eend, tj * kIntTile);
-            // (published by the barriers of the staging step)
-        }
+        if constexpr (EXCL) ex.tile(a, tj);
         int_v4d acc[2][2];
-        int_acc_zero(acc);
-        const double* Vg = a.V + (size_t)tj * kIntTile * a.Rp;
-        for (int kc0 = 0; kc0 < a.Rp; kc0 += kIntKC) {
-            const int kend = (a.Rp - kc0 < kIntKC) ? a.Rp - kc0 : kIntKC;  // multiple of 4
-            int_stage_chunk(Ug, Vg, a.Rp, kc0, kend, sA, sB);
-            int_mfma_chunk<false>(sA, sB, kend, nullptr, acc);
-        }
+        int_tile_product(Ug, a.V + (size_t)tj * kIntTile * a.Rp, a.Rp, sA, sB, acc);
         [[maybe_unused]] unsigned long long em[2][4];
-        if constexpr (EXCL) {
-#pragma unroll
-            for (int ra = 0; ra < 2; ++ra)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) em[ra][r] = emask[wr * 32 + ra * 16 + l4 + 4 * r];
-        }
+        if constexpr (EXCL) ex.rows(em);
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
             const int bit = wc * 32 + cb * 16 + l15;

@@ -49,10 +49,10 @@ def _lists():
     return T, E
 
 
-def _csr(rows):
+def _csr(rows, n_cand=C):
     r = np.array([b for b, cs in enumerate(rows) for _ in cs], dtype=np.int64)
     c = np.array([x for cs in rows for x in cs], dtype=np.int64)
-    return sp.coo_matrix((np.ones(len(r)), (r, c)), shape=(B, C)).tocsr()
+    return sp.coo_matrix((np.ones(len(r)), (r, c)), shape=(B, n_cand)).tocsr()
 
 
 def _beats(v, c, s, t):
@@ -180,6 +180,59 @@ def test_top_k_with_exclusions(case, part):
     assert (idx[3, :64] >= 0).all() and (idx[3, 64:] == -1).all() and np.isnan(val[3, 64:]).all()
     assert sorted(idx[3, :64]) == c.T[3]
     c.r._engine.rank_set_partition(0, 0)
+
+
+STRESS_C, STRESS_CTX = 400, 8  # candidates (seven tiles, the last partial); context columns
+STRESS_KEPT = (0, 63, 64, 255, 399)  # all that row 5 keeps
+
+
+@pytest.fixture(scope="module", params=["ascending", "descending"])
+def stress(request):
+    """Scores that are exact small integers and strictly monotone in the candidate id for every
+    row: candidate c has the one entry 1 in a column of its own and the linear term carries
+    +-(c + 1); P is zero on the candidate columns, so the product adds exact zeros.  Ascending,
+    every candidate beats all before it: every one survives and every tile past the buffer's
+    capacity forces a compaction.  Descending, nothing survives the first compaction."""
+    rng = np.random.RandomState(7)
+    up = request.param == "ascending"
+    est = fm(2, 1, STRESS_CTX + STRESS_C, None, True, seed=5)
+    est.P_[:] = 0.0
+    est.P_[0, 0, :STRESS_CTX] = rng.randint(-1, 2, size=STRESS_CTX)
+    est.w_[:STRESS_CTX] = rng.randint(-3, 4, size=STRESS_CTX)
+    est.w_[STRESS_CTX:] = (1.0 if up else -1.0) * np.arange(1, STRESS_C + 1)
+    X = sp.csr_matrix(np.hstack([rng.randint(-2, 3, size=(B, STRESS_CTX)).astype(np.float64),
+                                 np.zeros((B, STRESS_C))]))
+    Z = sp.csr_matrix(np.hstack([np.zeros((STRESS_C, STRESS_CTX)), np.eye(STRESS_C)]))
+    # (a) every row leaves out about one candidate in seven, (b) some rows their entire
+    # unexcluded top 130 as well, (c) row 5 all but five candidates
+    top = range(STRESS_C - 130, STRESS_C) if up else range(130)
+    E = [[c for c in range(STRESS_C) if (c + b) % 7 == 0] for b in range(B)]
+    for b in (2, 33, 64, 69):
+        E[b] = sorted(set(E[b]) | set(top))
+    E[5] = [c for c in range(STRESS_C) if c not in STRESS_KEPT]
+    with est.ranker(Z) as r:
+        D = r.scores(X)
+        assert D.shape == (B, STRESS_C) and (D == np.rint(D)).all() and np.abs(D).max() < 2 ** 20
+        assert ((np.diff(D, axis=1) > 0) if up else (np.diff(D, axis=1) < 0)).all()
+        yield types.SimpleNamespace(r=r, X=X, D=D, E=E, Em=_csr(E, STRESS_C))
+
+
+@pytest.mark.parametrize("excluded", [False, True])
+def test_selection_stress(stress, excluded):
+    """The ranker's entry to the shared selection under forced compactions, with and without the
+    exclusion masks; K = 128 fills the buffer to its capacity K + 64.  Default partition (one
+    strip of seven tiles) and cand_strip = 128 (four lists to merge)."""
+    s = stress
+    E = s.E if excluded else [[] for _ in range(B)]
+    for strip in (0, 128):
+        s.r._engine.rank_set_partition(0, strip)
+        for K in (1, 10, 128):
+            got = s.r.top_k(s.X, K, exclude=s.Em) if excluded else s.r.top_k(s.X, K)
+            _same_lists(got, numpy_topk(s.D, E, K))
+            if excluded and K >= 10:  # the short list: five entries, then -1 / NaN
+                assert sorted(got[0][5, :5]) == list(STRESS_KEPT) and (got[0][5, 5:] == -1).all()
+                assert np.isnan(got[1][5, 5:]).all()
+    s.r._engine.rank_set_partition(0, 0)
 
 
 def test_evaluate_and_rank_metrics(case):
