@@ -858,6 +858,72 @@ int spfm_explain_topk_csr(spfm_handle h, int64_t n, const int64_t* indptr, const
 int spfm_explain_set_partition(spfm_handle h, int64_t slab_nnz);
 int spfm_explain_info(spfm_handle h, int64_t* out4);
 
+/* -- per-row pair attributions ----------------------------------------------------------------
+ * Which pairs of a row's features produced its score.  The model, the blocks, the coefficient
+ * table and the CSR input are those of the block above.  Against the baseline x = 0 a monomial of
+ * one entry stays with that entry (its main effect), a monomial of t >= 2 entries is split
+ * equally among its t (t - 1) / 2 pairs: the Shapley-Taylor interaction index of order 2.  With
+ * z_sj = p_sj x_ij, the stored entries a < b (positions in the row) of row i get
+ *   main_ia = w_a x_ia + sum_q sum_s lams_s coef[q][s][1] z_sa
+ *   phi_iab = sum_q sum_s lams_s z_sa z_sb sum_{t=2..M} coef[q][s][t] 2 / (t (t - 1)) h_{t-2}
+ * with g_0 = h_0 = 1, g_t = A^t(p_s, x_i) - z_sa g_{t-1}, h_t = g_t - z_sb h_{t-1}: h_t is A^t of
+ * the row without the entries a and b.  Exact, not sampled:
+ *   sum_a main_ia + sum_{a<b} phi_iab = f(x_i) - f(0),
+ *   phi_ia of spfm_explain_csr = main_ia + 1/2 sum_{b != a} phi_iab,
+ * and for a plain block of degree 2 phi_iab = x_ia x_ib W[a][b].  Mode SPFM_PAIRS_HESSIAN gives
+ *   d2f / dx_ia dx_ib = sum_q sum_s lams_s p_sa p_sb sum_{t=2..M} coef[q][s][t] h_{t-2}
+ * on the stored pairs, the pattern held fixed.
+ * The pairs of a row of n_i entries are numbered by (first position, second position): the pair
+ * of positions a < b is pair a n_i - a (a + 1) / 2 + b - a - 1 of its n_i (n_i - 1) / 2, and the
+ * rows follow one another.  Read-only and sliced like the block above: a slab holds at most
+ * slab_nnz stored entries (spfm_explain_set_partition) and at most 2 slab_nnz pairs (2^24 at the
+ * default), always at least one whole row; the pair values of one slab are device scratch, held
+ * and freed with the explain scratch.  spfm_explain_info reports these calls like the others.
+ *
+ * Deterministic: a pair's value is the sum over the blocks in the caller's order, each a sum over
+ * the components in index order formed by one lane; a table cell adds its pairs in ascending pair
+ * index in one lane; the selection compares integers.  No result bit depends on the slab size or
+ * the launch shape.
+ *
+ * spfm_explain_pairs_csr: mode SPFM_PAIRS_INTERACTION or SPFM_PAIRS_HESSIAN; out_pairs
+ *   (sum_i n_i (n_i - 1) / 2, in the order above; slab by slab, so after an error its contents
+ *   are unspecified) and out_main (nnz, in the order of data; NULL: not computed; interaction
+ *   mode only).  More than SPFM_PAIRS_MAX_BYTES of pair values -> SPFM_ERR_UNSUPPORTED.
+ * spfm_explain_pairs_topk_csr: per row its min(K, pairs) pairs ordered by |value| descending,
+ *   then pair index ascending, in col_a / col_b / val (n x K, row-major; the two members' columns,
+ *   col_a the one stored first; val with its sign); the remaining slots hold -1, -1 and 0.
+ *   Exact.  1 <= K <= SPFM_PAIRS_MAX_K.  The pair values stay on the device.
+ * spfm_explain_pairs_grouped_csr: group (d ids in [0, G)) puts every column into a group.
+ *   out_pairs (n x G (G + 1) / 2, row-major): per row the upper triangle of a G x G table, cell
+ *   (g, h), g <= h, at g G - g (g - 1) / 2 + h - g, the sum of phi over the pairs with one member
+ *   in g and the other in h (the diagonal: both in g); out_main (n x G): main summed per group.
+ *   Interaction mode.  1 <= G <= SPFM_PAIRS_MAX_GROUPS.
+ * Errors: those of the block above; a mode other than the two, a group id outside [0, G), K < 1,
+ * G < 1, out_main with SPFM_PAIRS_HESSIAN -> SPFM_ERR_INVALID; K or G above its cap, a listing
+ * above SPFM_PAIRS_MAX_BYTES, a row of more than 65536 stored entries (its pair index would not
+ * fit the selection key) -> SPFM_ERR_UNSUPPORTED, never an approximate answer.  Every check
+ * precedes the first write to an output; n = 0 is valid and writes nothing. */
+#define SPFM_PAIRS_MAX_K 64
+#define SPFM_PAIRS_MAX_GROUPS 32
+#define SPFM_PAIRS_MAX_BYTES (1ll << 30) /* of listed pair values per call */
+#define SPFM_PAIRS_INTERACTION 0
+#define SPFM_PAIRS_HESSIAN 1
+int spfm_explain_pairs_csr(spfm_handle h, int64_t n, const int64_t* indptr, const int32_t* indices,
+                           const double* data, int n_blocks, const int32_t* order_idx,
+                           const int32_t* degree, const double* coef /* n_blocks x k x 7 */,
+                           int fit_linear, int mode, double* out_pairs, double* out_main);
+int spfm_explain_pairs_topk_csr(spfm_handle h, int64_t n, const int64_t* indptr,
+                                const int32_t* indices, const double* data, int n_blocks,
+                                const int32_t* order_idx, const int32_t* degree,
+                                const double* coef /* n_blocks x k x 7 */, int fit_linear,
+                                int mode, int K, int32_t* col_a, int32_t* col_b, double* val);
+int spfm_explain_pairs_grouped_csr(spfm_handle h, int64_t n, const int64_t* indptr,
+                                   const int32_t* indices, const double* data, int n_blocks,
+                                   const int32_t* order_idx, const int32_t* degree,
+                                   const double* coef /* n_blocks x k x 7 */, int fit_linear,
+                                   int G, const int32_t* group, double* out_pairs,
+                                   double* out_main);
+
 /* ---- model banks: F fitted models scored in one pass over the rows of X.
  * A bank is F models of one kind -- all of degree 2..SPFM_MAX_DEGREE or all all-subsets (-1),
  * the same blocks, the same use of a linear term, the same d columns -- that may differ in their

@@ -107,6 +107,7 @@ SYMBOLS = [
     "spfm_rank_topk_excl", "spfm_rank_eval",
     "spfm_explain_csr", "spfm_explain_topk_csr", "spfm_explain_set_partition",
     "spfm_explain_info",
+    "spfm_explain_pairs_csr", "spfm_explain_pairs_topk_csr", "spfm_explain_pairs_grouped_csr",
     "spfm_bank_set", "spfm_bank_scores", "spfm_bank_argmax", "spfm_bank_losses", "spfm_bank_mean",
     "spfm_bank_set_partition", "spfm_bank_info", "spfm_bank_release",
 ]
@@ -119,6 +120,10 @@ RANK_SCORES_MAX_BYTES = 1 << 30  # SPFM_RANK_SCORES_MAX_BYTES
 RANK_MAX_TARGETS = 64  # SPFM_RANK_MAX_TARGETS
 EXPLAIN_MAX_K = 64  # SPFM_EXPLAIN_MAX_K
 EXPLAIN_MODES = {"attribution": 0, "gradient": 1}  # SPFM_EXPLAIN_ATTRIBUTION / _GRADIENT
+PAIRS_MAX_K = 64  # SPFM_PAIRS_MAX_K
+PAIRS_MAX_GROUPS = 32  # SPFM_PAIRS_MAX_GROUPS
+PAIRS_MAX_BYTES = 1 << 30  # SPFM_PAIRS_MAX_BYTES
+PAIRS_MODES = {"interaction": 0, "hessian": 1}  # SPFM_PAIRS_INTERACTION / _HESSIAN
 BANK_MAX_MODELS = 64  # SPFM_BANK_MAX_MODELS
 BANK_MAX_COMPONENTS = 4096  # SPFM_BANK_MAX_COMPONENTS (stacked)
 
@@ -232,6 +237,9 @@ def load():
     L.spfm_explain_topk_csr.argtypes = _explain + [C.c_int, _ip, _dp]
     L.spfm_explain_set_partition.argtypes = [_h, C.c_int64]
     L.spfm_explain_info.argtypes = [_h, _lp]
+    L.spfm_explain_pairs_csr.argtypes = _explain + [C.c_int, _dp, _dp]
+    L.spfm_explain_pairs_topk_csr.argtypes = _explain + [C.c_int, C.c_int, _ip, _ip, _dp]
+    L.spfm_explain_pairs_grouped_csr.argtypes = _explain + [C.c_int, _ip, _dp, _dp]
     L.spfm_bank_set.argtypes = [_h, C.c_int32, C.c_int, _ip, C.c_int, _ip, _dp, _dp, _dp]
     _bank = [_h, C.c_int64, C.c_int32, _lp, _ip, _dp]
     L.spfm_bank_scores.argtypes = _bank + [_dp]

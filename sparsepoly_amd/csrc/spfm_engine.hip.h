@@ -4,8 +4,8 @@
 // cd_linear and the epoch drivers; prb: persistent 64-column passes, one translation unit per
 // storage type; wide: wide persistent passes; pbcd: multi-kernel pbcd; pbprb: persistent pbcd
 // pass, one unit per storage type; psgd; gram, objective, interactions (pairs and triples), rank,
-// explain, bank: the read-only feature units).  Every unit owns the extern "C" block of its entries.  See DESIGN.md
-// for the execution model.
+// explain, pairs, bank: the read-only feature units).  Every unit owns the extern "C" block of
+// its entries.  See DESIGN.md for the execution model.
 #pragma once
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -1152,12 +1152,14 @@ struct spfm_engine {
     DevBuf ex_out, ex_rs;         // its values and row sums
     DevBuf ex_coef;               // the blocks' coefficient tables (n_blocks x k x 7)
     DevBuf ex_ti, ex_tv;          // its top-K lists
+    static constexpr int64_t kExplainSlabMax = 1ll << 23;  // entries per slab: default and largest
     int64_t ex_slab_nnz = 0;      // spfm_explain_set_partition: stored entries per slab (0 = default)
     int64_t ex_slabs = 0;         // spfm_explain_info: slabs of the last call ...
     int ex_device_us = 0;         // ... and its kernels' device time
     size_t explain_scratch_bytes() const {
         return ex_rp.bytes + ex_ri.bytes + ex_rv.bytes + ex_out.bytes + ex_rs.bytes +
-               ex_coef.bytes + ex_ti.bytes + ex_tv.bytes;
+               ex_coef.bytes + ex_ti.bytes + ex_tv.bytes + ex_pp.bytes + ex_pv.bytes +
+               ex_grp.bytes + ex_gp.bytes + ex_gm.bytes;
     }
     void explain_release();
     struct ExplainCall {  // the arguments of spfm_explain_csr / spfm_explain_topk_csr
@@ -1177,6 +1179,9 @@ struct spfm_engine {
         double* val;
     };
     int explain_check(const char* what, const ExplainCall& c);
+    // its two halves, shared with the pair entries: the parameters and blocks; the CSR rows
+    int explain_check_model(const char* what, const ExplainCall& c);
+    int explain_check_rows(const char* what, const ExplainCall& c);
     template <typename T, int M>
     void explain_launch_block(int64_t rows, int64_t e0, const double* Pt_o, const double* coef_o,
                               int mode);
@@ -1184,6 +1189,32 @@ struct spfm_engine {
     int explain_slab(const ExplainCall& c, int64_t r0, int64_t r1);
     template <typename T>
     int explain_run(const char* what, const ExplainCall& c);
+
+    // ------------------------------- per-row pair attributions (spfm_engine_pairs.hip)
+    // phi_iab (Shapley-Taylor index of order 2 against a zero baseline) or d2f/dx_ia dx_ib on the
+    // stored pairs of every row, main_ia, the per-row top-K pairs and group x group tables
+    // (DESIGN.md section 16a).  On the explain unit's slab image, coefficient upload, checks,
+    // timing and partition; a slab additionally holds at most 2 slab_nnz pairs (2^24 at the
+    // default).  Its scratch is counted and freed with the explain scratch.
+    DevBuf ex_pp, ex_pv;          // pair offsets of one slab (rows + 1) and its pair values
+    DevBuf ex_grp, ex_gp, ex_gm;  // group of every column (d); a slab's tables and grouped main
+    struct PairsCall {
+        ExplainCall m;  // rows and model; K / idx (first columns) / val of the top-K entry
+        int kind;       // 0: listing, 1: top-K, 2: grouped
+        int pmode;      // SPFM_PAIRS_INTERACTION / _HESSIAN
+        int G;
+        const int32_t* group;
+        double *out_pairs, *out_main;
+        int32_t* col_b;
+    };
+    int pairs_check(const char* what, const PairsCall& c);
+    template <typename T, int M>
+    void pairs_launch_block(int64_t rows, int64_t e0, const double* Pt_o, const double* coef_o,
+                            int mode);
+    template <typename T>
+    int pairs_slab(const PairsCall& c, int64_t r0, int64_t r1, int64_t q0, int64_t nq);
+    template <typename T>
+    int pairs_run(const char* what, const PairsCall& c);
 
     // ------------------------------- model banks (spfm_engine_bank.hip)
     // F fitted models stacked along the component axis, resident until spfm_bank_release, the next

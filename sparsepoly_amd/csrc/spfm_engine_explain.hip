@@ -21,16 +21,15 @@ namespace {
 // 256 MiB budget, the rows of a slab are capped by what is left.
 constexpr int64_t kExplainBudget = 256ll << 20;
 constexpr int64_t kExplainEntryBytes = 20;
-constexpr int64_t kExplainSlabMax = 1ll << 23;  // stored entries per slab: default and largest
 }  // namespace
 
 void spfm_engine::explain_release() {
-    for (DevBuf* b : {&ex_rp, &ex_ri, &ex_rv, &ex_out, &ex_rs, &ex_coef, &ex_ti, &ex_tv})
+    for (DevBuf* b : {&ex_rp, &ex_ri, &ex_rv, &ex_out, &ex_rs, &ex_coef, &ex_ti, &ex_tv, &ex_pp,
+                      &ex_pv, &ex_grp, &ex_gp, &ex_gm})
         b->release();
 }
 
-// every check of the two entries, before any device work and before any output is written
-int spfm_engine::explain_check(const char* what, const ExplainCall& c) {
+int spfm_engine::explain_check_model(const char* what, const ExplainCall& c) {
     const std::string w(what);
     if (!have_params) FAIL(SPFM_ERR_INVALID, w + ": no parameters set");
     if (c.n_blocks < 0 || (c.n_blocks > 0 && (!c.order_idx || !c.degree || !c.coef)))
@@ -41,6 +40,22 @@ int spfm_engine::explain_check(const char* what, const ExplainCall& c) {
         if (c.order_idx[q] < 0 || c.order_idx[q] >= n_orders)
             FAIL(SPFM_ERR_INVALID, w + ": order_idx outside the parameters");
     }
+    return SPFM_OK;
+}
+
+int spfm_engine::explain_check_rows(const char* what, const ExplainCall& c) {
+    const std::string w(what);
+    SPFM_TRY(rank_check_csr(what, c.n, c.indptr, c.indices, c.data));
+    for (int64_t i = 0; i < c.n; ++i)
+        if (c.indptr[i + 1] - c.indptr[i] > INT32_MAX)
+            FAIL(SPFM_ERR_UNSUPPORTED, w + ": a row with more than 2^31 - 1 stored entries");
+    return SPFM_OK;
+}
+
+// every check of the two entries, before any device work and before any output is written
+int spfm_engine::explain_check(const char* what, const ExplainCall& c) {
+    const std::string w(what);
+    SPFM_TRY(explain_check_model(what, c));
     if (c.mode != SPFM_EXPLAIN_ATTRIBUTION && c.mode != SPFM_EXPLAIN_GRADIENT)
         FAIL(SPFM_ERR_INVALID, w + ": mode must be SPFM_EXPLAIN_ATTRIBUTION or _GRADIENT");
     if (c.topk) {
@@ -52,10 +67,7 @@ int spfm_engine::explain_check(const char* what, const ExplainCall& c) {
             FAIL(SPFM_ERR_UNSUPPORTED, buf);
         }
     }
-    SPFM_TRY(rank_check_csr(what, c.n, c.indptr, c.indices, c.data));
-    for (int64_t i = 0; i < c.n; ++i)
-        if (c.indptr[i + 1] - c.indptr[i] > INT32_MAX)
-            FAIL(SPFM_ERR_UNSUPPORTED, w + ": a row with more than 2^31 - 1 stored entries");
+    SPFM_TRY(explain_check_rows(what, c));
     if (c.n > 0 && c.topk && (!c.idx || !c.val)) FAIL(SPFM_ERR_INVALID, w + ": NULL output");
     if (c.n > 0 && !c.topk && c.indptr[c.n] > 0 && !c.out_vals)
         FAIL(SPFM_ERR_INVALID, w + ": out_vals is NULL");
@@ -186,7 +198,7 @@ int spfm_explain_topk_csr(spfm_handle h, int64_t n, const int64_t* indptr, const
 
 int spfm_explain_set_partition(spfm_handle h, int64_t slab_nnz) {
     if (!h) return SPFM_ERR_INVALID;
-    if (slab_nnz < 0 || slab_nnz > kExplainSlabMax) {
+    if (slab_nnz < 0 || slab_nnz > spfm_engine::kExplainSlabMax) {
         h->err = "explain_set_partition: slab_nnz must be in [0, 2^23]";
         return SPFM_ERR_INVALID;
     }

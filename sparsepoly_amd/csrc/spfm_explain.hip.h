@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void explain_block_kernel(
 
 // rowsum[i] = sum_j out[i, j]: lane l adds the entries l, l + 64, ... in order, then the fixed
 // butterfly of wave_sum
-__global__ __launch_bounds__(kBlock) void explain_rowsum_kernel(
+static __global__ __launch_bounds__(kBlock) void explain_rowsum_kernel(
     int64_t rows, int64_t e0, const int64_t* __restrict__ rptr, const double* __restrict__ vals,
     double* __restrict__ rowsum) {
     const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
@@ -148,7 +148,7 @@ __device__ __forceinline__ void explain_take(ExplainKey& best, const ExplainKey&
 // hold column -1 and value 0.  One wave per row, one exact selection round per slot: every lane
 // finds the best of its entries (l, l + 64, ...) that come strictly after the previous winner,
 // a butterfly over the lanes picks the round's winner.  Integer comparisons only.
-__global__ __launch_bounds__(kBlock) void explain_topk_kernel(
+static __global__ __launch_bounds__(kBlock) void explain_topk_kernel(
     int64_t rows, int64_t e0, const int64_t* __restrict__ rptr, const int32_t* __restrict__ ridx,
     const double* __restrict__ vals, int K, int32_t* __restrict__ oidx,
     double* __restrict__ oval) {

@@ -755,6 +755,75 @@ class HipEngine(object):
         return dict(scratch_kib=int((out[0] + 1023) // 1024), device_ms=out[1] / 1e3,
                     slab_nnz=int(out[2]), slabs=int(out[3]))
 
+    # ------------------------- per-row pair attributions: values, top-K, group tables (spfm.h)
+    def explain_pairs(self, X, blocks, coef, fit_linear, mode="interaction", main=False):
+        """``spfm_explain_pairs_csr``: ``(pair_ptr, vals, main)`` for the canonical CSR form of
+        ``X``: ``pair_ptr`` (n + 1) the rows' offsets into ``vals``, row ``i`` owning
+        ``n_i (n_i - 1) / 2`` values in the order (first position, second position); per pair
+        ``phi_iab`` or, with ``mode='hessian'``, ``d2f / dx_ia dx_ib``; ``main`` per stored entry
+        (``None`` unless asked for; interaction mode only).  More than ``SPFM_PAIRS_MAX_BYTES`` of
+        values: ValueError."""
+        if mode not in _capi.PAIRS_MODES:
+            raise ValueError("explain_pairs: mode must be 'interaction' or 'hessian', got %r"
+                             % (mode,))
+        if main and mode != "interaction":
+            raise ValueError("explain_pairs: main belongs to mode='interaction'")
+        Xr, args, keep = self._explain_args(X, blocks, coef, fit_linear, "explain_pairs")
+        n_i = np.diff(Xr.indptr).astype(np.int64)
+        ptr = np.concatenate([[0], np.cumsum(n_i * (n_i - 1) // 2)]).astype(np.int64)
+        if 8 * int(ptr[-1]) > _capi.PAIRS_MAX_BYTES:
+            raise ValueError("explain_pairs: %d pairs to list, more than SPFM_PAIRS_MAX_BYTES = %d "
+                             "bytes of values" % (int(ptr[-1]), _capi.PAIRS_MAX_BYTES))
+        vals = np.zeros(int(ptr[-1]))
+        mn = np.zeros(Xr.nnz) if main else None
+        self._check(self._lib.spfm_explain_pairs_csr(
+            *args, _capi.PAIRS_MODES[mode], vals.ctypes.data_as(_capi._dp),
+            mn.ctypes.data_as(_capi._dp) if main else None))
+        return ptr, vals, mn
+
+    def explain_pairs_topk(self, X, blocks, coef, fit_linear, K, mode="interaction"):
+        """``spfm_explain_pairs_topk_csr``: ``(col_a, col_b, vals)`` of shape (n, K): per row its
+        pairs largest by magnitude, by ``|value|`` descending, then pair index ascending; rows with
+        fewer than K pairs are padded with -1, -1 and 0.  ``K`` above ``SPFM_PAIRS_MAX_K``:
+        ValueError."""
+        K = int(K)
+        if mode not in _capi.PAIRS_MODES:
+            raise ValueError("explain_pairs_topk: mode must be 'interaction' or 'hessian', got %r"
+                             % (mode,))
+        if K > _capi.PAIRS_MAX_K:
+            raise ValueError("explain_pairs_topk: K = %d exceeds SPFM_PAIRS_MAX_K = %d (never "
+                             "answered approximately)" % (K, _capi.PAIRS_MAX_K))
+        Xr, args, keep = self._explain_args(X, blocks, coef, fit_linear, "explain_pairs_topk")
+        ca = np.full((Xr.shape[0], max(K, 1)), -1, dtype=np.int32)
+        cb = np.full((Xr.shape[0], max(K, 1)), -1, dtype=np.int32)
+        val = np.zeros((Xr.shape[0], max(K, 1)))
+        self._check(self._lib.spfm_explain_pairs_topk_csr(
+            *args, _capi.PAIRS_MODES[mode], K, ca.ctypes.data_as(_capi._ip),
+            cb.ctypes.data_as(_capi._ip), val.ctypes.data_as(_capi._dp)))
+        return ca, cb, val
+
+    def explain_pairs_grouped(self, X, blocks, coef, fit_linear, G, group):
+        """``spfm_explain_pairs_grouped_csr``: ``(cells, main)``: (n, G (G + 1) / 2) the upper
+        triangles of the rows' group x group tables, cell ``(g, h)``, ``g <= h``, at
+        ``g G - g (g - 1) / 2 + h - g``, and (n, G) the main effects summed per group.  ``group``:
+        int ids in ``[0, G)``, one per feature.  ``G`` above ``SPFM_PAIRS_MAX_GROUPS``:
+        ValueError."""
+        G = int(G)
+        if G > _capi.PAIRS_MAX_GROUPS:
+            raise ValueError("explain_pairs_grouped: G = %d exceeds SPFM_PAIRS_MAX_GROUPS = %d"
+                             % (G, _capi.PAIRS_MAX_GROUPS))
+        Xr, args, keep = self._explain_args(X, blocks, coef, fit_linear, "explain_pairs_grouped")
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        if group.shape != (self.d,):
+            raise ValueError("explain_pairs_grouped: group must hold one id per feature (%d), got "
+                             "shape %r" % (self.d, group.shape))
+        ga, gp = _capi.i32(group)
+        cells = np.zeros((Xr.shape[0], max(G, 1) * (max(G, 1) + 1) // 2))
+        mn = np.zeros((Xr.shape[0], max(G, 1)))
+        self._check(self._lib.spfm_explain_pairs_grouped_csr(
+            *args, G, gp, cells.ctypes.data_as(_capi._dp), mn.ctypes.data_as(_capi._dp)))
+        return cells, mn
+
     # ------------------------- model banks: F models scored in one pass over the rows (spfm.h)
     def bank_set(self, koff, degrees, Pt_bank, lams_bank, w_bank=None):
         """``spfm_bank_set``: make the stacked image resident.  ``Pt_bank`` (n_blocks, d, S),
