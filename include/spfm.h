@@ -982,6 +982,73 @@ int spfm_bank_set_partition(spfm_handle h, int64_t slab_nnz);
 int spfm_bank_info(spfm_handle h, int64_t* out4);
 int spfm_bank_release(spfm_handle h);
 
+/* -- fold-in of new columns -------------------------------------------------------------------
+ * Estimate the parameters of single columns (a new user, a new item, a column that collected new
+ * rows) with every other parameter fixed.  The model, the blocks and the coefficient table are
+ * those of spfm_explain_csr; here coef[q][s][0] is read too.  The ANOVA kernel is multilinear, so
+ * for a row i that stores the target column j, with x_i\j the row without that one entry,
+ *   f(x_i)  = c_i + z_i . theta_j
+ *   c_i     = offset + [w . x_i\j] + sum_q sum_s lams_s sum_{t=0..M_q} coef[q][s][t] A^t(p_s, x_i\j)
+ *   theta_j = ( w_j if fit_linear ; P[order_idx[q]][s][j], q = 0..n_blocks-1, s = 0..k-1 )
+ *   z_i     = x_ij ( 1 if fit_linear ; lams_s sum_{t=1..M_q} coef[q][s][t] A^{t-1}(p_s, x_i\j) )
+ * with R = n_blocks k (+ 1) unknowns, and the fold-in of column j is the unique minimiser of
+ *   F_j(theta) = sum_{i: x_ij stored} loss(c_i + z_i . theta, y_i)
+ *                + alpha/2 theta_w^2 + beta/2 |theta_P|^2,
+ * loss one of SPFM_LOSS_* exactly as the training engines evaluate it (the logistic loss with its
+ * branches at |y f| = 18).  alpha and beta stand against the SUM of the loss over the column's
+ * rows.  offset is a constant of the model that the caller owns (the linear weights of columns
+ * that are 1 in every row).  The A^t(x_i\j) are formed by a pass over the row that skips the
+ * target entry -- no downdate, hence no cancellation -- so no result bit depends on the values
+ * that column j holds in the handle's parameters.  Several target columns are independent when
+ * no row stores two of them; that is required, never worked around by alternating.
+ * The solver is a damped Newton iteration from theta = 0: g = Z^T l' + Lambda theta,
+ * H = Z^T diag(l'') Z + Lambda (l'' the derivative of the active branch of l': 1; 2 [1 - y f > 0];
+ * the three logistic branches), a Cholesky factorisation of H, an Armijo backtracking line search
+ * (sufficient decrease 1e-4, halving, at most 40 halvings).  It stops when
+ * max|grad F_j(theta)| <= tol max|grad F_j(0)| (converged = 1), at max_iter, or when the line
+ * search stalls (converged = 0 unless the criterion holds).  Squared loss ends after one step.
+ * Parameters only (spfm_set_params; no data, no spfm_configure), read-only as spfm_explain_csr:
+ * the handle's parameters are not changed, writing theta back is the caller's business.  Values
+ * are read in the handle's precision, all arithmetic is f64.  The target columns go through in
+ * groups of whole columns, in the caller's order, whose design matrix (rows x R padded to 4, f64)
+ * fits 256 MiB; the scratch stays allocated until spfm_set_params or spfm_destroy.
+ *
+ * Deterministic: a design entry is formed by one lane walking its row in stored order; c_i adds
+ * the linear term, then the blocks in the caller's order, each a fixed butterfly over 64
+ * components and the chunks of 64 in order; every sum over a column's rows (g, H, F) is formed by
+ * one thread per entry that walks the rows in ascending row order, and the factorisation is a
+ * fixed sequence.  A column's bits depend on its own rows alone: not on the other target columns,
+ * the group size or the launch shape.
+ *
+ * spfm_foldin_csr: cols (n_cols distinct columns in [0, d)); theta (n_cols x R, row-major),
+ *   n_rows, n_iter, converged, grad_norm (max|grad F_j| at the returned theta), obj0 = F_j(0),
+ *   obj1 = F_j(theta) (n_cols each).  Rows that store no target column are ignored (and counted,
+ *   spfm_foldin_info); a target column without rows gets theta = 0, n_iter = 0, converged = 1.
+ *   Results are written group by group, so after a runtime error their contents are unspecified.
+ * spfm_foldin_set_partition: rows per group of the following calls (0 = what fits the scratch).
+ *   A group always holds at least one whole column.  No result bit depends on it: it exists so
+ *   that a small problem can be made to run as many groups.
+ * spfm_foldin_info: out5 = {device scratch held in bytes, device time in microseconds (HIP events)
+ *   of the kernels of the last spfm_foldin_csr call without its copies, max_rows as set, groups of
+ *   the last call, rows it ignored}.
+ * Errors: those of spfm_explain_csr for the model and the rows; n_blocks < 1, NULL y / cols /
+ * outputs, a row that stores two target columns (the message names the row), a duplicate or
+ * out-of-range target column, beta <= 0, alpha <= 0 with fit_linear, max_iter < 1, tol negative
+ * or not finite, an unknown loss, max_rows < 0 -> SPFM_ERR_INVALID; R above
+ * SPFM_FOLDIN_MAX_UNKNOWNS, a single column whose design matrix exceeds the scratch
+ * -> SPFM_ERR_UNSUPPORTED, never an approximate answer.  Every check precedes the first write to
+ * an output; n = 0 is valid and writes the zero-row results. */
+#define SPFM_FOLDIN_MAX_UNKNOWNS 128
+int spfm_foldin_csr(spfm_handle h, int64_t n, const int64_t* indptr, const int32_t* indices,
+                    const double* data, const double* y, int n_blocks, const int32_t* order_idx,
+                    const int32_t* degree, const double* coef /* n_blocks x k x 7 */,
+                    int fit_linear, double offset, int loss, int64_t n_cols, const int32_t* cols,
+                    double alpha, double beta, int max_iter, double tol, double* theta,
+                    int64_t* n_rows, int32_t* n_iter, int32_t* converged, double* grad_norm,
+                    double* obj0, double* obj1);
+int spfm_foldin_set_partition(spfm_handle h, int64_t max_rows);
+int spfm_foldin_info(spfm_handle h, int64_t* out5);
+
 #ifdef __cplusplus
 }
 #endif

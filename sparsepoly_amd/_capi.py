@@ -110,6 +110,7 @@ SYMBOLS = [
     "spfm_explain_pairs_csr", "spfm_explain_pairs_topk_csr", "spfm_explain_pairs_grouped_csr",
     "spfm_bank_set", "spfm_bank_scores", "spfm_bank_argmax", "spfm_bank_losses", "spfm_bank_mean",
     "spfm_bank_set_partition", "spfm_bank_info", "spfm_bank_release",
+    "spfm_foldin_csr", "spfm_foldin_set_partition", "spfm_foldin_info",
 ]
 INTERACTION_BLOCK_MAX_BYTES = 1 << 30  # SPFM_INTERACTION_BLOCK_MAX_BYTES
 INTERACTION3_MAX_ACTIVE = 1 << 15  # SPFM_INTERACTION3_MAX_ACTIVE
@@ -126,6 +127,7 @@ PAIRS_MAX_BYTES = 1 << 30  # SPFM_PAIRS_MAX_BYTES
 PAIRS_MODES = {"interaction": 0, "hessian": 1}  # SPFM_PAIRS_INTERACTION / _HESSIAN
 BANK_MAX_MODELS = 64  # SPFM_BANK_MAX_MODELS
 BANK_MAX_COMPONENTS = 4096  # SPFM_BANK_MAX_COMPONENTS (stacked)
+FOLDIN_MAX_UNKNOWNS = 128  # SPFM_FOLDIN_MAX_UNKNOWNS
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -249,6 +251,12 @@ def load():
     L.spfm_bank_set_partition.argtypes = [_h, C.c_int64]
     L.spfm_bank_info.argtypes = [_h, _lp]
     L.spfm_bank_release.argtypes = [_h]
+    L.spfm_foldin_csr.argtypes = [_h, C.c_int64, _lp, _ip, _dp, _dp, C.c_int, _ip, _ip, _dp,
+                                  C.c_int, C.c_double, C.c_int, C.c_int64, _ip, C.c_double,
+                                  C.c_double, C.c_int, C.c_double, _dp, _lp, _ip, _ip, _dp, _dp,
+                                  _dp]
+    L.spfm_foldin_set_partition.argtypes = [_h, C.c_int64]
+    L.spfm_foldin_info.argtypes = [_h, _lp]
     for name in SYMBOLS:
         f = getattr(L, name)
         if name not in ("spfm_destroy", "spfm_last_error", "spfm_build_tag"):

@@ -1260,6 +1260,58 @@ struct spfm_engine {
     template <typename T>
     int bank_run(const char* what, const BankCall& c);
 
+    // ------------------------------- fold-in of new columns (spfm_engine_foldin.hip)
+    // With every other column fixed the model output is affine in the parameters of one column j:
+    // f(x_i) = c_i + z_i . theta_j on the rows that store j.  Per target column a ridge-regularised
+    // GLM in R = n_blocks k (+ 1) unknowns, solved by a damped Newton iteration, one workgroup
+    // per column.  Read-only like explain; the target columns go through
+    // in groups whose design matrix fits the scratch, which is kept until spfm_set_params or
+    // spfm_destroy.
+    DevBuf fi_rp, fi_ri, fi_rv;   // CSR image of one group's rows (values in the handle's precision)
+    DevBuf fi_tp, fi_y;           // per row: position of the target entry in its row, target
+    DevBuf fi_Z, fi_c;            // per row: its design row (R padded to 4) and offset
+    DevBuf fi_cp;                 // per column of the group: first row (columns + 1)
+    DevBuf fi_coef;               // the blocks' coefficient tables (n_blocks x k x 7)
+    DevBuf fi_theta, fi_stat, fi_it;  // per column: theta (Rp), 3 doubles, 2 ints
+    static constexpr int64_t kFoldinBudget = 256ll << 20;  // bytes of Z in one group
+    int64_t fi_max_rows = 0;      // spfm_foldin_set_partition: rows per group (0 = the scratch)
+    int64_t fi_groups = 0, fi_ignored = 0;  // spfm_foldin_info: of the last call ...
+    int fi_device_us = 0;         // ... and its kernels' device time
+    size_t foldin_scratch_bytes() const {
+        return fi_rp.bytes + fi_ri.bytes + fi_rv.bytes + fi_tp.bytes + fi_y.bytes + fi_Z.bytes +
+               fi_c.bytes + fi_cp.bytes + fi_coef.bytes + fi_theta.bytes + fi_stat.bytes +
+               fi_it.bytes;
+    }
+    void foldin_release();
+    struct FoldinCall {  // the arguments of spfm_foldin_csr
+        ExplainCall m;   // rows and model
+        const double* y;
+        double offset;
+        int loss;
+        int64_t n_cols;
+        const int32_t* cols;
+        double alpha, beta;
+        int max_iter;
+        double tol;
+        double* theta;
+        int64_t* n_rows;
+        int32_t *n_iter, *converged;
+        double *grad_norm, *obj0, *obj1;
+    };
+    struct FoldinPlan {  // what the checks leave behind: the participating rows per column
+        int R = 0, Rp = 0;
+        std::vector<int64_t> cptr;  // (n_cols + 1) into rows
+        std::vector<int64_t> rows;  // row ids, per column ascending
+        std::vector<int32_t> tpos;  // position of the target entry in its row
+    };
+    int foldin_check(const char* what, const FoldinCall& c, FoldinPlan& plan);
+    template <typename T, int M>
+    void foldin_launch_design(int64_t rows, int q, const FoldinCall& c, int Rp);
+    template <typename T>
+    int foldin_group(const FoldinCall& c, const FoldinPlan& plan, int64_t c0, int64_t c1);
+    template <typename T>
+    int foldin_run(const char* what, const FoldinCall& c);
+
     // diagnostics that need kernels of one translation unit
     int debug_stream_probe(int64_t* bytes_out);  // spfm_engine_pcd.hip
     int debug_write_probe(int bytes, int64_t* bytes_out);

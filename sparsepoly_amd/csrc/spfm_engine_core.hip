@@ -414,6 +414,7 @@ int spfm_engine::set_params(int n_orders_, int k_, int32_t d_, const double* P_,
     interaction_release();  // scratch of the interaction passes (sized by the old block)
     rank_release();         // candidate towers of the old parameters
     explain_release();      // slab scratch of the attribution entries
+    foldin_release();       // group scratch of the fold-in
     if (n_orders_ != n_orders || k_ != k) {
         configured = false;
         clear_graphs();

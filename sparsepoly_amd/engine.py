@@ -927,6 +927,52 @@ class HipEngine(object):
         self._check(self._lib.spfm_bank_release(self._h))
         self.bank_shape = None
 
+    # ------------------------- fold-in of new columns: per-column convex solves (spfm.h)
+    def foldin(self, X, y, blocks, coef, fit_linear, offset, loss, cols, alpha, beta, max_iter=50,
+               tol=1e-8):
+        """``spfm_foldin_csr``: the parameters of the target columns ``cols`` estimated from the
+        rows of ``X`` that store them, everything else fixed.  Returns a dict: ``theta``
+        (n_cols, R) with ``R = n_blocks k (+ 1)`` (the linear weight first, then the blocks in
+        the caller's order), ``n_rows``, ``n_iter``, ``converged``, ``grad_norm``, ``obj0``,
+        ``obj1`` per column.  ``blocks`` / ``coef`` as for ``explain``; ``offset``: a constant of
+        the model added to every row's output; ``loss`` a key of ``_capi.LOSSES``."""
+        if loss not in _capi.LOSSES:
+            raise ValueError("foldin: unknown loss %r" % (loss,))
+        Xr, args, keep = self._explain_args(X, blocks, coef, fit_linear, "foldin")
+        ya, yp = _capi.f64(y)
+        if ya.shape != (Xr.shape[0],):
+            raise ValueError("foldin: y must hold one target per row")
+        ca, cp = _capi.i32(cols)
+        m = ca.shape[0]
+        R = len(blocks) * self.k + int(bool(fit_linear))
+        theta = np.zeros((m, R))
+        n_rows = np.zeros(m, dtype=np.int64)
+        n_iter = np.zeros(m, dtype=np.int32)
+        conv = np.zeros(m, dtype=np.int32)
+        gn, o0, o1 = np.zeros(m), np.zeros(m), np.zeros(m)
+        dp, ip = _capi._dp, _capi._ip
+        self._check(self._lib.spfm_foldin_csr(
+            *args[:5], yp, *args[5:], float(offset), _capi.LOSSES[loss], m, cp, float(alpha),
+            float(beta), int(max_iter), float(tol), theta.ctypes.data_as(dp),
+            n_rows.ctypes.data_as(_capi._lp), n_iter.ctypes.data_as(ip), conv.ctypes.data_as(ip),
+            gn.ctypes.data_as(dp), o0.ctypes.data_as(dp), o1.ctypes.data_as(dp)))
+        return dict(theta=theta, n_rows=n_rows, n_iter=n_iter, converged=conv.astype(bool),
+                    grad_norm=gn, obj0=o0, obj1=o1)
+
+    def foldin_set_partition(self, max_rows=0):
+        """``spfm_foldin_set_partition``: rows per group of target columns of the following
+        fold-in calls (0: what fits the scratch).  No result bit depends on it."""
+        self._check(self._lib.spfm_foldin_set_partition(self._h, int(max_rows)))
+
+    def foldin_info(self):
+        """``spfm_foldin_info``: dict ``scratch_kib`` (device memory the fold-in holds),
+        ``device_ms`` (kernels of the last call), ``max_rows`` as set, ``groups`` and
+        ``ignored_rows`` of the last call."""
+        out = np.zeros(5, dtype=np.int64)
+        self._check(self._lib.spfm_foldin_info(self._h, out.ctypes.data_as(_capi._lp)))
+        return dict(scratch_kib=int((out[0] + 1023) // 1024), device_ms=out[1] / 1e3,
+                    max_rows=int(out[2]), groups=int(out[3]), ignored_rows=int(out[4]))
+
     # ------------------------- third-order weights T[a, j, l] = sum_s lams_s p_sa p_sj p_sl (spfm.h)
     def interaction3_stats(self, order_idx, tol=0.0, n_features=None):
         """``spfm_interaction3_stats``: dict ``nnz`` (triples a < j < l with ``|T| > tol``),

@@ -56,6 +56,7 @@ from .regularizer import REGULARIZATION
 from .interactions import InteractionMixin
 from .ranking import RankingMixin
 from .explain import ExplainMixin
+from .foldin import FoldInMixin
 from .monitor import ObjectiveMixin, callback_needs_params
 
 MAX_DEGREE = 6  # include/spfm.h SPFM_MAX_DEGREE
@@ -99,7 +100,7 @@ def _fingerprint(Xc, y):
 
 
 class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingMixin, ExplainMixin,
-                                      BaseSparsePoly, metaclass=ABCMeta):
+                                      FoldInMixin, BaseSparsePoly, metaclass=ABCMeta):
     _REGULARIZERS = REGULARIZATION
 
     @abstractmethod
