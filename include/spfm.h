@@ -253,6 +253,33 @@ int spfm_psgd_epoch_sharded(spfm_handle h, int degree, double alpha, double beta
                             const int32_t* indices_samples, int64_t n_global, int64_t row_lo,
                             int fit_linear, int64_t* it, double* sum_loss);
 
+/* Pairwise ranking fit: one pass of minibatch psgd over triples.  The
+ * handle's data is the stacked matrix [X; Z] (contexts, then candidates; the targets are not
+ * read).  Row k of `triples` (m, 3) is (anchor, plus, minus), three row indices into that matrix:
+ * context row `anchor` prefers candidate `plus` to candidate `minus`.  With
+ *   margin = f(x_anchor + z_plus) - f(x_anchor + z_minus)
+ * the loss of a triple is loss(margin, +1) with the configured loss ('logistic': BPR); the
+ * penalties, the step sizes, the prox, `it` and the options "psgd_eager", "psgd_graph_sweeps",
+ * "psgd_redone" are those of spfm_psgd_epoch.  The visiting order is the order of `triples` (the
+ * caller shuffles); minibatch bi covers the triples [bi * batch_size, ...), the last one may be
+ * shorter, and eta / B uses the triple count of the batch.  sum_loss: the sum of the per-triple
+ * losses at visiting time.  The linear weights of the anchors' columns receive no gradient (their
+ * term cancels in the margin); with alpha > 0 they only shrink.
+ * Requires spfm_configure(h, SPFM_SOLVER_PSGD, loss, reg, degree).  SPFM_ERR_INVALID, checked on
+ * the host before anything is launched (the parameters stay as they were): a row index outside
+ * [0, n), plus == minus, a column stored in an anchor row and in a plus / minus row, batch_size
+ * < 1, *it < 1, an unsupported learning_rate, a handle not configured for psgd.  A handle with a
+ * communicator: SPFM_ERR_UNSUPPORTED. */
+int spfm_psgd_pairs_epoch(spfm_handle h, int degree, double alpha, double beta, double gamma,
+                          double eta0, int learning_rate, double power_t, int64_t batch_size,
+                          const int32_t* triples /* (m,3): anchor, plus, minus rows */,
+                          int64_t m, int fit_linear, int64_t* it, double* sum_loss);
+/* The same triples at the live device parameters, nothing updated: sum_loss = sum of
+ * loss(margin, +1), n_ordered = number of triples with margin > 0.  Same preconditions and
+ * argument errors as spfm_psgd_pairs_epoch. */
+int spfm_psgd_pairs_eval(spfm_handle h, int degree, int fit_linear, const int32_t* triples,
+                         int64_t m, double* sum_loss, int64_t* n_ordered);
+
 /* -- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------
  * Rows are sharded; the column partial sums of every step are all-reduced
  * (sum, f64) so that every rank applies the identical prox.  id is an opaque

@@ -995,6 +995,25 @@ struct spfm_engine {
     // its local sample list, count) and the global batch size
     std::vector<int64_t> sg_lpos;
     std::vector<int32_t> sg_lB, sg_gB;
+    // what follows a gradient launch, shared by the pointwise and the pairwise gradient
+    template <int L, typename GradFn>
+    int psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_, int64_t n_items, int degree,
+                        double alpha, double beta, double gamma, double eta0, int lr,
+                        double power_t, int64_t batch_size, int fit_linear, int64_t* it);
+
+    // pairwise ranking fit: triples (anchor, plus, minus) of rows of the
+    // handle's data [X; Z]; buffers of their own (sg_samples and pred_tmp are sized by n)
+    DevBuf sg_triples, sg_lossrow, sg_ordered;
+    int psgd_pairs_check(const char* what, int degree, const int32_t* triples, int64_t m);
+    template <typename T, int L>
+    int psgd_pairs_epoch_tl(int degree, double alpha, double beta, double gamma, double eta0,
+                            int lr, double power_t, int64_t batch_size, int64_t m, int fit_linear,
+                            int64_t* it);
+    int psgd_pairs_epoch(int degree, double alpha, double beta, double gamma, double eta0, int lr,
+                         double power_t, int64_t batch_size, const int32_t* triples, int64_t m,
+                         int fit_linear, int64_t* it, double* sum_loss);
+    int psgd_pairs_eval(int degree, int fit_linear, const int32_t* triples, int64_t m,
+                        double* sum_loss, int64_t* n_ordered);
 
     // ------------------------------- objective terms, held-out set (spfm_engine_objective.hip)
     // Read-only views of the live state: they use buffers of their own, neither of the

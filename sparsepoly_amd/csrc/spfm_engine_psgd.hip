@@ -1,5 +1,6 @@
 // spfm_engine_psgd.hip -- minibatch solver (psgd)
 #include "spfm_engine.hip.h"
+#include "spfm_psgd_pairs.hip.h"
 
 using namespace spfm;
 
@@ -44,9 +45,17 @@ int spfm_engine::configure_psgd(int loss_, int reg_, int top_degree_) {
     return SPFM_OK;
 }
 
-template <typename T, int L>
-int spfm_engine::psgd_epoch_tl(int degree, double alpha, double beta, double gamma, double eta0, int lr,
-                  double power_t, int64_t batch_size, int fit_linear, int64_t* it) {
+// The minibatches of one epoch over `n_items` training items (samples of the pointwise fit,
+// triples of the pairwise one) behind a gradient launch: update, Michelot passes, table-driven
+// graph replay of runs of 32 with the eager redo from a snapshot.
+//   grad(pos, B, grid, table)  enqueues the gradient kernel of the items [pos, pos + B) on
+//                              `grid` workgroups; table: the kernel takes pos and B of batch
+//                              sg_idx[0] from sg_sched instead
+template <int L, typename GradFn>
+int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_, int64_t n_items,
+                                 int degree, double alpha, double beta, double gamma, double eta0,
+                                 int lr, double power_t, int64_t batch_size, int fit_linear,
+                                 int64_t* it) {
     const bool mich = (reg == SPFM_REG_SQUAREDL12 || reg == SPFM_REG_SQUAREDL21);
     constexpr int gpb = kBlock / L;
     const int nb_dense = (int)std::min<int64_t>(kPsgdNB, cdiv(d, gpb));
@@ -72,11 +81,11 @@ int spfm_engine::psgd_epoch_tl(int degree, double alpha, double beta, double gam
         const int kMichSweeps = psgd_graph_sweeps;  // recorded sweeps per minibatch (2 suffice
                                                     // with the warm start; a failed check
                                                     // redoes the epoch eagerly)
-        const int64_t nbat = cdiv(n, batch_size);
+        const int64_t nbat = cdiv(n_items, batch_size);
         h_sched.resize((size_t)nbat);
         for (int64_t bi = 0; bi < nbat; ++bi) {
             const int64_t pos = bi * batch_size;
-            const int B = (int)std::min<int64_t>(batch_size, n - pos);
+            const int B = (int)std::min<int64_t>(batch_size, n_items - pos);
             double eta_P, eta_w;
             psgd_eta(lr, eta0, alpha, beta, power_t, *it + bi, &eta_P, &eta_w);
             PsgdBatch& e = h_sched[(size_t)bi];
@@ -107,15 +116,9 @@ int spfm_engine::psgd_epoch_tl(int degree, double alpha, double beta, double gam
             HIPC(hipMemcpyAsync(sg_snapc.p, sg_cond.p, sizeof(double) * (size_t)ms.V,
                                 hipMemcpyDeviceToDevice, stream));
         }
-        const int gridg = cdiv(std::min<int64_t>(batch_size, n), gpb);
+        const int gridg = cdiv(std::min<int64_t>(batch_size, n_items), gpb);
         auto pair = [&]() {
-            hipLaunchKernelGGL((psgd_grad_kernel<T, L>), dim3(gridg), dim3(kBlock), 0, stream,
-                               sg_samples.as<int32_t>(), 0, rptr.as<int64_t>(),
-                               ridx.as<int32_t>(), rval.as<T>(), yy.as<T>(), Pt.as<double>(),
-                               w.as<double>(), lams.as<double>(), n_orders, k, d, degree, loss,
-                               fit_linear, sg_gradP.as<double>(), sg_gradw.as<double>(),
-                               pred_tmp.as<double>(), sg_sched.as<PsgdBatch>(),
-                               sg_idx.as<int>());
+            grad((int64_t)0, 0, gridg, true);
             hipLaunchKernelGGL((psgd_update_kernel<L>), dim3(nb_dense), dim3(kBlock), 0, stream,
                                Pt.as<double>(), sg_gradP.as<double>(), w.as<double>(),
                                sg_gradw.as<double>(), n_orders, k, d, reg, 0.0, 1.0, 0.0,
@@ -137,8 +140,8 @@ int spfm_engine::psgd_epoch_tl(int degree, double alpha, double beta, double gam
                                stream, Pt.as<double>(), sg_norms.as<double>(), n_orders, k, d,
                                reg, sg_thr.as<double>());
         };
-        const std::string key = fkey("psgd", {}, {degree, loss, reg, fit_linear, gridg, L,
-                                                  (int64_t)sizeof(T), (int64_t)mich,
+        const std::string key = fkey(tag, {}, {degree, loss, reg, fit_linear, gridg, L,
+                                                  tsize_, (int64_t)mich,
                                                   (int64_t)psgd_graph_sweeps});
         int64_t done_b = 0;
         for (; done_b + kPsgdRun <= nbat; done_b += kPsgdRun) {
@@ -172,20 +175,14 @@ int spfm_engine::psgd_epoch_tl(int degree, double alpha, double beta, double gam
     // one rank: the batches of its n samples; several ranks: the batches of the global order,
     // of which this rank holds samples [lpos, lpos + lB) of its local list (psgd_epoch)
     const bool sharded = dist();
-    const int64_t nbat_e = sharded ? (int64_t)sg_gB.size() : cdiv(n, batch_size);
+    const int64_t nbat_e = sharded ? (int64_t)sg_gB.size() : cdiv(n_items, batch_size);
     for (int64_t bi = 0; bi < nbat_e; ++bi) {
         const int64_t pos = sharded ? sg_lpos[(size_t)bi] : bi * batch_size;
-        const int lB = sharded ? sg_lB[(size_t)bi] : (int)std::min<int64_t>(batch_size, n - pos);
+        const int lB =
+            sharded ? sg_lB[(size_t)bi] : (int)std::min<int64_t>(batch_size, n_items - pos);
         const int B = sharded ? sg_gB[(size_t)bi] : lB;  // eta / B: the whole minibatch
         prof_begin(0, 0);
-        if (lB > 0)
-            hipLaunchKernelGGL((psgd_grad_kernel<T, L>), dim3(cdiv(lB, gpb)), dim3(kBlock), 0,
-                               stream, sg_samples.as<int32_t>() + pos, lB, rptr.as<int64_t>(),
-                               ridx.as<int32_t>(), rval.as<T>(), yy.as<T>(), Pt.as<double>(),
-                               w.as<double>(), lams.as<double>(), n_orders, k, d, degree, loss,
-                               fit_linear, sg_gradP.as<double>(), sg_gradw.as<double>(),
-                               pred_tmp.as<double>() + pos, (const PsgdBatch*)nullptr,
-                               (int*)nullptr);
+        if (lB > 0) grad(pos, lB, (int)cdiv(lB, gpb), false);
         prof_end(0);
         if (sharded) {  // sum of the ranks' gradients: identical bits on every rank
             int arc = allreduce(sg_gradP.as<double>(), (size_t)n_orders * k * d);
@@ -237,6 +234,24 @@ int spfm_engine::psgd_epoch_tl(int degree, double alpha, double beta, double gam
     }
     HIPC(hipGetLastError());
     return SPFM_OK;
+}
+
+// the pointwise gradient (one sample per group) in front of the shared minibatch driver
+template <typename T, int L>
+int spfm_engine::psgd_epoch_tl(int degree, double alpha, double beta, double gamma, double eta0, int lr,
+                  double power_t, int64_t batch_size, int fit_linear, int64_t* it) {
+    auto grad = [&](int64_t pos, int B, int grid, bool table) {
+        hipLaunchKernelGGL((psgd_grad_kernel<T, L>), dim3(grid), dim3(kBlock), 0, stream,
+                           sg_samples.as<int32_t>() + pos, B, rptr.as<int64_t>(),
+                           ridx.as<int32_t>(), rval.as<T>(), yy.as<T>(), Pt.as<double>(),
+                           w.as<double>(), lams.as<double>(), n_orders, k, d, degree, loss,
+                           fit_linear, sg_gradP.as<double>(), sg_gradw.as<double>(),
+                           pred_tmp.as<double>() + pos,
+                           table ? sg_sched.as<PsgdBatch>() : (const PsgdBatch*)nullptr,
+                           table ? sg_idx.as<int>() : (int*)nullptr);
+    };
+    return psgd_batches_tl<L>(grad, "psgd", (int64_t)sizeof(T), n, degree, alpha, beta, gamma,
+                              eta0, lr, power_t, batch_size, fit_linear, it);
 }
 
 // optimizer/psgd.py:125-199: one pass over indices_samples
@@ -321,3 +336,187 @@ int spfm_engine::psgd_epoch(int degree, double alpha, double beta, double gamma,
     psgd_warm = true;
     return SPFM_OK;
 }
+
+// ============================================================ pairwise ranking fit
+//  triples (anchor, plus, minus) of rows of the handle's data [X; Z]
+
+// first stage of a count: out[block] = number of set flags in the block's contiguous slice
+static __global__ __launch_bounds__(kBlock) void pair_count_partial_kernel(
+    const int* __restrict__ v, int64_t n, double* __restrict__ out) {
+    __shared__ double red[16];
+    const int64_t per = (n + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = per * blockIdx.x, hi = (lo + per < n) ? lo + per : n;
+    double a = 0, b = 0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) a += (double)v[i];
+    block_sum2(a, b, red);
+    if (threadIdx.x == 0) out[blockIdx.x] = a;
+}
+
+// Argument checks of both pair entries, on the host, before any launch: the state of the handle,
+// the row indices, plus != minus, and -- one flag per row the triples name, then one pass over
+// the columns' stored rows -- no column stored in an anchor row and in a plus / minus row.
+int spfm_engine::psgd_pairs_check(const char* what, int degree, const int32_t* triples, int64_t m) {
+    if (!have_data || !have_params || !configured)
+        FAIL(SPFM_ERR_INVALID, std::string(what) + ": data, parameters and configuration are required");
+    if (solver != SPFM_SOLVER_PSGD)
+        FAIL(SPFM_ERR_INVALID, std::string(what) + ": engine is not configured for psgd");
+    if (degree != top_degree)
+        FAIL(SPFM_ERR_INVALID, std::string(what) + ": degree differs from configure()");
+    if (m < 0 || (m > 0 && !triples) || m > INT32_MAX)
+        FAIL(SPFM_ERR_INVALID, std::string(what) + ": triples must hold 0 <= m < 2^31 rows of 3");
+    std::vector<uint8_t> side((size_t)(n > 0 ? n : 1), 0);  // 1: anchor, 2: plus / minus
+    for (int64_t q = 0; q < m; ++q) {
+        const int32_t b = triples[3 * q], cp = triples[3 * q + 1], cm = triples[3 * q + 2];
+        if (b < 0 || b >= n || cp < 0 || cp >= n || cm < 0 || cm >= n)
+            FAIL(SPFM_ERR_INVALID, std::string(what) + ": triple " + std::to_string(q) +
+                                       " names a row outside [0, n)");
+        if (cp == cm)
+            FAIL(SPFM_ERR_INVALID, std::string(what) + ": triple " + std::to_string(q) +
+                                       " has plus == minus");
+        side[(size_t)b] |= 1;
+        side[(size_t)cp] |= 2;
+        side[(size_t)cm] |= 2;
+    }
+    for (int32_t j = 0; j < d; ++j) {
+        unsigned both = 0;
+        for (int64_t e = h_cptr[(size_t)j]; e < h_cptr[(size_t)j + 1]; ++e)
+            both |= side[(size_t)h_cidx[(size_t)e]];
+        if (both == 3)
+            FAIL(SPFM_ERR_INVALID, std::string(what) + ": column " + std::to_string(j) +
+                                       " is stored in an anchor row and in a plus/minus row: the "
+                                       "two column sets must be disjoint");
+    }
+    return SPFM_OK;
+}
+
+template <typename T, int L>
+int spfm_engine::psgd_pairs_epoch_tl(int degree, double alpha, double beta, double gamma,
+                                     double eta0, int lr, double power_t, int64_t batch_size,
+                                     int64_t m, int fit_linear, int64_t* it) {
+    auto grad = [&](int64_t pos, int B, int grid, bool table) {
+        hipLaunchKernelGGL((psgd_pair_grad_kernel<T, L, false>), dim3(grid), dim3(kBlock), 0,
+                           stream, sg_triples.as<int32_t>() + 3 * pos, B, rptr.as<int64_t>(),
+                           ridx.as<int32_t>(), rval.as<T>(), Pt.as<double>(), w.as<double>(),
+                           lams.as<double>(), n_orders, k, d, degree, loss, fit_linear,
+                           sg_gradP.as<double>(), sg_gradw.as<double>(),
+                           sg_lossrow.as<double>() + pos, (int*)nullptr,
+                           table ? sg_sched.as<PsgdBatch>() : (const PsgdBatch*)nullptr,
+                           table ? sg_idx.as<int>() : (int*)nullptr);
+    };
+    return psgd_batches_tl<L>(grad, "psgd_pairs", (int64_t)sizeof(T), m, degree, alpha, beta,
+                              gamma, eta0, lr, power_t, batch_size, fit_linear, it);
+}
+
+int spfm_engine::psgd_pairs_epoch(int degree, double alpha, double beta, double gamma, double eta0,
+                                  int lr, double power_t, int64_t batch_size,
+                                  const int32_t* triples, int64_t m, int fit_linear, int64_t* it,
+                                  double* sum_loss) {
+    if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs: several ranks are not supported");
+    SPFM_TRY(psgd_pairs_check("psgd pairs", degree, triples, m));
+    if (!it) FAIL(SPFM_ERR_INVALID, "psgd pairs: it is required");
+    if (batch_size < 1) FAIL(SPFM_ERR_INVALID, "psgd pairs: batch_size must be >= 1");
+    if (lr < 0 || lr > 3) FAIL(SPFM_ERR_INVALID, "psgd pairs: learning_rate is not supported.");
+    if (*it < 1) FAIL(SPFM_ERR_INVALID, "psgd pairs: it must be >= 1");
+    if (m == 0) {
+        if (sum_loss) *sum_loss = 0.0;
+        return SPFM_OK;
+    }
+    SPFM_TRY(ensure_pt());
+    p_valid = false;
+    {  // (a new allocation changes the recorded kernel arguments)
+        const void *o1 = sg_triples.p, *o2 = sg_lossrow.p;
+        HIPC(sg_triples.alloc(sizeof(int32_t) * 3 * (size_t)m));
+        HIPC(sg_lossrow.alloc(sizeof(double) * (size_t)m));
+        if (sg_triples.p != o1 || sg_lossrow.p != o2) clear_graphs();
+    }
+    SPFM_TRY(upload_to(sg_triples.p, triples, 3 * (size_t)m));
+    HIPC(hipStreamSynchronize(stream));  // caller may reuse triples
+#define SPFM_PAIRS_GO(L)                                                                      \
+    psgd_pairs_epoch_tl<T, L>(degree, alpha, beta, gamma, eta0, lr, power_t, batch_size, m, \
+                              fit_linear, it)
+    int rc = SPFM_DISPATCH(dtype, return k <= 16   ? SPFM_PAIRS_GO(16)
+                                         : k <= 32 ? SPFM_PAIRS_GO(32)
+                                                   : SPFM_PAIRS_GO(64));
+#undef SPFM_PAIRS_GO
+    if (rc) return rc;
+    hipLaunchKernelGGL(reduce_partial_kernel, dim3(256), dim3(kBlock), 0, stream,
+                       sg_lossrow.as<double>(), m, partial.as<double>());
+    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(kBlock), 0, stream,
+                       partial.as<double>(), 256, scalar.as<double>());
+    HIPC(hipGetLastError());
+    SPFM_TRY(download(h_scalar, scalar.p, 1));
+    HIPC(hipStreamSynchronize(stream));
+    prof_collect();
+    if (sum_loss) *sum_loss = h_scalar[0];
+    psgd_warm = true;
+    return SPFM_OK;
+}
+
+// loss sum and number of triples with m > 0 at the live parameters; nothing is updated
+int spfm_engine::psgd_pairs_eval(int degree, int fit_linear, const int32_t* triples, int64_t m,
+                                 double* sum_loss, int64_t* n_ordered) {
+    (void)fit_linear;  // the margin reads w as it stands (zeros when no linear term was fitted)
+    if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs eval: several ranks are not supported");
+    SPFM_TRY(psgd_pairs_check("psgd pairs eval", degree, triples, m));
+    if (sum_loss) *sum_loss = 0.0;
+    if (n_ordered) *n_ordered = 0;
+    if (m == 0) return SPFM_OK;
+    SPFM_TRY(ensure_pt());
+    {
+        const void *o1 = sg_triples.p, *o2 = sg_lossrow.p;
+        HIPC(sg_triples.alloc(sizeof(int32_t) * 3 * (size_t)m));
+        HIPC(sg_lossrow.alloc(sizeof(double) * (size_t)m));
+        if (sg_triples.p != o1 || sg_lossrow.p != o2) clear_graphs();
+    }
+    HIPC(sg_ordered.alloc(sizeof(int) * (size_t)m));
+    SPFM_TRY(upload_to(sg_triples.p, triples, 3 * (size_t)m));
+#define SPFM_PAIRS_EV(L)                                                                       \
+    hipLaunchKernelGGL((psgd_pair_grad_kernel<T, L, true>), dim3(cdiv(m, kBlock / L)),        \
+                       dim3(kBlock), 0, stream, sg_triples.as<int32_t>(), (int)m,             \
+                       rptr.as<int64_t>(), ridx.as<int32_t>(), rval.as<T>(), Pt.as<double>(), \
+                       w.as<double>(), lams.as<double>(), n_orders, k, d, degree, loss, 0,    \
+                       (double*)nullptr, (double*)nullptr, sg_lossrow.as<double>(),           \
+                       sg_ordered.as<int>(), (const PsgdBatch*)nullptr, (int*)nullptr)
+    SPFM_DISPATCH(dtype, {
+        if (k <= 16)
+            SPFM_PAIRS_EV(16);
+        else if (k <= 32)
+            SPFM_PAIRS_EV(32);
+        else
+            SPFM_PAIRS_EV(64);
+    });
+#undef SPFM_PAIRS_EV
+    hipLaunchKernelGGL(reduce_partial_kernel, dim3(256), dim3(kBlock), 0, stream,
+                       sg_lossrow.as<double>(), m, partial.as<double>());
+    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(kBlock), 0, stream,
+                       partial.as<double>(), 256, scalar.as<double>());
+    hipLaunchKernelGGL(pair_count_partial_kernel, dim3(256), dim3(kBlock), 0, stream,
+                       sg_ordered.as<int>(), m, partial.as<double>() + 256);
+    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(kBlock), 0, stream,
+                       partial.as<double>() + 256, 256, scalar.as<double>() + 1);
+    HIPC(hipGetLastError());
+    SPFM_TRY(download(h_scalar, scalar.p, 2));
+    HIPC(hipStreamSynchronize(stream));
+    if (sum_loss) *sum_loss = h_scalar[0];
+    if (n_ordered) *n_ordered = (int64_t)h_scalar[1];
+    return SPFM_OK;
+}
+
+extern "C" {
+
+int spfm_psgd_pairs_epoch(spfm_handle h, int degree, double alpha, double beta, double gamma,
+                          double eta0, int learning_rate, double power_t, int64_t batch_size,
+                          const int32_t* triples, int64_t m, int fit_linear, int64_t* it,
+                          double* sum_loss) {
+    SPFM_GUARD(h);
+    return h->psgd_pairs_epoch(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                               batch_size, triples, m, fit_linear, it, sum_loss);
+}
+
+int spfm_psgd_pairs_eval(spfm_handle h, int degree, int fit_linear, const int32_t* triples,
+                         int64_t m, double* sum_loss, int64_t* n_ordered) {
+    SPFM_GUARD(h);
+    return h->psgd_pairs_eval(degree, fit_linear, triples, m, sum_loss, n_ordered);
+}
+
+}  // extern "C"

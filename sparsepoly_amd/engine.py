@@ -1191,6 +1191,40 @@ class HipEngine(object):
             int(bool(fit_linear)), C.byref(itc), C.byref(sl)))
         return sl.value, itc.value
 
+    @staticmethod
+    def _triples(triples):
+        t = np.ascontiguousarray(triples, dtype=np.int32)
+        if t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError("triples must have shape (m, 3), got %r" % (t.shape,))
+        return t
+
+    def psgd_pairs_epoch(self, degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                         batch_size, triples, fit_linear, it):
+        """One pass of minibatch psgd over the triples (anchor, plus, minus) -- rows of the
+        handle's data ``[X; Z]`` -- in the order given (``spfm_psgd_pairs_epoch``).  Returns
+        (sum_loss, it)."""
+        t = self._triples(triples)
+        itc = C.c_int64(int(it))
+        sl = C.c_double()
+        lr = (_capi.LEARNING_RATE[learning_rate] if isinstance(learning_rate, str)
+              else int(learning_rate))
+        self._check(self._lib.spfm_psgd_pairs_epoch(
+            self._h, int(degree), float(alpha), float(beta), float(gamma), float(eta0), lr,
+            float(power_t), int(batch_size), t.ctypes.data_as(_capi._ip), t.shape[0],
+            int(bool(fit_linear)), C.byref(itc), C.byref(sl)))
+        return sl.value, itc.value
+
+    def psgd_pairs_eval(self, degree, fit_linear, triples):
+        """(sum of the triples' losses, number of triples with margin > 0) at the live device
+        parameters; nothing is updated (``spfm_psgd_pairs_eval``)."""
+        t = self._triples(triples)
+        sl = C.c_double()
+        no = C.c_int64()
+        self._check(self._lib.spfm_psgd_pairs_eval(
+            self._h, int(degree), int(bool(fit_linear)), t.ctypes.data_as(_capi._ip), t.shape[0],
+            C.byref(sl), C.byref(no)))
+        return sl.value, no.value
+
     # ------------------------------------------------------------- multi-GPU
     @staticmethod
     def comm_unique_id():

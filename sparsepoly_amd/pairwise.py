@@ -1,0 +1,500 @@
+"""Pairwise ranking fit on the device: minibatch psgd over triples.
+
+A training example is a triple ``(b, c+, c-)``: context row ``b`` of ``X`` prefers candidate
+``c+`` of ``Z`` to candidate ``c-``.  With the margin
+
+    m = f(x_b + z_c+) - f(x_b + z_c-)
+
+the loss of a triple is ``loss(m, +1)`` -- ``'logistic'`` is BPR, ``'squared_hinge'`` and
+``'squared'`` come with it -- and the penalties ``alpha/2 |w|^2 + beta/2 |P|^2 + gamma Omega(P)``,
+the step sizes and the prox are exactly those of ``solver='psgd'``.  ``X`` and ``Z`` use the
+vocabulary of ``ranking.py``: one feature space, disjoint column sets.  The stacked matrix
+``[X; Z]`` goes to the device once per fit and a triple is three row indices into it
+(``spfm_psgd_pairs_epoch``, ``include/spfm.h``): 12 bytes per triple, no materialised row
+``x_b + z_c``, nothing to rebuild when the negatives are drawn again.
+
+``sample_triples`` draws the negatives (NumPy).  ``restate_margins`` / ``restate_pair_gradient`` /
+``restate_pairwise_epoch`` are plain NumPy restatements, test aids that never touch the device.
+There is no CPU path of the fit: without the library or a GPU it raises.
+"""
+import numpy as np
+import scipy.sparse as sp
+from sklearn.utils import check_random_state
+from sklearn.utils.validation import NotFittedError
+
+from . import _capi
+from .loss import CLASSIFICATION_LOSSES
+from .ranking import _canonical, _check_disjoint, _pattern, _prepare, _widen
+from .sparse_factorization_machines import MAX_DEGREE, _BaseSparseFactorizationMachine
+from .monitor import callback_needs_params
+
+PSGD_REGULARIZERS = ("l1", "l21", "squaredl12", "squaredl21")
+
+
+# ------------------------------------------------------------------ negative sampling
+def sample_triples(interactions, n_negatives=1, random_state=None, exclude=None):
+    """``(m, 3)`` int32 triples ``(b, c+, c-)``: for every stored ``(b, c+)`` of the sparse
+    ``(B, C)`` matrix ``interactions`` (pattern only), ``n_negatives`` candidates drawn uniformly
+    from those stored neither in row ``b`` of ``interactions`` nor in row ``b`` of ``exclude``;
+    ``m = nnz * n_negatives``, positives in canonical CSR order, the draws of one positive side by
+    side.  Vectorised rejection: all draws at once, only the hits are drawn again.  Reproducible
+    for a given seed.  ``ValueError`` for a row with a positive and no admissible candidate, and
+    for ``m >= 2**31``."""
+    if int(n_negatives) != n_negatives or n_negatives < 1:
+        raise ValueError("n_negatives must be an integer >= 1, got %r" % (n_negatives,))
+    n_negatives = int(n_negatives)
+    if not sp.issparse(interactions):
+        interactions = sp.csr_matrix(np.asarray(interactions))
+    B, C = interactions.shape
+    I = _pattern(interactions, B, C, "interactions")
+    F = I
+    if exclude is not None:
+        F = (I + _pattern(exclude, B, C, "exclude")).tocsr()
+        F.sort_indices()
+    m = int(I.nnz) * n_negatives
+    if m >= 2 ** 31:
+        raise ValueError("%d triples: the triple list is limited to 2**31 - 1 rows" % m)
+    full = (np.diff(F.indptr) >= C) & (np.diff(I.indptr) > 0)
+    if full.any():
+        raise ValueError("row %d stores every candidate (interactions and exclude together): no "
+                         "negative can be drawn for it" % int(np.argmax(full)))
+    rng = check_random_state(random_state)
+    b = np.repeat(np.repeat(np.arange(B, dtype=np.int64), np.diff(I.indptr)), n_negatives)
+    cp = np.repeat(I.indices.astype(np.int64), n_negatives)
+    # (row, candidate) keys of the forbidden pairs, ascending: F is row-major with sorted indices
+    keys = np.repeat(np.arange(B, dtype=np.int64), np.diff(F.indptr)) * C + F.indices
+    cm = rng.randint(0, C, size=m).astype(np.int64)
+    todo = np.arange(m)
+    while todo.size:
+        q = b[todo] * C + cm[todo]
+        pos = np.searchsorted(keys, q)
+        hit = (pos < keys.size) & (keys[np.minimum(pos, keys.size - 1)] == q)
+        todo = todo[hit]
+        if todo.size:
+            cm[todo] = rng.randint(0, C, size=todo.size)
+    return np.stack([b, cp, cm], axis=1).astype(np.int32)
+
+
+def epoch_triples(rng, n_epochs, interactions=None, triples=None, n_negatives=1, resample=True,
+                  shuffle=False, exclude=None):
+    """The triple list of every epoch of ``SparseFactorizationMachineRanker.fit``, in the order
+    the device visits it, as the fit draws it from ``rng`` (a ``RandomState``): negatives are
+    drawn before the first epoch and, with ``resample``, before every later one; with ``shuffle``
+    the list is then permuted.  A generator of ``(m, 3)`` int32 arrays in context / candidate
+    numbering."""
+    cur = None if triples is None else np.asarray(triples, dtype=np.int32)
+    for ep in range(n_epochs):
+        if interactions is not None and (cur is None or resample):
+            cur = sample_triples(interactions, n_negatives, rng, exclude)
+        out = cur
+        if shuffle:
+            out = cur[rng.permutation(cur.shape[0])]
+        yield out
+
+
+def check_triples(triples, B, C):
+    """``(m, 3)`` int32 triples ``(b, c+, c-)`` in context / candidate numbering, checked against
+    ``B`` contexts and ``C`` candidates; ``ValueError`` for a wrong shape, an index out of range,
+    ``c+ == c-`` and ``m >= 2**31``.  Needs no device."""
+    t = np.asarray(triples)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("triples must have shape (m, 3), got %r" % (t.shape,))
+    if t.shape[0] >= 2 ** 31:
+        raise ValueError("%d triples: the triple list is limited to 2**31 - 1 rows" % t.shape[0])
+    if t.size and not np.issubdtype(t.dtype, np.integer):
+        if not np.all(t == np.floor(t)):
+            raise ValueError("triples must hold integers")
+    t = t.astype(np.int64)
+    if t.size:
+        if t[:, 0].min() < 0 or t[:, 0].max() >= B:
+            raise ValueError("triples: context index out of range [0, %d)" % B)
+        if t[:, 1:].min() < 0 or t[:, 1:].max() >= C:
+            raise ValueError("triples: candidate index out of range [0, %d)" % C)
+        same = np.flatnonzero(t[:, 1] == t[:, 2])
+        if same.size:
+            raise ValueError("triple %d has c+ == c- (candidate %d)"
+                             % (int(same[0]), int(t[same[0], 1])))
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def _prepare_pairs(est, X, Z):
+    """Canonical, checked, widened (X, Z) of one width, for an estimator that need not be fitted;
+    every argument error is raised here, before a handle exists."""
+    X = _canonical(X)
+    Z = _canonical(Z)
+    if X.shape[1] != Z.shape[1]:
+        raise ValueError("X has %d features, Z has %d" % (X.shape[1], Z.shape[1]))
+    if X.shape[0] < 1 or Z.shape[0] < 2:
+        raise ValueError("a pairwise fit needs a context row and two candidate rows")
+    _check_disjoint(X, Z)
+    return _widen(est, X, Z)
+
+
+# ------------------------------------------------------------------ NumPy restatement (test aid)
+def _loss_pos(loss, m):
+    """loss(m, +1) and its derivative, as ``loss_dev`` / ``dloss_dev`` compute them"""
+    one = m.dtype.type(1)
+    if loss == "squared":
+        return (m - one) * (m - one) / 2, m - one
+    if loss == "squared_hinge":
+        z = one - m
+        return np.where(z > 0, z * z, 0), np.where(z > 0, -2 * z, 0)
+    if loss == "logistic":
+        mc = np.clip(m, -18, 18)
+        val = np.where(m > 18, np.exp(-m), np.where(m < -18, -m, np.log(1 + np.exp(-mc))))
+        der = np.where(m > 18, -np.exp(-m), np.where(m < -18, -one, -one / (np.exp(mc) + 1)))
+        return val, der
+    raise ValueError("Loss function %r is not supported." % (loss,))
+
+
+def _dense_sides(X, Z, dtype):
+    Xd = np.asarray(sp.csr_matrix(X).todense(), dtype=dtype)
+    Zd = np.asarray(sp.csr_matrix(Z).todense(), dtype=dtype)
+    return Xd, Zd
+
+
+def _anova_rows(Po, V, deg):
+    """a[t] (t = 0..deg), each (n, k): the ANOVA DP of the rows V (n, d) with P_o (k, d)"""
+    n, k = V.shape[0], Po.shape[0]
+    a = [np.ones((n, k), dtype=V.dtype)] + [np.zeros((n, k), dtype=V.dtype) for _ in range(deg)]
+    for j in np.flatnonzero(np.any(V != 0, axis=0)):
+        px = V[:, j, None] * Po[None, :, j]
+        for t in range(deg, 0, -1):
+            a[t] = a[t] + a[t - 1] * px
+    return a
+
+
+def _rows_output(P, lams, V, degree):
+    """sum over the orders o (degree ``degree - o``) of sum_s lams_s a^deg_s(row), and the DP
+    arrays per order"""
+    out = np.zeros(V.shape[0], dtype=V.dtype)
+    dps = []
+    for o in range(P.shape[0]):
+        a = _anova_rows(P[o], V, degree - o)
+        dps.append(a)
+        out = out + a[degree - o] @ lams
+    return out, dps
+
+
+def _as(dtype, *arrays):
+    return tuple(np.asarray(a, dtype=dtype) for a in arrays)
+
+
+def restate_margins(P, w, lams, X, Z, triples, degree, wide=False):
+    """Test aid, NumPy only: the margins ``f(x_b + z_c+) - f(x_b + z_c-)`` of the triples
+    ``(b, c+, c-)`` (context / candidate numbering) by evaluating the ANOVA recurrence on both
+    dense summed rows; every order ``o`` of ``P`` (n_orders, k, d) enters with degree
+    ``degree - o``, as in the minibatch solver, and ``w`` as it stands.  float64, or
+    ``np.longdouble`` with ``wide``."""
+    dtype = np.longdouble if wide else np.double
+    P, w, lams = _as(dtype, P, w, lams)
+    P = P[None] if P.ndim == 2 else P
+    Xd, Zd = _dense_sides(X, Z, dtype)
+    t = np.asarray(triples, dtype=np.int64)
+    fp, _ = _rows_output(P, lams, Xd[t[:, 0]] + Zd[t[:, 1]], degree)
+    fm, _ = _rows_output(P, lams, Xd[t[:, 0]] + Zd[t[:, 2]], degree)
+    return (fp - fm) + (Zd[t[:, 1]] - Zd[t[:, 2]]) @ w
+
+
+def restate_pair_gradient(P, w, lams, X, Z, triples, degree, loss, wide=False):
+    """Test aid, NumPy only: ``(losses (m,), grad_P (n_orders, k, d), grad_w (d,))`` of the
+    summed loss of the triples at ``(P, w)`` -- the sums one minibatch scatters.  ``grad_w`` is
+    formed from ``z_c+ - z_c-`` alone: the context's term cancels and its columns are exactly
+    zero."""
+    dtype = np.longdouble if wide else np.double
+    P, w, lams = _as(dtype, P, w, lams)
+    P = P[None] if P.ndim == 2 else P
+    Xd, Zd = _dense_sides(X, Z, dtype)
+    t = np.asarray(triples, dtype=np.int64)
+    Vp, Vm = Xd[t[:, 0]] + Zd[t[:, 1]], Xd[t[:, 0]] + Zd[t[:, 2]]
+    fp, dpp = _rows_output(P, lams, Vp, degree)
+    fm, dpm = _rows_output(P, lams, Vm, degree)
+    dz = Zd[t[:, 1]] - Zd[t[:, 2]]
+    val, dL = _loss_pos(loss, (fp - fm) + dz @ w)
+    gP = np.zeros_like(P)
+    for o in range(P.shape[0]):
+        deg = degree - o
+        for V, dps, sign in ((Vp, dpp[o], 1), (Vm, dpm[o], -1)):
+            # _grad_anova: d a^deg / d p_sj by the recurrence dprev <- x (a[t] - p dprev)
+            x = V[:, None, :]
+            dprev = np.broadcast_to(x, (V.shape[0], P.shape[1], V.shape[1]))
+            for tt in range(1, deg):
+                dprev = x * (dps[tt][:, :, None] - P[o][None] * dprev)
+            gP[o] += sign * np.einsum("r,s,rsj->sj", dL, lams, dprev)
+    return val, gP, dL @ dz
+
+
+def _psgd_eta(learning_rate, eta0, alpha, beta, power_t, it):
+    """optimizer/psgd.py:9-22 (``spfm_engine::psgd_eta``)"""
+    lr = _capi.LEARNING_RATE[learning_rate] if isinstance(learning_rate, str) else learning_rate
+    if lr == 0:
+        return eta0, eta0
+    if lr == 1:
+        e = eta0 * float(it)
+        return eta0 / (1.0 + e * beta) ** power_t, eta0 / (1.0 + e * alpha) ** power_t
+    if lr == 2:
+        return 1.0 / (beta * float(it)), 1.0 / (alpha * float(it))
+    e = eta0 / float(it) ** power_t
+    return e, e
+
+
+def _soft(v, thr):
+    return np.sign(v) * np.maximum(np.abs(v) - thr, 0)
+
+
+def _prox_squaredl12(p, c):
+    """prox of c (sum_i |p_i|)^2 by the monotone Michelot fixed point the device iterates:
+    G <- {i : |p_i| >= tau(G)}, tau(G) = 2 c S_G / (1 + 2 c |G|), from G = all"""
+    a = np.abs(p)
+    cond, theta = a.dtype.type(0), -1
+    while True:
+        G = a >= cond
+        S, th = a[G].sum(), int(G.sum())
+        den = 1 + 2 * c * th
+        cond = 2 * c * S / den
+        if th == theta:
+            return _soft(p, 2 * c * (S / den))
+        theta = th
+
+
+def _prox(regularizer, Po, c):
+    """regularizer.prox on one order's block P_o (k, d), features along the second axis"""
+    if regularizer == "l1":
+        return _soft(Po, c)
+    if regularizer == "l21":
+        nr = np.sqrt((np.abs(Po) ** 2).sum(axis=0))
+        nr = np.where(nr <= c, np.inf, nr)
+        return Po * (1 - c / nr)
+    if regularizer == "squaredl12":
+        return np.stack([_prox_squaredl12(Po[s], c) for s in range(Po.shape[0])])
+    if regularizer == "squaredl21":
+        nr = np.sqrt((np.abs(Po) ** 2).sum(axis=0))
+        unit = Po / np.where(nr > 0, nr, 1)
+        return unit * _prox_squaredl12(nr, c)
+    raise ValueError("regularizer %r cannot be used with a pairwise fit" % (regularizer,))
+
+
+def restate_pairwise_epoch(P, w, lams, X, Z, triples, degree, loss="logistic", regularizer="l1",
+                           alpha=1.0, beta=1.0, gamma=1.0, eta0=1.0, learning_rate="optimal",
+                           power_t=1.0, batch_size=1, fit_linear=True, it=1, wide=False):
+    """Test aid, NumPy only: one epoch of the pairwise fit over ``triples`` (context / candidate
+    numbering, visited in the order given) from ``P`` (n_orders, k, d) and ``w``.  Minibatch
+    ``bi`` covers the triples ``[bi * batch_size, ...)``, the last one may be shorter; per batch
+    the gradient sums, the step ``eta / B`` with ``psgd_eta`` at ``it``, the shrink and the prox of
+    the minibatch solver.  Returns ``(P, w, sum_loss, it)`` (new arrays)."""
+    dtype = np.longdouble if wide else np.double
+    P, w, lams = _as(dtype, P, w, lams)
+    P = (P[None] if P.ndim == 2 else P).copy()
+    w = w.copy()
+    t = np.asarray(triples, dtype=np.int64)
+    sum_loss = dtype(0)
+    for pos in range(0, t.shape[0], int(batch_size)):
+        tb = t[pos:pos + int(batch_size)]
+        val, gP, gw = restate_pair_gradient(P, w, lams, X, Z, tb, degree, loss, wide)
+        sum_loss += val.sum()
+        eta_P, eta_w = _psgd_eta(learning_rate, eta0, alpha, beta, power_t, it)
+        if fit_linear:
+            w = (w - gw * (eta_w / tb.shape[0])) / (1 + eta_w * alpha)
+        P = (P - gP * (eta_P / tb.shape[0])) / (1 + eta_P * beta)
+        strength = gamma * eta_P / (1 + eta_P * beta)
+        P = np.stack([_prox(regularizer, P[o], dtype(strength)) for o in range(P.shape[0])])
+        it += 1
+    return P, w, sum_loss, it
+
+
+# ------------------------------------------------------------------ the estimator
+class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
+    """Factorization machine trained for an order: minibatch psgd on the pairwise loss
+    ``loss(f(x_b + z_c+) - f(x_b + z_c-), +1)`` over triples.  The constructor takes the keywords
+    of the classifier (``loss='logistic'``: BPR); ``solver`` must be ``'psgd'``, the regularizer
+    one of ``'l1'``, ``'l21'``, ``'squaredl12'``, ``'squaredl21'``, and ``distributed`` False.
+    The fitted object has ``P_``, ``w_``, ``lams_`` like every estimator here: ``ranker``,
+    ``rank_metrics``, ``fold_in``, the explain calls and the interaction views work on it."""
+
+    _LOSSES = CLASSIFICATION_LOSSES
+
+    def __init__(
+        self,
+        degree=2,
+        loss="logistic",
+        n_components=2,
+        solver="psgd",
+        regularizer="squaredl12",
+        alpha=1,
+        beta=1,
+        gamma=1,
+        mean=False,
+        tol=1e-6,
+        fit_lower="explicit",
+        fit_linear=True,
+        warm_start=False,
+        init_lambdas="ones",
+        max_iter=100,
+        shuffle=False,
+        batch_size="auto",
+        eta0=1.0,
+        learning_rate="optimal",
+        power_t=1.0,
+        n_iter_no_change=5,
+        verbose=False,
+        callback=None,
+        n_calls=10,
+        random_state=None,
+        schedule="exact",
+        precision="f32",
+        device=None,
+        distributed=False,
+    ):
+        super(SparseFactorizationMachineRanker, self).__init__(
+            degree, loss, n_components, solver, regularizer, alpha, beta, gamma, mean, tol,
+            fit_lower, fit_linear, warm_start, init_lambdas, max_iter, shuffle, batch_size, eta0,
+            learning_rate, power_t, n_iter_no_change, verbose, callback, n_calls, random_state,
+            schedule, precision, device, distributed,
+        )
+
+    def _check_config(self):
+        if self.solver != "psgd":
+            raise ValueError("Solver %s is not supported by the pairwise fit: it is minibatch "
+                             "psgd over triples (solver='psgd')." % (self.solver,))
+        if self.regularizer not in PSGD_REGULARIZERS:
+            raise ValueError("regularizer %r cannot be used with the pairwise fit; choose from %s"
+                             % (self.regularizer, list(PSGD_REGULARIZERS)))
+        if self.distributed:
+            raise ValueError("the pairwise fit runs on one GPU (distributed=False).")
+        self._get_loss(self.loss)
+        if self.learning_rate not in _capi.LEARNING_RATE:
+            raise ValueError("learning_rate %s is not supported. Choose from %s."
+                             % (self.learning_rate, _capi.LEARNING_RATE))
+        if self.degree > MAX_DEGREE:
+            raise NotImplementedError("degree > %d is not supported by the HIP engine"
+                                      % MAX_DEGREE)
+
+    def fit(self, X, Z, interactions=None, triples=None, n_negatives=1, resample=True):
+        """Fit on contexts ``X`` (B, d) and candidates ``Z`` (C, d) with disjoint column sets.
+        Exactly one of ``interactions`` -- a sparse (B, C) matrix whose stored entries are the
+        positives; ``n_negatives`` negatives per positive are drawn with ``sample_triples``,
+        again before every epoch when ``resample`` -- and ``triples`` -- (m, 3) rows
+        ``(b, c+, c-)`` in context / candidate numbering -- is given.  ``[X; Z]`` is uploaded
+        once; an epoch uploads its 12 m bytes of triples.  Stopping rule, ``verbose`` lines,
+        callbacks, ``it_``, ``n_iter_`` and ``warm_start`` as for ``solver='psgd'``, with the
+        mean loss per triple."""
+        self._check_config()
+        if (interactions is None) == (triples is None):
+            raise ValueError("exactly one of interactions and triples must be given")
+        Xa, Za = _prepare_pairs(self, X, Z)
+        B, C = Xa.shape[0], Za.shape[0]
+        n_features = Xa.shape[1]
+        if interactions is not None:
+            if not sp.issparse(interactions):
+                interactions = sp.csr_matrix(np.asarray(interactions))
+            interactions = _pattern(interactions, B, C, "interactions")
+            if interactions.nnz == 0:
+                raise ValueError("interactions has no stored entry")
+        else:
+            triples = check_triples(triples, B, C)
+            if triples.shape[0] == 0:
+                raise ValueError("triples is empty")
+        rng = check_random_state(self.random_state)
+        if not (self.warm_start and hasattr(self, "w_")):
+            self.w_ = np.zeros(n_features, dtype=np.double)
+        n_orders = self.degree - 1 if self.fit_lower == "explicit" else 1
+        if not (self.warm_start and hasattr(self, "P_")):
+            self.P_ = 0.01 * rng.randn(n_orders, self.n_components, n_features)
+        if not (self.warm_start and hasattr(self, "lams_")):
+            if self.init_lambdas == "ones":
+                self.lams_ = np.ones(self.n_components)
+            elif self.init_lambdas == "random_signs":
+                self.lams_ = np.sign(rng.randn(self.n_components))
+            else:
+                raise ValueError("Lambdas must be initialized as ones (init_lambdas='ones') or "
+                                 "as random +/- 1 (init_lambdas='random_signs').")
+        if np.unique(np.abs(self.lams_)) != np.array([1.0]):
+            raise ValueError("Lambdas must be +1 or -1.")
+        if self.P_.shape != (n_orders, self.n_components, n_features) or \
+                self.w_.shape != (n_features,):
+            raise ValueError("warm_start: P_ / w_ do not fit this data and configuration")
+        if not (self.warm_start and hasattr(self, "it_")):
+            self.it_ = 1
+        S = sp.vstack([Xa, Za], format="csr")
+        S.sort_indices()
+        if self.batch_size == "auto":
+            batch_size = max(1, int(S.shape[0] * n_features / max(S.nnz, 1)))
+        else:
+            batch_size = self.batch_size
+        engine = self._new_engine()
+        try:
+            engine.set_data(S, np.zeros(S.shape[0]))
+            self.P_ = np.ascontiguousarray(self.P_, dtype=np.double)
+            self.w_ = np.ascontiguousarray(self.w_, dtype=np.double)
+            engine.set_params(self.P_, self.w_, self.lams_)
+            engine.configure("psgd", self.loss, self.regularizer, self.degree)
+            converged, self.n_iter_ = self._fit_pairs(engine, B, rng, batch_size, interactions,
+                                                      triples, n_negatives, resample)
+        finally:
+            engine.close()
+        return self._finish_fit(converged)
+
+    def _fit_pairs(self, engine, B, rng, batch_size, interactions, triples, n_negatives,
+                   resample):
+        """the loop of ``_fit_psgd`` over the epochs' triple lists"""
+        converged = False
+        no_improvement_count = 0
+        best_loss = np.inf
+        epoch = 0
+        lists = epoch_triples(rng, self.max_iter, interactions, triples, n_negatives, resample,
+                              self.shuffle)
+        for epoch, t in enumerate(lists):
+            stacked = t + np.array([0, B, B], dtype=np.int32)  # rows of [X; Z]
+            sum_loss, self.it_ = engine.psgd_pairs_epoch(
+                self.degree, self.alpha, self.beta, self.gamma, self.eta0, self.learning_rate,
+                self.power_t, batch_size, stacked, self.fit_linear, self.it_)
+            if (self.callback is not None) and epoch % self.n_calls == 0:
+                if callback_needs_params(self.callback):
+                    self._sync_params(engine, with_P=False)
+                if self.callback(self) is not None:
+                    break
+            sum_loss /= t.shape[0]
+            if self.verbose:
+                print(f"Epoch {epoch+1} loss {sum_loss}")
+            if sum_loss > (best_loss - self.tol):
+                no_improvement_count += 1
+            else:
+                no_improvement_count = 0
+            if sum_loss < best_loss:
+                best_loss = sum_loss
+            if no_improvement_count >= self.n_iter_no_change:
+                if self.verbose:
+                    print(f"Converged at iteration {epoch+1}")
+                converged = True
+                break
+        self._sync_params(engine)
+        return converged, epoch
+
+    def pairwise_loss(self, X, Z, triples):
+        """``(mean loss, share of triples with margin > 0)`` of the fitted model on the triples
+        ``(b, c+, c-)`` (context / candidate numbering), on the device
+        (``spfm_psgd_pairs_eval``).  Like the fit the margin sums every order of ``P_``."""
+        if not hasattr(self, "P_"):
+            raise NotFittedError("Estimator not fitted.")
+        self._check_config()
+        Xa, Za = _prepare(self, X, Z)
+        t = check_triples(triples, Xa.shape[0], Za.shape[0])
+        if t.shape[0] == 0:
+            raise ValueError("triples is empty")
+        S = sp.vstack([Xa, Za], format="csr")
+        S.sort_indices()
+        engine = self._new_engine()
+        try:
+            engine.set_data(S, np.zeros(S.shape[0]))
+            engine.set_params(np.ascontiguousarray(self.P_, dtype=np.double), self.w_, self.lams_)
+            engine.configure("psgd", self.loss, self.regularizer, self.degree)
+            sum_loss, n_ordered = engine.psgd_pairs_eval(
+                self.degree, self.fit_linear, t + np.array([0, Xa.shape[0], Xa.shape[0]],
+                                                           dtype=np.int32))
+        finally:
+            engine.close()
+        return sum_loss / t.shape[0], n_ordered / t.shape[0]
+
+    def decision_function(self, rows):
+        """The model output of every row of ``rows`` (n, d), e.g. of ``x_b + z_c``."""
+        return self._predict(rows)
