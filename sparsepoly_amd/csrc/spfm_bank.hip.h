@@ -36,13 +36,6 @@ constexpr int kBankMaxComponents = 4096;   // stacked components: 64 chunk sweep
 
 enum { BANK_SCORES = 0, BANK_ARGMAX = 1, BANK_LOSSES = 2, BANK_MEAN = 3 };
 
-// LDS written by some lanes of a wave, read by others of the same wave (as explain_wave_sync)
-__device__ __forceinline__ void bank_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 // One block of the bank on the rows of one slab: out[row][f] = B + lin (first) or += B.
 // rptr holds the slab's rows with the matrix's own offsets, ridx / rval its entries from e0 on.
 template <typename T, int M>
@@ -69,38 +62,32 @@ __global__ __launch_bounds__(kBlock) void bank_predict_kernel(
     for (int c0 = 0; c0 < S; c0 += kWave) {
         const int s = c0 + lane;
         const bool active = s < S;
+        const auto px = [&](int u) { return Pt[(size_t)js[u] * S + s] * xs[u]; };
         double a[M + 1];
-        a[0] = 1.0;
-#pragma unroll
-        for (int t = 1; t <= M; ++t) a[t] = 0.0;
+        anova_dp_init<M>(a);
         for (int tile = 0; tile < ntile; ++tile) {
             const int len = min(kBankStage, n_i - tile * kBankStage);
             if (ntile > 1 || c0 == 0) {  // a short row stays staged for every chunk
-                bank_wave_sync();        // the previous tile has been read
+                wave_lds_sync();         // the previous tile has been read
                 for (int u = lane; u < len; u += kWave) {
                     const int64_t ii = b + (int64_t)tile * kBankStage + u;
                     js[u] = ridx[ii];
                     xs[u] = (double)rval[ii];
                 }
-                bank_wave_sync();
+                wave_lds_sync();
             }
             if (c0 == 0 && wb != nullptr && lane < F)
                 for (int u = 0; u < len; ++u) lin += xs[u] * wb[(size_t)js[u] * F + lane];
             if (active) {
-                for (int u = 0; u < len; ++u) {
-                    if constexpr (M == 0) {  // all-subsets kernel, as anova_predict_kernel
-                        a[0] *= 1 + xs[u] * Pt[(size_t)js[u] * S + s];
-                    } else {
-                        const double px = Pt[(size_t)js[u] * S + s] * xs[u];
-#pragma unroll
-                        for (int t = M; t >= 1; --t) a[t] += a[t - 1] * px;
-                    }
-                }
+                if constexpr (M == 0)  // all-subsets kernel, as anova_predict_kernel
+                    subsets_dp_add(a[0], 0, len, px);
+                else
+                    anova_dp_add<M>(a, 0, len, px);
             }
         }
-        bank_wave_sync();  // the previous chunk's terms have been read
+        wave_lds_sync();  // the previous chunk's terms have been read
         ts[lane] = active ? a[M] * lams[s] : 0.0;
-        bank_wave_sync();
+        wave_lds_sync();
         const int s0 = max(lo, c0), s1 = min(hi, c0 + kWave);
         for (int c = s0; c < s1; ++c) acc += ts[c - c0];
     }

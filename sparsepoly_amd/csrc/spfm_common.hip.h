@@ -178,6 +178,40 @@ __device__ __forceinline__ double grad_factor(const double* a, double x, double 
     }
 }
 
+// The ANOVA kernels a[t] = A^t(p, x), t = 0..N, of the entries of one row, by the DP of
+// pcd.py:23-30: a = (1, 0, ..., 0), then per entry a[t] += a[t-1] * (p x), t descending.  The
+// read-only row-wise units (predict, towers, banks, attributions, fold-in) share this one copy;
+// what differs between them is px(u) -- p x of entry u, from wherever the caller keeps p and x --
+// the range [b, e) and N.  (The training kernels associate the product as a[t-1] * p * x and
+// keep their own loops.)
+template <int N>
+__device__ __forceinline__ void anova_dp_init(double* a) {
+    a[0] = 1.0;
+#pragma unroll
+    for (int t = 1; t <= N; ++t) a[t] = 0.0;
+}
+template <int N, typename I, typename PX>
+__device__ __forceinline__ void anova_dp_add(double* a, I b, I e, PX&& px) {
+    for (I u = b; u < e; ++u) {
+        const double z = px(u);
+#pragma unroll
+        for (int t = N; t >= 1; --t) a[t] += a[t - 1] * z;
+    }
+}
+// the all-subsets kernel prod (1 + p x) (kernels.py:117-137) in the same style: a = 1, then
+template <typename I, typename PX>
+__device__ __forceinline__ void subsets_dp_add(double& a, I b, I e, PX&& px) {
+    for (I u = b; u < e; ++u) a *= 1 + px(u);
+}
+
+// LDS written by some lanes of a wave, read by others of the same wave: the wave's LDS
+// operations complete in order; this keeps the compiler from moving them across the point
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
 // ------------------------------------------------------------ control kernels
 
 static __global__ void begin_pass_kernel(Ctl* ctl, const int32_t* comp_order, const double* lams) {

@@ -30,6 +30,7 @@
 
 #include "../../include/spfm.h"
 #include "spfm_common.hip.h"
+#include "spfm_slab_host.h"  // slab_end
 #include "spfm_prb.hip.h"    // PrbArgs
 #include "spfm_pcdw.hip.h"   // PcdwArgs, PcdwParams
 #include "spfm_psgd.hip.h"   // PsgdBatch
@@ -186,6 +187,30 @@ struct DevBuf {
 #define SPFM_DISPATCH(dt, ...)                                    \
     ((dt) == SPFM_F32 ? [&] { using T = float; __VA_ARGS__; }()   \
                       : [&] { using T = double; __VA_ARGS__; }())
+
+// The one place that maps a run-time model kind -- a degree 2..6, or 0 (all-subsets) where AS
+// says the caller has that form -- to a compile-time M: runs the statement with M, e.g.
+// SPFM_DISPATCH_KIND(kind_of(degree), true, launch_anova<T, M>(rows, ...)).  False, and nothing
+// run, for any other kind: the caller reports it in its own words.
+template <bool AS, typename F>
+static inline bool dispatch_kind(int kind, F&& f) {
+    switch (kind) {
+        case 0:
+            if constexpr (AS) return f(std::integral_constant<int, 0>{}), true;
+            return false;
+        case 2: return f(std::integral_constant<int, 2>{}), true;
+        case 3: return f(std::integral_constant<int, 3>{}), true;
+        case 4: return f(std::integral_constant<int, 4>{}), true;
+        case 5: return f(std::integral_constant<int, 5>{}), true;
+        case 6: return f(std::integral_constant<int, 6>{}), true;
+        default: return false;
+    }
+}
+#define SPFM_DISPATCH_KIND(kind, AS, ...)               \
+    dispatch_kind<AS>((kind), [&](auto m_) {            \
+        constexpr int M = decltype(m_)::value;          \
+        __VA_ARGS__;                                    \
+    })
 
 static inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
@@ -508,6 +533,27 @@ struct spfm_engine {
         return SPFM_OK;
     }
 
+    // Staged work of the read-only units: `enqueue` issues a call's copies and kernels on `stream`
+    // and returns a status, this waits for them.  Every allocation comes first, in the caller:
+    // once the staging copies are in flight, nothing returns before a sync -- host staging vectors
+    // (and the caller's arrays) may still be read by a copy in flight, so on an error the stream
+    // is synchronised all the same and the first error's message is kept.  After a clean sync the
+    // timer is collected and its time added to *device_us (microseconds, saturating at 2e9).
+    template <typename F>
+    int run_staged(F&& enqueue, DeviceTimer* timer = nullptr, int* device_us = nullptr) {
+        const int rc = enqueue();
+        if (rc) {
+            const std::string first = err;
+            (void)sync();
+            err = first;
+            return rc;
+        }
+        SPFM_TRY(sync());  // staging and the caller's arrays are not read after this
+        if (timer) timer->collect();
+        if (timer && device_us) *device_us = (int)std::min(*device_us + timer->ms * 1e3, 2e9);
+        return SPFM_OK;
+    }
+
     // Rows [r0, r1) of a host CSR matrix into (rp, ri, rv), the values as T (the whole matrix:
     // r0 = 0).  indptr goes up unshifted: a kernel that is given a block r0 > 0 gets the entry
     // base indptr[r0] separately.  The entry buffers hold at least `min_entries` elements.  `hv`
@@ -734,7 +780,7 @@ struct spfm_engine {
     void launch_anova(int64_t rows, const int64_t* rp, const int32_t* ri, const T* rv,
                       const double* Pt_o, double* out);
     template <typename T>
-    int anova_dispatch(int M, int64_t rows, const int64_t* rp, const int32_t* ri, const T* rv,
+    int anova_dispatch(int kind, int64_t rows, const int64_t* rp, const int32_t* ri, const T* rv,
                        const double* Pt_o, double* out);
 
     template <typename T>
@@ -1140,8 +1186,10 @@ struct spfm_engine {
                rk_pairs.bytes;
     }
     void rank_release();  // frees the scratch and forgets the candidates
-    int rank_check_csr(const char* what, int64_t rows, const int64_t* indptr,
-                       const int32_t* indices, const double* data);
+    // a caller's CSR rows before any device work: indptr starts at 0 and does not decrease, no
+    // row longer than max_row_len, column ids in [0, d_)
+    int check_csr(const char* what, int64_t rows, const int64_t* indptr, const int32_t* indices,
+                  const double* data, int d_, int64_t max_row_len);
     template <int M>
     void rank_launch_tower(int64_t row0, int64_t rows, int order_idx, bool lin, int side, int col0,
                            double* img, double* cst);
@@ -1217,9 +1265,10 @@ struct spfm_engine {
     // default).  Its scratch is counted and freed with the explain scratch.
     DevBuf ex_pp, ex_pv;          // pair offsets of one slab (rows + 1) and its pair values
     DevBuf ex_grp, ex_gp, ex_gm;  // group of every column (d); a slab's tables and grouped main
+    enum { PAIRS_LIST = 0, PAIRS_TOPK = 1, PAIRS_GROUPED = 2 };  // the three entries
     struct PairsCall {
         ExplainCall m;  // rows and model; K / idx (first columns) / val of the top-K entry
-        int kind;       // 0: listing, 1: top-K, 2: grouped
+        int kind;       // PAIRS_LIST ...
         int pmode;      // SPFM_PAIRS_INTERACTION / _HESSIAN
         int G;
         const int32_t* group;
@@ -1231,7 +1280,7 @@ struct spfm_engine {
     void pairs_launch_block(int64_t rows, int64_t e0, const double* Pt_o, const double* coef_o,
                             int mode);
     template <typename T>
-    int pairs_slab(const PairsCall& c, int64_t r0, int64_t r1, int64_t q0, int64_t nq);
+    int pairs_slab(const PairsCall& c, const int64_t* pp, int64_t r0, int64_t r1);
     template <typename T>
     int pairs_run(const char* what, const PairsCall& c);
 

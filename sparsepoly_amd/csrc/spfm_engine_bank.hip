@@ -63,25 +63,19 @@ int spfm_engine::bank_set(int32_t d_, int F, const int32_t* koff, int n_blocks,
             FAIL(SPFM_ERR_UNSUPPORTED, "bank_set: degree outside 2..6 and -1 (one block)");
     }
     bank_release();
-    // every allocation first: once the copies are in flight, nothing returns before the sync
     HIPC(bk_pt.alloc(sizeof(double) * (size_t)n_blocks * d_ * S));
     HIPC(bk_lams.alloc(sizeof(double) * (size_t)S));
     HIPC(bk_koff.alloc(sizeof(int32_t) * (size_t)(F + 1)));
     if (w_bank) HIPC(bk_w.alloc(sizeof(double) * (size_t)d_ * F));
-    int rc = upload_to(bk_pt.p, Pt_bank, (size_t)n_blocks * d_ * S);
-    if (!rc) rc = upload_to(bk_lams.p, lams_bank, (size_t)S);
-    if (!rc) rc = upload_to(bk_koff.p, koff, (size_t)(F + 1));
-    if (!rc && w_bank) rc = upload_to(bk_w.p, w_bank, (size_t)d_ * F);
-    const std::string first = err;
-    const int rs = sync();  // the caller's arrays are not read after this
+    const int rc = run_staged([&]() -> int {
+        SPFM_TRY(upload_to(bk_pt.p, Pt_bank, (size_t)n_blocks * d_ * S));
+        SPFM_TRY(upload_to(bk_lams.p, lams_bank, (size_t)S));
+        SPFM_TRY(upload_to(bk_koff.p, koff, (size_t)(F + 1)));
+        return w_bank ? upload_to(bk_w.p, w_bank, (size_t)d_ * F) : SPFM_OK;
+    });
     if (rc) {
-        err = first;
         bank_release();
         return rc;
-    }
-    if (rs) {
-        bank_release();
-        return rs;
     }
     bk_have = true;
     bk_lin = w_bank != nullptr;
@@ -98,24 +92,14 @@ int spfm_engine::bank_set(int32_t d_, int F, const int32_t* koff, int n_blocks,
 int spfm_engine::bank_check(const char* what, const BankCall& c) {
     const std::string w(what);
     if (!bk_have) FAIL(SPFM_ERR_INVALID, w + ": no bank set (spfm_bank_set)");
-    if (c.n < 0 || !c.indptr) FAIL(SPFM_ERR_INVALID, w + ": bad arguments");
+    if (c.n < 0 || !c.indptr) FAIL(SPFM_ERR_INVALID, w + ": bad arguments");  // (ahead of d)
     if (c.d != bk_d) {
         char buf[128];
         snprintf(buf, sizeof buf, "%s: the matrix has d = %d, the bank has d = %d", what, (int)c.d,
                  bk_d);
         FAIL(SPFM_ERR_INVALID, buf);
     }
-    if (c.indptr[0] != 0) FAIL(SPFM_ERR_INVALID, w + ": indptr[0] must be 0");
-    for (int64_t i = 0; i < c.n; ++i) {
-        if (c.indptr[i + 1] < c.indptr[i]) FAIL(SPFM_ERR_INVALID, w + ": indptr is not monotone");
-        if (c.indptr[i + 1] - c.indptr[i] > INT32_MAX)
-            FAIL(SPFM_ERR_UNSUPPORTED, w + ": a row with more than 2^31 - 1 stored entries");
-    }
-    const int64_t nz = c.indptr[c.n];
-    if (nz > 0 && (!c.indices || !c.data)) FAIL(SPFM_ERR_INVALID, w + ": NULL array");
-    for (int64_t ii = 0; ii < nz; ++ii)
-        if (c.indices[ii] < 0 || c.indices[ii] >= bk_d)
-            FAIL(SPFM_ERR_INVALID, w + ": column index out of range");
+    SPFM_TRY(check_csr(what, c.n, c.indptr, c.indices, c.data, bk_d, INT32_MAX));
     if (c.what == BANK_LOSSES) {
         if (c.loss != SPFM_LOSS_SQUARED && c.loss != SPFM_LOSS_SQUARED_HINGE &&
             c.loss != SPFM_LOSS_LOGISTIC)
@@ -146,7 +130,6 @@ template <typename T>
 int spfm_engine::bank_slab(const BankCall& c, int64_t r0, int64_t r1, int64_t part0) {
     const int64_t rows = r1 - r0, e0 = c.indptr[r0];
     const int F = bk_F;
-    // every allocation first: once the staging copies are in flight, nothing returns before a sync
     HIPC(bk_sc.alloc(sizeof(double) * (size_t)rows * F));
     if (c.what == BANK_ARGMAX) {
         HIPC(bk_oi.alloc(sizeof(int32_t) * (size_t)rows));
@@ -156,22 +139,15 @@ int spfm_engine::bank_slab(const BankCall& c, int64_t r0, int64_t r1, int64_t pa
     if (c.what == BANK_MEAN) HIPC(bk_o0.alloc(sizeof(double) * (size_t)rows));
     if (c.what == BANK_LOSSES)
         HIPC(bk_y.alloc(sizeof(double) * (size_t)rows * (c.per_model ? F : 1)));
-    std::vector<T> hv;  // staging of the values: alive until the sync below
-    auto enqueue = [&]() -> int {
+    std::vector<T> hv;  // staging of the values
+    return run_staged([&]() -> int {
         SPFM_TRY(stage_csr_rows<T>(bk_rp, bk_ri, bk_rv, hv, c.indptr, c.indices, c.data, r0, r1));
         if (c.what == BANK_LOSSES)
             SPFM_TRY(upload_to(bk_y.p, c.y + (size_t)r0 * (c.per_model ? F : 1),
                                (size_t)rows * (c.per_model ? F : 1)));
         for (int q = 0; q < bk_blocks; ++q) {
-            const int first = q == 0;
-            switch (bk_degree[q]) {
-                case -1: bank_launch_block<T, 0>(rows, e0, q, first); break;
-                case 2: bank_launch_block<T, 2>(rows, e0, q, first); break;
-                case 3: bank_launch_block<T, 3>(rows, e0, q, first); break;
-                case 4: bank_launch_block<T, 4>(rows, e0, q, first); break;
-                case 5: bank_launch_block<T, 5>(rows, e0, q, first); break;
-                default: bank_launch_block<T, 6>(rows, e0, q, first); break;
-            }
+            (void)SPFM_DISPATCH_KIND(kind_of(bk_degree[q]), true,  // (2..6 or -1: bank_set)
+                                     bank_launch_block<T, M>(rows, e0, q, q == 0));
         }
         const unsigned row_blocks = cdiv(rows, kBlock);
         const double* sc = bk_sc.as<double>();
@@ -195,15 +171,7 @@ int spfm_engine::bank_slab(const BankCall& c, int64_t r0, int64_t r1, int64_t pa
         }
         if (c.what == BANK_MEAN) SPFM_TRY(download(c.out + r0, bk_o0.p, (size_t)rows));
         return SPFM_OK;
-    };
-    const int rc = enqueue();
-    if (rc) {  // keep the first error's message; `hv` may still be read by a copy in flight
-        const std::string first = err;
-        (void)sync();
-        err = first;
-        return rc;
-    }
-    return sync();  // `hv` and the caller's arrays are not read after this
+    });
 }
 
 template <typename T>
@@ -215,13 +183,11 @@ int spfm_engine::bank_run(const char* what, const BankCall& c) {
         if (c.what == BANK_LOSSES) std::fill(c.out, c.out + F, 0.0);
         return SPFM_OK;
     }
-    // the slabs: as many whole rows as fit the entry bound and the row cap, at least one
     const int64_t slab_nnz = bk_slab_nnz > 0 ? bk_slab_nnz : kBankSlabMax;
     const int64_t row_cap = std::max<int64_t>(1, kBankRowBudget / (16 * (int64_t)F));
     std::vector<int64_t> cut{0}, part{0};
     for (int64_t r0 = 0; r0 < c.n;) {
-        int64_t r1 = r0 + 1;
-        while (r1 < c.n && r1 - r0 < row_cap && c.indptr[r1 + 1] - c.indptr[r0] <= slab_nnz) ++r1;
+        const int64_t r1 = slab_end(r0, c.n, row_cap, {c.indptr, slab_nnz});
         cut.push_back(r1);
         part.push_back(part.back() + (r1 - r0 + kBlock - 1) / kBlock);
         r0 = r1;
@@ -231,13 +197,10 @@ int spfm_engine::bank_run(const char* what, const BankCall& c) {
         HIPC(bk_fin.alloc(sizeof(double) * (size_t)F));
     }
     if (c.what == BANK_MEAN) {
-        const std::vector<double> hw((size_t)F, 1.0 / (double)F);
+        const std::vector<double> hw((size_t)F, 1.0 / (double)F);  // staging of the default
         HIPC(bk_wt.alloc(sizeof(double) * (size_t)F));
-        const int rc = upload_to(bk_wt.p, c.wt ? c.wt : hw.data(), (size_t)F);
-        const std::string first = err;
-        const int rs = sync();  // `hw` is not read after this
-        if (rc) err = first;
-        if (rc || rs) return rc ? rc : rs;
+        const double* wt = c.wt ? c.wt : hw.data();
+        SPFM_TRY(run_staged([&] { return upload_to(bk_wt.p, wt, (size_t)F); }));
     }
     for (size_t s = 0; s + 1 < cut.size(); ++s) {
         SPFM_TRY(bank_slab<T>(c, cut[s], cut[s + 1], part[s]));

@@ -718,17 +718,10 @@ void spfm_engine::launch_anova(int64_t rows, const int64_t* rp, const int32_t* r
 }
 
 template <typename T>
-int spfm_engine::anova_dispatch(int M, int64_t rows, const int64_t* rp, const int32_t* ri, const T* rv,
+int spfm_engine::anova_dispatch(int kind, int64_t rows, const int64_t* rp, const int32_t* ri, const T* rv,
                    const double* Pt_o, double* out) {
-    switch (M) {
-        case 0: launch_anova<T, 0>(rows, rp, ri, rv, Pt_o, out); break;
-        case 2: launch_anova<T, 2>(rows, rp, ri, rv, Pt_o, out); break;
-        case 3: launch_anova<T, 3>(rows, rp, ri, rv, Pt_o, out); break;
-        case 4: launch_anova<T, 4>(rows, rp, ri, rv, Pt_o, out); break;
-        case 5: launch_anova<T, 5>(rows, rp, ri, rv, Pt_o, out); break;
-        case 6: launch_anova<T, 6>(rows, rp, ri, rv, Pt_o, out); break;
-        default: FAIL(SPFM_ERR_UNSUPPORTED, "degree outside 2..6");
-    }
+    if (!SPFM_DISPATCH_KIND(kind, true, launch_anova<T, M>(rows, rp, ri, rv, Pt_o, out)))
+        FAIL(SPFM_ERR_UNSUPPORTED, "degree outside 2..6");
     HIPC(hipGetLastError());
     return SPFM_OK;
 }

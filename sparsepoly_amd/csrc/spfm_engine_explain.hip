@@ -44,12 +44,7 @@ int spfm_engine::explain_check_model(const char* what, const ExplainCall& c) {
 }
 
 int spfm_engine::explain_check_rows(const char* what, const ExplainCall& c) {
-    const std::string w(what);
-    SPFM_TRY(rank_check_csr(what, c.n, c.indptr, c.indices, c.data));
-    for (int64_t i = 0; i < c.n; ++i)
-        if (c.indptr[i + 1] - c.indptr[i] > INT32_MAX)
-            FAIL(SPFM_ERR_UNSUPPORTED, w + ": a row with more than 2^31 - 1 stored entries");
-    return SPFM_OK;
+    return check_csr(what, c.n, c.indptr, c.indices, c.data, d, INT32_MAX);
 }
 
 // every check of the two entries, before any device work and before any output is written
@@ -87,16 +82,15 @@ void spfm_engine::explain_launch_block(int64_t rows, int64_t e0, const double* P
 template <typename T>
 int spfm_engine::explain_slab(const ExplainCall& c, int64_t r0, int64_t r1) {
     const int64_t rows = r1 - r0, e0 = c.indptr[r0], ne = c.indptr[r1] - e0;
-    // every allocation first: once the staging copies are in flight, nothing returns before a sync
     HIPC(ex_out.alloc(sizeof(double) * (size_t)ne));
     if (c.out_rowsum) HIPC(ex_rs.alloc(sizeof(double) * (size_t)rows));
     if (c.K > 0) {
         HIPC(ex_ti.alloc(sizeof(int32_t) * (size_t)rows * c.K));
         HIPC(ex_tv.alloc(sizeof(double) * (size_t)rows * c.K));
     }
-    std::vector<T> hv;  // staging of the values: alive until the sync below
+    std::vector<T> hv;  // staging of the values
     DeviceTimer timer;
-    auto enqueue = [&]() -> int {
+    const auto enqueue = [&]() -> int {
         SPFM_TRY(stage_csr_rows<T>(ex_rp, ex_ri, ex_rv, hv, c.indptr, c.indices, c.data, r0, r1));
         timer.begin(stream);
         if (ne > 0) {
@@ -107,13 +101,8 @@ int spfm_engine::explain_slab(const ExplainCall& c, int64_t r0, int64_t r1) {
             for (int q = 0; q < c.n_blocks; ++q) {
                 const double* Pt_o = Pt.as<double>() + (size_t)c.order_idx[q] * k * d;
                 const double* coef_o = ex_coef.as<double>() + (size_t)q * k * kExplainCoefs;
-                switch (c.degree[q]) {
-                    case 2: explain_launch_block<T, 2>(rows, e0, Pt_o, coef_o, c.mode); break;
-                    case 3: explain_launch_block<T, 3>(rows, e0, Pt_o, coef_o, c.mode); break;
-                    case 4: explain_launch_block<T, 4>(rows, e0, Pt_o, coef_o, c.mode); break;
-                    case 5: explain_launch_block<T, 5>(rows, e0, Pt_o, coef_o, c.mode); break;
-                    default: explain_launch_block<T, 6>(rows, e0, Pt_o, coef_o, c.mode); break;
-                }
+                (void)SPFM_DISPATCH_KIND(  // (2..6: explain_check_model)
+                    c.degree[q], false, explain_launch_block<T, M>(rows, e0, Pt_o, coef_o, c.mode));
             }
         }
         const unsigned row_waves = cdiv(rows * kWave, kBlock);
@@ -135,17 +124,7 @@ int spfm_engine::explain_slab(const ExplainCall& c, int64_t r0, int64_t r1) {
         }
         return SPFM_OK;
     };
-    const int rc = enqueue();
-    if (rc) {  // keep the first error's message; `hv` may still be read by a copy in flight
-        const std::string first = err;
-        (void)sync();
-        err = first;
-        return rc;
-    }
-    SPFM_TRY(sync());  // `hv` and the caller's arrays are not read after this
-    timer.collect();
-    ex_device_us = (int)std::min(ex_device_us + timer.ms * 1e3, 2e9);
-    return SPFM_OK;
+    return run_staged(enqueue, &timer, &ex_device_us);
 }
 
 template <typename T>
@@ -162,9 +141,7 @@ int spfm_engine::explain_run(const char* what, const ExplainCall& c) {
     ex_device_us = 0;
     ex_slabs = 0;
     for (int64_t r0 = 0; r0 < c.n;) {
-        // as many whole rows as fit the entry bound, at least one
-        int64_t r1 = r0 + 1;
-        while (r1 < c.n && r1 - r0 < row_cap && c.indptr[r1 + 1] - c.indptr[r0] <= slab_nnz) ++r1;
+        const int64_t r1 = slab_end(r0, c.n, row_cap, {c.indptr, slab_nnz});
         SPFM_TRY(explain_slab<T>(c, r0, r1));
         ++ex_slabs;
         r0 = r1;

@@ -150,7 +150,6 @@ int spfm_engine::foldin_group(const FoldinCall& c, const FoldinPlan& plan, int64
     for (int64_t q = 0; q <= ncg; ++q) hcp[(size_t)q] = plan.cptr[(size_t)(c0 + q)] - q0;
     std::vector<double> hth((size_t)ncg * R), hst((size_t)ncg * 3);
     std::vector<int32_t> hit((size_t)ncg * 2);
-    // every allocation first: once the staging copies are in flight, nothing returns before a sync
     HIPC(fi_Z.alloc(sizeof(double) * (size_t)rows * Rp));
     HIPC(fi_c.alloc(sizeof(double) * (size_t)rows));
     HIPC(fi_theta.alloc(sizeof(double) * (size_t)ncg * R));
@@ -160,7 +159,7 @@ int spfm_engine::foldin_group(const FoldinCall& c, const FoldinPlan& plan, int64
     HIPC(hipFuncSetAttribute((const void*)foldin_solve_kernel,
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     DeviceTimer timer;
-    auto enqueue = [&]() -> int {
+    const auto enqueue = [&]() -> int {
         SPFM_TRY(upload(fi_rp, hp.data(), hp.size()));
         SPFM_TRY(upload(fi_ri, hi.data(), hi.size()));
         SPFM_TRY(upload(fi_rv, hv.data(), hv.size()));
@@ -169,13 +168,9 @@ int spfm_engine::foldin_group(const FoldinCall& c, const FoldinPlan& plan, int64
         SPFM_TRY(upload(fi_cp, hcp.data(), hcp.size()));
         timer.begin(stream);
         if (rows > 0)
-            for (int q = 0; q < c.m.n_blocks; ++q) switch (c.m.degree[q]) {
-                    case 2: foldin_launch_design<T, 2>(rows, q, c, Rp); break;
-                    case 3: foldin_launch_design<T, 3>(rows, q, c, Rp); break;
-                    case 4: foldin_launch_design<T, 4>(rows, q, c, Rp); break;
-                    case 5: foldin_launch_design<T, 5>(rows, q, c, Rp); break;
-                    default: foldin_launch_design<T, 6>(rows, q, c, Rp); break;
-                }
+            for (int q = 0; q < c.m.n_blocks; ++q)
+                (void)SPFM_DISPATCH_KIND(c.m.degree[q], false,  // (2..6: explain_check_model)
+                                         foldin_launch_design<T, M>(rows, q, c, Rp));
         const FoldinSolveArgs a = {R, Rp, c.m.fit_linear ? 1 : 0, c.loss, c.max_iter, c.alpha,
                                    c.beta, c.tol, fi_cp.as<int64_t>(), fi_Z.as<double>(),
                                    fi_c.as<double>(), fi_y.as<double>(), fi_theta.as<double>(),
@@ -188,16 +183,7 @@ int spfm_engine::foldin_group(const FoldinCall& c, const FoldinPlan& plan, int64
         SPFM_TRY(download(hit.data(), fi_it.p, hit.size()));
         return SPFM_OK;
     };
-    const int rc = enqueue();
-    if (rc) {  // keep the first error's message; the staging may still be read by a copy in flight
-        const std::string first = err;
-        (void)sync();
-        err = first;
-        return rc;
-    }
-    SPFM_TRY(sync());
-    timer.collect();
-    fi_device_us = (int)std::min(fi_device_us + timer.ms * 1e3, 2e9);
+    SPFM_TRY(run_staged(enqueue, &timer, &fi_device_us));
     std::copy(hth.begin(), hth.end(), c.theta + (size_t)c0 * R);
     for (int64_t q = 0; q < ncg; ++q) {
         c.n_rows[c0 + q] = hcp[(size_t)q + 1] - hcp[(size_t)q];
@@ -236,9 +222,8 @@ int spfm_engine::foldin_run(const char* what, const FoldinCall& c) {
     int64_t cap = kFoldinBudget / ((int64_t)sizeof(double) * plan.Rp);
     if (fi_max_rows > 0) cap = std::min(cap, fi_max_rows);
     for (int64_t c0 = 0; c0 < c.n_cols;) {
-        // as many whole columns as fit the row bound, at least one
-        int64_t c1 = c0 + 1;
-        while (c1 < c.n_cols && plan.cptr[(size_t)c1 + 1] - plan.cptr[(size_t)c0] <= cap) ++c1;
+        // whole columns, bounded by the rows of their design matrix
+        const int64_t c1 = slab_end(c0, c.n_cols, kSlabNoCap, {plan.cptr.data(), cap});
         SPFM_TRY(foldin_group<T>(c, plan, c0, c1));
         ++fi_groups;
         c0 = c1;

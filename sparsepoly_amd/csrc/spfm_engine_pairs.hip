@@ -32,7 +32,7 @@ int spfm_engine::pairs_check(const char* what, const PairsCall& c) {
     SPFM_TRY(explain_check_model(what, c.m));
     if (c.pmode != SPFM_PAIRS_INTERACTION && c.pmode != SPFM_PAIRS_HESSIAN)
         FAIL(SPFM_ERR_INVALID, w + ": mode must be SPFM_PAIRS_INTERACTION or _HESSIAN");
-    if (c.kind == 1) {
+    if (c.kind == PAIRS_TOPK) {
         if (c.m.K < 1) FAIL(SPFM_ERR_INVALID, w + ": K must be >= 1");
         if (c.m.K > SPFM_PAIRS_MAX_K) {
             snprintf(buf, sizeof buf, "%s: K must be <= SPFM_PAIRS_MAX_K = %d", what,
@@ -40,7 +40,7 @@ int spfm_engine::pairs_check(const char* what, const PairsCall& c) {
             FAIL(SPFM_ERR_UNSUPPORTED, buf);
         }
     }
-    if (c.kind == 2) {
+    if (c.kind == PAIRS_GROUPED) {
         if (c.G < 1) FAIL(SPFM_ERR_INVALID, w + ": G must be >= 1");
         if (c.G > SPFM_PAIRS_MAX_GROUPS) {
             snprintf(buf, sizeof buf, "%s: G must be <= SPFM_PAIRS_MAX_GROUPS = %d", what,
@@ -59,7 +59,7 @@ int spfm_engine::pairs_check(const char* what, const PairsCall& c) {
             FAIL(SPFM_ERR_UNSUPPORTED, w + ": a row with more than 65536 stored entries");
         total += row_pairs(c.m.indptr, i);
     }
-    if (c.kind == 0) {
+    if (c.kind == PAIRS_LIST) {
         if (total > SPFM_PAIRS_MAX_BYTES / (int64_t)sizeof(double)) {
             snprintf(buf, sizeof buf, "%s: %lld pairs to list, more than SPFM_PAIRS_MAX_BYTES",
                      what, (long long)total);
@@ -69,9 +69,9 @@ int spfm_engine::pairs_check(const char* what, const PairsCall& c) {
         if (c.out_main && c.pmode != SPFM_PAIRS_INTERACTION)
             FAIL(SPFM_ERR_INVALID, w + ": out_main belongs to SPFM_PAIRS_INTERACTION");
     }
-    if (c.m.n > 0 && c.kind == 1 && (!c.m.idx || !c.col_b || !c.m.val))
+    if (c.m.n > 0 && c.kind == PAIRS_TOPK && (!c.m.idx || !c.col_b || !c.m.val))
         FAIL(SPFM_ERR_INVALID, w + ": NULL output");
-    if (c.m.n > 0 && c.kind == 2 && (!c.out_pairs || !c.out_main))
+    if (c.m.n > 0 && c.kind == PAIRS_GROUPED && (!c.out_pairs || !c.out_main))
         FAIL(SPFM_ERR_INVALID, w + ": NULL output");
     return SPFM_OK;
 }
@@ -85,31 +85,31 @@ void spfm_engine::pairs_launch_block(int64_t rows, int64_t e0, const double* Pt_
                        ex_pv.as<double>());
 }
 
-// rows [r0, r1), nq pairs, the first of them pair q0 of the call: stage, main, the blocks in the
-// caller's order, top-K or tables, copy back
+// rows [r0, r1), pp the pair offsets of the call's rows: stage, main, the blocks in the caller's
+// order, top-K or tables, copy back
 template <typename T>
-int spfm_engine::pairs_slab(const PairsCall& c, int64_t r0, int64_t r1, int64_t q0, int64_t nq) {
+int spfm_engine::pairs_slab(const PairsCall& c, const int64_t* pp, int64_t r0, int64_t r1) {
     const ExplainCall& m = c.m;
     const int64_t rows = r1 - r0, e0 = m.indptr[r0], ne = m.indptr[r1] - e0;
-    const bool want_main = c.kind == 2 || c.out_main != nullptr;
+    const int64_t q0 = pp[r0], nq = pp[r1] - q0;
+    const bool want_main = c.kind == PAIRS_GROUPED || c.out_main != nullptr;
     const int cells = c.G * (c.G + 1) / 2;
-    std::vector<int64_t> hp((size_t)rows + 1, 0);  // alive until the sync below, as `hv`
-    for (int64_t i = 0; i < rows; ++i) hp[(size_t)i + 1] = hp[(size_t)i] + row_pairs(m.indptr, r0 + i);
-    // every allocation first: once the staging copies are in flight, nothing returns before a sync
+    std::vector<int64_t> hp((size_t)rows + 1);  // the slab's pair offsets, from 0: staging as `hv`
+    for (int64_t i = 0; i <= rows; ++i) hp[(size_t)i] = pp[r0 + i] - q0;
     HIPC(ex_pv.alloc(sizeof(double) * (size_t)nq));
     HIPC(ex_pp.alloc(sizeof(int64_t) * ((size_t)rows + 1)));
     if (want_main) HIPC(ex_out.alloc(sizeof(double) * (size_t)ne));
-    if (c.kind == 1) {
+    if (c.kind == PAIRS_TOPK) {
         HIPC(ex_ti.alloc(sizeof(int32_t) * (size_t)rows * m.K * 2));
         HIPC(ex_tv.alloc(sizeof(double) * (size_t)rows * m.K));
     }
-    if (c.kind == 2) {
+    if (c.kind == PAIRS_GROUPED) {
         HIPC(ex_gp.alloc(sizeof(double) * (size_t)rows * cells));
         HIPC(ex_gm.alloc(sizeof(double) * (size_t)rows * c.G));
     }
     std::vector<T> hv;
     DeviceTimer timer;
-    auto enqueue = [&]() -> int {
+    const auto enqueue = [&]() -> int {
         SPFM_TRY(stage_csr_rows<T>(ex_rp, ex_ri, ex_rv, hv, m.indptr, m.indices, m.data, r0, r1));
         SPFM_TRY(upload_to(ex_pp.p, hp.data(), hp.size()));
         timer.begin(stream);
@@ -127,31 +127,26 @@ int spfm_engine::pairs_slab(const PairsCall& c, int64_t r0, int64_t r1, int64_t 
                                    stream, ne, k, ex_ri.as<int32_t>(), ex_rv.as<T>(), Pt_o,
                                    lams.as<double>(), coef_o, ex_out.as<double>());
             if (nq == 0) continue;
-            switch (m.degree[q]) {
-                case 2: pairs_launch_block<T, 2>(rows, e0, Pt_o, coef_o, c.pmode); break;
-                case 3: pairs_launch_block<T, 3>(rows, e0, Pt_o, coef_o, c.pmode); break;
-                case 4: pairs_launch_block<T, 4>(rows, e0, Pt_o, coef_o, c.pmode); break;
-                case 5: pairs_launch_block<T, 5>(rows, e0, Pt_o, coef_o, c.pmode); break;
-                default: pairs_launch_block<T, 6>(rows, e0, Pt_o, coef_o, c.pmode); break;
-            }
+            (void)SPFM_DISPATCH_KIND(m.degree[q], false,  // (2..6: explain_check_model)
+                                     pairs_launch_block<T, M>(rows, e0, Pt_o, coef_o, c.pmode));
         }
         const unsigned row_waves = cdiv(rows * kWave, kBlock);
-        if (c.kind == 1)
+        if (c.kind == PAIRS_TOPK)
             hipLaunchKernelGGL(pairs_topk_kernel, dim3(row_waves), dim3(kBlock), 0, stream, rows,
                                e0, ex_rp.as<int64_t>(), ex_ri.as<int32_t>(), ex_pp.as<int64_t>(),
                                ex_pv.as<double>(), m.K, ex_ti.as<int32_t>(),
                                ex_ti.as<int32_t>() + (size_t)rows * m.K, ex_tv.as<double>());
-        if (c.kind == 2)
+        if (c.kind == PAIRS_GROUPED)
             hipLaunchKernelGGL(pairs_group_kernel, dim3(row_waves), dim3(kBlock), 0, stream, rows,
                                e0, ex_rp.as<int64_t>(), ex_ri.as<int32_t>(), ex_pp.as<int64_t>(),
                                ex_pv.as<double>(), ex_out.as<double>(), c.G, ex_grp.as<int32_t>(),
                                ex_gp.as<double>(), ex_gm.as<double>());
         HIPC(hipGetLastError());
         timer.end(stream);
-        if (c.kind == 0) {
+        if (c.kind == PAIRS_LIST) {
             SPFM_TRY(download(c.out_pairs + q0, ex_pv.p, (size_t)nq));
             if (c.out_main) SPFM_TRY(download(c.out_main + e0, ex_out.p, (size_t)ne));
-        } else if (c.kind == 1) {
+        } else if (c.kind == PAIRS_TOPK) {
             const size_t cnt = (size_t)rows * m.K;
             SPFM_TRY(download(m.idx + (size_t)r0 * m.K, ex_ti.p, cnt));
             SPFM_TRY(download(c.col_b + (size_t)r0 * m.K, ex_ti.as<int32_t>() + cnt, cnt));
@@ -162,17 +157,7 @@ int spfm_engine::pairs_slab(const PairsCall& c, int64_t r0, int64_t r1, int64_t 
         }
         return SPFM_OK;
     };
-    const int rc = enqueue();
-    if (rc) {  // keep the first error's message; `hv`, `hp` may still be read by a copy in flight
-        const std::string first = err;
-        (void)sync();
-        err = first;
-        return rc;
-    }
-    SPFM_TRY(sync());  // `hv`, `hp` and the caller's arrays are not read after this
-    timer.collect();
-    ex_device_us = (int)std::min(ex_device_us + timer.ms * 1e3, 2e9);
-    return SPFM_OK;
+    return run_staged(enqueue, &timer, &ex_device_us);
 }
 
 template <typename T>
@@ -184,26 +169,21 @@ int spfm_engine::pairs_run(const char* what, const PairsCall& c) {
     pt_valid = false;  // P is the source of truth here, as in output_t
     SPFM_TRY(ensure_pt());
     SPFM_TRY(upload(ex_coef, m.coef, (size_t)m.n_blocks * k * kExplainCoefs));
-    if (c.kind == 2) SPFM_TRY(upload(ex_grp, c.group, (size_t)d));
+    if (c.kind == PAIRS_GROUPED) SPFM_TRY(upload(ex_grp, c.group, (size_t)d));
     const int64_t slab_nnz = ex_slab_nnz > 0 ? ex_slab_nnz : kExplainSlabMax;
     const int64_t slab_pairs = 2 * slab_nnz;  // 2^24 at the default
     const int64_t cells = (int64_t)c.G * (c.G + 1) / 2;
     const int64_t row_cap =
         std::max<int64_t>(1, kPairsRowBudget / (24 + 16 * (int64_t)m.K + 8 * (cells + c.G)));
+    std::vector<int64_t> pp((size_t)m.n + 1, 0);  // pair offsets of the call's rows
+    for (int64_t i = 0; i < m.n; ++i) pp[(size_t)i + 1] = pp[(size_t)i] + row_pairs(m.indptr, i);
     ex_device_us = 0;
     ex_slabs = 0;
-    int64_t q0 = 0;
     for (int64_t r0 = 0; r0 < m.n;) {
-        // as many whole rows as fit the entry bound and the pair bound, at least one
-        int64_t r1 = r0 + 1, nq = row_pairs(m.indptr, r0);
-        while (r1 < m.n && r1 - r0 < row_cap && m.indptr[r1 + 1] - m.indptr[r0] <= slab_nnz &&
-               nq + row_pairs(m.indptr, r1) <= slab_pairs) {
-            nq += row_pairs(m.indptr, r1);
-            ++r1;
-        }
-        SPFM_TRY(pairs_slab<T>(c, r0, r1, q0, nq));
+        const int64_t r1 =
+            slab_end(r0, m.n, row_cap, {m.indptr, slab_nnz}, {pp.data(), slab_pairs});
+        SPFM_TRY(pairs_slab<T>(c, pp.data(), r0, r1));
         ++ex_slabs;
-        q0 += nq;
         r0 = r1;
     }
     return SPFM_OK;
@@ -219,7 +199,7 @@ int spfm_explain_pairs_csr(spfm_handle h, int64_t n, const int64_t* indptr, cons
     const spfm_engine::PairsCall c = {
         {n, indptr, indices, data, n_blocks, order_idx, degree, coef, fit_linear,
          SPFM_EXPLAIN_ATTRIBUTION, nullptr, nullptr, false, 0, nullptr, nullptr},
-        0, mode, 0, nullptr, out_pairs, out_main, nullptr};
+        spfm_engine::PAIRS_LIST, mode, 0, nullptr, out_pairs, out_main, nullptr};
     return SPFM_DISPATCH(h->dtype, return h->pairs_run<T>("explain_pairs_csr", c));
 }
 
@@ -232,7 +212,7 @@ int spfm_explain_pairs_topk_csr(spfm_handle h, int64_t n, const int64_t* indptr,
     const spfm_engine::PairsCall c = {
         {n, indptr, indices, data, n_blocks, order_idx, degree, coef, fit_linear,
          SPFM_EXPLAIN_ATTRIBUTION, nullptr, nullptr, true, K, col_a, val},
-        1, mode, 0, nullptr, nullptr, nullptr, col_b};
+        spfm_engine::PAIRS_TOPK, mode, 0, nullptr, nullptr, nullptr, col_b};
     return SPFM_DISPATCH(h->dtype, return h->pairs_run<T>("explain_pairs_topk_csr", c));
 }
 
@@ -245,7 +225,7 @@ int spfm_explain_pairs_grouped_csr(spfm_handle h, int64_t n, const int64_t* indp
     const spfm_engine::PairsCall c = {
         {n, indptr, indices, data, n_blocks, order_idx, degree, coef, fit_linear,
          SPFM_EXPLAIN_ATTRIBUTION, nullptr, nullptr, false, 0, nullptr, nullptr},
-        2, SPFM_PAIRS_INTERACTION, G, group, out_pairs, out_main, nullptr};
+        spfm_engine::PAIRS_GROUPED, SPFM_PAIRS_INTERACTION, G, group, out_pairs, out_main, nullptr};
     return SPFM_DISPATCH(h->dtype, return h->pairs_run<T>("explain_pairs_grouped_csr", c));
 }
 

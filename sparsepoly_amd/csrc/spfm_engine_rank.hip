@@ -28,19 +28,22 @@ void spfm_engine::rank_release() {
     rk_C = 0;
 }
 
-// indptr starts at 0 and does not decrease, column ids in [0, d)
-int spfm_engine::rank_check_csr(const char* what, int64_t rows, const int64_t* indptr,
-                                const int32_t* indices, const double* data) {
-    if (rows < 0 || !indptr) FAIL(SPFM_ERR_INVALID, std::string(what) + ": bad arguments");
-    if (indptr[0] != 0) FAIL(SPFM_ERR_INVALID, std::string(what) + ": indptr[0] must be 0");
-    for (int64_t i = 0; i < rows; ++i)
-        if (indptr[i + 1] < indptr[i])
-            FAIL(SPFM_ERR_INVALID, std::string(what) + ": indptr is not monotone");
+int spfm_engine::check_csr(const char* what, int64_t rows, const int64_t* indptr,
+                           const int32_t* indices, const double* data, int d_,
+                           int64_t max_row_len) {
+    const std::string w(what);
+    if (rows < 0 || !indptr) FAIL(SPFM_ERR_INVALID, w + ": bad arguments");
+    if (indptr[0] != 0) FAIL(SPFM_ERR_INVALID, w + ": indptr[0] must be 0");
+    for (int64_t i = 0; i < rows; ++i) {
+        if (indptr[i + 1] < indptr[i]) FAIL(SPFM_ERR_INVALID, w + ": indptr is not monotone");
+        if (indptr[i + 1] - indptr[i] > max_row_len)  // (the one cap in use: INT32_MAX)
+            FAIL(SPFM_ERR_UNSUPPORTED, w + ": a row with more than 2^31 - 1 stored entries");
+    }
     const int64_t nz = indptr[rows];
-    if (nz > 0 && (!indices || !data)) FAIL(SPFM_ERR_INVALID, std::string(what) + ": NULL array");
+    if (nz > 0 && (!indices || !data)) FAIL(SPFM_ERR_INVALID, w + ": NULL array");
     for (int64_t ii = 0; ii < nz; ++ii)
-        if (indices[ii] < 0 || indices[ii] >= d)
-            FAIL(SPFM_ERR_INVALID, std::string(what) + ": column index out of range");
+        if (indices[ii] < 0 || indices[ii] >= d_)
+            FAIL(SPFM_ERR_INVALID, w + ": column index out of range");
     return SPFM_OK;
 }
 
@@ -60,15 +63,9 @@ int spfm_engine::rank_towers(int64_t row0, int64_t rows, int side, double* img, 
     HIPC(hipMemsetAsync(img, 0, sizeof(double) * (size_t)pad * rk_Rp, stream));
     HIPC(hipMemsetAsync(cst, 0, sizeof(double) * (size_t)pad, stream));
     const bool lin = rk_lin != 0;
-    switch (kind_of(rk_degree)) {
-        case 0: rank_launch_tower<0>(row0, rows, 0, false, side, 0, img, cst); break;
-        case 2: rank_launch_tower<2>(row0, rows, 0, lin, side, 0, img, cst); break;
-        case 3: rank_launch_tower<3>(row0, rows, 0, lin, side, 0, img, cst); break;
-        case 4: rank_launch_tower<4>(row0, rows, 0, lin, side, 0, img, cst); break;
-        case 5: rank_launch_tower<5>(row0, rows, 0, lin, side, 0, img, cst); break;
-        case 6: rank_launch_tower<6>(row0, rows, 0, lin, side, 0, img, cst); break;
-        default: FAIL(SPFM_ERR_UNSUPPORTED, "rank: degree outside 2..6 and -1");
-    }
+    if (!SPFM_DISPATCH_KIND(kind_of(rk_degree), true,  // (all-subsets: no linear term)
+                            rank_launch_tower<M>(row0, rows, 0, M != 0 && lin, side, 0, img, cst)))
+        FAIL(SPFM_ERR_UNSUPPORTED, "rank: degree outside 2..6 and -1");
     if (rk_lower)  // the order-2 term on P[1]
         rank_launch_tower<2>(row0, rows, 1, false, side, k * (rk_degree - 1), img, cst);
     HIPC(hipGetLastError());
@@ -86,7 +83,7 @@ int spfm_engine::rank_set_candidates(int degree, int fit_linear, int add_lower, 
     if (n_cand < 1) FAIL(SPFM_ERR_INVALID, "rank_set_candidates: n_cand must be >= 1");
     if (n_cand > INT32_MAX - kIntTile)
         FAIL(SPFM_ERR_UNSUPPORTED, "rank_set_candidates: more than 2^31 - 65 candidates");
-    SPFM_TRY(rank_check_csr("rank_set_candidates", n_cand, indptr, indices, data));
+    SPFM_TRY(check_csr("rank_set_candidates", n_cand, indptr, indices, data, d, INT64_MAX));
     const int64_t R = (degree == -1 ? (int64_t)k : (int64_t)k * (degree - 1)) + (add_lower ? k : 0);
     const int64_t Rp = round_up(R, 4), pad = round_up(n_cand, kIntTile);
     rank_release();
@@ -115,7 +112,7 @@ int spfm_engine::rank_contexts(const char* what, int64_t n_ctx, const int64_t* i
                                const int32_t* indices, const double* data) {
     if (!have_params) FAIL(SPFM_ERR_INVALID, std::string(what) + ": no parameters set");
     if (!rk_have) FAIL(SPFM_ERR_INVALID, std::string(what) + ": call spfm_rank_set_candidates first");
-    SPFM_TRY(rank_check_csr(what, n_ctx, indptr, indices, data));
+    SPFM_TRY(check_csr(what, n_ctx, indptr, indices, data, d, INT64_MAX));
     const int64_t nz = indptr[n_ctx];
     for (int64_t ii = 0; ii < nz; ++ii)
         if (rk_zflag[(size_t)indices[ii]]) {

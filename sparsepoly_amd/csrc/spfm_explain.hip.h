@@ -19,14 +19,6 @@ constexpr int kExplainChunk = 64;  // components per LDS table: one per lane of 
 constexpr int kExplainCoefs = 7;   // c[s][0..6], column 0 unused on the device
 enum { EXPLAIN_ATTRIBUTION = 0, EXPLAIN_GRADIENT = 1 };
 
-// LDS written by some lanes of a wave, read by others of the same wave: the wave's LDS
-// operations complete in order; this keeps the compiler from moving them across the point
-__device__ __forceinline__ void explain_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 // out[e] = w_j x_e (attribution), w_j (gradient) or 0 (no linear term): the first term of every
 // entry, the blocks add to it in launch order
 template <typename T>
@@ -68,14 +60,10 @@ __global__ __launch_bounds__(kBlock) void explain_block_kernel(
         const int s = s0 + lane;
         if (s < k) {
             double a[M];
-            a[0] = 1.0;
-#pragma unroll
-            for (int t = 1; t < M; ++t) a[t] = 0.0;
-            for (int64_t ii = b; ii < e; ++ii) {
-                const double px = Pt[(size_t)ridx[ii] * k + s] * (double)rval[ii];
-#pragma unroll
-                for (int t = M - 1; t >= 1; --t) a[t] += a[t - 1] * px;
-            }
+            anova_dp_init<M - 1>(a);
+            anova_dp_add<M - 1>(a, b, e, [&](int64_t ii) {
+                return Pt[(size_t)ridx[ii] * k + s] * (double)rval[ii];
+            });
 #pragma unroll
             for (int t = 1; t < M; ++t) tw[t - 1][lane] = a[t];
             const double lam = lams[s];
@@ -86,7 +74,7 @@ __global__ __launch_bounds__(kBlock) void explain_block_kernel(
                 tw[M - 2 + t][lane] = lam * c;
             }
         }
-        explain_wave_sync();
+        wave_lds_sync();
         const int ns = (k - s0 < kExplainChunk) ? k - s0 : kExplainChunk;
         for (int64_t ii = b + lane; ii < e; ii += kWave) {
             const double x = (double)rval[ii];
@@ -105,7 +93,7 @@ __global__ __launch_bounds__(kBlock) void explain_block_kernel(
             if (mode == EXPLAIN_ATTRIBUTION) acc *= x;
             out[ii] += acc;
         }
-        explain_wave_sync();  // the next chunk overwrites the table
+        wave_lds_sync();  // the next chunk overwrites the table
     }
 }
 
@@ -144,28 +132,25 @@ __device__ __forceinline__ void explain_take(ExplainKey& best, const ExplainKey&
     best.val = take ? c.val : best.val;
 }
 
-// The min(K, n_i) entries of every row largest by |value|, in that order; the rest of the K slots
-// hold column -1 and value 0.  One wave per row, one exact selection round per slot: every lane
-// finds the best of its entries (l, l + 64, ...) that come strictly after the previous winner,
-// a butterfly over the lanes picks the round's winner.  Integer comparisons only.
-static __global__ __launch_bounds__(kBlock) void explain_topk_kernel(
-    int64_t rows, int64_t e0, const int64_t* __restrict__ rptr, const int32_t* __restrict__ ridx,
-    const double* __restrict__ vals, int K, int32_t* __restrict__ oidx,
-    double* __restrict__ oval) {
-    const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    const int64_t b = rptr[row] - e0;
-    const int n = (int)(rptr[row + 1] - e0 - b);  // (the host refuses longer rows)
-    int32_t* oi = oidx + (size_t)row * K;
-    double* ov = oval + (size_t)row * K;
-    ExplainKey prev = {INT64_MAX, -1, -1, 0.0};  // every entry comes after it
+// The per-row exact top-K of this unit and of the pair attributions: one wave selects the
+// min(K, n) of a row's n values largest by |value|, in that order.  One exact selection round per
+// slot: every lane finds the best of its values (l, l + 64, ...) that come strictly after the
+// previous winner, a butterfly over the lanes picks the round's winner.  Integer comparisons only.
+// col_of(p) is the key column of position p; COL = false: it is 0 for all (the order is by
+// position alone) and is not carried through the butterfly.  Lane 0 calls write(q, best) for
+// every slot; a slot past the row's values gets mag = pos = -1, val = 0 and column -1 (COL) or 0.
+// (Not the streaming selection of spfm_select.hip.h: that one keeps sorted lists per strip and
+// breaks ties by candidate id -- another algorithm with other tie rules.)
+template <bool COL, typename ColFn, typename WriteFn>
+__device__ __forceinline__ void explain_select(const double* __restrict__ vals, int n, int K,
+                                               int lane, ColFn&& col_of, WriteFn&& write) {
+    ExplainKey prev = {INT64_MAX, -1, -1, 0.0};  // every value comes after it
     for (int q = 0; q < K; ++q) {
-        ExplainKey best = {-1, -1, -1, 0.0};
+        ExplainKey best = {-1, COL ? -1 : 0, -1, 0.0};
         if (q < n) {
             for (int p = lane; p < n; p += kWave) {
-                const double v = vals[b + p];
-                const ExplainKey c = {__double_as_longlong(fabs(v)), ridx[b + p], p, v};
+                const double v = vals[p];
+                const ExplainKey c = {__double_as_longlong(fabs(v)), col_of(p), p, v};
                 const bool after = explain_beats(prev, c), wins = explain_beats(c, best);
                 explain_take(best, c, after && wins);
             }
@@ -173,18 +158,35 @@ static __global__ __launch_bounds__(kBlock) void explain_topk_kernel(
             for (int m = 32; m >= 1; m >>= 1) {
                 ExplainKey o;
                 o.mag = __shfl_xor(best.mag, m, kWave);
-                o.col = __shfl_xor(best.col, m, kWave);
+                o.col = COL ? __shfl_xor(best.col, m, kWave) : best.col;
                 o.pos = __shfl_xor(best.pos, m, kWave);
                 o.val = __shfl_xor(best.val, m, kWave);
                 explain_take(best, o, explain_beats(o, best));
             }
-            prev = best;  // (q < n: there was an entry left, in every lane's view the same)
+            prev = best;  // (q < n: there was a value left, in every lane's view the same)
         }
-        if (lane == 0) {
+        if (lane == 0) write(q, best);
+    }
+}
+
+// The min(K, n_i) entries of every row largest by |value|, in that order; the rest of the K slots
+// hold column -1 and value 0.  One wave per row; the order is (|value|, column, position).
+static __global__ __launch_bounds__(kBlock) void explain_topk_kernel(
+    int64_t rows, int64_t e0, const int64_t* __restrict__ rptr, const int32_t* __restrict__ ridx,
+    const double* __restrict__ vals, int K, int32_t* __restrict__ oidx,
+    double* __restrict__ oval) {
+    const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    if (row >= rows) return;
+    const int64_t b = rptr[row] - e0;
+    const int n = (int)(rptr[row + 1] - e0 - b);  // (the host refuses longer rows)
+    int32_t* oi = oidx + (size_t)row * K;
+    double* ov = oval + (size_t)row * K;
+    explain_select<true>(
+        vals + b, n, K, threadIdx.x & 63, [&](int p) { return ridx[b + p]; },
+        [&](int q, const ExplainKey& best) {
             oi[q] = best.col;
             ov[q] = best.val;
-        }
-    }
+        });
 }
 
 }  // namespace spfm

@@ -57,16 +57,15 @@ __global__ __launch_bounds__(kBlock) void foldin_design_kernel(
         const int s = s0 + lane;
         double v = 0.0;
         if (s < k) {
+            const auto px = [&](int64_t ii) {
+                return Pt[(size_t)ridx[ii] * k + s] * (double)rval[ii];
+            };
             double a[M + 1];
-            a[0] = 1.0;
-#pragma unroll
-            for (int t = 1; t <= M; ++t) a[t] = 0.0;
-            for (int64_t ii = b; ii < e; ++ii) {
-                if (ii == tt) continue;  // (wave-uniform)
-                const double px = Pt[(size_t)ridx[ii] * k + s] * (double)rval[ii];
-#pragma unroll
-                for (int t = M; t >= 1; --t) a[t] += a[t - 1] * px;
-            }
+            anova_dp_init<M>(a);
+            // the row without its target entry: [b, tt), then [tt + 1, e) -- one copy of the loop
+#pragma nounroll
+            for (int half = 0; half < 2; ++half)
+                anova_dp_add<M>(a, half ? tt + 1 : b, half ? e : tt, px);
             const double* __restrict__ cs = coef + (size_t)s * kFoldinCoefs;
             const double lam = lams[s];
             double zs = 0.0, cv = cs[0];

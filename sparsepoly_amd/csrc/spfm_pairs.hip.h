@@ -94,14 +94,10 @@ __global__ __launch_bounds__(kBlock) void pairs_block_kernel(
         if (s < k) {
             if constexpr (M > 2) {
                 double a[M - 1];
-                a[0] = 1.0;
-#pragma unroll
-                for (int t = 1; t < M - 1; ++t) a[t] = 0.0;
-                for (int64_t ii = b; ii < e; ++ii) {
-                    const double px = Pt[(size_t)ridx[ii] * k + s] * (double)rval[ii];
-#pragma unroll
-                    for (int t = M - 2; t >= 1; --t) a[t] += a[t - 1] * px;
-                }
+                anova_dp_init<M - 2>(a);
+                anova_dp_add<M - 2>(a, b, e, [&](int64_t ii) {
+                    return Pt[(size_t)ridx[ii] * k + s] * (double)rval[ii];
+                });
 #pragma unroll
                 for (int t = 1; t < M - 1; ++t) tw[t - 1][lane] = a[t];
             }
@@ -113,7 +109,7 @@ __global__ __launch_bounds__(kBlock) void pairs_block_kernel(
                 tw[NA + t - 2][lane] = lam * c;
             }
         }
-        explain_wave_sync();
+        wave_lds_sync();
         const int ns = (k - s0 < kExplainChunk) ? k - s0 : kExplainChunk;
         for (int q0 = 0; q0 < np; q0 += kWave) {  // (np < 2^31 - 64: no overflow)
             const int q = q0 + lane;
@@ -143,51 +139,30 @@ __global__ __launch_bounds__(kBlock) void pairs_block_kernel(
                 out[q] += acc;
             }
         }
-        explain_wave_sync();  // the next chunk overwrites the table
+        wave_lds_sync();  // the next chunk overwrites the table
     }
 }
 
 // The min(K, pairs of the row) pairs of every row largest by |value|, in that order; the rest of
-// the K slots hold columns -1, -1 and value 0.  The selection rounds of explain_topk_kernel over
-// the row's pair values with the order (|value| descending, pair index ascending): the key's
-// column is the same for all, its position is the pair index.  The winner's index is turned into
-// the two columns when it is written.
+// the K slots hold columns -1, -1 and value 0.  explain_select (spfm_explain.hip.h) over the row's
+// pair values with the order (|value| descending, pair index ascending): the key's column is the
+// same for all, its position is the pair index.  The winner's index is turned into the two
+// columns when it is written.
 static __global__ __launch_bounds__(kBlock) void pairs_topk_kernel(
     int64_t rows, int64_t e0, const int64_t* __restrict__ rptr, const int32_t* __restrict__ ridx,
     const int64_t* __restrict__ pptr, const double* __restrict__ pv, int K,
     int32_t* __restrict__ ocola, int32_t* __restrict__ ocolb, double* __restrict__ oval) {
     const int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
     if (row >= rows) return;
     const int64_t b = rptr[row] - e0;
     const int n = (int)(rptr[row + 1] - e0 - b);
     const int np = (int)(pptr[row + 1] - pptr[row]);
-    const double* __restrict__ vals = pv + pptr[row];
     int32_t* oa = ocola + (size_t)row * K;
     int32_t* ob = ocolb + (size_t)row * K;
     double* ov = oval + (size_t)row * K;
-    ExplainKey prev = {INT64_MAX, -1, -1, 0.0};  // every pair comes after it
-    for (int r = 0; r < K; ++r) {
-        ExplainKey best = {-1, 0, -1, 0.0};
-        if (r < np) {
-            for (int q = lane; q < np; q += kWave) {
-                const double v = vals[q];
-                const ExplainKey c = {__double_as_longlong(fabs(v)), 0, q, v};
-                const bool after = explain_beats(prev, c), wins = explain_beats(c, best);
-                explain_take(best, c, after && wins);
-            }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                ExplainKey o;
-                o.mag = __shfl_xor(best.mag, m, kWave);
-                o.col = 0;
-                o.pos = __shfl_xor(best.pos, m, kWave);
-                o.val = __shfl_xor(best.val, m, kWave);
-                explain_take(best, o, explain_beats(o, best));
-            }
-            prev = best;  // (r < np: there was a pair left, in every lane's view the same)
-        }
-        if (lane == 0) {
+    explain_select<false>(
+        pv + pptr[row], np, K, threadIdx.x & 63, [](int) { return 0; },
+        [&](int r, const ExplainKey& best) {
             int ca = -1, cb = -1;
             if (r < np) {
                 int ia, ib;
@@ -198,8 +173,7 @@ static __global__ __launch_bounds__(kBlock) void pairs_topk_kernel(
             oa[r] = ca;
             ob[r] = cb;
             ov[r] = best.val;
-        }
-    }
+        });
 }
 
 // Per row the upper-triangular G x G table of its pair values by the groups of the two members,

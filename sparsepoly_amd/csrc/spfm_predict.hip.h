@@ -32,21 +32,15 @@ __global__ __launch_bounds__(kBlock) void anova_predict_kernel(
     double acc = 0.0;
     const int64_t b = rptr[row], e = rptr[row + 1];
     for (int s = lane; s < k; s += kWave) {
+        const auto px = [&](int64_t ii) { return Pt[(size_t)ridx[ii] * k + s] * (double)rval[ii]; };
         if constexpr (M == 0) {  // all-subsets kernel, kernels.py:117-137
             double a = 1.0;
-            for (int64_t ii = b; ii < e; ++ii)
-                a *= 1 + (double)rval[ii] * Pt[(size_t)ridx[ii] * k + s];
+            subsets_dp_add(a, b, e, px);
             acc += a * lams[s];
         } else {
             double a[M + 1];
-            a[0] = 1.0;
-#pragma unroll
-            for (int t = 1; t <= M; ++t) a[t] = 0.0;
-            for (int64_t ii = b; ii < e; ++ii) {
-                const double px = Pt[(size_t)ridx[ii] * k + s] * (double)rval[ii];
-#pragma unroll
-                for (int t = M; t >= 1; --t) a[t] += a[t - 1] * px;
-            }
+            anova_dp_init<M>(a);
+            anova_dp_add<M>(a, b, e, px);
             acc += a[M] * lams[s];
         }
     }

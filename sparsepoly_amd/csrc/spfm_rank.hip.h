@@ -72,21 +72,17 @@ __global__ __launch_bounds__(kBlock) void tower_kernel(
     double acc = 0.0;
     for (int s = lane; s < k; s += kWave) {
         const double lam = lams[s];
+        const auto px = [&](int64_t ii) {
+            return base[s * ss + (int64_t)ridx[ii] * sj] * (double)rval[ii];
+        };
         if constexpr (M == 0) {
             double a = 1.0;
-            for (int64_t ii = b; ii < e; ++ii)
-                a *= 1 + (double)rval[ii] * base[s * ss + (int64_t)ridx[ii] * sj];
+            subsets_dp_add(a, b, e, px);
             out[s] = (side == RANK_CTX) ? lam * a : a;
         } else {
             double a[M + 1];
-            a[0] = 1.0;
-#pragma unroll
-            for (int t = 1; t <= M; ++t) a[t] = 0.0;
-            for (int64_t ii = b; ii < e; ++ii) {
-                const double px = base[s * ss + (int64_t)ridx[ii] * sj] * (double)rval[ii];
-#pragma unroll
-                for (int t = M; t >= 1; --t) a[t] += a[t - 1] * px;
-            }
+            anova_dp_init<M>(a);
+            anova_dp_add<M>(a, b, e, px);
 #pragma unroll
             for (int t = 1; t < M; ++t)
                 out[(size_t)(t - 1) * k + s] = (side == RANK_CTX) ? lam * a[t] : a[M - t];
