@@ -280,6 +280,43 @@ int spfm_psgd_pairs_epoch(spfm_handle h, int degree, double alpha, double beta, 
 int spfm_psgd_pairs_eval(spfm_handle h, int degree, int fit_linear, const int32_t* triples,
                          int64_t m, double* sum_loss, int64_t* n_ordered);
 
+/* Negatives of the pairwise fit drawn on the device.  Rows [0, n_ctx) of
+ * the handle's data are the contexts and the next n_cand rows the candidates (n_ctx + n_cand ==
+ * n).  pos_ptr / pos_idx: the positives as a CSR over (n_ctx, n_cand); forb_ptr / forb_idx: the
+ * candidates that may not be drawn for a context, a CSR of the same shape that contains the
+ * positives (NULL, NULL: the positives themselves).  Both are uploaded once and stay until the next
+ * spfm_set_data_* / spfm_share_data.  Checked once, on the host (SPFM_ERR_INVALID): n_ctx + n_cand
+ * != n, no positive, an index outside [0, n_cand) or not strictly ascending within its row, a
+ * positive the forbidden set lacks, a context with a positive whose row forbids all n_cand
+ * candidates, a column stored both in a context row that has a positive and in a candidate row. */
+int spfm_psgd_pairs_set_sampler(spfm_handle h, int64_t n_ctx, int64_t n_cand,
+                                const int64_t* pos_ptr, const int32_t* pos_idx,
+                                const int64_t* forb_ptr, const int32_t* forb_idx);
+/* Fills the device-resident triple list with m = nnz(positives) * n_negatives triples (m < 2^31):
+ * triple r = q * n_negatives + i is the i-th negative of positive q (canonical CSR order).  Draw t
+ * of triple r is draw_u64(seed, epoch, r, t) (stateless, integer only), its
+ * candidate ((u >> 32) * n_cand) >> 32; a draw is admitted when its candidate is not forbidden for
+ * the context.  Among the first n_candidates admitted draws with t < max_draws (fewer: those; none:
+ * the first admissible candidate upwards, cyclically, from the last drawn one) the negative is the
+ * one with the largest score sum_o sum_s lams_s a_s^{degree-o}(x_b + z_c) + <w, z_c> at the live
+ * parameters, ties to the earliest draw; n_candidates == 1 scores nothing (uniform negatives, the
+ * scores are 0).  Triple r goes to slot order[r] (order: NULL or a permutation of 0..m-1, checked
+ * on the host) as (b, n_ctx + c+, n_ctx + c-).  triples_out (m, 3) / scores_out (m): optional host
+ * copies, by slot.  Nothing is updated.  SPFM_ERR_INVALID: no sampler set, not configured for psgd,
+ * degree differs from spfm_configure, n_negatives / n_candidates / max_draws < 1, m >= 2^31, seed
+ * or epoch < 0.  A handle with a communicator: SPFM_ERR_UNSUPPORTED. */
+int spfm_psgd_pairs_sample(spfm_handle h, int degree, int64_t n_negatives, int64_t n_candidates,
+                           int64_t max_draws, int64_t seed, int64_t epoch, const int32_t* order,
+                           int32_t* triples_out, double* scores_out);
+/* spfm_psgd_pairs_epoch over the list the last spfm_psgd_pairs_sample left on the device: no
+ * upload, no per-epoch host check.  SPFM_ERR_INVALID when the resident list is not the output of a
+ * sample call (a later spfm_psgd_pairs_epoch / _eval upload, or new data, invalidates it), and for
+ * batch_size < 1, *it < 1, an unsupported learning_rate. */
+int spfm_psgd_pairs_epoch_sampled(spfm_handle h, int degree, double alpha, double beta,
+                                  double gamma, double eta0, int learning_rate, double power_t,
+                                  int64_t batch_size, int fit_linear, int64_t* it,
+                                  double* sum_loss);
+
 /* -- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------
  * Rows are sharded; the column partial sums of every step are all-reduced
  * (sum, f64) so that every rank applies the identical prox.  id is an opaque

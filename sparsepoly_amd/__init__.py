@@ -3,7 +3,8 @@ factorization machines; drop-in for the pcd / pbcd path of neonnnnn/sparsepoly
 (reference ``sparsepoly/__init__.py:1-19`` exports the same estimator and
 regularizer names)."""
 from .bank import ModelBank
-from .pairwise import SparseFactorizationMachineRanker, sample_triples
+from .pairwise import (SparseFactorizationMachineRanker, draw_u64, restate_sample,
+                       sample_triples)
 from .regularizer import L1, L21, OmegaCS, OmegaTI, SquaredL12, SquaredL21
 from .sparse_all_subsets import SparseAllSubsetsClassifier, SparseAllSubsetsRegressor
 from .sparse_factorization_machines import (
@@ -25,4 +26,6 @@ __all__ = [
     "SparseFactorizationMachineRanker",
     "SparseFactorizationMachineRegressor",
     "sample_triples",
+    "draw_u64",
+    "restate_sample",
 ]

@@ -91,6 +91,7 @@ SYMBOLS = [
     "spfm_cd_linear_epoch",
     "spfm_pcd_epoch", "spfm_pbcd_epoch", "spfm_psgd_epoch", "spfm_psgd_epoch_sharded",
     "spfm_psgd_pairs_epoch", "spfm_psgd_pairs_eval",
+    "spfm_psgd_pairs_set_sampler", "spfm_psgd_pairs_sample", "spfm_psgd_pairs_epoch_sampled",
     "spfm_host_epoch_begin",
     "spfm_host_pass_begin", "spfm_host_step_sums", "spfm_host_step_apply", "spfm_host_epoch_end", "spfm_comm_unique_id", "spfm_comm_init", "spfm_comm_init_shm", "spfm_peer_alloc", "spfm_peer_connect",
     "spfm_profile_enable", "spfm_profile_get", "spfm_profile_reset", "spfm_set_use_graph",
@@ -187,6 +188,12 @@ def load():
                                         C.c_double, C.c_int, C.c_double, C.c_int64, _ip,
                                         C.c_int64, C.c_int, _lp, _dp]
     L.spfm_psgd_pairs_eval.argtypes = [_h, C.c_int, C.c_int, _ip, C.c_int64, _dp, _lp]
+    L.spfm_psgd_pairs_set_sampler.argtypes = [_h, C.c_int64, C.c_int64, _lp, _ip, _lp, _ip]
+    L.spfm_psgd_pairs_sample.argtypes = [_h, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                         C.c_int64, _ip, _ip, _dp]
+    L.spfm_psgd_pairs_epoch_sampled.argtypes = [_h, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                C.c_double, C.c_int, C.c_double, C.c_int64,
+                                                C.c_int, _lp, _dp]
     L.spfm_host_epoch_begin.argtypes = [_h, C.c_int, C.c_int]
     L.spfm_host_pass_begin.argtypes = [_h, C.c_int]
     L.spfm_host_step_sums.argtypes = [_h, C.c_int, _dp]

@@ -1060,6 +1060,26 @@ struct spfm_engine {
                          int fit_linear, int64_t* it, double* sum_loss);
     int psgd_pairs_eval(int degree, int fit_linear, const int32_t* triples, int64_t m,
                         double* sum_loss, int64_t* n_ordered);
+    // what follows the checks and the filling of sg_triples: the batches and the loss sum
+    int psgd_pairs_run(int degree, double alpha, double beta, double gamma, double eta0, int lr,
+                       double power_t, int64_t batch_size, int64_t m, int fit_linear, int64_t* it,
+                       double* sum_loss);
+
+    // negatives drawn on the device: the positives (context and
+    // candidate of each, canonical CSR order) and the forbidden CSR, uploaded once per data set;
+    // sg_triples filled by psgd_pair_sample_kernel is `sampled` until an upload overwrites it
+    DevBuf sm_posrow, sm_posidx, sm_fptr, sm_fidx, sg_scores, sg_order;
+    int64_t sm_nctx = 0, sm_ncand = 0, sm_npos = 0, sampled_m = 0;
+    bool have_sampler = false, sampled = false;
+    int psgd_pairs_set_sampler(int64_t n_ctx, int64_t n_cand, const int64_t* pos_ptr,
+                               const int32_t* pos_idx, const int64_t* forb_ptr,
+                               const int32_t* forb_idx);
+    int psgd_pairs_sample(int degree, int64_t n_negatives, int64_t n_candidates,
+                          int64_t max_draws, int64_t seed, int64_t epoch, const int32_t* order,
+                          int32_t* triples_out, double* scores_out);
+    int psgd_pairs_epoch_sampled(int degree, double alpha, double beta, double gamma, double eta0,
+                                 int lr, double power_t, int64_t batch_size, int fit_linear,
+                                 int64_t* it, double* sum_loss);
 
     // ------------------------------- objective terms, held-out set (spfm_engine_objective.hip)
     // Read-only views of the live state: they use buffers of their own, neither of the

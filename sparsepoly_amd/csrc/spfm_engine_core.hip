@@ -240,6 +240,8 @@ int spfm_engine::data_installed(const double* y) {
     }
     have_data = true;
     configured = false;
+    have_sampler = false;  // the positives and the drawn triples named rows of the old data
+    sampled = false;
     col_norm_reduced = false;
     invalidate(kInvSchedule | kInvGraphs);
     HIPC(viol_col.alloc(sizeof(double) * (size_t)d));

@@ -1,6 +1,7 @@
 // spfm_engine_psgd.hip -- minibatch solver (psgd)
 #include "spfm_engine.hip.h"
 #include "spfm_psgd_pairs.hip.h"
+#include "spfm_psgd_sample.hip.h"
 
 using namespace spfm;
 
@@ -422,7 +423,7 @@ int spfm_engine::psgd_pairs_epoch(int degree, double alpha, double beta, double 
         return SPFM_OK;
     }
     SPFM_TRY(ensure_pt());
-    p_valid = false;
+    sampled = false;  // the upload overwrites a drawn list
     {  // (a new allocation changes the recorded kernel arguments)
         const void *o1 = sg_triples.p, *o2 = sg_lossrow.p;
         HIPC(sg_triples.alloc(sizeof(int32_t) * 3 * (size_t)m));
@@ -431,6 +432,15 @@ int spfm_engine::psgd_pairs_epoch(int degree, double alpha, double beta, double 
     }
     SPFM_TRY(upload_to(sg_triples.p, triples, 3 * (size_t)m));
     HIPC(hipStreamSynchronize(stream));  // caller may reuse triples
+    return psgd_pairs_run(degree, alpha, beta, gamma, eta0, lr, power_t, batch_size, m, fit_linear,
+                          it, sum_loss);
+}
+
+// the batches over the resident triple list sg_triples[0, m) and the sum of the triples' losses
+int spfm_engine::psgd_pairs_run(int degree, double alpha, double beta, double gamma, double eta0,
+                                int lr, double power_t, int64_t batch_size, int64_t m,
+                                int fit_linear, int64_t* it, double* sum_loss) {
+    p_valid = false;
 #define SPFM_PAIRS_GO(L)                                                                      \
     psgd_pairs_epoch_tl<T, L>(degree, alpha, beta, gamma, eta0, lr, power_t, batch_size, m, \
                               fit_linear, it)
@@ -469,6 +479,7 @@ int spfm_engine::psgd_pairs_eval(int degree, int fit_linear, const int32_t* trip
         if (sg_triples.p != o1 || sg_lossrow.p != o2) clear_graphs();
     }
     HIPC(sg_ordered.alloc(sizeof(int) * (size_t)m));
+    sampled = false;  // the upload overwrites a drawn list
     SPFM_TRY(upload_to(sg_triples.p, triples, 3 * (size_t)m));
 #define SPFM_PAIRS_EV(L)                                                                       \
     hipLaunchKernelGGL((psgd_pair_grad_kernel<T, L, true>), dim3(cdiv(m, kBlock / L)),        \
@@ -502,7 +513,201 @@ int spfm_engine::psgd_pairs_eval(int degree, int fit_linear, const int32_t* trip
     return SPFM_OK;
 }
 
+// ============================================================ negatives drawn on the device
+// 
+
+// one CSR over n_cand columns: in range, strictly ascending within a row
+static const char* sampler_csr_error(int64_t rows, int64_t n_cand, const int64_t* ptr,
+                                     const int32_t* idx) {
+    if (!ptr || ptr[0] != 0) return "indptr[0] != 0";
+    for (int64_t b = 0; b < rows; ++b) {
+        if (ptr[b + 1] < ptr[b]) return "indptr not monotone";
+        if (ptr[b + 1] > ptr[b] && !idx) return "indices missing";
+        for (int64_t e = ptr[b]; e < ptr[b + 1]; ++e) {
+            if (idx[e] < 0 || idx[e] >= n_cand) return "a candidate index outside [0, n_cand)";
+            if (e > ptr[b] && idx[e] <= idx[e - 1]) return "indices not strictly ascending";
+        }
+    }
+    return nullptr;
+}
+
+int spfm_engine::psgd_pairs_set_sampler(int64_t n_ctx, int64_t n_cand, const int64_t* pos_ptr,
+                                        const int32_t* pos_idx, const int64_t* forb_ptr,
+                                        const int32_t* forb_idx) {
+    have_sampler = false;
+    sampled = false;
+    if (!have_data) FAIL(SPFM_ERR_INVALID, "set_sampler: data is required");
+    if (n_ctx < 1 || n_cand < 1 || n_ctx + n_cand != n)
+        FAIL(SPFM_ERR_INVALID, "set_sampler: n_ctx + n_cand must be the handle's row count");
+    if (const char* e = sampler_csr_error(n_ctx, n_cand, pos_ptr, pos_idx))
+        FAIL(SPFM_ERR_INVALID, std::string("set_sampler: positives: ") + e);
+    if (!forb_ptr) {
+        forb_ptr = pos_ptr;
+        forb_idx = pos_idx;
+    } else if (const char* e = sampler_csr_error(n_ctx, n_cand, forb_ptr, forb_idx)) {
+        FAIL(SPFM_ERR_INVALID, std::string("set_sampler: forbidden: ") + e);
+    }
+    const int64_t npos = pos_ptr[n_ctx];
+    if (npos < 1 || npos > INT32_MAX)
+        FAIL(SPFM_ERR_INVALID, "set_sampler: 1 <= nnz(positives) < 2^31 is required");
+    std::vector<uint8_t> side((size_t)n, 0);  // 1: context with a positive, 2: candidate
+    std::vector<int32_t> prow((size_t)npos);
+    for (int64_t b = 0; b < n_ctx; ++b) {
+        const int64_t p0 = pos_ptr[b], p1 = pos_ptr[b + 1];
+        if (p1 == p0) continue;
+        side[(size_t)b] = 1;
+        int64_t f = forb_ptr[b];
+        const int64_t f1 = forb_ptr[b + 1];
+        for (int64_t e = p0; e < p1; ++e) {  // both sorted: one merge
+            prow[(size_t)e] = (int32_t)b;
+            while (f < f1 && forb_idx[f] < pos_idx[e]) ++f;
+            if (f == f1 || forb_idx[f] != pos_idx[e])
+                FAIL(SPFM_ERR_INVALID, "set_sampler: row " + std::to_string(b) +
+                                           " of the forbidden set lacks one of its positives");
+        }
+        if (f1 - forb_ptr[b] >= n_cand)
+            FAIL(SPFM_ERR_INVALID, "set_sampler: row " + std::to_string(b) +
+                                       " forbids every candidate: no negative can be drawn");
+    }
+    for (int64_t c = n_ctx; c < n; ++c) side[(size_t)c] = 2;
+    for (int32_t j = 0; j < d; ++j) {  // the rule of psgd_pairs_check
+        unsigned both = 0;
+        for (int64_t e = h_cptr[(size_t)j]; e < h_cptr[(size_t)j + 1]; ++e)
+            both |= side[(size_t)h_cidx[(size_t)e]];
+        if (both == 3)
+            FAIL(SPFM_ERR_INVALID, "set_sampler: column " + std::to_string(j) +
+                                       " is stored in a context row with a positive and in a "
+                                       "candidate row: the two column sets must be disjoint");
+    }
+    SPFM_TRY(upload(sm_posrow, prow.data(), (size_t)npos));
+    SPFM_TRY(upload(sm_posidx, pos_idx, (size_t)npos));
+    SPFM_TRY(upload(sm_fptr, forb_ptr, (size_t)n_ctx + 1));
+    SPFM_TRY(upload(sm_fidx, forb_idx, (size_t)forb_ptr[n_ctx], 1));
+    HIPC(hipStreamSynchronize(stream));  // prow dies here; the caller may reuse its arrays
+    sm_nctx = n_ctx;
+    sm_ncand = n_cand;
+    sm_npos = npos;
+    have_sampler = true;
+    return SPFM_OK;
+}
+
+int spfm_engine::psgd_pairs_sample(int degree, int64_t n_negatives, int64_t n_candidates,
+                                   int64_t max_draws, int64_t seed, int64_t epoch,
+                                   const int32_t* order, int32_t* triples_out,
+                                   double* scores_out) {
+    if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs sample: several ranks are not supported");
+    if (!have_data || !have_params || !configured)
+        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: data, parameters and configuration are required");
+    if (solver != SPFM_SOLVER_PSGD)
+        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: engine is not configured for psgd");
+    if (degree != top_degree)
+        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: degree differs from configure()");
+    if (!have_sampler)
+        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: call spfm_psgd_pairs_set_sampler first");
+    if (n_negatives < 1 || n_candidates < 1 || max_draws < 1)
+        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: n_negatives, n_candidates and max_draws must "
+                               "be >= 1");
+    if (n_candidates > INT32_MAX || max_draws > INT32_MAX || n_negatives > INT32_MAX ||
+        sm_npos * n_negatives > INT32_MAX)
+        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: the triple list is limited to 2^31 - 1 rows");
+    if (seed < 0 || epoch < 0)
+        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: seed and epoch must be >= 0");
+    const int64_t m = sm_npos * n_negatives;
+    if (order) {
+        std::vector<char> seen((size_t)m, 0);
+        for (int64_t q = 0; q < m; ++q) {
+            const int32_t i = order[q];
+            if (i < 0 || i >= m || seen[(size_t)i])
+                FAIL(SPFM_ERR_INVALID, "psgd pairs sample: order is not a permutation of 0..m-1");
+            seen[(size_t)i] = 1;
+        }
+    }
+    SPFM_TRY(ensure_pt());
+    sampled = false;
+    {  // (a new allocation changes the recorded kernel arguments)
+        const void *o1 = sg_triples.p, *o2 = sg_lossrow.p;
+        HIPC(sg_triples.alloc(sizeof(int32_t) * 3 * (size_t)m));
+        HIPC(sg_lossrow.alloc(sizeof(double) * (size_t)m));
+        if (sg_triples.p != o1 || sg_lossrow.p != o2) clear_graphs();
+    }
+    HIPC(sg_scores.alloc(sizeof(double) * (size_t)m));
+    if (order) SPFM_TRY(upload(sg_order, order, (size_t)m));
+#define SPFM_SAMPLE_GO(L)                                                                       \
+    hipLaunchKernelGGL((psgd_pair_sample_kernel<T, L>), dim3(cdiv(m, kBlock / L)), dim3(kBlock), \
+                       0, stream, (int)m, (int)n_negatives, (int)n_candidates, (int)max_draws,  \
+                       (uint64_t)seed, (uint64_t)epoch, (int)sm_nctx, (int)sm_ncand,            \
+                       sm_posrow.as<int32_t>(), sm_posidx.as<int32_t>(), sm_fptr.as<int64_t>(), \
+                       sm_fidx.as<int32_t>(),                                                   \
+                       order ? sg_order.as<int32_t>() : (const int32_t*)nullptr,                \
+                       rptr.as<int64_t>(), ridx.as<int32_t>(), rval.as<T>(), Pt.as<double>(),   \
+                       w.as<double>(), lams.as<double>(), n_orders, k, d, degree,               \
+                       sg_triples.as<int32_t>(), sg_scores.as<double>())
+    SPFM_DISPATCH(dtype, {
+        if (k <= 16)
+            SPFM_SAMPLE_GO(16);
+        else if (k <= 32)
+            SPFM_SAMPLE_GO(32);
+        else
+            SPFM_SAMPLE_GO(64);
+    });
+#undef SPFM_SAMPLE_GO
+    HIPC(hipGetLastError());
+    if (triples_out) SPFM_TRY(download(triples_out, sg_triples.p, 3 * (size_t)m));
+    if (scores_out) SPFM_TRY(download(scores_out, sg_scores.p, (size_t)m));
+    HIPC(hipStreamSynchronize(stream));  // order may be reused; the copies have landed
+    sampled = true;
+    sampled_m = m;
+    return SPFM_OK;
+}
+
+// the epoch of psgd_pairs_epoch over the list the sample call left on the device: nothing is
+// uploaded and nothing re-checked (the list is valid by construction)
+int spfm_engine::psgd_pairs_epoch_sampled(int degree, double alpha, double beta, double gamma,
+                                          double eta0, int lr, double power_t, int64_t batch_size,
+                                          int fit_linear, int64_t* it, double* sum_loss) {
+    if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs: several ranks are not supported");
+    if (!have_data || !have_params || !configured)
+        FAIL(SPFM_ERR_INVALID, "psgd pairs: data, parameters and configuration are required");
+    if (solver != SPFM_SOLVER_PSGD)
+        FAIL(SPFM_ERR_INVALID, "psgd pairs: engine is not configured for psgd");
+    if (degree != top_degree) FAIL(SPFM_ERR_INVALID, "psgd pairs: degree differs from configure()");
+    if (!sampled)
+        FAIL(SPFM_ERR_INVALID, "psgd pairs: the resident triple list is not the output of "
+                               "spfm_psgd_pairs_sample");
+    if (!it) FAIL(SPFM_ERR_INVALID, "psgd pairs: it is required");
+    if (batch_size < 1) FAIL(SPFM_ERR_INVALID, "psgd pairs: batch_size must be >= 1");
+    if (lr < 0 || lr > 3) FAIL(SPFM_ERR_INVALID, "psgd pairs: learning_rate is not supported.");
+    if (*it < 1) FAIL(SPFM_ERR_INVALID, "psgd pairs: it must be >= 1");
+    SPFM_TRY(ensure_pt());
+    return psgd_pairs_run(degree, alpha, beta, gamma, eta0, lr, power_t, batch_size, sampled_m,
+                          fit_linear, it, sum_loss);
+}
+
 extern "C" {
+
+int spfm_psgd_pairs_set_sampler(spfm_handle h, int64_t n_ctx, int64_t n_cand,
+                                const int64_t* pos_ptr, const int32_t* pos_idx,
+                                const int64_t* forb_ptr, const int32_t* forb_idx) {
+    SPFM_GUARD(h);
+    return h->psgd_pairs_set_sampler(n_ctx, n_cand, pos_ptr, pos_idx, forb_ptr, forb_idx);
+}
+
+int spfm_psgd_pairs_sample(spfm_handle h, int degree, int64_t n_negatives, int64_t n_candidates,
+                           int64_t max_draws, int64_t seed, int64_t epoch, const int32_t* order,
+                           int32_t* triples_out, double* scores_out) {
+    SPFM_GUARD(h);
+    return h->psgd_pairs_sample(degree, n_negatives, n_candidates, max_draws, seed, epoch, order,
+                                triples_out, scores_out);
+}
+
+int spfm_psgd_pairs_epoch_sampled(spfm_handle h, int degree, double alpha, double beta,
+                                  double gamma, double eta0, int learning_rate, double power_t,
+                                  int64_t batch_size, int fit_linear, int64_t* it,
+                                  double* sum_loss) {
+    SPFM_GUARD(h);
+    return h->psgd_pairs_epoch_sampled(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                                       batch_size, fit_linear, it, sum_loss);
+}
 
 int spfm_psgd_pairs_epoch(spfm_handle h, int degree, double alpha, double beta, double gamma,
                           double eta0, int learning_rate, double power_t, int64_t batch_size,

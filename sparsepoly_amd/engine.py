@@ -1225,6 +1225,64 @@ class HipEngine(object):
             C.byref(sl), C.byref(no)))
         return sl.value, no.value
 
+    def psgd_pairs_set_sampler(self, n_ctx, n_cand, positives, forbidden=None):
+        """Hand the positives -- a sparse ``(n_ctx, n_cand)`` matrix, pattern only -- and the
+        forbidden set (the same shape, a superset; ``None``: the positives) to the device sampler
+        of the pairwise fit (``spfm_psgd_pairs_set_sampler``).  Rows ``[0, n_ctx)`` of the
+        handle's data are the contexts, the next ``n_cand`` the candidates."""
+        def csr(M):
+            M = sp.csr_matrix(M)
+            if not M.has_sorted_indices:
+                M = M.sorted_indices()
+            return (np.ascontiguousarray(M.indptr, dtype=np.int64),
+                    np.ascontiguousarray(M.indices, dtype=np.int32))
+
+        pp, pi = csr(positives)
+        if forbidden is None:
+            fp = fi = None
+        else:
+            fp, fi = csr(forbidden)
+        self._check(self._lib.spfm_psgd_pairs_set_sampler(
+            self._h, int(n_ctx), int(n_cand), pp.ctypes.data_as(_capi._lp),
+            pi.ctypes.data_as(_capi._ip),
+            None if fp is None else fp.ctypes.data_as(_capi._lp),
+            None if fi is None else fi.ctypes.data_as(_capi._ip)))
+        self._sampler_npos = int(pp[-1])
+
+    def psgd_pairs_sample(self, degree, n_negatives, n_candidates, max_draws, seed, epoch,
+                          order=None, want_triples=True, want_scores=True):
+        """Draw the negatives of every positive on the device at the live parameters and leave
+        the triple list resident (``spfm_psgd_pairs_sample``).  Returns ``(m, triples, scores)``:
+        the number of triples and the host copies -- ``(m, 3)`` int32 rows of ``[X; Z]`` and
+        ``(m,)`` float64, by slot -- or ``None`` for a copy that was not asked for."""
+        m = getattr(self, "_sampler_npos", 0) * max(int(n_negatives), 0)
+        o = None
+        if order is not None:
+            o = np.ascontiguousarray(order, dtype=np.int32)
+            if o.shape != (m,):
+                raise ValueError("order must have shape (%d,), got %r" % (m, o.shape))
+        t = np.empty((m, 3), dtype=np.int32) if want_triples else None
+        sc = np.empty(m, dtype=np.float64) if want_scores else None
+        self._check(self._lib.spfm_psgd_pairs_sample(
+            self._h, int(degree), int(n_negatives), int(n_candidates), int(max_draws), int(seed),
+            int(epoch), None if o is None else o.ctypes.data_as(_capi._ip),
+            None if t is None else t.ctypes.data_as(_capi._ip),
+            None if sc is None else sc.ctypes.data_as(_capi._dp)))
+        return m, t, sc
+
+    def psgd_pairs_epoch_sampled(self, degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                                 batch_size, fit_linear, it):
+        """``psgd_pairs_epoch`` over the list ``psgd_pairs_sample`` left on the device
+        (``spfm_psgd_pairs_epoch_sampled``).  Returns (sum_loss, it)."""
+        itc = C.c_int64(int(it))
+        sl = C.c_double()
+        lr = (_capi.LEARNING_RATE[learning_rate] if isinstance(learning_rate, str)
+              else int(learning_rate))
+        self._check(self._lib.spfm_psgd_pairs_epoch_sampled(
+            self._h, int(degree), float(alpha), float(beta), float(gamma), float(eta0), lr,
+            float(power_t), int(batch_size), int(bool(fit_linear)), C.byref(itc), C.byref(sl)))
+        return sl.value, itc.value
+
     # ------------------------------------------------------------- multi-GPU
     @staticmethod
     def comm_unique_id():

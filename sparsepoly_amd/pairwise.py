@@ -13,7 +13,9 @@ vocabulary of ``ranking.py``: one feature space, disjoint column sets.  The stac
 (``spfm_psgd_pairs_epoch``, ``include/spfm.h``): 12 bytes per triple, no materialised row
 ``x_b + z_c``, nothing to rebuild when the negatives are drawn again.
 
-``sample_triples`` draws the negatives (NumPy).  ``restate_margins`` / ``restate_pair_gradient`` /
+``sample_triples`` draws the negatives with NumPy (``sampler='host'``); ``sampler='uniform'`` and
+``'dynamic'`` draw them on the device (``draw_u64`` / ``restate_sample``
+restate that in NumPy).  ``restate_margins`` / ``restate_pair_gradient`` /
 ``restate_pairwise_epoch`` are plain NumPy restatements, test aids that never touch the device.
 There is no CPU path of the fit: without the library or a GPU it raises.
 """
@@ -115,6 +117,134 @@ def check_triples(triples, B, C):
             raise ValueError("triple %d has c+ == c- (candidate %d)"
                              % (int(same[0]), int(t[same[0], 1])))
     return np.ascontiguousarray(t, dtype=np.int32)
+
+
+SAMPLERS = ("host", "uniform", "dynamic")
+_MASK64 = np.uint64(0xFFFFFFFFFFFFFFFF)
+
+
+def _mix64(z):
+    """the splitmix64 finaliser on uint64 arrays (arithmetic modulo 2**64)"""
+    z = z ^ (z >> np.uint64(30))
+    z = z * np.uint64(0xBF58476D1CE4E5B9)
+    z = z ^ (z >> np.uint64(27))
+    z = z * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def draw_u64(seed, epoch, r, t):
+    """Test aid, NumPy only: draw ``t`` of output triple ``r`` in ``(seed, epoch)`` as the device
+    sampler forms it (``sample_key`` / ``sample_draw``): stateless, integer
+    arithmetic modulo 2**64, broadcasting over ``uint64`` arrays.
+
+        a   = mix((seed << 32) ^ (epoch & 0xFFFFFFFF))
+        key = mix(a ^ (r * 0x9E3779B97F4A7C15))
+        u   = mix(key + (t + 1) * 0x9E3779B97F4A7C15)        mix: the splitmix64 finaliser
+
+    The candidate of a draw is ``((u >> 32) * C) >> 32`` (``draw_candidates``)."""
+    g = np.uint64(0x9E3779B97F4A7C15)
+    seed, epoch, r, t = (np.asarray(v).astype(np.uint64) for v in (seed, epoch, r, t))
+    with np.errstate(over="ignore"):
+        a = _mix64((seed << np.uint64(32)) ^ (epoch & np.uint64(0xFFFFFFFF)))
+        key = _mix64(a ^ (r * g))
+        return _mix64(key + (t + np.uint64(1)) * g)
+
+
+def draw_candidates(u, C):
+    """``((u >> 32) * C) >> 32`` on uint64 arrays: a candidate in ``[0, C)``; no floating point,
+    no modulo"""
+    return (((np.asarray(u, dtype=np.uint64) >> np.uint64(32)) * np.uint64(C))
+            >> np.uint64(32)).astype(np.int64)
+
+
+def _forbidden(interactions, exclude, B, C):
+    """(I, F): the canonical patterns of the positives and of ``interactions`` + ``exclude``"""
+    I = _pattern(interactions, B, C, "interactions")
+    F = I
+    if exclude is not None:
+        F = (I + _pattern(exclude, B, C, "exclude")).tocsr()
+        F.sort_indices()
+    full = (np.diff(F.indptr) >= C) & (np.diff(I.indptr) > 0)
+    if full.any():
+        raise ValueError("row %d stores every candidate (interactions and exclude together): no "
+                         "negative can be drawn for it" % int(np.argmax(full)))
+    return I, F
+
+
+def _admitted_sets(I, F, n_negatives, n_candidates, max_draws, seed, epoch):
+    """per output triple r: (b, c+, the admitted candidates in the order of their draws); the
+    fallback candidate alone where no draw with t < max_draws is admitted"""
+    B, C = I.shape
+    rows = np.repeat(np.arange(B), np.diff(I.indptr))
+    t = np.arange(max_draws, dtype=np.uint64)
+    out = []
+    for r in range(I.nnz * n_negatives):
+        q = r // n_negatives
+        b = int(rows[q])
+        forb = F.indices[F.indptr[b]:F.indptr[b + 1]]
+        cand = draw_candidates(draw_u64(seed, epoch, r, t), C)
+        adm = cand[~np.isin(cand, forb)][:n_candidates]
+        if adm.size == 0:  # upwards, cyclically, from the last drawn candidate
+            c = int(cand[-1])
+            for _ in range(C):
+                c = 0 if c + 1 == C else c + 1
+                if c not in forb:
+                    break
+            adm = np.array([c], dtype=np.int64)
+        out.append((b, int(I.indices[q]), adm))
+    return out
+
+
+def restate_sample(P, w, lams, X, Z, interactions, degree, n_negatives, n_candidates, max_draws,
+                   seed, epoch, exclude=None, order=None, wide=False, details=False):
+    """Test aid, NumPy only: what ``spfm_psgd_pairs_sample`` leaves on the device.  For output
+    triple ``r = q * n_negatives + i`` (positive ``q`` of ``interactions`` in canonical CSR order)
+    the first ``n_candidates`` admitted draws among ``t < max_draws`` (admitted: the candidate is
+    stored neither in row ``b`` of ``interactions`` nor of ``exclude``; none admitted: the first
+    admissible candidate upwards, cyclically, from the last drawn one), scored by dense evaluation
+    of ``s(b, c) = sum_o sum_s lams_s a_s^{degree-o}(x_b + z_c) + <w, z_c>``; the negative is the
+    one with the largest score, ties to the earliest draw.  Returns ``(triples, scores, gap)`` by
+    slot (``order[r]``, or ``r``): ``(m, 3)`` int32 in context / candidate numbering, the chosen
+    scores (zeros for ``n_candidates == 1``, which scores nothing) and the distance between the
+    best score and the best score of a *different* candidate of the set (``inf`` without one).
+    ``details``: a fourth item, per ``r`` (not slot) the pair (admitted candidates, their
+    scores)."""
+    dtype = np.longdouble if wide else np.double
+    P, w, lams = _as(dtype, P, w, lams)
+    P = P[None] if P.ndim == 2 else P
+    B, C = X.shape[0], Z.shape[0]
+    if not sp.issparse(interactions):
+        interactions = sp.csr_matrix(np.asarray(interactions))
+    I, F = _forbidden(interactions, exclude, B, C)
+    sets = _admitted_sets(I, F, int(n_negatives), int(n_candidates), int(max_draws), seed, epoch)
+    m = len(sets)
+    Xd, Zd = _dense_sides(X, Z, dtype)
+    lin = Zd @ w
+    cache = {}
+
+    def row_scores(b):
+        if b not in cache:
+            cache[b] = _rows_output(P, lams, Xd[b][None, :] + Zd, degree)[0] + lin
+        return cache[b]
+
+    slots = np.arange(m) if order is None else np.asarray(order, dtype=np.int64)
+    triples = np.empty((m, 3), dtype=np.int32)
+    scores = np.zeros(m, dtype=dtype)
+    gap = np.full(m, np.inf)
+    det = []
+    for r, (b, cp, adm) in enumerate(sets):
+        sc = row_scores(b)[adm]
+        best = int(np.argmax(sc))  # the first maximum: the earliest admitted draw
+        other = sc[adm != adm[best]]
+        if other.size:
+            gap[slots[r]] = float(sc[best] - other.max())
+        triples[slots[r]] = (b, cp, adm[best])
+        if n_candidates > 1:
+            scores[slots[r]] = sc[best]
+        det.append((adm, sc))
+    if details:
+        return triples, scores, gap, det
+    return triples, scores, gap
 
 
 def _prepare_pairs(est, X, Z):
@@ -369,27 +499,58 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
             raise NotImplementedError("degree > %d is not supported by the HIP engine"
                                       % MAX_DEGREE)
 
-    def fit(self, X, Z, interactions=None, triples=None, n_negatives=1, resample=True):
+    def fit(self, X, Z, interactions=None, triples=None, n_negatives=1, resample=True,
+            sampler="host", n_candidates=8, exclude=None):
         """Fit on contexts ``X`` (B, d) and candidates ``Z`` (C, d) with disjoint column sets.
         Exactly one of ``interactions`` -- a sparse (B, C) matrix whose stored entries are the
-        positives; ``n_negatives`` negatives per positive are drawn with ``sample_triples``,
-        again before every epoch when ``resample`` -- and ``triples`` -- (m, 3) rows
-        ``(b, c+, c-)`` in context / candidate numbering -- is given.  ``[X; Z]`` is uploaded
-        once; an epoch uploads its 12 m bytes of triples.  Stopping rule, ``verbose`` lines,
-        callbacks, ``it_``, ``n_iter_`` and ``warm_start`` as for ``solver='psgd'``, with the
-        mean loss per triple."""
+        positives; ``n_negatives`` negatives per positive are drawn, again before every epoch
+        when ``resample`` -- and ``triples`` -- (m, 3) rows ``(b, c+, c-)`` in context /
+        candidate numbering -- is given.  ``exclude`` (sparse (B, C), pattern only): candidates
+        that are never drawn as negatives of a context, besides its positives.  ``sampler``:
+
+        * ``'host'``: ``sample_triples`` (NumPy, uniform); an epoch uploads its 12 m bytes.
+        * ``'uniform'``: the device draws them, uniformly.
+        * ``'dynamic'``: the device draws ``n_candidates`` admissible candidates per triple and
+          trains against the one the current parameters score highest (dynamic negative
+          sampling; the choice is made once per epoch, at the epoch's first parameters).
+
+        The device samplers take one seed from ``random_state`` after the parameter
+        initialisation and use the epoch number as the stream's second key; with ``shuffle`` a
+        permutation of the slots (4 m bytes) is uploaded per sampling; with ``resample=False``
+        they sample once and every epoch visits that one list.  ``[X; Z]`` is uploaded once.
+        Stopping rule, ``verbose`` lines, callbacks, ``it_``, ``n_iter_`` and ``warm_start`` as
+        for ``solver='psgd'``, with the mean loss per triple."""
         self._check_config()
+        if sampler not in SAMPLERS:
+            raise ValueError("sampler %r is not supported. Choose from %s."
+                             % (sampler, list(SAMPLERS)))
         if (interactions is None) == (triples is None):
             raise ValueError("exactly one of interactions and triples must be given")
+        if sampler != "host" and triples is not None:
+            raise ValueError("sampler=%r draws the negatives on the device: give interactions, "
+                             "not triples" % (sampler,))
+        if int(n_candidates) != n_candidates or n_candidates < 1:
+            raise ValueError("n_candidates must be an integer >= 1, got %r" % (n_candidates,))
         Xa, Za = _prepare_pairs(self, X, Z)
         B, C = Xa.shape[0], Za.shape[0]
         n_features = Xa.shape[1]
+        forbidden = None
         if interactions is not None:
             if not sp.issparse(interactions):
                 interactions = sp.csr_matrix(np.asarray(interactions))
             interactions = _pattern(interactions, B, C, "interactions")
             if interactions.nnz == 0:
                 raise ValueError("interactions has no stored entry")
+            if exclude is not None:
+                exclude = _pattern(exclude, B, C, "exclude")
+            if sampler != "host":
+                if int(n_negatives) != n_negatives or n_negatives < 1:
+                    raise ValueError("n_negatives must be an integer >= 1, got %r"
+                                     % (n_negatives,))
+                if interactions.nnz * int(n_negatives) >= 2 ** 31:
+                    raise ValueError("%d triples: the triple list is limited to 2**31 - 1 rows"
+                                     % (interactions.nnz * int(n_negatives)))
+                interactions, forbidden = _forbidden(interactions, exclude, B, C)
         else:
             triples = check_triples(triples, B, C)
             if triples.shape[0] == 0:
@@ -428,32 +589,58 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
             self.w_ = np.ascontiguousarray(self.w_, dtype=np.double)
             engine.set_params(self.P_, self.w_, self.lams_)
             engine.configure("psgd", self.loss, self.regularizer, self.degree)
-            converged, self.n_iter_ = self._fit_pairs(engine, B, rng, batch_size, interactions,
-                                                      triples, n_negatives, resample)
+            if sampler == "host":
+                lists = epoch_triples(rng, self.max_iter, interactions, triples, n_negatives,
+                                      resample, self.shuffle, exclude)
+            else:
+                engine.psgd_pairs_set_sampler(B, C, interactions, forbidden)
+                lists = self._device_lists(engine, rng, interactions.nnz * int(n_negatives),
+                                           int(n_negatives),
+                                           1 if sampler == "uniform" else int(n_candidates),
+                                           resample)
+            converged, self.n_iter_ = self._fit_pairs(engine, B, batch_size, lists)
         finally:
             engine.close()
         return self._finish_fit(converged)
 
-    def _fit_pairs(self, engine, B, rng, batch_size, interactions, triples, n_negatives,
-                   resample):
-        """the loop of ``_fit_psgd`` over the epochs' triple lists"""
+    def _device_lists(self, engine, rng, m, n_negatives, n_candidates, resample):
+        """per epoch: have the device draw the epoch's negatives (before the first epoch and,
+        with ``resample``, before every later one) and yield the number of resident triples"""
+        seed = rng.randint(0, 2 ** 31 - 1)
+        for ep in range(self.max_iter):
+            if ep == 0 or resample:
+                order = rng.permutation(m) if self.shuffle else None
+                engine.psgd_pairs_sample(self.degree, n_negatives, n_candidates,
+                                         64 * n_candidates, seed, ep, order,
+                                         want_triples=False, want_scores=False)
+            yield m
+
+    def _fit_pairs(self, engine, B, batch_size, lists):
+        """the loop of ``_fit_psgd`` over the epochs' triple lists: (m, 3) arrays to upload
+        (context / candidate numbering), or the size of the list the device sampler left"""
         converged = False
         no_improvement_count = 0
         best_loss = np.inf
         epoch = 0
-        lists = epoch_triples(rng, self.max_iter, interactions, triples, n_negatives, resample,
-                              self.shuffle)
         for epoch, t in enumerate(lists):
-            stacked = t + np.array([0, B, B], dtype=np.int32)  # rows of [X; Z]
-            sum_loss, self.it_ = engine.psgd_pairs_epoch(
-                self.degree, self.alpha, self.beta, self.gamma, self.eta0, self.learning_rate,
-                self.power_t, batch_size, stacked, self.fit_linear, self.it_)
+            if isinstance(t, np.ndarray):
+                m = t.shape[0]
+                stacked = t + np.array([0, B, B], dtype=np.int32)  # rows of [X; Z]
+                sum_loss, self.it_ = engine.psgd_pairs_epoch(
+                    self.degree, self.alpha, self.beta, self.gamma, self.eta0,
+                    self.learning_rate, self.power_t, batch_size, stacked, self.fit_linear,
+                    self.it_)
+            else:
+                m = t
+                sum_loss, self.it_ = engine.psgd_pairs_epoch_sampled(
+                    self.degree, self.alpha, self.beta, self.gamma, self.eta0,
+                    self.learning_rate, self.power_t, batch_size, self.fit_linear, self.it_)
             if (self.callback is not None) and epoch % self.n_calls == 0:
                 if callback_needs_params(self.callback):
-                    self._sync_params(engine, with_P=False)
+                    self._sync_params(engine)  # P_ and w_ as they stand after this epoch
                 if self.callback(self) is not None:
                     break
-            sum_loss /= t.shape[0]
+            sum_loss /= m
             if self.verbose:
                 print(f"Epoch {epoch+1} loss {sum_loss}")
             if sum_loss > (best_loss - self.tol):
@@ -469,6 +656,47 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                 break
         self._sync_params(engine)
         return converged, epoch
+
+    def sample_negatives(self, X, Z, interactions, n_negatives=1, n_candidates=8, exclude=None,
+                         random_state=None):
+        """Hard negatives under the fitted model, drawn and scored on the device
+        (``spfm_psgd_pairs_sample``): for every stored ``(b, c+)`` of
+        ``interactions``, ``n_negatives`` times the highest-scored of ``n_candidates`` admissible
+        candidates (stored neither in row ``b`` of ``interactions`` nor of ``exclude``).  Returns
+        ``(triples, scores)``: ``(m, 3)`` int32 rows ``(b, c+, c-)`` in context / candidate
+        numbering and the chosen candidates' scores (zeros for ``n_candidates == 1``).  The seed
+        is ``check_random_state(random_state).randint(0, 2**31 - 1)``, the epoch key 0."""
+        if not hasattr(self, "P_"):
+            raise NotFittedError("Estimator not fitted.")
+        self._check_config()
+        if int(n_negatives) != n_negatives or n_negatives < 1:
+            raise ValueError("n_negatives must be an integer >= 1, got %r" % (n_negatives,))
+        if int(n_candidates) != n_candidates or n_candidates < 1:
+            raise ValueError("n_candidates must be an integer >= 1, got %r" % (n_candidates,))
+        Xa, Za = _prepare(self, X, Z)
+        B, C = Xa.shape[0], Za.shape[0]
+        if not sp.issparse(interactions):
+            interactions = sp.csr_matrix(np.asarray(interactions))
+        I, F = _forbidden(interactions, exclude, B, C)
+        if I.nnz == 0:
+            raise ValueError("interactions has no stored entry")
+        if I.nnz * int(n_negatives) >= 2 ** 31:
+            raise ValueError("%d triples: the triple list is limited to 2**31 - 1 rows"
+                             % (I.nnz * int(n_negatives)))
+        seed = check_random_state(random_state).randint(0, 2 ** 31 - 1)
+        S = sp.vstack([Xa, Za], format="csr")
+        S.sort_indices()
+        engine = self._new_engine()
+        try:
+            engine.set_data(S, np.zeros(S.shape[0]))
+            engine.set_params(np.ascontiguousarray(self.P_, dtype=np.double), self.w_, self.lams_)
+            engine.configure("psgd", self.loss, self.regularizer, self.degree)
+            engine.psgd_pairs_set_sampler(B, C, I, F)
+            _, t, sc = engine.psgd_pairs_sample(self.degree, int(n_negatives), int(n_candidates),
+                                                64 * int(n_candidates), seed, 0)
+        finally:
+            engine.close()
+        return t - np.array([0, B, B], dtype=np.int32), sc
 
     def pairwise_loss(self, X, Z, triples):
         """``(mean loss, share of triples with margin > 0)`` of the fitted model on the triples
