@@ -33,7 +33,7 @@
 #include "spfm_slab_host.h"  // slab_end
 #include "spfm_prb.hip.h"    // PrbArgs
 #include "spfm_pcdw.hip.h"   // PcdwArgs, PcdwParams
-#include "spfm_psgd.hip.h"   // PsgdBatch
+#include "spfm_psgd.hip.h"   // PsgdBatch, PsgdStep (spfm_psgd_host.h)
 
 namespace spfm {
 struct IntArgs;  // spfm_interactions.hip.h
@@ -187,6 +187,14 @@ struct DevBuf {
 #define SPFM_DISPATCH(dt, ...)                                    \
     ((dt) == SPFM_F32 ? [&] { using T = float; __VA_ARGS__; }()   \
                       : [&] { using T = double; __VA_ARGS__; }())
+
+// The one place that maps a component count to the lanes of a group in the psgd unit's kernels:
+// runs the statement with L = 16, 32 or 64 (more than 64 components: chunks of 64), e.g.
+// SPFM_DISPATCH(dtype, return SPFM_DISPATCH_L(k, return psgd_epoch_tl<T, L>(st))).
+#define SPFM_DISPATCH_L(k_, ...)                                      \
+    ((k_) <= 16   ? [&] { constexpr int L = 16; __VA_ARGS__; }()      \
+     : (k_) <= 32 ? [&] { constexpr int L = 32; __VA_ARGS__; }()      \
+                  : [&] { constexpr int L = 64; __VA_ARGS__; }())
 
 // The one place that maps a run-time model kind -- a degree 2..6, or 0 (all-subsets) where AS
 // says the caller has that form -- to a compile-time M: runs the statement with M, e.g.
@@ -1009,61 +1017,39 @@ struct spfm_engine {
 
     int configure_psgd(int loss_, int reg_, int top_degree_);
 
-    // psgd.py:9-22
-    static void psgd_eta(int lr, double eta0, double alpha, double beta, double power_t,
-                         int64_t it, double* eta_P, double* eta_w) {
-        if (lr == 0) {
-            *eta_P = eta0;
-            *eta_w = eta0;
-        } else if (lr == 1) {
-            const double eta_it = eta0 * (double)it;
-            *eta_P = eta0 / std::pow(1.0 + eta_it * beta, power_t);
-            *eta_w = eta0 / std::pow(1.0 + eta_it * alpha, power_t);
-        } else if (lr == 2) {
-            *eta_P = 1.0 / (beta * (double)it);
-            *eta_w = 1.0 / (alpha * (double)it);
-        } else {
-            const double eta = eta0 / std::pow((double)it, power_t);
-            *eta_P = eta;
-            *eta_w = eta;
-        }
-    }
-
+    // The psgd unit (spfm_engine_psgd.hip).  The pure host rules -- step sizes, the tabulated
+    // epoch, the sharded lists, the sampler's CSR checks -- live in spfm_psgd_host.h; a PsgdStep
+    // is filled once per extern "C" entry and handed down by reference.
+    int psgd_ready(const char* what, int degree);  // data, parameters, configured for psgd
+    template <typename S>
+    void loss_sum(const S* src, int64_t n_items, int slot);  // scalar[slot] = sum src[0, n)
+    int psgd_epoch_end(const double* loss_row, int64_t n_items, double* sum_loss);
     template <typename T, int L>
-    int psgd_epoch_tl(int degree, double alpha, double beta, double gamma, double eta0, int lr,
-                      double power_t, int64_t batch_size, int fit_linear, int64_t* it);
-
-    // row_lo / n_global: several ranks (spfm_psgd_epoch_sharded); one rank: 0 / n
-    int psgd_epoch(int degree, double alpha, double beta, double gamma, double eta0, int lr,
-                   double power_t, int64_t batch_size, const int32_t* indices_samples,
-                   int64_t n_samples, int64_t row_lo, int fit_linear, int64_t* it, double* sum_loss);
+    int psgd_epoch_tl(const PsgdStep& st);
+    // row_lo / n_samples: several ranks (spfm_psgd_epoch_sharded); one rank: 0 / n
+    int psgd_epoch(const PsgdStep& st, const int32_t* indices_samples, int64_t n_samples,
+                   int64_t row_lo, double* sum_loss);
     // several ranks: per minibatch of the GLOBAL order this rank's samples (first position in
-    // its local sample list, count) and the global batch size
+    // its local sample list, count) and the global batch size (shard_batches)
     std::vector<int64_t> sg_lpos;
     std::vector<int32_t> sg_lB, sg_gB;
     // what follows a gradient launch, shared by the pointwise and the pairwise gradient
     template <int L, typename GradFn>
-    int psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_, int64_t n_items, int degree,
-                        double alpha, double beta, double gamma, double eta0, int lr,
-                        double power_t, int64_t batch_size, int fit_linear, int64_t* it);
+    int psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_, int64_t n_items,
+                        const PsgdStep& st);
 
     // pairwise ranking fit: triples (anchor, plus, minus) of rows of the
     // handle's data [X; Z]; buffers of their own (sg_samples and pred_tmp are sized by n)
     DevBuf sg_triples, sg_lossrow, sg_ordered;
     int psgd_pairs_check(const char* what, int degree, const int32_t* triples, int64_t m);
+    int pairs_reserve(int64_t m);  // sg_triples / sg_lossrow; a moved buffer clears the graphs
     template <typename T, int L>
-    int psgd_pairs_epoch_tl(int degree, double alpha, double beta, double gamma, double eta0,
-                            int lr, double power_t, int64_t batch_size, int64_t m, int fit_linear,
-                            int64_t* it);
-    int psgd_pairs_epoch(int degree, double alpha, double beta, double gamma, double eta0, int lr,
-                         double power_t, int64_t batch_size, const int32_t* triples, int64_t m,
-                         int fit_linear, int64_t* it, double* sum_loss);
+    int psgd_pairs_epoch_tl(const PsgdStep& st, int64_t m);
+    int psgd_pairs_epoch(const PsgdStep& st, const int32_t* triples, int64_t m, double* sum_loss);
     int psgd_pairs_eval(int degree, int fit_linear, const int32_t* triples, int64_t m,
                         double* sum_loss, int64_t* n_ordered);
     // what follows the checks and the filling of sg_triples: the batches and the loss sum
-    int psgd_pairs_run(int degree, double alpha, double beta, double gamma, double eta0, int lr,
-                       double power_t, int64_t batch_size, int64_t m, int fit_linear, int64_t* it,
-                       double* sum_loss);
+    int psgd_pairs_run(const PsgdStep& st, int64_t m, double* sum_loss);
 
     // negatives drawn on the device: the positives (context and
     // candidate of each, canonical CSR order) and the forbidden CSR, uploaded once per data set;
@@ -1077,9 +1063,7 @@ struct spfm_engine {
     int psgd_pairs_sample(int degree, int64_t n_negatives, int64_t n_candidates,
                           int64_t max_draws, int64_t seed, int64_t epoch, const int32_t* order,
                           int32_t* triples_out, double* scores_out);
-    int psgd_pairs_epoch_sampled(int degree, double alpha, double beta, double gamma, double eta0,
-                                 int lr, double power_t, int64_t batch_size, int fit_linear,
-                                 int64_t* it, double* sum_loss);
+    int psgd_pairs_epoch_sampled(const PsgdStep& st, double* sum_loss);
 
     // ------------------------------- objective terms, held-out set (spfm_engine_objective.hip)
     // Read-only views of the live state: they use buffers of their own, neither of the

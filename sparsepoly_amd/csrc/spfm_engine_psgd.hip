@@ -46,6 +46,56 @@ int spfm_engine::configure_psgd(int loss_, int reg_, int top_degree_) {
     return SPFM_OK;
 }
 
+// the state every entry of the unit but the pointwise epoch asks for, in `what`'s words
+int spfm_engine::psgd_ready(const char* what, int degree) {
+    const std::string w = std::string(what) + ": ";
+    if (!have_data || !have_params || !configured)
+        FAIL(SPFM_ERR_INVALID, w + "data, parameters and configuration are required");
+    if (solver != SPFM_SOLVER_PSGD) FAIL(SPFM_ERR_INVALID, w + "engine is not configured for psgd");
+    if (degree != top_degree) FAIL(SPFM_ERR_INVALID, w + "degree differs from configure()");
+    return SPFM_OK;
+}
+
+// first stage of a count: out[block] = number of set flags in the block's contiguous slice
+static __global__ __launch_bounds__(kBlock) void pair_count_partial_kernel(
+    const int* __restrict__ v, int64_t n, double* __restrict__ out) {
+    __shared__ double red[16];
+    const int64_t per = (n + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = per * blockIdx.x, hi = (lo + per < n) ? lo + per : n;
+    double a = 0, b = 0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) a += (double)v[i];
+    block_sum2(a, b, red);
+    if (threadIdx.x == 0) out[blockIdx.x] = a;
+}
+
+// scalar[slot] = sum of src[0, n): 256 partials of the slot's own, then one block (S = int: a
+// count of set flags)
+template <typename S>
+void spfm_engine::loss_sum(const S* src, int64_t n_items, int slot) {
+    double* part = partial.as<double>() + 256 * slot;
+    if constexpr (std::is_same<S, int>::value)
+        hipLaunchKernelGGL(pair_count_partial_kernel, dim3(256), dim3(kBlock), 0, stream, src,
+                           n_items, part);
+    else
+        hipLaunchKernelGGL(reduce_partial_kernel, dim3(256), dim3(kBlock), 0, stream, src, n_items,
+                           part);
+    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(kBlock), 0, stream, part, 256,
+                       scalar.as<double>() + slot);
+}
+
+// the end of an epoch on either route: the sum of the items' losses (over the ranks, if several)
+int spfm_engine::psgd_epoch_end(const double* loss_row, int64_t n_items, double* sum_loss) {
+    loss_sum(loss_row, n_items, 0);
+    HIPC(hipGetLastError());
+    if (dist()) SPFM_TRY(allreduce(scalar.as<double>(), 1));
+    SPFM_TRY(download(h_scalar, scalar.p, 1));
+    HIPC(hipStreamSynchronize(stream));
+    prof_collect();
+    if (sum_loss) *sum_loss = h_scalar[0];
+    psgd_warm = true;
+    return SPFM_OK;
+}
+
 // The minibatches of one epoch over `n_items` training items (samples of the pointwise fit,
 // triples of the pairwise one) behind a gradient launch: update, Michelot passes, table-driven
 // graph replay of runs of 32 with the eager redo from a snapshot.
@@ -54,9 +104,7 @@ int spfm_engine::configure_psgd(int loss_, int reg_, int top_degree_) {
 //                              sg_idx[0] from sg_sched instead
 template <int L, typename GradFn>
 int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_, int64_t n_items,
-                                 int degree, double alpha, double beta, double gamma, double eta0,
-                                 int lr, double power_t, int64_t batch_size, int fit_linear,
-                                 int64_t* it) {
+                                 const PsgdStep& st) {
     const bool mich = (reg == SPFM_REG_SQUAREDL12 || reg == SPFM_REG_SQUAREDL21);
     constexpr int gpb = kBlock / L;
     const int nb_dense = (int)std::min<int64_t>(kPsgdNB, cdiv(d, gpb));
@@ -71,6 +119,32 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
     ms.NB = nb_dense;
     const int nb_fin = cdiv(ms.V, kBlock / kWave);
     int* h_done = reinterpret_cast<int*>(h_scalar + 4);
+    // what follows a gradient, for both routes below: with a table (graph replay) the kernels
+    // read the minibatch's scalars from sched[idx[1]] and the ones passed here are placeholders
+    auto update = [&](double cp, double denp, double strength, double cw, double denw,
+                      const PsgdBatch* sched, int* idx) {
+        hipLaunchKernelGGL((psgd_update_kernel<L>), dim3(nb_dense), dim3(kBlock), 0, stream,
+                           Pt.as<double>(), sg_gradP.as<double>(), w.as<double>(),
+                           sg_gradw.as<double>(), n_orders, k, d, reg, cp, denp, strength,
+                           st.fit_linear, cw, denw, sg_norms.as<double>(), ms, sched, idx);
+    };
+    auto mich_finish = [&](double strength, const PsgdBatch* sched, const int* idx) {
+        hipLaunchKernelGGL(psgd_mich_finish_kernel, dim3(nb_fin), dim3(kBlock), 0, stream, ms,
+                           strength, sched, idx);
+    };
+    auto mich_sweeps = [&](int count, double strength, const PsgdBatch* sched, const int* idx) {
+        for (int sweep = 0; sweep < count; ++sweep) {
+            hipLaunchKernelGGL((psgd_mich_reduce_kernel<L>), dim3(nb_dense), dim3(kBlock), 0,
+                               stream, Pt.as<double>(), sg_norms.as<double>(), n_orders, k, d, reg,
+                               ms);
+            mich_finish(strength, sched, idx);
+        }
+    };
+    auto mich_apply = [&]() {
+        hipLaunchKernelGGL((psgd_mich_apply_kernel<L>), dim3(nb_dense), dim3(kBlock), 0, stream,
+                           Pt.as<double>(), sg_norms.as<double>(), n_orders, k, d, reg,
+                           sg_thr.as<double>());
+    };
     // l1 / l21 (no host round trip inside a minibatch): tabulate the epoch and replay runs
     // of kPsgdRun minibatches from one hipGraph -- the kernels take the batch from a device
     // table, so every (gradient, update) pair has identical arguments
@@ -82,23 +156,8 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
         const int kMichSweeps = psgd_graph_sweeps;  // recorded sweeps per minibatch (2 suffice
                                                     // with the warm start; a failed check
                                                     // redoes the epoch eagerly)
-        const int64_t nbat = cdiv(n_items, batch_size);
-        h_sched.resize((size_t)nbat);
-        for (int64_t bi = 0; bi < nbat; ++bi) {
-            const int64_t pos = bi * batch_size;
-            const int B = (int)std::min<int64_t>(batch_size, n_items - pos);
-            double eta_P, eta_w;
-            psgd_eta(lr, eta0, alpha, beta, power_t, *it + bi, &eta_P, &eta_w);
-            PsgdBatch& e = h_sched[(size_t)bi];
-            e.pos = pos;
-            e.B = B;
-            e.pad = 0;
-            e.cp = eta_P / (double)B;
-            e.denp = 1.0 + eta_P * beta;
-            e.strength = gamma * eta_P / (1 + eta_P * beta);
-            e.cw = eta_w / (double)B;
-            e.denw = 1 + eta_w * alpha;
-        }
+        tabulate_epoch(st, n_items, *st.it, h_sched);
+        const int64_t nbat = (int64_t)h_sched.size();
         const void* old = sg_sched.p;
         HIPC(sg_sched.alloc(sizeof(PsgdBatch) * (size_t)nbat));
         HIPC(sg_idx.alloc(sizeof(int) * 4));
@@ -117,31 +176,20 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
             HIPC(hipMemcpyAsync(sg_snapc.p, sg_cond.p, sizeof(double) * (size_t)ms.V,
                                 hipMemcpyDeviceToDevice, stream));
         }
-        const int gridg = cdiv(std::min<int64_t>(batch_size, n_items), gpb);
+        const int gridg = cdiv(std::min<int64_t>(st.batch_size, n_items), gpb);
+        const PsgdBatch* sched = sg_sched.as<PsgdBatch>();
+        int* idx = sg_idx.as<int>();
         auto pair = [&]() {
             grad((int64_t)0, 0, gridg, true);
-            hipLaunchKernelGGL((psgd_update_kernel<L>), dim3(nb_dense), dim3(kBlock), 0, stream,
-                               Pt.as<double>(), sg_gradP.as<double>(), w.as<double>(),
-                               sg_gradw.as<double>(), n_orders, k, d, reg, 0.0, 1.0, 0.0,
-                               fit_linear, 0.0, 1.0, sg_norms.as<double>(), ms,
-                               sg_sched.as<PsgdBatch>(), sg_idx.as<int>());
+            update(0.0, 1.0, 0.0, 0.0, 1.0, sched, idx);
             if (!mich) return;
-            hipLaunchKernelGGL(psgd_mich_finish_kernel, dim3(nb_fin), dim3(kBlock), 0, stream,
-                               ms, 0.0, sg_sched.as<PsgdBatch>(), sg_idx.as<int>());
-            for (int sweep = 0; sweep < kMichSweeps; ++sweep) {
-                hipLaunchKernelGGL((psgd_mich_reduce_kernel<L>), dim3(nb_dense), dim3(kBlock),
-                                   0, stream, Pt.as<double>(), sg_norms.as<double>(), n_orders,
-                                   k, d, reg, ms);
-                hipLaunchKernelGGL(psgd_mich_finish_kernel, dim3(nb_fin), dim3(kBlock), 0,
-                                   stream, ms, 0.0, sg_sched.as<PsgdBatch>(), sg_idx.as<int>());
-            }
+            mich_finish(0.0, sched, idx);
+            mich_sweeps(kMichSweeps, 0.0, sched, idx);
             hipLaunchKernelGGL(psgd_mich_verify_kernel, dim3(1), dim3(kBlock), 0, stream, ms,
-                               sg_idx.as<int>() + 2);
-            hipLaunchKernelGGL((psgd_mich_apply_kernel<L>), dim3(nb_dense), dim3(kBlock), 0,
-                               stream, Pt.as<double>(), sg_norms.as<double>(), n_orders, k, d,
-                               reg, sg_thr.as<double>());
+                               idx + 2);
+            mich_apply();
         };
-        const std::string key = fkey(tag, {}, {degree, loss, reg, fit_linear, gridg, L,
+        const std::string key = fkey(tag, {}, {st.degree, loss, reg, st.fit_linear, gridg, L,
                                                   tsize_, (int64_t)mich,
                                                   (int64_t)psgd_graph_sweeps});
         int64_t done_b = 0;
@@ -159,7 +207,7 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
             SPFM_TRY(download(&failed, sg_idx.as<int>() + 2, 1));
         HIPC(hipStreamSynchronize(stream));  // h_sched may be rewritten by the next epoch
         if (!failed) {
-            *it += nbat;
+            *st.it += nbat;
             return SPFM_OK;
         }
         // some minibatch needed more sweeps than were recorded: restore and redo eagerly
@@ -176,11 +224,11 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
     // one rank: the batches of its n samples; several ranks: the batches of the global order,
     // of which this rank holds samples [lpos, lpos + lB) of its local list (psgd_epoch)
     const bool sharded = dist();
-    const int64_t nbat_e = sharded ? (int64_t)sg_gB.size() : cdiv(n_items, batch_size);
+    const int64_t nbat_e = sharded ? (int64_t)sg_gB.size() : cdiv(n_items, st.batch_size);
     for (int64_t bi = 0; bi < nbat_e; ++bi) {
-        const int64_t pos = sharded ? sg_lpos[(size_t)bi] : bi * batch_size;
+        const int64_t pos = sharded ? sg_lpos[(size_t)bi] : bi * st.batch_size;
         const int lB =
-            sharded ? sg_lB[(size_t)bi] : (int)std::min<int64_t>(batch_size, n_items - pos);
+            sharded ? sg_lB[(size_t)bi] : (int)std::min<int64_t>(st.batch_size, n_items - pos);
         const int B = sharded ? sg_gB[(size_t)bi] : lB;  // eta / B: the whole minibatch
         prof_begin(0, 0);
         if (lB > 0) grad(pos, lB, (int)cdiv(lB, gpb), false);
@@ -188,37 +236,22 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
         if (sharded) {  // sum of the ranks' gradients: identical bits on every rank
             int arc = allreduce(sg_gradP.as<double>(), (size_t)n_orders * k * d);
             if (arc) return arc;
-            if (fit_linear) {
+            if (st.fit_linear) {
                 arc = allreduce(sg_gradw.as<double>(), (size_t)d);
                 if (arc) return arc;
             }
         }
-        double eta_P, eta_w;
-        psgd_eta(lr, eta0, alpha, beta, power_t, *it, &eta_P, &eta_w);
-        const double strength = gamma * eta_P / (1 + eta_P * beta);
+        const PsgdBatch b = st.batch(*st.it, B);
         prof_begin(1, 0);
-        hipLaunchKernelGGL((psgd_update_kernel<L>), dim3(nb_dense), dim3(kBlock), 0, stream,
-                           Pt.as<double>(), sg_gradP.as<double>(), w.as<double>(),
-                           sg_gradw.as<double>(), n_orders, k, d, reg, eta_P / (double)B,
-                           1.0 + eta_P * beta, strength, fit_linear, eta_w / (double)B,
-                           1 + eta_w * alpha, sg_norms.as<double>(), ms,
-                           (const PsgdBatch*)nullptr, (int*)nullptr);
+        update(b.cp, b.denp, b.strength, b.cw, b.denw, nullptr, nullptr);
         prof_end(1);
         if (mich) {
             prof_begin(2, 0);
-            hipLaunchKernelGGL(psgd_mich_finish_kernel, dim3(nb_fin), dim3(kBlock), 0, stream,
-                               ms, strength, (const PsgdBatch*)nullptr, (const int*)nullptr);
+            mich_finish(b.strength, nullptr, nullptr);
             // the iteration is monotone after the first sweep, so it terminates (<= d
             // sweeps; 2-4 with the warm start); the host looks at the flag per chunk
             for (int guard = 0;; ++guard) {
-                for (int sweep = 0; sweep < 2; ++sweep) {
-                    hipLaunchKernelGGL((psgd_mich_reduce_kernel<L>), dim3(nb_dense),
-                                       dim3(kBlock), 0, stream, Pt.as<double>(),
-                                       sg_norms.as<double>(), n_orders, k, d, reg, ms);
-                    hipLaunchKernelGGL(psgd_mich_finish_kernel, dim3(nb_fin), dim3(kBlock),
-                                       0, stream, ms, strength, (const PsgdBatch*)nullptr,
-                                       (const int*)nullptr);
-                }
+                mich_sweeps(2, b.strength, nullptr, nullptr);
                 hipLaunchKernelGGL(psgd_mich_check_kernel, dim3(1), dim3(kBlock), 0, stream,
                                    ms);
                 SPFM_TRY(download(h_done, sg_done.p, 1));
@@ -226,12 +259,10 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
                 if (*h_done) break;
                 if (guard > d) FAIL(SPFM_ERR_RUNTIME, "psgd: prox support search did not settle");
             }
-            hipLaunchKernelGGL((psgd_mich_apply_kernel<L>), dim3(nb_dense), dim3(kBlock), 0,
-                               stream, Pt.as<double>(), sg_norms.as<double>(), n_orders, k, d,
-                               reg, sg_thr.as<double>());
+            mich_apply();
             prof_end(2);
         }
-        *it += 1;
+        *st.it += 1;
     }
     HIPC(hipGetLastError());
     return SPFM_OK;
@@ -239,74 +270,47 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
 
 // the pointwise gradient (one sample per group) in front of the shared minibatch driver
 template <typename T, int L>
-int spfm_engine::psgd_epoch_tl(int degree, double alpha, double beta, double gamma, double eta0, int lr,
-                  double power_t, int64_t batch_size, int fit_linear, int64_t* it) {
+int spfm_engine::psgd_epoch_tl(const PsgdStep& st) {
     auto grad = [&](int64_t pos, int B, int grid, bool table) {
         hipLaunchKernelGGL((psgd_grad_kernel<T, L>), dim3(grid), dim3(kBlock), 0, stream,
                            sg_samples.as<int32_t>() + pos, B, rptr.as<int64_t>(),
                            ridx.as<int32_t>(), rval.as<T>(), yy.as<T>(), Pt.as<double>(),
-                           w.as<double>(), lams.as<double>(), n_orders, k, d, degree, loss,
-                           fit_linear, sg_gradP.as<double>(), sg_gradw.as<double>(),
+                           w.as<double>(), lams.as<double>(), n_orders, k, d, st.degree, loss,
+                           st.fit_linear, sg_gradP.as<double>(), sg_gradw.as<double>(),
                            pred_tmp.as<double>() + pos,
                            table ? sg_sched.as<PsgdBatch>() : (const PsgdBatch*)nullptr,
                            table ? sg_idx.as<int>() : (int*)nullptr);
     };
-    return psgd_batches_tl<L>(grad, "psgd", (int64_t)sizeof(T), n, degree, alpha, beta, gamma,
-                              eta0, lr, power_t, batch_size, fit_linear, it);
+    return psgd_batches_tl<L>(grad, "psgd", (int64_t)sizeof(T), n, st);
 }
 
 // optimizer/psgd.py:125-199: one pass over indices_samples
-int spfm_engine::psgd_epoch(int degree, double alpha, double beta, double gamma, double eta0, int lr,
-               double power_t, int64_t batch_size, const int32_t* indices_samples,
-               int64_t n_samples, int64_t row_lo, int fit_linear, int64_t* it, double* sum_loss) {
+int spfm_engine::psgd_epoch(const PsgdStep& st, const int32_t* indices_samples, int64_t n_samples,
+                            int64_t row_lo, double* sum_loss) {
+    // (this entry's three state messages share no prefix: psgd_ready cannot word them)
     if (!have_data || !have_params || !configured)
         FAIL(SPFM_ERR_INVALID, "epoch: data, parameters and configuration are required");
     if (solver != SPFM_SOLVER_PSGD) FAIL(SPFM_ERR_INVALID, "engine is not configured for psgd");
-    if (degree != top_degree) FAIL(SPFM_ERR_INVALID, "psgd: degree differs from configure()");
+    if (st.degree != top_degree) FAIL(SPFM_ERR_INVALID, "psgd: degree differs from configure()");
     const bool sharded = dist();
-    if (!indices_samples || !it || (!sharded && (n_samples != n || row_lo != 0)))
+    if (!indices_samples || !st.it || (!sharded && (n_samples != n || row_lo != 0)))
         FAIL(SPFM_ERR_INVALID, "psgd: indices_samples must list every sample once");
     if (sharded && (row_lo < 0 || row_lo + n > n_samples || n_samples > INT32_MAX))
         FAIL(SPFM_ERR_INVALID, "psgd: the handle's rows [row_lo, row_lo + n) lie outside the "
                                "global sample range");
-    if (batch_size < 1) FAIL(SPFM_ERR_INVALID, "psgd: batch_size must be >= 1");
-    if (lr < 0 || lr > 3) FAIL(SPFM_ERR_INVALID, "psgd: learning_rate is not supported.");
-    if (*it < 1) FAIL(SPFM_ERR_INVALID, "psgd: it must be >= 1");
-    {
-        std::vector<char> seen((size_t)n_samples, 0);
-        for (int64_t q = 0; q < n_samples; ++q) {
-            const int i = indices_samples[q];
-            if (i < 0 || i >= n_samples || seen[(size_t)i])
-                FAIL(SPFM_ERR_INVALID, "psgd: indices_samples is not a permutation");
-            seen[(size_t)i] = 1;
-        }
-    }
+    if (const std::string e = st.check("psgd"); !e.empty()) FAIL(SPFM_ERR_INVALID, e);
+    if (!is_permutation(indices_samples, n_samples))
+        FAIL(SPFM_ERR_INVALID, "psgd: indices_samples is not a permutation");
     if (n_samples == 0) {
         if (sum_loss) *sum_loss = 0.0;
         return SPFM_OK;
     }
-    int rc = ensure_pt();
-    if (rc) return rc;
+    SPFM_TRY(ensure_pt());
     p_valid = false;
     std::vector<int32_t> local;  // several ranks: this rank's samples in visiting order
     if (sharded) {
-        const int64_t nbat = cdiv(n_samples, batch_size);
-        sg_lpos.assign((size_t)nbat, 0);
-        sg_lB.assign((size_t)nbat, 0);
-        sg_gB.assign((size_t)nbat, 0);
-        local.reserve((size_t)n);
-        for (int64_t bi = 0; bi < nbat; ++bi) {
-            const int64_t pos = bi * batch_size;
-            const int64_t B = std::min<int64_t>(batch_size, n_samples - pos);
-            sg_lpos[(size_t)bi] = (int64_t)local.size();
-            for (int64_t q = pos; q < pos + B; ++q) {
-                const int64_t i = (int64_t)indices_samples[q] - row_lo;
-                if (i >= 0 && i < n) local.push_back((int32_t)i);
-            }
-            sg_lB[(size_t)bi] = (int32_t)((int64_t)local.size() - sg_lpos[(size_t)bi]);
-            sg_gB[(size_t)bi] = (int32_t)B;
-        }
-        if ((int64_t)local.size() != n)
+        if (!shard_batches(indices_samples, n_samples, row_lo, n, st.batch_size, sg_lpos, sg_lB,
+                           sg_gB, local))
             FAIL(SPFM_ERR_INVALID, "psgd: the global order does not hold this rank's rows once");
         indices_samples = local.data();
     }
@@ -314,55 +318,18 @@ int spfm_engine::psgd_epoch(int degree, double alpha, double beta, double gamma,
         SPFM_TRY(upload_to(sg_samples.p, indices_samples, (size_t)n));
         HIPC(hipStreamSynchronize(stream));  // caller may reuse indices_samples
     }
-#define SPFM_PSGD_GO(L)                                                                     \
-    psgd_epoch_tl<T, L>(degree, alpha, beta, gamma, eta0, lr, power_t, batch_size, fit_linear, it)
-    rc = SPFM_DISPATCH(dtype, return k <= 16   ? SPFM_PSGD_GO(16)
-                                     : k <= 32 ? SPFM_PSGD_GO(32)
-                                               : SPFM_PSGD_GO(64));
-#undef SPFM_PSGD_GO
-    if (rc) return rc;
-    hipLaunchKernelGGL(reduce_partial_kernel, dim3(256), dim3(kBlock), 0, stream,
-                       pred_tmp.as<double>(), n, partial.as<double>());
-    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(kBlock), 0, stream,
-                       partial.as<double>(), 256, scalar.as<double>());
-    HIPC(hipGetLastError());
-    if (sharded) {
-        rc = allreduce(scalar.as<double>(), 1);
-        if (rc) return rc;
-    }
-    SPFM_TRY(download(h_scalar, scalar.p, 1));
-    HIPC(hipStreamSynchronize(stream));
-    prof_collect();
-    if (sum_loss) *sum_loss = h_scalar[0];
-    psgd_warm = true;
-    return SPFM_OK;
+    SPFM_TRY(SPFM_DISPATCH(dtype, return SPFM_DISPATCH_L(k, return psgd_epoch_tl<T, L>(st))));
+    return psgd_epoch_end(pred_tmp.as<double>(), n, sum_loss);
 }
 
 // ============================================================ pairwise ranking fit
 //  triples (anchor, plus, minus) of rows of the handle's data [X; Z]
 
-// first stage of a count: out[block] = number of set flags in the block's contiguous slice
-static __global__ __launch_bounds__(kBlock) void pair_count_partial_kernel(
-    const int* __restrict__ v, int64_t n, double* __restrict__ out) {
-    __shared__ double red[16];
-    const int64_t per = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t lo = per * blockIdx.x, hi = (lo + per < n) ? lo + per : n;
-    double a = 0, b = 0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) a += (double)v[i];
-    block_sum2(a, b, red);
-    if (threadIdx.x == 0) out[blockIdx.x] = a;
-}
-
 // Argument checks of both pair entries, on the host, before any launch: the state of the handle,
 // the row indices, plus != minus, and -- one flag per row the triples name, then one pass over
 // the columns' stored rows -- no column stored in an anchor row and in a plus / minus row.
 int spfm_engine::psgd_pairs_check(const char* what, int degree, const int32_t* triples, int64_t m) {
-    if (!have_data || !have_params || !configured)
-        FAIL(SPFM_ERR_INVALID, std::string(what) + ": data, parameters and configuration are required");
-    if (solver != SPFM_SOLVER_PSGD)
-        FAIL(SPFM_ERR_INVALID, std::string(what) + ": engine is not configured for psgd");
-    if (degree != top_degree)
-        FAIL(SPFM_ERR_INVALID, std::string(what) + ": degree differs from configure()");
+    SPFM_TRY(psgd_ready(what, degree));
     if (m < 0 || (m > 0 && !triples) || m > INT32_MAX)
         FAIL(SPFM_ERR_INVALID, std::string(what) + ": triples must hold 0 <= m < 2^31 rows of 3");
     std::vector<uint8_t> side((size_t)(n > 0 ? n : 1), 0);  // 1: anchor, 2: plus / minus
@@ -378,88 +345,62 @@ int spfm_engine::psgd_pairs_check(const char* what, int degree, const int32_t* t
         side[(size_t)cp] |= 2;
         side[(size_t)cm] |= 2;
     }
-    for (int32_t j = 0; j < d; ++j) {
-        unsigned both = 0;
-        for (int64_t e = h_cptr[(size_t)j]; e < h_cptr[(size_t)j + 1]; ++e)
-            both |= side[(size_t)h_cidx[(size_t)e]];
-        if (both == 3)
-            FAIL(SPFM_ERR_INVALID, std::string(what) + ": column " + std::to_string(j) +
-                                       " is stored in an anchor row and in a plus/minus row: the "
-                                       "two column sets must be disjoint");
-    }
+    const int32_t j = first_shared_column(side, d, h_cptr.data(), h_cidx.data());
+    if (j >= 0)
+        FAIL(SPFM_ERR_INVALID, std::string(what) + ": column " + std::to_string(j) +
+                                   " is stored in an anchor row and in a plus/minus row: the "
+                                   "two column sets must be disjoint");
+    return SPFM_OK;
+}
+
+// room for m triples and their losses (a new allocation changes the recorded kernel arguments);
+// whatever list was drawn on the device is about to be overwritten
+int spfm_engine::pairs_reserve(int64_t m) {
+    sampled = false;
+    const void *o1 = sg_triples.p, *o2 = sg_lossrow.p;
+    HIPC(sg_triples.alloc(sizeof(int32_t) * 3 * (size_t)m));
+    HIPC(sg_lossrow.alloc(sizeof(double) * (size_t)m));
+    if (sg_triples.p != o1 || sg_lossrow.p != o2) clear_graphs();
     return SPFM_OK;
 }
 
 template <typename T, int L>
-int spfm_engine::psgd_pairs_epoch_tl(int degree, double alpha, double beta, double gamma,
-                                     double eta0, int lr, double power_t, int64_t batch_size,
-                                     int64_t m, int fit_linear, int64_t* it) {
+int spfm_engine::psgd_pairs_epoch_tl(const PsgdStep& st, int64_t m) {
     auto grad = [&](int64_t pos, int B, int grid, bool table) {
         hipLaunchKernelGGL((psgd_pair_grad_kernel<T, L, false>), dim3(grid), dim3(kBlock), 0,
                            stream, sg_triples.as<int32_t>() + 3 * pos, B, rptr.as<int64_t>(),
                            ridx.as<int32_t>(), rval.as<T>(), Pt.as<double>(), w.as<double>(),
-                           lams.as<double>(), n_orders, k, d, degree, loss, fit_linear,
+                           lams.as<double>(), n_orders, k, d, st.degree, loss, st.fit_linear,
                            sg_gradP.as<double>(), sg_gradw.as<double>(),
                            sg_lossrow.as<double>() + pos, (int*)nullptr,
                            table ? sg_sched.as<PsgdBatch>() : (const PsgdBatch*)nullptr,
                            table ? sg_idx.as<int>() : (int*)nullptr);
     };
-    return psgd_batches_tl<L>(grad, "psgd_pairs", (int64_t)sizeof(T), m, degree, alpha, beta,
-                              gamma, eta0, lr, power_t, batch_size, fit_linear, it);
+    return psgd_batches_tl<L>(grad, "psgd_pairs", (int64_t)sizeof(T), m, st);
 }
 
-int spfm_engine::psgd_pairs_epoch(int degree, double alpha, double beta, double gamma, double eta0,
-                                  int lr, double power_t, int64_t batch_size,
-                                  const int32_t* triples, int64_t m, int fit_linear, int64_t* it,
+int spfm_engine::psgd_pairs_epoch(const PsgdStep& st, const int32_t* triples, int64_t m,
                                   double* sum_loss) {
     if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs: several ranks are not supported");
-    SPFM_TRY(psgd_pairs_check("psgd pairs", degree, triples, m));
-    if (!it) FAIL(SPFM_ERR_INVALID, "psgd pairs: it is required");
-    if (batch_size < 1) FAIL(SPFM_ERR_INVALID, "psgd pairs: batch_size must be >= 1");
-    if (lr < 0 || lr > 3) FAIL(SPFM_ERR_INVALID, "psgd pairs: learning_rate is not supported.");
-    if (*it < 1) FAIL(SPFM_ERR_INVALID, "psgd pairs: it must be >= 1");
+    SPFM_TRY(psgd_pairs_check("psgd pairs", st.degree, triples, m));
+    if (const std::string e = st.check("psgd pairs"); !e.empty()) FAIL(SPFM_ERR_INVALID, e);
     if (m == 0) {
         if (sum_loss) *sum_loss = 0.0;
         return SPFM_OK;
     }
     SPFM_TRY(ensure_pt());
-    sampled = false;  // the upload overwrites a drawn list
-    {  // (a new allocation changes the recorded kernel arguments)
-        const void *o1 = sg_triples.p, *o2 = sg_lossrow.p;
-        HIPC(sg_triples.alloc(sizeof(int32_t) * 3 * (size_t)m));
-        HIPC(sg_lossrow.alloc(sizeof(double) * (size_t)m));
-        if (sg_triples.p != o1 || sg_lossrow.p != o2) clear_graphs();
-    }
+    SPFM_TRY(pairs_reserve(m));
     SPFM_TRY(upload_to(sg_triples.p, triples, 3 * (size_t)m));
     HIPC(hipStreamSynchronize(stream));  // caller may reuse triples
-    return psgd_pairs_run(degree, alpha, beta, gamma, eta0, lr, power_t, batch_size, m, fit_linear,
-                          it, sum_loss);
+    return psgd_pairs_run(st, m, sum_loss);
 }
 
 // the batches over the resident triple list sg_triples[0, m) and the sum of the triples' losses
-int spfm_engine::psgd_pairs_run(int degree, double alpha, double beta, double gamma, double eta0,
-                                int lr, double power_t, int64_t batch_size, int64_t m,
-                                int fit_linear, int64_t* it, double* sum_loss) {
+int spfm_engine::psgd_pairs_run(const PsgdStep& st, int64_t m, double* sum_loss) {
     p_valid = false;
-#define SPFM_PAIRS_GO(L)                                                                      \
-    psgd_pairs_epoch_tl<T, L>(degree, alpha, beta, gamma, eta0, lr, power_t, batch_size, m, \
-                              fit_linear, it)
-    int rc = SPFM_DISPATCH(dtype, return k <= 16   ? SPFM_PAIRS_GO(16)
-                                         : k <= 32 ? SPFM_PAIRS_GO(32)
-                                                   : SPFM_PAIRS_GO(64));
-#undef SPFM_PAIRS_GO
-    if (rc) return rc;
-    hipLaunchKernelGGL(reduce_partial_kernel, dim3(256), dim3(kBlock), 0, stream,
-                       sg_lossrow.as<double>(), m, partial.as<double>());
-    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(kBlock), 0, stream,
-                       partial.as<double>(), 256, scalar.as<double>());
-    HIPC(hipGetLastError());
-    SPFM_TRY(download(h_scalar, scalar.p, 1));
-    HIPC(hipStreamSynchronize(stream));
-    prof_collect();
-    if (sum_loss) *sum_loss = h_scalar[0];
-    psgd_warm = true;
-    return SPFM_OK;
+    SPFM_TRY(SPFM_DISPATCH(dtype,
+                           return SPFM_DISPATCH_L(k, return psgd_pairs_epoch_tl<T, L>(st, m))));
+    return psgd_epoch_end(sg_lossrow.as<double>(), m, sum_loss);
 }
 
 // loss sum and number of triples with m > 0 at the live parameters; nothing is updated
@@ -472,39 +413,17 @@ int spfm_engine::psgd_pairs_eval(int degree, int fit_linear, const int32_t* trip
     if (n_ordered) *n_ordered = 0;
     if (m == 0) return SPFM_OK;
     SPFM_TRY(ensure_pt());
-    {
-        const void *o1 = sg_triples.p, *o2 = sg_lossrow.p;
-        HIPC(sg_triples.alloc(sizeof(int32_t) * 3 * (size_t)m));
-        HIPC(sg_lossrow.alloc(sizeof(double) * (size_t)m));
-        if (sg_triples.p != o1 || sg_lossrow.p != o2) clear_graphs();
-    }
+    SPFM_TRY(pairs_reserve(m));
     HIPC(sg_ordered.alloc(sizeof(int) * (size_t)m));
-    sampled = false;  // the upload overwrites a drawn list
     SPFM_TRY(upload_to(sg_triples.p, triples, 3 * (size_t)m));
-#define SPFM_PAIRS_EV(L)                                                                       \
-    hipLaunchKernelGGL((psgd_pair_grad_kernel<T, L, true>), dim3(cdiv(m, kBlock / L)),        \
-                       dim3(kBlock), 0, stream, sg_triples.as<int32_t>(), (int)m,             \
-                       rptr.as<int64_t>(), ridx.as<int32_t>(), rval.as<T>(), Pt.as<double>(), \
-                       w.as<double>(), lams.as<double>(), n_orders, k, d, degree, loss, 0,    \
-                       (double*)nullptr, (double*)nullptr, sg_lossrow.as<double>(),           \
-                       sg_ordered.as<int>(), (const PsgdBatch*)nullptr, (int*)nullptr)
-    SPFM_DISPATCH(dtype, {
-        if (k <= 16)
-            SPFM_PAIRS_EV(16);
-        else if (k <= 32)
-            SPFM_PAIRS_EV(32);
-        else
-            SPFM_PAIRS_EV(64);
-    });
-#undef SPFM_PAIRS_EV
-    hipLaunchKernelGGL(reduce_partial_kernel, dim3(256), dim3(kBlock), 0, stream,
-                       sg_lossrow.as<double>(), m, partial.as<double>());
-    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(kBlock), 0, stream,
-                       partial.as<double>(), 256, scalar.as<double>());
-    hipLaunchKernelGGL(pair_count_partial_kernel, dim3(256), dim3(kBlock), 0, stream,
-                       sg_ordered.as<int>(), m, partial.as<double>() + 256);
-    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(kBlock), 0, stream,
-                       partial.as<double>() + 256, 256, scalar.as<double>() + 1);
+    SPFM_DISPATCH(dtype, SPFM_DISPATCH_L(k, hipLaunchKernelGGL(
+        (psgd_pair_grad_kernel<T, L, true>), dim3(cdiv(m, kBlock / L)), dim3(kBlock), 0, stream,
+        sg_triples.as<int32_t>(), (int)m, rptr.as<int64_t>(), ridx.as<int32_t>(), rval.as<T>(),
+        Pt.as<double>(), w.as<double>(), lams.as<double>(), n_orders, k, d, degree, loss, 0,
+        (double*)nullptr, (double*)nullptr, sg_lossrow.as<double>(), sg_ordered.as<int>(),
+        (const PsgdBatch*)nullptr, (int*)nullptr)));
+    loss_sum(sg_lossrow.as<double>(), m, 0);
+    loss_sum(sg_ordered.as<int>(), m, 1);
     HIPC(hipGetLastError());
     SPFM_TRY(download(h_scalar, scalar.p, 2));
     HIPC(hipStreamSynchronize(stream));
@@ -515,21 +434,6 @@ int spfm_engine::psgd_pairs_eval(int degree, int fit_linear, const int32_t* trip
 
 // ============================================================ negatives drawn on the device
 // 
-
-// one CSR over n_cand columns: in range, strictly ascending within a row
-static const char* sampler_csr_error(int64_t rows, int64_t n_cand, const int64_t* ptr,
-                                     const int32_t* idx) {
-    if (!ptr || ptr[0] != 0) return "indptr[0] != 0";
-    for (int64_t b = 0; b < rows; ++b) {
-        if (ptr[b + 1] < ptr[b]) return "indptr not monotone";
-        if (ptr[b + 1] > ptr[b] && !idx) return "indices missing";
-        for (int64_t e = ptr[b]; e < ptr[b + 1]; ++e) {
-            if (idx[e] < 0 || idx[e] >= n_cand) return "a candidate index outside [0, n_cand)";
-            if (e > ptr[b] && idx[e] <= idx[e - 1]) return "indices not strictly ascending";
-        }
-    }
-    return nullptr;
-}
 
 int spfm_engine::psgd_pairs_set_sampler(int64_t n_ctx, int64_t n_cand, const int64_t* pos_ptr,
                                         const int32_t* pos_idx, const int64_t* forb_ptr,
@@ -550,35 +454,26 @@ int spfm_engine::psgd_pairs_set_sampler(int64_t n_ctx, int64_t n_cand, const int
     const int64_t npos = pos_ptr[n_ctx];
     if (npos < 1 || npos > INT32_MAX)
         FAIL(SPFM_ERR_INVALID, "set_sampler: 1 <= nnz(positives) < 2^31 is required");
+    int64_t bad = 0;
+    if (const int kind = check_positives_in_forbidden(n_ctx, n_cand, pos_ptr, pos_idx, forb_ptr,
+                                                      forb_idx, &bad))
+        FAIL(SPFM_ERR_INVALID,
+             "set_sampler: row " + std::to_string(bad) +
+                 (kind == kForbiddenLacksPositive
+                      ? " of the forbidden set lacks one of its positives"
+                      : " forbids every candidate: no negative can be drawn"));
     std::vector<uint8_t> side((size_t)n, 0);  // 1: context with a positive, 2: candidate
     std::vector<int32_t> prow((size_t)npos);
     for (int64_t b = 0; b < n_ctx; ++b) {
-        const int64_t p0 = pos_ptr[b], p1 = pos_ptr[b + 1];
-        if (p1 == p0) continue;
-        side[(size_t)b] = 1;
-        int64_t f = forb_ptr[b];
-        const int64_t f1 = forb_ptr[b + 1];
-        for (int64_t e = p0; e < p1; ++e) {  // both sorted: one merge
-            prow[(size_t)e] = (int32_t)b;
-            while (f < f1 && forb_idx[f] < pos_idx[e]) ++f;
-            if (f == f1 || forb_idx[f] != pos_idx[e])
-                FAIL(SPFM_ERR_INVALID, "set_sampler: row " + std::to_string(b) +
-                                           " of the forbidden set lacks one of its positives");
-        }
-        if (f1 - forb_ptr[b] >= n_cand)
-            FAIL(SPFM_ERR_INVALID, "set_sampler: row " + std::to_string(b) +
-                                       " forbids every candidate: no negative can be drawn");
+        if (pos_ptr[b + 1] > pos_ptr[b]) side[(size_t)b] = 1;
+        for (int64_t e = pos_ptr[b]; e < pos_ptr[b + 1]; ++e) prow[(size_t)e] = (int32_t)b;
     }
     for (int64_t c = n_ctx; c < n; ++c) side[(size_t)c] = 2;
-    for (int32_t j = 0; j < d; ++j) {  // the rule of psgd_pairs_check
-        unsigned both = 0;
-        for (int64_t e = h_cptr[(size_t)j]; e < h_cptr[(size_t)j + 1]; ++e)
-            both |= side[(size_t)h_cidx[(size_t)e]];
-        if (both == 3)
-            FAIL(SPFM_ERR_INVALID, "set_sampler: column " + std::to_string(j) +
-                                       " is stored in a context row with a positive and in a "
-                                       "candidate row: the two column sets must be disjoint");
-    }
+    const int32_t j = first_shared_column(side, d, h_cptr.data(), h_cidx.data());
+    if (j >= 0)  // the rule of psgd_pairs_check
+        FAIL(SPFM_ERR_INVALID, "set_sampler: column " + std::to_string(j) +
+                                   " is stored in a context row with a positive and in a "
+                                   "candidate row: the two column sets must be disjoint");
     SPFM_TRY(upload(sm_posrow, prow.data(), (size_t)npos));
     SPFM_TRY(upload(sm_posidx, pos_idx, (size_t)npos));
     SPFM_TRY(upload(sm_fptr, forb_ptr, (size_t)n_ctx + 1));
@@ -596,12 +491,7 @@ int spfm_engine::psgd_pairs_sample(int degree, int64_t n_negatives, int64_t n_ca
                                    const int32_t* order, int32_t* triples_out,
                                    double* scores_out) {
     if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs sample: several ranks are not supported");
-    if (!have_data || !have_params || !configured)
-        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: data, parameters and configuration are required");
-    if (solver != SPFM_SOLVER_PSGD)
-        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: engine is not configured for psgd");
-    if (degree != top_degree)
-        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: degree differs from configure()");
+    SPFM_TRY(psgd_ready("psgd pairs sample", degree));
     if (!have_sampler)
         FAIL(SPFM_ERR_INVALID, "psgd pairs sample: call spfm_psgd_pairs_set_sampler first");
     if (n_negatives < 1 || n_candidates < 1 || max_draws < 1)
@@ -613,44 +503,20 @@ int spfm_engine::psgd_pairs_sample(int degree, int64_t n_negatives, int64_t n_ca
     if (seed < 0 || epoch < 0)
         FAIL(SPFM_ERR_INVALID, "psgd pairs sample: seed and epoch must be >= 0");
     const int64_t m = sm_npos * n_negatives;
-    if (order) {
-        std::vector<char> seen((size_t)m, 0);
-        for (int64_t q = 0; q < m; ++q) {
-            const int32_t i = order[q];
-            if (i < 0 || i >= m || seen[(size_t)i])
-                FAIL(SPFM_ERR_INVALID, "psgd pairs sample: order is not a permutation of 0..m-1");
-            seen[(size_t)i] = 1;
-        }
-    }
+    if (order && !is_permutation(order, m))
+        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: order is not a permutation of 0..m-1");
     SPFM_TRY(ensure_pt());
-    sampled = false;
-    {  // (a new allocation changes the recorded kernel arguments)
-        const void *o1 = sg_triples.p, *o2 = sg_lossrow.p;
-        HIPC(sg_triples.alloc(sizeof(int32_t) * 3 * (size_t)m));
-        HIPC(sg_lossrow.alloc(sizeof(double) * (size_t)m));
-        if (sg_triples.p != o1 || sg_lossrow.p != o2) clear_graphs();
-    }
+    SPFM_TRY(pairs_reserve(m));
     HIPC(sg_scores.alloc(sizeof(double) * (size_t)m));
     if (order) SPFM_TRY(upload(sg_order, order, (size_t)m));
-#define SPFM_SAMPLE_GO(L)                                                                       \
-    hipLaunchKernelGGL((psgd_pair_sample_kernel<T, L>), dim3(cdiv(m, kBlock / L)), dim3(kBlock), \
-                       0, stream, (int)m, (int)n_negatives, (int)n_candidates, (int)max_draws,  \
-                       (uint64_t)seed, (uint64_t)epoch, (int)sm_nctx, (int)sm_ncand,            \
-                       sm_posrow.as<int32_t>(), sm_posidx.as<int32_t>(), sm_fptr.as<int64_t>(), \
-                       sm_fidx.as<int32_t>(),                                                   \
-                       order ? sg_order.as<int32_t>() : (const int32_t*)nullptr,                \
-                       rptr.as<int64_t>(), ridx.as<int32_t>(), rval.as<T>(), Pt.as<double>(),   \
-                       w.as<double>(), lams.as<double>(), n_orders, k, d, degree,               \
-                       sg_triples.as<int32_t>(), sg_scores.as<double>())
-    SPFM_DISPATCH(dtype, {
-        if (k <= 16)
-            SPFM_SAMPLE_GO(16);
-        else if (k <= 32)
-            SPFM_SAMPLE_GO(32);
-        else
-            SPFM_SAMPLE_GO(64);
-    });
-#undef SPFM_SAMPLE_GO
+    SPFM_DISPATCH(dtype, SPFM_DISPATCH_L(k, hipLaunchKernelGGL(
+        (psgd_pair_sample_kernel<T, L>), dim3(cdiv(m, kBlock / L)), dim3(kBlock), 0, stream,
+        (int)m, (int)n_negatives, (int)n_candidates, (int)max_draws, (uint64_t)seed,
+        (uint64_t)epoch, (int)sm_nctx, (int)sm_ncand, sm_posrow.as<int32_t>(),
+        sm_posidx.as<int32_t>(), sm_fptr.as<int64_t>(), sm_fidx.as<int32_t>(),
+        order ? sg_order.as<int32_t>() : (const int32_t*)nullptr, rptr.as<int64_t>(),
+        ridx.as<int32_t>(), rval.as<T>(), Pt.as<double>(), w.as<double>(), lams.as<double>(),
+        n_orders, k, d, degree, sg_triples.as<int32_t>(), sg_scores.as<double>())));
     HIPC(hipGetLastError());
     if (triples_out) SPFM_TRY(download(triples_out, sg_triples.p, 3 * (size_t)m));
     if (scores_out) SPFM_TRY(download(scores_out, sg_scores.p, (size_t)m));
@@ -662,28 +528,42 @@ int spfm_engine::psgd_pairs_sample(int degree, int64_t n_negatives, int64_t n_ca
 
 // the epoch of psgd_pairs_epoch over the list the sample call left on the device: nothing is
 // uploaded and nothing re-checked (the list is valid by construction)
-int spfm_engine::psgd_pairs_epoch_sampled(int degree, double alpha, double beta, double gamma,
-                                          double eta0, int lr, double power_t, int64_t batch_size,
-                                          int fit_linear, int64_t* it, double* sum_loss) {
+int spfm_engine::psgd_pairs_epoch_sampled(const PsgdStep& st, double* sum_loss) {
     if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs: several ranks are not supported");
-    if (!have_data || !have_params || !configured)
-        FAIL(SPFM_ERR_INVALID, "psgd pairs: data, parameters and configuration are required");
-    if (solver != SPFM_SOLVER_PSGD)
-        FAIL(SPFM_ERR_INVALID, "psgd pairs: engine is not configured for psgd");
-    if (degree != top_degree) FAIL(SPFM_ERR_INVALID, "psgd pairs: degree differs from configure()");
+    SPFM_TRY(psgd_ready("psgd pairs", st.degree));
     if (!sampled)
         FAIL(SPFM_ERR_INVALID, "psgd pairs: the resident triple list is not the output of "
                                "spfm_psgd_pairs_sample");
-    if (!it) FAIL(SPFM_ERR_INVALID, "psgd pairs: it is required");
-    if (batch_size < 1) FAIL(SPFM_ERR_INVALID, "psgd pairs: batch_size must be >= 1");
-    if (lr < 0 || lr > 3) FAIL(SPFM_ERR_INVALID, "psgd pairs: learning_rate is not supported.");
-    if (*it < 1) FAIL(SPFM_ERR_INVALID, "psgd pairs: it must be >= 1");
+    if (const std::string e = st.check("psgd pairs"); !e.empty()) FAIL(SPFM_ERR_INVALID, e);
     SPFM_TRY(ensure_pt());
-    return psgd_pairs_run(degree, alpha, beta, gamma, eta0, lr, power_t, batch_size, sampled_m,
-                          fit_linear, it, sum_loss);
+    return psgd_pairs_run(st, sampled_m, sum_loss);
 }
 
 extern "C" {
+
+int spfm_psgd_epoch(spfm_handle h, int degree, double alpha, double beta, double gamma,
+                    double eta0, int learning_rate, double power_t, int64_t batch_size,
+                    const int32_t* indices_samples, int64_t n_samples, int fit_linear,
+                    int64_t* it, double* sum_loss) {
+    SPFM_GUARD(h);
+    if (h->dist()) {
+        h->err = "psgd: several ranks share this handle's communicator -- use spfm_psgd_epoch_sharded";
+        return SPFM_ERR_INVALID;
+    }
+    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
+                      fit_linear, it};
+    return h->psgd_epoch(st, indices_samples, n_samples, 0, sum_loss);
+}
+
+int spfm_psgd_epoch_sharded(spfm_handle h, int degree, double alpha, double beta, double gamma,
+                            double eta0, int learning_rate, double power_t, int64_t batch_size,
+                            const int32_t* indices_samples, int64_t n_global, int64_t row_lo,
+                            int fit_linear, int64_t* it, double* sum_loss) {
+    SPFM_GUARD(h);
+    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
+                      fit_linear, it};
+    return h->psgd_epoch(st, indices_samples, n_global, row_lo, sum_loss);
+}
 
 int spfm_psgd_pairs_set_sampler(spfm_handle h, int64_t n_ctx, int64_t n_cand,
                                 const int64_t* pos_ptr, const int32_t* pos_idx,
@@ -705,8 +585,9 @@ int spfm_psgd_pairs_epoch_sampled(spfm_handle h, int degree, double alpha, doubl
                                   int64_t batch_size, int fit_linear, int64_t* it,
                                   double* sum_loss) {
     SPFM_GUARD(h);
-    return h->psgd_pairs_epoch_sampled(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
-                                       batch_size, fit_linear, it, sum_loss);
+    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
+                      fit_linear, it};
+    return h->psgd_pairs_epoch_sampled(st, sum_loss);
 }
 
 int spfm_psgd_pairs_epoch(spfm_handle h, int degree, double alpha, double beta, double gamma,
@@ -714,8 +595,9 @@ int spfm_psgd_pairs_epoch(spfm_handle h, int degree, double alpha, double beta, 
                           const int32_t* triples, int64_t m, int fit_linear, int64_t* it,
                           double* sum_loss) {
     SPFM_GUARD(h);
-    return h->psgd_pairs_epoch(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
-                               batch_size, triples, m, fit_linear, it, sum_loss);
+    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
+                      fit_linear, it};
+    return h->psgd_pairs_epoch(st, triples, m, sum_loss);
 }
 
 int spfm_psgd_pairs_eval(spfm_handle h, int degree, int fit_linear, const int32_t* triples,

@@ -15,21 +15,9 @@
 // sweep is one coalesced read of P, and consecutive minibatches warm-start each other.
 #pragma once
 #include "spfm_common.hip.h"
+#include "spfm_psgd_host.h"  // PsgdBatch: one minibatch as the table-driven kernels see it
 
 namespace spfm {
-
-// One minibatch as the kernels see it when a whole run of minibatches is replayed from a
-// hipGraph (identical kernel arguments for every batch): the host tabulates the epoch
-// (psgd.py:9-22 step sizes included) and two device counters walk through the table --
-// the gradient kernel reads idx[0] and leaves idx[1] = that batch for the update kernel,
-// which leaves idx[0] = batch + 1 when it is done.  Kernels on one stream run one after
-// the other, so a counter is never written while a kernel that reads it is running.
-struct PsgdBatch {
-    long long pos;  // first position of the batch in the sample order
-    int B;          // rows in the batch
-    int pad;
-    double cp, denp, strength, cw, denw;  // eta_P/B, 1+eta_P*beta, prox strength, eta_w/B, 1+eta_w*alpha
-};
 
 constexpr int kPsgdNB = 1024;  // workgroups of the dense passes (partials per vector)
 constexpr int kPsgdMaxC = 4;   // component chunks per lane (k <= 4 * 64)
@@ -102,6 +90,34 @@ __device__ __forceinline__ void psgd_a_init(double* a) {
     for (int t = 1; t <= kMaxDegree; ++t) a[t] = 0.0;
 }
 
+// _anova over the entries [lo, hi) of a row for one (order, component chunk), kPsgdRC at a time,
+// CONTINUING a[] (the caller initialises it: the pair fit runs a context and a candidate through
+// one array).  The chunk of the last trip stays in `ch`.  Used by the pair gradient and the
+// sampler; psgd_grad_kernel keeps the loop written out (the same code allocates its registers
+// differently behind the call, and its stacked epoch measured 0.8 % slower).
+template <typename T, int L>
+__device__ __forceinline__ void psgd_row_dp(PsgdChunk<T, L>& ch, int64_t lo, int64_t hi, int ln,
+                                            const int32_t* __restrict__ ridx,
+                                            const T* __restrict__ rval,
+                                            const double* __restrict__ Pcol, int k, bool act,
+                                            int deg, double* a) {
+    for (int64_t tb = lo; tb < hi; tb += kPsgdRC) {
+        ch.load_entries(tb, hi, ln, ridx, rval);
+        ch.load_p(Pcol, k, act);
+        ch.dp(a, deg);
+    }
+}
+
+// Table-driven launch (graph replay) of a gradient kernel: it handles batch idx[0] and leaves
+// idx[1] = that batch for the update kernel.
+__device__ __forceinline__ void psgd_table_batch(const PsgdBatch* __restrict__ sched,
+                                                 int* __restrict__ idx, int& B, long long& pos) {
+    const int bi = idx[0];
+    if (blockIdx.x == 0 && threadIdx.x == 0) idx[1] = bi;
+    B = sched[bi].B;
+    pos = sched[bi].pos;
+}
+
 // One L-lane group per row of the minibatch.
 template <typename T, int L>
 __global__ __launch_bounds__(kBlock) void psgd_grad_kernel(
@@ -114,12 +130,11 @@ __global__ __launch_bounds__(kBlock) void psgd_grad_kernel(
     constexpr int gpb = kBlock / L;
     const int grp = threadIdx.x / L, ln = threadIdx.x % L;
     const int r = blockIdx.x * gpb + grp;
-    if (sched) {  // table-driven (graph replay): this launch handles batch idx[0]
-        const int bi = idx[0];
-        if (blockIdx.x == 0 && threadIdx.x == 0) idx[1] = bi;
-        B = sched[bi].B;
-        samples += sched[bi].pos;
-        loss_row += sched[bi].pos;
+    if (sched) {
+        long long pos;
+        psgd_table_batch(sched, idx, B, pos);
+        samples += pos;
+        loss_row += pos;
     }
     if (r >= B) return;  // whole groups leave; no block-level synchronisation below
     const int i = samples[r];
@@ -141,11 +156,13 @@ __global__ __launch_bounds__(kBlock) void psgd_grad_kernel(
             const bool act = s < k;
             const double* Pcol = Pt + (size_t)o * d * k + (act ? s : 0);
             psgd_a_init(a);
-            for (int64_t tb = lo; tb < hi; tb += kPsgdRC) {
-                ch.load_entries(tb, hi, ln, ridx, rval);
-                ch.load_p(Pcol, k, act);
+            for (int64_t tb = lo; tb < hi; tb += kPsgdRC) {  // (psgd_row_dp, written out: with
+                ch.load_entries(tb, hi, ln, ridx, rval);     // the call this kernel's registers
+                ch.load_p(Pcol, k, act);                     // are allocated differently)
                 ch.dp(a, deg);
             }
+            // a[deg], selected among values (the pair fit's pair_top_diff and the sampler's
+            // sample_top are the other two forms of this selection, each with its reason)
             double top = a[1];
 #pragma unroll
             for (int t = 2; t <= kMaxDegree; ++t)
@@ -175,9 +192,9 @@ __global__ __launch_bounds__(kBlock) void psgd_grad_kernel(
             double* Gcol = grad_P + (size_t)o * d * k + (act ? s : 0);
             const double dl = act ? dL * lams[s] : 0.0;
             psgd_a_init(a);
-            for (int64_t tb = lo; tb < hi; tb += kPsgdRC) {
-                ch.load_entries(tb, hi, ln, ridx, rval);
-                ch.load_p(Pcol, k, act);
+            for (int64_t tb = lo; tb < hi; tb += kPsgdRC) {  // (psgd_row_dp, written out: with
+                ch.load_entries(tb, hi, ln, ridx, rval);     // the call this kernel's registers
+                ch.load_p(Pcol, k, act);                     // are allocated differently)
                 ch.dp(a, deg);
             }
             for (int64_t tb = lo; tb < hi; tb += kPsgdRC) {

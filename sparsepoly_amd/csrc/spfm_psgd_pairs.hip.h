@@ -115,28 +115,18 @@ __device__ __forceinline__ void pair_dp_rows(PsgdChunk<T, L>& ch, int64_t l0, in
                                              const double* __restrict__ Pcol, int k, bool act,
                                              int deg, double* ap, double* am) {
     psgd_a_init(ap);
-    for (int64_t tb = l0; tb < h0; tb += kPsgdRC) {
-        ch.load_entries(tb, h0, ln, ridx, rval);
-        ch.load_p(Pcol, k, act);
-        ch.dp(ap, deg);
-    }
+    psgd_row_dp(ch, l0, h0, ln, ridx, rval, Pcol, k, act, deg, ap);
 #pragma unroll
     for (int t = 0; t <= kMaxDegree; ++t) am[t] = ap[t];
-    for (int64_t tb = l1; tb < h1; tb += kPsgdRC) {
-        ch.load_entries(tb, h1, ln, ridx, rval);
-        ch.load_p(Pcol, k, act);
-        ch.dp(ap, deg);
-    }
-    for (int64_t tb = l2; tb < h2; tb += kPsgdRC) {
-        ch.load_entries(tb, h2, ln, ridx, rval);
-        ch.load_p(Pcol, k, act);
-        ch.dp(am, deg);
-    }
+    psgd_row_dp(ch, l1, h1, ln, ridx, rval, Pcol, k, act, deg, ap);
+    psgd_row_dp(ch, l2, h2, ln, ridx, rval, Pcol, k, act, deg, am);
 }
 
 // a+[deg] - a-[deg].  Every order's difference is formed first and the one wanted is selected
 // among VALUES: a selection among the array elements themselves becomes an indexed load, which
-// moves both arrays out of the registers.
+// moves both arrays out of the registers.  (One of three forms of this selection, each fitted to
+// its kernel's registers: sample_top in spfm_psgd_sample.hip.h sums masked values, psgd_grad_kernel
+// selects inline among the values of its one array.)
 __device__ __forceinline__ double pair_top_diff(const double* ap, const double* am, int deg) {
     double df[kMaxDegree + 1];
 #pragma unroll
@@ -217,12 +207,11 @@ __global__ __launch_bounds__(kBlock) void psgd_pair_grad_kernel(
     constexpr int gpb = kBlock / L;
     const int grp = threadIdx.x / L, ln = threadIdx.x % L;
     const int r = blockIdx.x * gpb + grp;
-    if (sched) {  // table-driven (graph replay): this launch handles batch idx[0]
-        const int bi = idx[0];
-        if (blockIdx.x == 0 && threadIdx.x == 0) idx[1] = bi;
-        B = sched[bi].B;
-        triples += 3 * sched[bi].pos;
-        loss_row += sched[bi].pos;
+    if (sched) {
+        long long pos;
+        psgd_table_batch(sched, idx, B, pos);
+        triples += 3 * pos;
+        loss_row += pos;
     }
     if (r >= B) return;  // whole groups leave; no block-level synchronisation below
     const int ib = triples[3 * (size_t)r], ip = triples[3 * (size_t)r + 1],

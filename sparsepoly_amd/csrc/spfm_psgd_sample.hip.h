@@ -55,24 +55,11 @@ __device__ __forceinline__ bool sample_stored(const int32_t* __restrict__ idx, i
     return false;
 }
 
-// DP of the context's entries [l0, h0) for one (order, component chunk), in chunks of kPsgdRC
-template <typename T, int L>
-__device__ __forceinline__ void sample_ctx_dp(PsgdChunk<T, L>& ch, int64_t l0, int64_t h0, int ln,
-                                              const int32_t* __restrict__ ridx,
-                                              const T* __restrict__ rval,
-                                              const double* __restrict__ Pcol, int k, bool act,
-                                              int deg, double* a) {
-    psgd_a_init(a);
-    for (int64_t tb = l0; tb < h0; tb += kPsgdRC) {
-        ch.load_entries(tb, h0, ln, ridx, rval);
-        ch.load_p(Pcol, k, act);
-        ch.dp(a, deg);
-    }
-}
-
 // a[deg] as a sum of masked values (exact: one term, the rest zeros).  A selection among the
 // array elements themselves becomes an indexed load and moves the DP arrays of the candidates in
-// flight to scratch (240 bytes per lane in every instance; see pair_top_diff).
+// flight to scratch (240 bytes per lane in every instance; see pair_top_diff).  (The other two
+// forms of this selection: pair_top_diff in spfm_psgd_pairs.hip.h, and the inline one of
+// psgd_grad_kernel in spfm_psgd.hip.h.)
 __device__ __forceinline__ double sample_top(const double* a, int deg) {
     double top = 0.0;
 #pragma unroll
@@ -112,7 +99,8 @@ __global__ __launch_bounds__(kBlock) void psgd_pair_sample_kernel(
     if (M > 1 && keep) {
         PsgdChunk<T, L> ch;
         const bool act = ln < k;
-        sample_ctx_dp(ch, l0, h0, ln, ridx, rval, Pt + (act ? ln : 0), k, act, degree, a);
+        psgd_a_init(a);
+        psgd_row_dp(ch, l0, h0, ln, ridx, rval, Pt + (act ? ln : 0), k, act, degree, a);
     }
 
     int best = -1, cnt = 0;
@@ -159,7 +147,8 @@ __global__ __launch_bounds__(kBlock) void psgd_pair_sample_kernel(
                     const double* Pcol = Pt + (size_t)o * d * k + (act ? s : 0);
                     if (!keep) {
                         PsgdChunk<T, L> ch;
-                        sample_ctx_dp(ch, l0, h0, ln, ridx, rval, Pcol, k, act, deg, a);
+                        psgd_a_init(a);
+                        psgd_row_dp(ch, l0, h0, ln, ridx, rval, Pcol, k, act, deg, a);
                     }
                     double ac[kSampleNF][kMaxDegree + 1];
 #pragma unroll
@@ -218,7 +207,8 @@ __global__ __launch_bounds__(kBlock) void psgd_pair_sample_kernel(
                     const double* Pcol = Pt + (size_t)o * d * k + (act ? s : 0);
                     if (!keep) {
                         PsgdChunk<T, L> ch;
-                        sample_ctx_dp(ch, l0, h0, ln, ridx, rval, Pcol, k, act, deg, a);
+                        psgd_a_init(a);
+                        psgd_row_dp(ch, l0, h0, ln, ridx, rval, Pcol, k, act, deg, a);
                     }
                     double ac[kMaxDegree + 1];
 #pragma unroll

@@ -3,6 +3,8 @@ target upload, storage-type dispatch, entry guard).
 
 * Every refused call of tools/record_errors.py answers with the return code and the message the
   parent commit gave (profiles/errors_parent_438713e297d8.json), for both storage types.
+* The same for the psgd unit's own table (profiles/errors_psgd_parent_06084fb635e5.json, recorded
+  on the commit before the unit's shared pieces were folded into one copy each).
 * Shapes at which a count is 0 or a buffer is shared behave as before: they pin behaviour, each
   of them passes on the parent commit too.
 
@@ -23,6 +25,7 @@ import record_errors as rec  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 PARENT = os.path.join(ROOT, "profiles", "errors_parent_438713e297d8.json")
+PSGD_PARENT = os.path.join(ROOT, "profiles", "errors_psgd_parent_06084fb635e5.json")
 DTYPES = ("f32", "f64")
 N, D, K = rec.N, rec.D, rec.K
 
@@ -55,6 +58,19 @@ def test_refusals_answer_as_on_the_parent(dtype):
     assert sum(rc != 0 for rc, _ in want.values()) == len(want)  # every case is a refusal
     lib = rec._capi.load()
     got = {name: rec.run_case(lib, dtype, state, call) for name, state, call in rec.CASES}
+    diff = {name: (got[name], want[name]) for name in want if got[name] != want[name]}
+    assert not diff, diff
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_psgd_refusals_answer_as_on_the_parent(dtype):
+    with open(PSGD_PARENT) as f:
+        want = json.load(f)["cases"][dtype]
+    assert set(want) == {name for name, _, _ in rec.PSGD_CASES}
+    assert sum(rc != 0 for rc, _ in want.values()) == len(want)  # every case is a refusal
+    lib = rec._capi.load()
+    got = {name: rec.run_psgd_case(lib, dtype, state, call)
+           for name, state, call in rec.PSGD_CASES}
     diff = {name: (got[name], want[name]) for name in want if got[name] != want[name]}
     assert not diff, diff
 

@@ -9,6 +9,10 @@ spfm_objective_terms, the five spfm_interaction_* entries, the two spfm_gram_* e
 spfm_predict_csr.  (Not reachable at this size: the tie bound of interaction_topk, which needs
 more than 2^20 candidates, and the internal consistency checks that answer SPFM_ERR_RUNTIME.)
 tests/test_hip_errors.py replays the table against the recording of the parent commit.
+
+    python tools/record_errors.py --psgd profiles/errors_psgd_parent_<sha>.json
+
+records the second table, the psgd unit's own (PSGD_CASES below), in the same form.
 """
 import ctypes as C
 import json
@@ -352,7 +356,310 @@ def record():
             for dt in DTYPES}
 
 
+# ====================================================================== the psgd unit
+# A table of its own (python tools/record_errors.py --psgd profiles/errors_psgd_parent_<sha>.json):
+# every refusal that a small pair problem can reach in spfm_psgd_epoch, spfm_psgd_epoch_sharded (no
+# communicator: its argument checks only), spfm_psgd_pairs_epoch, spfm_psgd_pairs_eval,
+# spfm_psgd_pairs_set_sampler, spfm_psgd_pairs_sample and spfm_psgd_pairs_epoch_sampled.  6 context
+# rows (columns 0..4) over 5 candidate rows (columns 5..8), k = 2.  (Not reachable at this size:
+# more than 2^31 - 1 positives, and everything behind a communicator.)
+PS_NCTX, PS_NCAND, PS_D, PS_K = 6, 5, 9, 2
+PS_N = PS_NCTX + PS_NCAND
+
+
+def _psgd_problem():
+    rng = np.random.RandomState(11)
+    dense = np.zeros((PS_N, PS_D))
+    for i in range(PS_N):
+        cols = np.arange(0, 5) if i < PS_NCTX else np.arange(5, PS_D)
+        pick = rng.choice(cols, 2, replace=False)
+        dense[i, pick] = rng.randn(2)
+    shared = dense.copy()
+    shared[PS_NCTX + 1, np.flatnonzero(dense[0])[0]] = 0.5  # a column of context 0 in candidate 1
+
+    def csr(a):
+        indptr = np.zeros(PS_N + 1, np.int64)
+        indices, data = [], []
+        for i in range(PS_N):
+            nzc = np.flatnonzero(a[i])
+            indices += list(nzc)
+            data += list(a[i, nzc])
+            indptr[i + 1] = len(indices)
+        return indptr, np.asarray(indices, np.int32), np.asarray(data, np.float64)
+
+    return (csr(dense), csr(shared), np.zeros(PS_N), 0.1 * rng.randn(1, PS_K, PS_D),
+            0.1 * rng.randn(PS_D), np.ones(PS_K))
+
+
+PS_X, PS_XSHARED, PS_Y, PS_P, PS_W, PS_LAMS = _psgd_problem()
+# positives: every context but 4 has some; forbidden = positives + one more in rows 0 and 2
+PS_POS_PTR, PS_POS_IDX = i64(0, 2, 3, 4, 6, 6, 7), i32(0, 3, 1, 2, 0, 4, 3)
+PS_FORB_PTR, PS_FORB_IDX = i64(0, 3, 4, 6, 8, 8, 9), i32(0, 2, 3, 1, 2, 4, 0, 4, 3)
+PS_NPOS = int(PS_POS_PTR[-1])
+PS_TRIPLES = i32(0, 6, 7, 1, 8, 6, 5, 10, 9)  # three valid triples (context, plus, minus)
+PS_STEP = (0.01, 0.5, 0.003, 0.05)  # alpha, beta, gamma, eta0
+
+
+class PsgdHandle:
+    """A fresh handle brought to a named state by calls that all succeed."""
+
+    STEPS = {
+        "fresh": "", "data": "d", "unconfigured": "dp", "pcd": "dpc", "psgd": "dpg",
+        "shared": "Dpg", "sampler": "dpgs", "sampled": "dpgsS", "sampled_eval": "dpgsSe",
+        "sampled_epoch": "dpgsSu", "pcd_sampler": "dpcs",
+    }
+
+    def __init__(self, lib, dtype, state):
+        self.lib = lib
+        self.h = C.c_void_p()
+        assert lib.spfm_create(C.byref(self.h), 0, _capi.DTYPES[dtype]) == 0
+        for s in self.STEPS[state]:
+            getattr(self, "_" + s)()
+
+    def ok(self, rc):
+        assert rc == 0, (rc, self.lib.spfm_last_error(self.h))
+
+    def _data(self, X):
+        self.ok(self.lib.spfm_set_data_csr(self.h, PS_N, PS_D, ptr(X[0]), ptr(X[1]), ptr(X[2]),
+                                           ptr(PS_Y)))
+
+    def _d(self):
+        self._data(PS_X)
+
+    def _D(self):
+        self._data(PS_XSHARED)
+
+    def _p(self):
+        self.ok(self.lib.spfm_set_params(self.h, 1, PS_K, PS_D, ptr(PS_P), ptr(PS_W), ptr(PS_LAMS)))
+
+    def _configure(self, solver):
+        self.ok(self.lib.spfm_configure(self.h, _capi.SOLVERS[solver], _capi.LOSSES["logistic"],
+                                        _capi.REGULARIZERS["l1"], 2))
+
+    def _c(self):
+        self._configure("pcd")
+
+    def _g(self):
+        self._configure("psgd")
+
+    def _s(self):
+        self.ok(self.lib.spfm_psgd_pairs_set_sampler(self.h, PS_NCTX, PS_NCAND, ptr(PS_POS_PTR),
+                                                     ptr(PS_POS_IDX), ptr(PS_FORB_PTR),
+                                                     ptr(PS_FORB_IDX)))
+
+    def _S(self):
+        self.ok(self.lib.spfm_psgd_pairs_sample(self.h, 2, 1, 1, 16, 1, 0, NULL, NULL, NULL))
+
+    def _e(self):
+        self.ok(self.lib.spfm_psgd_pairs_eval(self.h, 2, 1, ptr(PS_TRIPLES), 3, NULL, NULL))
+
+    def _u(self):
+        it = i64(1)
+        self.ok(self.lib.spfm_psgd_pairs_epoch(self.h, 2, *PS_STEP, 1, 0.8, 2, ptr(PS_TRIPLES), 3,
+                                               1, ptr(it), NULL))
+
+    def close(self):
+        self.lib.spfm_destroy(self.h)
+
+
+def _psgd_cases():
+    """(name, state, call(lib, h) -> rc); `h` is None for the NULL-handle cases"""
+    cases = []
+    big = 1 << 31
+    perm = np.arange(PS_N, dtype=np.int32)[::-1].copy()
+    preamble = ("fresh", "data", "unconfigured", "pcd")
+
+    def add(name, state, call):
+        cases.append((name, state, call))
+
+    def tri(*rows):
+        return i32(*rows)
+
+    def with_(a, pos, v):
+        b = a.copy()
+        b[pos] = v
+        return b
+
+    not_perm = (("repeat", lambda a: with_(a, 1, a[0])), ("negative", lambda a: with_(a, 2, -1)),
+                ("entry_m", lambda a: with_(a, 0, a.size)))
+
+    # ---- spfm_psgd_epoch / spfm_psgd_epoch_sharded (no communicator)
+    def ep(degree=2, lr=1, batch=4, order=perm, n=PS_N, it=1, with_it=True, row_lo=None):
+        def call(L, h):
+            itv = i64(it)
+            head = (h, degree) + PS_STEP + (lr, 0.8, batch, ptr(order), n)
+            tail = (1, ptr(itv) if with_it else NULL, NULL)
+            if row_lo is None:
+                return L.spfm_psgd_epoch(*(head + tail))
+            return L.spfm_psgd_epoch_sharded(*(head + (row_lo,) + tail))
+        return call
+    for ent, kw in (("psgd_epoch", {}), ("psgd_epoch_sharded", dict(row_lo=0))):
+        add(ent + ":null_handle", None, ep(**kw))
+        for st in preamble:
+            add(ent + ":state_" + st, st, ep(**kw))
+        add(ent + ":degree_differs", "psgd", ep(degree=3, **kw))
+        add(ent + ":indices_null", "psgd", ep(order=None, **kw))
+        add(ent + ":it_null", "psgd", ep(with_it=False, **kw))
+        add(ent + ":n_samples_differs", "psgd", ep(n=PS_N - 1, **kw))
+        add(ent + ":batch_size_0", "psgd", ep(batch=0, **kw))
+        add(ent + ":learning_rate_negative", "psgd", ep(lr=-1, **kw))
+        add(ent + ":learning_rate_4", "psgd", ep(lr=4, **kw))
+        add(ent + ":it_0", "psgd", ep(it=0, **kw))
+        for nm, mk in not_perm:
+            add(ent + ":not_a_permutation_" + nm, "psgd", ep(order=mk(perm), **kw))
+    add("psgd_epoch_sharded:row_lo_1", "psgd", ep(row_lo=1))
+    add("psgd_epoch_sharded:row_lo_negative", "psgd", ep(row_lo=-1))
+
+    # ---- the triples of spfm_psgd_pairs_epoch / spfm_psgd_pairs_eval
+    def pe(degree=2, lr=1, batch=2, triples=PS_TRIPLES, m=3, it=1, with_it=True):
+        def call(L, h):
+            itv = i64(it)
+            return L.spfm_psgd_pairs_epoch(h, degree, *PS_STEP, lr, 0.8, batch, ptr(triples), m, 1,
+                                           ptr(itv) if with_it else NULL, NULL)
+        return call
+
+    def pv(degree=2, triples=PS_TRIPLES, m=3, **_):
+        return lambda L, h: L.spfm_psgd_pairs_eval(h, degree, 1, ptr(triples), m, NULL, NULL)
+    for ent, mk in (("pairs_epoch", pe), ("pairs_eval", pv)):
+        add(ent + ":null_handle", None, mk())
+        for st in preamble:
+            add(ent + ":state_" + st, st, mk())
+        add(ent + ":degree_differs", "psgd", mk(degree=3))
+        add(ent + ":m_negative", "psgd", mk(m=-1))
+        add(ent + ":triples_null", "psgd", mk(triples=None))
+        add(ent + ":m_2^31", "psgd", mk(m=big))
+        add(ent + ":anchor_negative", "psgd", mk(triples=tri(0, 6, 7, -1, 8, 6, 5, 10, 9)))
+        add(ent + ":anchor_n", "psgd", mk(triples=tri(PS_N, 6, 7, 1, 8, 6, 5, 10, 9)))
+        add(ent + ":plus_n", "psgd", mk(triples=tri(0, 6, 7, 1, PS_N, 6, 5, 10, 9)))
+        add(ent + ":plus_negative", "psgd", mk(triples=tri(0, -3, 7, 1, 8, 6, 5, 10, 9)))
+        add(ent + ":minus_n", "psgd", mk(triples=tri(0, 6, 7, 1, 8, 6, 5, 10, PS_N)))
+        add(ent + ":minus_negative", "psgd", mk(triples=tri(0, 6, -1, 1, 8, 6, 5, 10, 9)))
+        add(ent + ":plus_is_minus", "psgd", mk(triples=tri(0, 6, 7, 1, 8, 8, 5, 10, 9)))
+        add(ent + ":shared_column", "shared", mk())
+        # a context row as a candidate: its columns are stored on both sides
+        add(ent + ":context_as_candidate", "psgd", mk(triples=tri(0, 6, 7, 1, 8, 0, 5, 10, 9)))
+    add("pairs_epoch:it_null", "psgd", pe(with_it=False))
+    add("pairs_epoch:batch_size_0", "psgd", pe(batch=0))
+    add("pairs_epoch:learning_rate_negative", "psgd", pe(lr=-1))
+    add("pairs_epoch:learning_rate_4", "psgd", pe(lr=4))
+    add("pairs_epoch:it_0", "psgd", pe(it=0))
+
+    # ---- spfm_psgd_pairs_set_sampler
+    def ss(n_ctx=PS_NCTX, n_cand=PS_NCAND, pp=PS_POS_PTR, pi=PS_POS_IDX, fp=PS_FORB_PTR,
+           fi=PS_FORB_IDX):
+        return lambda L, h: L.spfm_psgd_pairs_set_sampler(h, n_ctx, n_cand, ptr(pp), ptr(pi),
+                                                          ptr(fp), ptr(fi))
+    add("set_sampler:null_handle", None, ss())
+    add("set_sampler:no_data", "fresh", ss())
+    add("set_sampler:n_ctx_0", "psgd", ss(n_ctx=0, n_cand=PS_N))
+    add("set_sampler:n_cand_0", "psgd", ss(n_ctx=PS_N, n_cand=0))
+    add("set_sampler:rows_differ", "psgd", ss(n_ctx=PS_NCTX - 1))
+    for side, ip, ix in (("positives", PS_POS_PTR, PS_POS_IDX), ("forbidden", PS_FORB_PTR, PS_FORB_IDX)):
+        def sd(indptr=ip, indices=ix, side=side):
+            if side == "positives":  # (no forbidden set: the positives stand in for it)
+                return ss(pp=indptr, pi=indices, fp=None, fi=None)
+            return ss(fp=indptr, fi=indices)
+        if side == "positives":
+            add("set_sampler:positives:indptr_null", "psgd", sd(indptr=None))
+        add("set_sampler:%s:indptr0" % side, "psgd", sd(indptr=with_(ip, 0, 1)))
+        add("set_sampler:%s:indptr_not_monotone" % side, "psgd", sd(indptr=with_(ip, 2, ip[1] - 1)))
+        add("set_sampler:%s:indices_null" % side, "psgd", sd(indices=None))
+        add("set_sampler:%s:index_negative" % side, "psgd", sd(indices=with_(ix, 0, -1)))
+        add("set_sampler:%s:index_n_cand" % side, "psgd", sd(indices=with_(ix, 1, PS_NCAND)))
+        add("set_sampler:%s:repeat" % side, "psgd", sd(indices=with_(ix, 1, ix[0])))
+        add("set_sampler:%s:descending" % side, "psgd",
+            sd(indices=with_(with_(ix, 0, ix[1]), 1, ix[0])))
+    add("set_sampler:no_positive", "psgd",
+        ss(pp=np.zeros(PS_NCTX + 1, np.int64), pi=None, fp=None, fi=None))
+    add("set_sampler:forbidden_lacks_a_positive", "psgd",
+        ss(fp=i64(0, 3, 4, 6, 8, 8, 9), fi=i32(0, 2, 3, 1, 3, 4, 0, 4, 3)))
+    add("set_sampler:forbidden_lacks_the_last_positive", "psgd",
+        ss(fp=i64(0, 3, 4, 6, 7, 7, 8), fi=i32(0, 2, 3, 1, 2, 4, 0, 3)))
+    # row 4 has no positive: all five candidates forbidden there is accepted; row 3 with four of
+    # five is accepted too (PS_FORB has two); all five in row 3 is refused
+    add("set_sampler:row_forbids_every_candidate", "psgd",
+        ss(fp=i64(0, 3, 4, 6, 11, 11, 12), fi=i32(0, 2, 3, 1, 2, 4, 0, 1, 2, 3, 4, 3)))
+    add("set_sampler:shared_column", "shared", ss())
+
+    # ---- spfm_psgd_pairs_sample
+    order = np.arange(PS_NPOS, dtype=np.int32)[::-1].copy()
+
+    def sa(degree=2, n_neg=1, n_cand=2, max_draws=16, seed=1, epoch=0, order=None):
+        return lambda L, h: L.spfm_psgd_pairs_sample(h, degree, n_neg, n_cand, max_draws, seed,
+                                                     epoch, ptr(order), NULL, NULL)
+    add("pairs_sample:null_handle", None, sa())
+    for st in preamble:
+        add("pairs_sample:state_" + st, st, sa())
+    add("pairs_sample:state_pcd_with_sampler", "pcd_sampler", sa())
+    add("pairs_sample:degree_differs", "sampler", sa(degree=3))
+    add("pairs_sample:before_set_sampler", "psgd", sa())
+    add("pairs_sample:n_negatives_0", "sampler", sa(n_neg=0))
+    add("pairs_sample:n_candidates_0", "sampler", sa(n_cand=0))
+    add("pairs_sample:max_draws_0", "sampler", sa(max_draws=0))
+    add("pairs_sample:n_candidates_2^31", "sampler", sa(n_cand=big))
+    add("pairs_sample:max_draws_2^31", "sampler", sa(max_draws=big))
+    add("pairs_sample:n_negatives_2^31", "sampler", sa(n_neg=big))
+    add("pairs_sample:list_above_2^31", "sampler", sa(n_neg=1 << 30))
+    add("pairs_sample:seed_negative", "sampler", sa(seed=-1))
+    add("pairs_sample:epoch_negative", "sampler", sa(epoch=-1))
+    for nm, mk in not_perm:
+        add("pairs_sample:order_not_a_permutation_" + nm, "sampler", sa(order=mk(order)))
+
+    # ---- spfm_psgd_pairs_epoch_sampled
+    def es(degree=2, lr=1, batch=2, it=1, with_it=True):
+        def call(L, h):
+            itv = i64(it)
+            return L.spfm_psgd_pairs_epoch_sampled(h, degree, *PS_STEP, lr, 0.8, batch, 1,
+                                                   ptr(itv) if with_it else NULL, NULL)
+        return call
+    add("epoch_sampled:null_handle", None, es())
+    for st in preamble:
+        add("epoch_sampled:state_" + st, st, es())
+    add("epoch_sampled:degree_differs", "sampled", es(degree=3))
+    add("epoch_sampled:before_set_sampler", "psgd", es())
+    add("epoch_sampled:before_sample", "sampler", es())
+    add("epoch_sampled:after_eval_upload", "sampled_eval", es())
+    add("epoch_sampled:after_epoch_upload", "sampled_epoch", es())
+    add("epoch_sampled:it_null", "sampled", es(with_it=False))
+    add("epoch_sampled:batch_size_0", "sampled", es(batch=0))
+    add("epoch_sampled:learning_rate_negative", "sampled", es(lr=-1))
+    add("epoch_sampled:learning_rate_4", "sampled", es(lr=4))
+    add("epoch_sampled:it_0", "sampled", es(it=0))
+    return cases
+
+
+PSGD_CASES = _psgd_cases()
+
+
+def run_psgd_case(lib, dtype, state, call):
+    """(rc, message) of one refused call on a fresh handle in `state`"""
+    if state is None:
+        rc = call(lib, None)
+        return [int(rc), lib.spfm_last_error(None).decode()]
+    hd = PsgdHandle(lib, dtype, state)
+    try:
+        rc = call(lib, hd.h)
+        return [int(rc), lib.spfm_last_error(hd.h).decode()]
+    finally:
+        hd.close()
+
+
+def record_psgd():
+    lib = _capi.load()
+    return {dt: {name: run_psgd_case(lib, dt, state, call) for name, state, call in PSGD_CASES}
+            for dt in DTYPES}
+
+
 def main(argv):
+    if len(argv) > 1 and argv[1] == "--psgd":
+        res = {"build_tag": _capi.build_tag(), "n_ctx": PS_NCTX, "n_cand": PS_NCAND, "d": PS_D,
+               "k": PS_K, "cases": record_psgd()}
+        refused = sum(rc != 0 for per in res["cases"].values() for rc, _ in per.values())
+        with open(argv[2], "w") as f:
+            f.write(json.dumps(res, indent=1, sort_keys=True) + "\n")
+        print("recorded %d psgd cases per storage type, %d refusals in all"
+              % (len(PSGD_CASES), refused), file=sys.stderr)
+        return
     res = {"build_tag": _capi.build_tag(), "n": N, "d": D, "k": K, "cases": record()}
     refused = sum(rc != 0 for per in res["cases"].values() for rc, _ in per.values())
     text = json.dumps(res, indent=1, sort_keys=True)
