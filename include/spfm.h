@@ -317,6 +317,49 @@ int spfm_psgd_pairs_epoch_sampled(spfm_handle h, int degree, double alpha, doubl
                                   int64_t batch_size, int fit_linear, int64_t* it,
                                   double* sum_loss);
 
+/* Listwise ranking fit: the training item is a LIST, a positive
+ * (anchor, plus) with its n_negatives = M negatives.  `triples` (m, 3) is GROUPED: rows
+ * q M .. q M + M - 1 share anchor and plus and hold the M negatives of list q -- the layout
+ * spfm_psgd_pairs_sample writes with order == NULL.  With the scores
+ *   s_i = sum_o sum_s lams_s a_s^{degree-o}(x_anchor + z_{c_i}) + <w, z_{c_i}>,  c_0 = plus,
+ * (the anchor's linear term is the same for all of them and is left out) the loss of a list is
+ *   SPFM_LIST_SOFTMAX   -s_0 + log sum_{i=0..M} exp(s_i)        (sampled softmax; a candidate
+ *                                                                 that appears twice counts twice)
+ *   SPFM_LIST_PAIRMEAN  (1/M) sum_{i>=1} loss(s_0 - s_i, +1)     (the configured loss; an epoch
+ *       over B lists per batch is arithmetically spfm_psgd_pairs_epoch over the same triples
+ *       with batch_size B M)
+ * The context's share of the gradient is formed once per list whatever M is (one DP, one
+ * gradient pass, one atomic per context column).  batch_size, eta / B and sum_loss count lists;
+ * penalties, step sizes, prox, `it` and the psgd options are those of spfm_psgd_epoch.
+ * SPFM_ERR_INVALID, checked on the host before anything is launched (the parameters stay as they
+ * were): everything spfm_psgd_pairs_epoch rejects, m % n_negatives != 0, n_negatives outside
+ * [1, SPFM_LIST_MAX_NEG], a group whose rows differ in anchor or plus, an unknown list_loss.  A
+ * handle with a communicator: SPFM_ERR_UNSUPPORTED. */
+#define SPFM_LIST_SOFTMAX 0
+#define SPFM_LIST_PAIRMEAN 1
+#define SPFM_LIST_MAX_NEG 63
+int spfm_psgd_lists_epoch(spfm_handle h, int degree, double alpha, double beta, double gamma,
+                          double eta0, int learning_rate, double power_t, int64_t batch_size,
+                          const int32_t* triples /* (m,3), grouped by list */, int64_t m,
+                          int64_t n_negatives, int list_loss, int fit_linear, int64_t* it,
+                          double* sum_loss);
+/* The same epoch over the list the last spfm_psgd_pairs_sample left on the device.  list_order:
+ * NULL, or the visiting order of the Q = m / n_negatives lists (a permutation of 0..Q-1, checked
+ * on the host, 4 Q bytes uploaded).  SPFM_ERR_INVALID: no resident sampled list, a sample call
+ * that used a slot `order` or another n_negatives, list_order not a permutation, and the step
+ * argument errors of spfm_psgd_lists_epoch. */
+int spfm_psgd_lists_epoch_sampled(spfm_handle h, int degree, double alpha, double beta,
+                                  double gamma, double eta0, int learning_rate, double power_t,
+                                  int64_t batch_size, int64_t n_negatives, int list_loss,
+                                  const int32_t* list_order /* Q or NULL */, int fit_linear,
+                                  int64_t* it, double* sum_loss);
+/* The same lists at the live device parameters, nothing updated: sum_loss = sum of the lists'
+ * losses, n_first = number of lists with s_0 > max_{i>=1} s_i.  Same preconditions and argument
+ * errors as spfm_psgd_lists_epoch. */
+int spfm_psgd_lists_eval(spfm_handle h, int degree, int fit_linear, const int32_t* triples,
+                         int64_t m, int64_t n_negatives, int list_loss, double* sum_loss,
+                         int64_t* n_first);
+
 /* -- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------
  * Rows are sharded; the column partial sums of every step are all-reduced
  * (sum, f64) so that every rank applies the identical prox.  id is an opaque

@@ -92,6 +92,7 @@ SYMBOLS = [
     "spfm_pcd_epoch", "spfm_pbcd_epoch", "spfm_psgd_epoch", "spfm_psgd_epoch_sharded",
     "spfm_psgd_pairs_epoch", "spfm_psgd_pairs_eval",
     "spfm_psgd_pairs_set_sampler", "spfm_psgd_pairs_sample", "spfm_psgd_pairs_epoch_sampled",
+    "spfm_psgd_lists_epoch", "spfm_psgd_lists_epoch_sampled", "spfm_psgd_lists_eval",
     "spfm_host_epoch_begin",
     "spfm_host_pass_begin", "spfm_host_step_sums", "spfm_host_step_apply", "spfm_host_epoch_end", "spfm_comm_unique_id", "spfm_comm_init", "spfm_comm_init_shm", "spfm_peer_alloc", "spfm_peer_connect",
     "spfm_profile_enable", "spfm_profile_get", "spfm_profile_reset", "spfm_set_use_graph",
@@ -130,6 +131,8 @@ PAIRS_MODES = {"interaction": 0, "hessian": 1}  # SPFM_PAIRS_INTERACTION / _HESS
 BANK_MAX_MODELS = 64  # SPFM_BANK_MAX_MODELS
 BANK_MAX_COMPONENTS = 4096  # SPFM_BANK_MAX_COMPONENTS (stacked)
 FOLDIN_MAX_UNKNOWNS = 128  # SPFM_FOLDIN_MAX_UNKNOWNS
+LIST_LOSSES = {"softmax": 0, "list": 1}  # SPFM_LIST_SOFTMAX / _PAIRMEAN
+LIST_MAX_NEG = 63  # SPFM_LIST_MAX_NEG
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -194,6 +197,14 @@ def load():
     L.spfm_psgd_pairs_epoch_sampled.argtypes = [_h, C.c_int, C.c_double, C.c_double, C.c_double,
                                                 C.c_double, C.c_int, C.c_double, C.c_int64,
                                                 C.c_int, _lp, _dp]
+    L.spfm_psgd_lists_epoch.argtypes = [_h, C.c_int, C.c_double, C.c_double, C.c_double,
+                                        C.c_double, C.c_int, C.c_double, C.c_int64, _ip,
+                                        C.c_int64, C.c_int64, C.c_int, C.c_int, _lp, _dp]
+    L.spfm_psgd_lists_epoch_sampled.argtypes = [_h, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                C.c_double, C.c_int, C.c_double, C.c_int64,
+                                                C.c_int64, C.c_int, _ip, C.c_int, _lp, _dp]
+    L.spfm_psgd_lists_eval.argtypes = [_h, C.c_int, C.c_int, _ip, C.c_int64, C.c_int64, C.c_int,
+                                       _dp, _lp]
     L.spfm_host_epoch_begin.argtypes = [_h, C.c_int, C.c_int]
     L.spfm_host_pass_begin.argtypes = [_h, C.c_int]
     L.spfm_host_step_sums.argtypes = [_h, C.c_int, _dp]

@@ -1065,6 +1065,26 @@ struct spfm_engine {
                           int32_t* triples_out, double* scores_out);
     int psgd_pairs_epoch_sampled(const PsgdStep& st, double* sum_loss);
 
+    // listwise fit: a positive and its n_negatives negatives are one
+    // item, read from the grouped triples in sg_triples; what the last sample call used is
+    // remembered (a sampled list epoch needs order == NULL and the same n_negatives)
+    DevBuf sg_listorder;
+    int64_t sampled_nneg = 0;
+    bool sampled_slots = false;
+    int psgd_lists_check(const char* what, int degree, const int32_t* triples, int64_t m,
+                         int64_t n_negatives, int list_loss);
+    template <typename T, int L>
+    int psgd_lists_epoch_tl(const PsgdStep& st, int64_t n_lists, int M, int list_loss,
+                            bool ordered);
+    int psgd_lists_run(const PsgdStep& st, int64_t n_lists, int M, int list_loss, bool ordered,
+                       double* sum_loss);
+    int psgd_lists_epoch(const PsgdStep& st, const int32_t* triples, int64_t m,
+                         int64_t n_negatives, int list_loss, double* sum_loss);
+    int psgd_lists_epoch_sampled(const PsgdStep& st, int64_t n_negatives, int list_loss,
+                                 const int32_t* list_order, double* sum_loss);
+    int psgd_lists_eval(int degree, int fit_linear, const int32_t* triples, int64_t m,
+                        int64_t n_negatives, int list_loss, double* sum_loss, int64_t* n_first);
+
     // ------------------------------- objective terms, held-out set (spfm_engine_objective.hip)
     // Read-only views of the live state: they use buffers of their own, neither of the
     // P / Pt validity flags changes, nothing an epoch reads is written.

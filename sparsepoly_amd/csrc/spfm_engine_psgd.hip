@@ -2,6 +2,7 @@
 #include "spfm_engine.hip.h"
 #include "spfm_psgd_pairs.hip.h"
 #include "spfm_psgd_sample.hip.h"
+#include "spfm_psgd_lists.hip.h"
 
 using namespace spfm;
 
@@ -523,6 +524,8 @@ int spfm_engine::psgd_pairs_sample(int degree, int64_t n_negatives, int64_t n_ca
     HIPC(hipStreamSynchronize(stream));  // order may be reused; the copies have landed
     sampled = true;
     sampled_m = m;
+    sampled_nneg = n_negatives;
+    sampled_slots = order != nullptr;
     return SPFM_OK;
 }
 
@@ -537,6 +540,155 @@ int spfm_engine::psgd_pairs_epoch_sampled(const PsgdStep& st, double* sum_loss) 
     if (const std::string e = st.check("psgd pairs"); !e.empty()) FAIL(SPFM_ERR_INVALID, e);
     SPFM_TRY(ensure_pt());
     return psgd_pairs_run(st, sampled_m, sum_loss);
+}
+
+// ============================================================ listwise ranking fit
+//  a positive with its n_negatives negatives is one training item
+
+static_assert(kListMaxNeg == SPFM_LIST_MAX_NEG && kListSoftmax == SPFM_LIST_SOFTMAX &&
+                  kListPairMean == SPFM_LIST_PAIRMEAN,
+              "spfm.h and spfm_psgd_lists.hip.h disagree");
+
+// the list arguments of every list entry, in `what`'s words; empty: none failed
+static std::string lists_args_error(const char* what, int64_t n_negatives, int list_loss) {
+    const char* e = (n_negatives < 1 || n_negatives > SPFM_LIST_MAX_NEG)
+                        ? "n_negatives must be in [1, SPFM_LIST_MAX_NEG = 63]"
+                    : (list_loss != SPFM_LIST_SOFTMAX && list_loss != SPFM_LIST_PAIRMEAN)
+                        ? "list_loss must be SPFM_LIST_SOFTMAX or SPFM_LIST_PAIRMEAN"
+                        : nullptr;
+    return e ? std::string(what) + ": " + e : std::string();
+}
+
+// Argument checks of the two list entries that take triples, on the host, before any launch:
+// those of the pair entries, the list arguments, and the grouping of the rows.
+int spfm_engine::psgd_lists_check(const char* what, int degree, const int32_t* triples, int64_t m,
+                                  int64_t n_negatives, int list_loss) {
+    SPFM_TRY(psgd_pairs_check(what, degree, triples, m));
+    if (const std::string e = lists_args_error(what, n_negatives, list_loss); !e.empty())
+        FAIL(SPFM_ERR_INVALID, e);
+    if (m % n_negatives != 0)
+        FAIL(SPFM_ERR_INVALID, std::string(what) + ": m is not a multiple of n_negatives");
+    for (int64_t q = 0; q < m; ++q) {
+        const int64_t q0 = q - q % n_negatives;
+        if (triples[3 * q] != triples[3 * q0] || triples[3 * q + 1] != triples[3 * q0 + 1])
+            FAIL(SPFM_ERR_INVALID, std::string(what) + ": triple " + std::to_string(q) +
+                                       " differs from the first of its list in anchor or plus: "
+                                       "the triples must be grouped by list");
+    }
+    return SPFM_OK;
+}
+
+template <typename T, int L>
+int spfm_engine::psgd_lists_epoch_tl(const PsgdStep& st, int64_t n_lists, int M, int list_loss,
+                                     bool ordered) {
+    auto grad = [&](int64_t pos, int B, int grid, bool table) {
+        hipLaunchKernelGGL((psgd_list_grad_kernel<T, L, false>), dim3(grid), dim3(kBlock), 0,
+                           stream, sg_triples.as<int32_t>(),
+                           ordered ? sg_listorder.as<int32_t>() : (const int32_t*)nullptr,
+                           (long long)pos, B, M, list_loss, rptr.as<int64_t>(),
+                           ridx.as<int32_t>(), rval.as<T>(), Pt.as<double>(), w.as<double>(),
+                           lams.as<double>(), n_orders, k, d, st.degree, loss, st.fit_linear,
+                           sg_gradP.as<double>(), sg_gradw.as<double>(), sg_lossrow.as<double>(),
+                           (int*)nullptr,
+                           table ? sg_sched.as<PsgdBatch>() : (const PsgdBatch*)nullptr,
+                           table ? sg_idx.as<int>() : (int*)nullptr);
+    };
+    // the recorded kernel arguments hold M, list_loss and the order pointer: part of the graph key
+    const std::string tag = "psgd_lists|" + std::to_string(M) + "|" + std::to_string(list_loss) +
+                            "|" + std::to_string((int)ordered);
+    return psgd_batches_tl<L>(grad, tag.c_str(), (int64_t)sizeof(T), n_lists, st);
+}
+
+// the batches over the lists of the resident grouped triples and the sum of the lists' losses
+int spfm_engine::psgd_lists_run(const PsgdStep& st, int64_t n_lists, int M, int list_loss,
+                                bool ordered, double* sum_loss) {
+    p_valid = false;
+    SPFM_TRY(SPFM_DISPATCH(dtype, return SPFM_DISPATCH_L(k, return psgd_lists_epoch_tl<T, L>(
+                                                                 st, n_lists, M, list_loss,
+                                                                 ordered))));
+    return psgd_epoch_end(sg_lossrow.as<double>(), n_lists, sum_loss);
+}
+
+int spfm_engine::psgd_lists_epoch(const PsgdStep& st, const int32_t* triples, int64_t m,
+                                  int64_t n_negatives, int list_loss, double* sum_loss) {
+    if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd lists: several ranks are not supported");
+    SPFM_TRY(psgd_lists_check("psgd lists", st.degree, triples, m, n_negatives, list_loss));
+    if (const std::string e = st.check("psgd lists"); !e.empty()) FAIL(SPFM_ERR_INVALID, e);
+    if (m == 0) {
+        if (sum_loss) *sum_loss = 0.0;
+        return SPFM_OK;
+    }
+    SPFM_TRY(ensure_pt());
+    SPFM_TRY(pairs_reserve(m));
+    SPFM_TRY(upload_to(sg_triples.p, triples, 3 * (size_t)m));
+    HIPC(hipStreamSynchronize(stream));  // caller may reuse triples
+    return psgd_lists_run(st, m / n_negatives, (int)n_negatives, list_loss, false, sum_loss);
+}
+
+// the epoch of psgd_lists_epoch over the list the sample call left on the device: nothing is
+// re-checked but that the sample call grouped it the way this call reads it
+int spfm_engine::psgd_lists_epoch_sampled(const PsgdStep& st, int64_t n_negatives, int list_loss,
+                                          const int32_t* list_order, double* sum_loss) {
+    if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd lists: several ranks are not supported");
+    SPFM_TRY(psgd_ready("psgd lists", st.degree));
+    if (!sampled)
+        FAIL(SPFM_ERR_INVALID, "psgd lists: the resident triple list is not the output of "
+                               "spfm_psgd_pairs_sample");
+    if (const std::string e = lists_args_error("psgd lists", n_negatives, list_loss); !e.empty())
+        FAIL(SPFM_ERR_INVALID, e);
+    if (sampled_slots)
+        FAIL(SPFM_ERR_INVALID, "psgd lists: the sample call scattered its triples by `order`; "
+                               "lists need order == NULL");
+    if (sampled_nneg != n_negatives)
+        FAIL(SPFM_ERR_INVALID, "psgd lists: the sample call drew " + std::to_string(sampled_nneg) +
+                                   " negatives per positive, not " + std::to_string(n_negatives));
+    if (const std::string e = st.check("psgd lists"); !e.empty()) FAIL(SPFM_ERR_INVALID, e);
+    const int64_t n_lists = sampled_m / n_negatives;
+    if (list_order && !is_permutation(list_order, n_lists))
+        FAIL(SPFM_ERR_INVALID, "psgd lists: list_order is not a permutation of the lists");
+    SPFM_TRY(ensure_pt());
+    if (list_order) {
+        const void* old = sg_listorder.p;
+        HIPC(sg_listorder.alloc(sizeof(int32_t) * (size_t)n_lists));
+        if (sg_listorder.p != old) clear_graphs();
+        SPFM_TRY(upload_to(sg_listorder.p, list_order, (size_t)n_lists));
+        HIPC(hipStreamSynchronize(stream));  // caller may reuse list_order
+    }
+    return psgd_lists_run(st, n_lists, (int)n_negatives, list_loss, list_order != nullptr,
+                          sum_loss);
+}
+
+// loss sum and number of lists whose positive scores first at the live parameters; nothing is
+// updated
+int spfm_engine::psgd_lists_eval(int degree, int fit_linear, const int32_t* triples, int64_t m,
+                                 int64_t n_negatives, int list_loss, double* sum_loss,
+                                 int64_t* n_first) {
+    (void)fit_linear;  // the scores read w as it stands (zeros when no linear term was fitted)
+    if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd lists eval: several ranks are not supported");
+    SPFM_TRY(psgd_lists_check("psgd lists eval", degree, triples, m, n_negatives, list_loss));
+    if (sum_loss) *sum_loss = 0.0;
+    if (n_first) *n_first = 0;
+    if (m == 0) return SPFM_OK;
+    const int64_t n_lists = m / n_negatives;
+    SPFM_TRY(ensure_pt());
+    SPFM_TRY(pairs_reserve(m));
+    HIPC(sg_ordered.alloc(sizeof(int) * (size_t)n_lists));
+    SPFM_TRY(upload_to(sg_triples.p, triples, 3 * (size_t)m));
+    SPFM_DISPATCH(dtype, SPFM_DISPATCH_L(k, hipLaunchKernelGGL(
+        (psgd_list_grad_kernel<T, L, true>), dim3(cdiv(n_lists, kBlock / L)), dim3(kBlock), 0,
+        stream, sg_triples.as<int32_t>(), (const int32_t*)nullptr, 0LL, (int)n_lists,
+        (int)n_negatives, list_loss, rptr.as<int64_t>(), ridx.as<int32_t>(), rval.as<T>(),
+        Pt.as<double>(), w.as<double>(), lams.as<double>(), n_orders, k, d, degree, loss, 0,
+        (double*)nullptr, (double*)nullptr, sg_lossrow.as<double>(), sg_ordered.as<int>(),
+        (const PsgdBatch*)nullptr, (int*)nullptr)));
+    loss_sum(sg_lossrow.as<double>(), n_lists, 0);
+    loss_sum(sg_ordered.as<int>(), n_lists, 1);
+    HIPC(hipGetLastError());
+    SPFM_TRY(download(h_scalar, scalar.p, 2));
+    HIPC(hipStreamSynchronize(stream));
+    if (sum_loss) *sum_loss = h_scalar[0];
+    if (n_first) *n_first = (int64_t)h_scalar[1];
+    return SPFM_OK;
 }
 
 extern "C" {
@@ -604,6 +756,35 @@ int spfm_psgd_pairs_eval(spfm_handle h, int degree, int fit_linear, const int32_
                          int64_t m, double* sum_loss, int64_t* n_ordered) {
     SPFM_GUARD(h);
     return h->psgd_pairs_eval(degree, fit_linear, triples, m, sum_loss, n_ordered);
+}
+
+int spfm_psgd_lists_epoch(spfm_handle h, int degree, double alpha, double beta, double gamma,
+                          double eta0, int learning_rate, double power_t, int64_t batch_size,
+                          const int32_t* triples, int64_t m, int64_t n_negatives, int list_loss,
+                          int fit_linear, int64_t* it, double* sum_loss) {
+    SPFM_GUARD(h);
+    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
+                      fit_linear, it};
+    return h->psgd_lists_epoch(st, triples, m, n_negatives, list_loss, sum_loss);
+}
+
+int spfm_psgd_lists_epoch_sampled(spfm_handle h, int degree, double alpha, double beta,
+                                  double gamma, double eta0, int learning_rate, double power_t,
+                                  int64_t batch_size, int64_t n_negatives, int list_loss,
+                                  const int32_t* list_order, int fit_linear, int64_t* it,
+                                  double* sum_loss) {
+    SPFM_GUARD(h);
+    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
+                      fit_linear, it};
+    return h->psgd_lists_epoch_sampled(st, n_negatives, list_loss, list_order, sum_loss);
+}
+
+int spfm_psgd_lists_eval(spfm_handle h, int degree, int fit_linear, const int32_t* triples,
+                         int64_t m, int64_t n_negatives, int list_loss, double* sum_loss,
+                         int64_t* n_first) {
+    SPFM_GUARD(h);
+    return h->psgd_lists_eval(degree, fit_linear, triples, m, n_negatives, list_loss, sum_loss,
+                              n_first);
 }
 
 }  // extern "C"

@@ -82,6 +82,21 @@ struct PsgdChunk {
             if (act && u < cnt) unsafeAtomicAdd(&Gcol[(size_t)j * k], dl * dprev);
         }
     }
+    // grad on a linear combination of DP arrays (the list fit, spfm_psgd_lists.hip.h): the
+    // recurrence is linear in a[0..deg-1], so it starts from dprev = x * a0 where grad has a[0] = 1
+    __device__ __forceinline__ void grad_from(const double* a, double a0, int deg, double dl,
+                                              double* __restrict__ Gcol, int k, bool act) const {
+#pragma unroll
+        for (int u = 0; u < kPsgdRC; ++u) {
+            const int j = col(u);
+            const double x = val(u);
+            double dprev = x * a0;
+#pragma unroll
+            for (int t = 1; t < kMaxDegree; ++t)
+                if (t < deg) dprev = x * (a[t] - p[u] * dprev);
+            if (act && u < cnt) unsafeAtomicAdd(&Gcol[(size_t)j * k], dl * dprev);
+        }
+    }
 };
 
 __device__ __forceinline__ void psgd_a_init(double* a) {

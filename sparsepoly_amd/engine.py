@@ -1283,6 +1283,68 @@ class HipEngine(object):
             float(power_t), int(batch_size), int(bool(fit_linear)), C.byref(itc), C.byref(sl)))
         return sl.value, itc.value
 
+    @staticmethod
+    def _list_loss(list_loss):
+        if isinstance(list_loss, str):
+            if list_loss not in _capi.LIST_LOSSES:
+                raise ValueError("list_loss %r is not supported. Choose from %s."
+                                 % (list_loss, sorted(_capi.LIST_LOSSES)))
+            return _capi.LIST_LOSSES[list_loss]
+        return int(list_loss)
+
+    def psgd_lists_epoch(self, degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                         batch_size, triples, n_negatives, list_loss, fit_linear, it):
+        """One pass of minibatch psgd over lists -- a positive with its ``n_negatives``
+        negatives, rows ``q M .. q M + M - 1`` of the grouped ``triples`` (rows of ``[X; Z]``) --
+        in the order given; ``list_loss``: ``'softmax'`` or ``'list'``; ``batch_size`` counts
+        lists (``spfm_psgd_lists_epoch``).  Returns (sum_loss over the lists, it)."""
+        t = self._triples(triples)
+        itc = C.c_int64(int(it))
+        sl = C.c_double()
+        lr = (_capi.LEARNING_RATE[learning_rate] if isinstance(learning_rate, str)
+              else int(learning_rate))
+        self._check(self._lib.spfm_psgd_lists_epoch(
+            self._h, int(degree), float(alpha), float(beta), float(gamma), float(eta0), lr,
+            float(power_t), int(batch_size), t.ctypes.data_as(_capi._ip), t.shape[0],
+            int(n_negatives), self._list_loss(list_loss), int(bool(fit_linear)), C.byref(itc),
+            C.byref(sl)))
+        return sl.value, itc.value
+
+    def psgd_lists_epoch_sampled(self, degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                                 batch_size, n_negatives, list_loss, fit_linear, it,
+                                 list_order=None):
+        """``psgd_lists_epoch`` over the list ``psgd_pairs_sample(order=None)`` left on the
+        device; ``list_order``: the visiting order of the lists, or ``None``
+        (``spfm_psgd_lists_epoch_sampled``).  Returns (sum_loss, it)."""
+        itc = C.c_int64(int(it))
+        sl = C.c_double()
+        lr = (_capi.LEARNING_RATE[learning_rate] if isinstance(learning_rate, str)
+              else int(learning_rate))
+        o = None
+        if list_order is not None:
+            o = np.ascontiguousarray(list_order, dtype=np.int32)
+            q = getattr(self, "_sampler_npos", 0)
+            if o.shape != (q,):
+                raise ValueError("list_order must have shape (%d,), got %r" % (q, o.shape))
+        self._check(self._lib.spfm_psgd_lists_epoch_sampled(
+            self._h, int(degree), float(alpha), float(beta), float(gamma), float(eta0), lr,
+            float(power_t), int(batch_size), int(n_negatives), self._list_loss(list_loss),
+            None if o is None else o.ctypes.data_as(_capi._ip), int(bool(fit_linear)),
+            C.byref(itc), C.byref(sl)))
+        return sl.value, itc.value
+
+    def psgd_lists_eval(self, degree, fit_linear, triples, n_negatives, list_loss):
+        """(sum of the lists' losses, number of lists whose positive scores above all of its
+        negatives) at the live device parameters; nothing is updated
+        (``spfm_psgd_lists_eval``)."""
+        t = self._triples(triples)
+        sl = C.c_double()
+        nf = C.c_int64()
+        self._check(self._lib.spfm_psgd_lists_eval(
+            self._h, int(degree), int(bool(fit_linear)), t.ctypes.data_as(_capi._ip), t.shape[0],
+            int(n_negatives), self._list_loss(list_loss), C.byref(sl), C.byref(nf)))
+        return sl.value, nf.value
+
     # ------------------------------------------------------------- multi-GPU
     @staticmethod
     def comm_unique_id():

@@ -17,6 +17,9 @@ vocabulary of ``ranking.py``: one feature space, disjoint column sets.  The stac
 ``'dynamic'`` draw them on the device (``draw_u64`` / ``restate_sample``
 restate that in NumPy).  ``restate_margins`` / ``restate_pair_gradient`` /
 ``restate_pairwise_epoch`` are plain NumPy restatements, test aids that never touch the device.
+``objective='list'`` and ``'softmax'`` make a positive with its ``n_negatives`` negatives ONE
+training item (``restate_list_scores`` / ``restate_list_gradient`` /
+``restate_list_epoch`` restate it).
 There is no CPU path of the fit: without the library or a GPU it raises.
 """
 import numpy as np
@@ -432,6 +435,158 @@ def restate_pairwise_epoch(P, w, lams, X, Z, triples, degree, loss="logistic", r
     return P, w, sum_loss, it
 
 
+# ------------------------------------------------------------------ lists
+OBJECTIVES = ("pairwise", "list", "softmax")
+
+
+def check_lists(triples, n_negatives, objective="softmax"):
+    """The list arguments of the fit, checked without a device: ``objective`` one of
+    ``'list'``, ``'softmax'``; ``n_negatives`` an integer in ``[1, SPFM_LIST_MAX_NEG]``; and, when
+    ``triples`` is given, ``(m, 3)`` rows grouped by list -- ``m`` a multiple of ``n_negatives``,
+    rows ``q M .. q M + M - 1`` with one context and one ``c+``.  ``ValueError`` otherwise."""
+    if objective not in OBJECTIVES[1:]:
+        raise ValueError("objective %r is not a list objective. Choose from %s."
+                         % (objective, list(OBJECTIVES[1:])))
+    if int(n_negatives) != n_negatives or not 1 <= n_negatives <= _capi.LIST_MAX_NEG:
+        raise ValueError("objective=%r: n_negatives must be an integer in [1, %d], got %r"
+                         % (objective, _capi.LIST_MAX_NEG, n_negatives))
+    if triples is None:
+        return
+    t = np.asarray(triples)
+    M = int(n_negatives)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("triples must have shape (m, 3), got %r" % (t.shape,))
+    if t.shape[0] % M:
+        raise ValueError("objective=%r: %d triples are not a multiple of n_negatives = %d"
+                         % (objective, t.shape[0], M))
+    head = np.repeat(t[::M, :2], M, axis=0)
+    bad = np.flatnonzero((t[:, :2] != head).any(axis=1))
+    if bad.size:
+        raise ValueError("objective=%r: triple %d differs from the first of its list in context "
+                         "or c+: the triples must be grouped, n_negatives rows per positive"
+                         % (objective, int(bad[0])))
+
+
+def _list_candidates(triples, n_negatives):
+    """(contexts (Q,), candidates (Q, M + 1)) of grouped triples; column 0 is the positive"""
+    t = np.asarray(triples, dtype=np.int64).reshape(-1, int(n_negatives), 3)
+    return t[:, 0, 0], np.concatenate([t[:, :1, 1], t[:, :, 2]], axis=1)
+
+
+def restate_list_scores(P, w, lams, X, Z, triples, n_negatives, degree, wide=False):
+    """Test aid, NumPy only: the scores ``s_i = s(b, c_i)`` of every list of the grouped
+    ``triples``, ``(Q, M + 1)`` with the positive in column 0 -- every order of ``P``, ``w`` as it
+    stands, the context's linear term left out (``restate_sample``'s score)."""
+    dtype = np.longdouble if wide else np.double
+    P, w, lams = _as(dtype, P, w, lams)
+    P = P[None] if P.ndim == 2 else P
+    Xd, Zd = _dense_sides(X, Z, dtype)
+    b, cand = _list_candidates(triples, n_negatives)
+    cols = [_rows_output(P, lams, Xd[b] + Zd[cand[:, i]], degree)[0] + Zd[cand[:, i]] @ w
+            for i in range(cand.shape[1])]
+    return np.stack(cols, axis=1)
+
+
+def _list_coefs(s, objective, loss):
+    """(loss per list (Q,), coef = dLoss/ds (Q, M + 1)) from the scores"""
+    M = s.shape[1] - 1
+    if objective == "softmax":
+        mx = s.max(axis=1)
+        ex = np.exp(s - mx[:, None])
+        z = ex.sum(axis=1)
+        coef = ex / z[:, None]
+        coef[:, 0] -= 1
+        return (mx - s[:, 0]) + np.log(z), coef
+    if objective != "list":
+        raise ValueError("objective %r is not a list objective" % (objective,))
+    val, der = _loss_pos(loss, s[:, :1] - s[:, 1:])
+    coef = np.empty_like(s)
+    coef[:, 1:] = -der / M
+    coef[:, 0] = -coef[:, 1:].sum(axis=1)
+    return val.sum(axis=1) / M, coef
+
+
+def restate_list_gradient(P, w, lams, X, Z, triples, n_negatives, degree, objective="softmax",
+                          loss="logistic", wide=False):
+    """Test aid, NumPy only: ``(losses (Q,), grad_P (n_orders, k, d), grad_w (d,))`` of the
+    summed loss of the lists at ``(P, w)``.  ``'softmax'``: ``-s_0 + log sum_i exp(s_i)``;
+    ``'list'``: ``(1/M) sum_{i>=1} loss(s_0 - s_i, +1)``.  The gradient is the plain sum over the
+    ``M + 1`` candidates of ``coef_i`` times the gradient of ``s_i`` on the dense row
+    ``x_b + z_{c_i}`` -- the device's combined DP array is NOT used here.  ``grad_w`` is formed
+    from the ``z_{c_i}`` alone: the coefficients of a list sum to zero and the context's columns
+    are exactly zero."""
+    dtype = np.longdouble if wide else np.double
+    P, w, lams = _as(dtype, P, w, lams)
+    P = P[None] if P.ndim == 2 else P
+    Xd, Zd = _dense_sides(X, Z, dtype)
+    b, cand = _list_candidates(triples, n_negatives)
+    rows, dps, cols = [], [], []
+    for i in range(cand.shape[1]):
+        V = Xd[b] + Zd[cand[:, i]]
+        f, dp = _rows_output(P, lams, V, degree)
+        rows.append(V)
+        dps.append(dp)
+        cols.append(f + Zd[cand[:, i]] @ w)
+    val, coef = _list_coefs(np.stack(cols, axis=1), objective, loss)
+    gP = np.zeros_like(P)
+    gw = np.zeros_like(w)
+    for i, V in enumerate(rows):
+        gw += coef[:, i] @ Zd[cand[:, i]]
+        x = V[:, None, :]
+        for o in range(P.shape[0]):
+            dprev = np.broadcast_to(x, (V.shape[0], P.shape[1], V.shape[1]))
+            for tt in range(1, degree - o):
+                dprev = x * (dps[i][o][tt][:, :, None] - P[o][None] * dprev)
+            gP[o] += np.einsum("r,s,rsj->sj", coef[:, i], lams, dprev)
+    return val, gP, gw
+
+
+def restate_list_epoch(P, w, lams, X, Z, triples, n_negatives, degree, objective="softmax",
+                       loss="logistic", regularizer="l1", alpha=1.0, beta=1.0, gamma=1.0,
+                       eta0=1.0, learning_rate="optimal", power_t=1.0, batch_size=1,
+                       fit_linear=True, it=1, wide=False):
+    """Test aid, NumPy only: one epoch of the list fit over the grouped ``triples`` (lists
+    visited in the order given).  ``restate_pairwise_epoch`` with lists as items: minibatch ``bi``
+    covers the lists ``[bi * batch_size, ...)``, the step is ``eta / B`` with ``B`` lists.
+    Returns ``(P, w, sum_loss over the lists, it)`` (new arrays)."""
+    dtype = np.longdouble if wide else np.double
+    P, w, lams = _as(dtype, P, w, lams)
+    P = (P[None] if P.ndim == 2 else P).copy()
+    w = w.copy()
+    M = int(n_negatives)
+    t = np.asarray(triples, dtype=np.int64)
+    sum_loss = dtype(0)
+    for pos in range(0, t.shape[0] // M, int(batch_size)):
+        tb = t[pos * M:(pos + int(batch_size)) * M]
+        B = tb.shape[0] // M
+        val, gP, gw = restate_list_gradient(P, w, lams, X, Z, tb, M, degree, objective, loss,
+                                            wide)
+        sum_loss += val.sum()
+        eta_P, eta_w = _psgd_eta(learning_rate, eta0, alpha, beta, power_t, it)
+        if fit_linear:
+            w = (w - gw * (eta_w / B)) / (1 + eta_w * alpha)
+        P = (P - gP * (eta_P / B)) / (1 + eta_P * beta)
+        strength = gamma * eta_P / (1 + eta_P * beta)
+        P = np.stack([_prox(regularizer, P[o], dtype(strength)) for o in range(P.shape[0])])
+        it += 1
+    return P, w, sum_loss, it
+
+
+def epoch_lists(rng, n_epochs, interactions=None, triples=None, n_negatives=1, resample=True,
+                shuffle=False, exclude=None):
+    """``epoch_triples`` for the list objectives: the grouped triples of every epoch, with
+    ``shuffle`` the LISTS permuted (``rng.permutation(Q)``), never the rows within one."""
+    M = int(n_negatives)
+    cur = None if triples is None else np.asarray(triples, dtype=np.int32)
+    for ep in range(n_epochs):
+        if interactions is not None and (cur is None or resample):
+            cur = sample_triples(interactions, M, rng, exclude)
+        out = cur
+        if shuffle:
+            out = cur.reshape(-1, M, 3)[rng.permutation(cur.shape[0] // M)].reshape(-1, 3)
+        yield out
+
+
 # ------------------------------------------------------------------ the estimator
 class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
     """Factorization machine trained for an order: minibatch psgd on the pairwise loss
@@ -500,7 +655,7 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                                       % MAX_DEGREE)
 
     def fit(self, X, Z, interactions=None, triples=None, n_negatives=1, resample=True,
-            sampler="host", n_candidates=8, exclude=None):
+            sampler="host", n_candidates=8, exclude=None, objective="pairwise"):
         """Fit on contexts ``X`` (B, d) and candidates ``Z`` (C, d) with disjoint column sets.
         Exactly one of ``interactions`` -- a sparse (B, C) matrix whose stored entries are the
         positives; ``n_negatives`` negatives per positive are drawn, again before every epoch
@@ -519,8 +674,22 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
         permutation of the slots (4 m bytes) is uploaded per sampling; with ``resample=False``
         they sample once and every epoch visits that one list.  ``[X; Z]`` is uploaded once.
         Stopping rule, ``verbose`` lines, callbacks, ``it_``, ``n_iter_`` and ``warm_start`` as
-        for ``solver='psgd'``, with the mean loss per triple."""
+        for ``solver='psgd'``, with the mean loss per triple.
+
+        ``objective``: ``'pairwise'`` is the above.  ``'softmax'`` and
+        ``'list'`` make a positive and its ``n_negatives`` (at most 63) negatives one training
+        item: ``'softmax'`` is the sampled softmax ``-s_0 + log sum_i exp(s_i)``, ``'list'`` the
+        mean of the ``n_negatives`` pairwise losses (the pairwise fit's arithmetic with
+        ``batch_size`` counted in positives).  ``batch_size``, the shuffle and the mean loss of
+        the stopping rule count lists; explicit ``triples`` must arrive grouped, ``n_negatives``
+        rows per positive."""
         self._check_config()
+        if objective not in OBJECTIVES:
+            raise ValueError("objective %r is not supported. Choose from %s."
+                             % (objective, list(OBJECTIVES)))
+        listwise = objective != "pairwise"
+        if listwise:
+            check_lists(triples, n_negatives, objective)
         if sampler not in SAMPLERS:
             raise ValueError("sampler %r is not supported. Choose from %s."
                              % (sampler, list(SAMPLERS)))
@@ -590,24 +759,38 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
             engine.set_params(self.P_, self.w_, self.lams_)
             engine.configure("psgd", self.loss, self.regularizer, self.degree)
             if sampler == "host":
-                lists = epoch_triples(rng, self.max_iter, interactions, triples, n_negatives,
-                                      resample, self.shuffle, exclude)
+                lists = (epoch_lists if listwise else epoch_triples)(
+                    rng, self.max_iter, interactions, triples, n_negatives, resample,
+                    self.shuffle, exclude)
             else:
                 engine.psgd_pairs_set_sampler(B, C, interactions, forbidden)
                 lists = self._device_lists(engine, rng, interactions.nnz * int(n_negatives),
                                            int(n_negatives),
                                            1 if sampler == "uniform" else int(n_candidates),
-                                           resample)
-            converged, self.n_iter_ = self._fit_pairs(engine, B, batch_size, lists)
+                                           resample, listwise)
+            converged, self.n_iter_ = self._fit_pairs(engine, B, batch_size, lists,
+                                                      objective, int(n_negatives))
         finally:
             engine.close()
         return self._finish_fit(converged)
 
-    def _device_lists(self, engine, rng, m, n_negatives, n_candidates, resample):
+    def _device_lists(self, engine, rng, m, n_negatives, n_candidates, resample,
+                      listwise=False):
         """per epoch: have the device draw the epoch's negatives (before the first epoch and,
-        with ``resample``, before every later one) and yield the number of resident triples"""
+        with ``resample``, before every later one) and yield the number of resident triples;
+        ``listwise``: the triples stay grouped and ``(m, visiting order of the lists or None)``
+        is yielded"""
         seed = rng.randint(0, 2 ** 31 - 1)
+        list_order = None
         for ep in range(self.max_iter):
+            if listwise:
+                if ep == 0 or resample:
+                    list_order = rng.permutation(m // n_negatives) if self.shuffle else None
+                    engine.psgd_pairs_sample(self.degree, n_negatives, n_candidates,
+                                             64 * n_candidates, seed, ep, None,
+                                             want_triples=False, want_scores=False)
+                yield m, list_order
+                continue
             if ep == 0 or resample:
                 order = rng.permutation(m) if self.shuffle else None
                 engine.psgd_pairs_sample(self.degree, n_negatives, n_candidates,
@@ -615,15 +798,27 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                                          want_triples=False, want_scores=False)
             yield m
 
-    def _fit_pairs(self, engine, B, batch_size, lists):
+    def _fit_pairs(self, engine, B, batch_size, lists, objective="pairwise", n_negatives=1):
         """the loop of ``_fit_psgd`` over the epochs' triple lists: (m, 3) arrays to upload
-        (context / candidate numbering), or the size of the list the device sampler left"""
+        (context / candidate numbering), or the size of the list the device sampler left (a list
+        objective: with the visiting order of its lists); ``m`` counts the training items"""
         converged = False
         no_improvement_count = 0
         best_loss = np.inf
         epoch = 0
+        step = (self.degree, self.alpha, self.beta, self.gamma, self.eta0, self.learning_rate,
+                self.power_t, batch_size)
         for epoch, t in enumerate(lists):
-            if isinstance(t, np.ndarray):
+            if objective != "pairwise" and isinstance(t, np.ndarray):
+                m = t.shape[0] // n_negatives
+                stacked = t + np.array([0, B, B], dtype=np.int32)  # rows of [X; Z]
+                sum_loss, self.it_ = engine.psgd_lists_epoch(
+                    *step, stacked, n_negatives, objective, self.fit_linear, self.it_)
+            elif objective != "pairwise":
+                m = t[0] // n_negatives
+                sum_loss, self.it_ = engine.psgd_lists_epoch_sampled(
+                    *step, n_negatives, objective, self.fit_linear, self.it_, list_order=t[1])
+            elif isinstance(t, np.ndarray):
                 m = t.shape[0]
                 stacked = t + np.array([0, B, B], dtype=np.int32)  # rows of [X; Z]
                 sum_loss, self.it_ = engine.psgd_pairs_epoch(
@@ -722,6 +917,36 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
         finally:
             engine.close()
         return sum_loss / t.shape[0], n_ordered / t.shape[0]
+
+    def list_loss(self, X, Z, triples, n_negatives, objective="softmax"):
+        """``(mean loss per list, share of lists whose positive scores above all of its
+        negatives)`` of the fitted model on the grouped triples -- ``n_negatives`` rows
+        ``(b, c+, c-)`` per positive, context / candidate numbering -- on the device
+        (``spfm_psgd_lists_eval``); ``objective``: ``'softmax'`` or ``'list'`` (the estimator's
+        ``loss``)."""
+        if not hasattr(self, "P_"):
+            raise NotFittedError("Estimator not fitted.")
+        self._check_config()
+        check_lists(triples, n_negatives, objective)
+        Xa, Za = _prepare(self, X, Z)
+        t = check_triples(triples, Xa.shape[0], Za.shape[0])
+        if t.shape[0] == 0:
+            raise ValueError("triples is empty")
+        S = sp.vstack([Xa, Za], format="csr")
+        S.sort_indices()
+        engine = self._new_engine()
+        try:
+            engine.set_data(S, np.zeros(S.shape[0]))
+            engine.set_params(np.ascontiguousarray(self.P_, dtype=np.double), self.w_, self.lams_)
+            engine.configure("psgd", self.loss, self.regularizer, self.degree)
+            sum_loss, n_first = engine.psgd_lists_eval(
+                self.degree, self.fit_linear,
+                t + np.array([0, Xa.shape[0], Xa.shape[0]], dtype=np.int32), int(n_negatives),
+                objective)
+        finally:
+            engine.close()
+        q = t.shape[0] // int(n_negatives)
+        return sum_loss / q, n_first / q
 
     def decision_function(self, rows):
         """The model output of every row of ``rows`` (n, d), e.g. of ``x_b + z_c``."""
