@@ -317,6 +317,51 @@ int spfm_psgd_pairs_epoch_sampled(spfm_handle h, int degree, double alpha, doubl
                                   int64_t batch_size, int fit_linear, int64_t* it,
                                   double* sum_loss);
 
+/* Weighted triples, proposal distributions and the WARP sampler.
+ *
+ * spfm_psgd_pairs_epoch with one weight per triple: weights[q] >= 0 multiplies the loss and the
+ * gradient of triple q (a triple of weight 0 is skipped); sum_loss is the sum of wt * loss; eta / B
+ * still counts triples, not weight.  SPFM_ERR_INVALID, on the host before any launch (the
+ * parameters stay as they were): a weight that is negative or not finite, and everything
+ * spfm_psgd_pairs_epoch rejects.  A handle with a communicator: SPFM_ERR_UNSUPPORTED. */
+int spfm_psgd_pairs_epoch_weighted(spfm_handle h, int degree, double alpha, double beta,
+                                   double gamma, double eta0, int learning_rate, double power_t,
+                                   int64_t batch_size, const int32_t* triples,
+                                   const double* weights /* (m) */, int64_t m, int fit_linear,
+                                   int64_t* it, double* sum_loss);
+/* The proposal distribution of BOTH sample entries.  cum (n_cand): the inclusive cumulative sums of
+ * non-negative integer weights -- non-decreasing, W = cum[n_cand - 1] in [1, 2^32).  With a table
+ * the candidate of draw u is the smallest c with cum[c] > ((u >> 32) * W) >> 32 (integer only: a
+ * binary search over cum); admission and the fallback walk are unchanged, so the walk may end on a
+ * candidate of weight 0.  NULL restores the uniform draw.  Uploaded once, dropped with the sampler
+ * (spfm_psgd_pairs_set_sampler, new data).  SPFM_ERR_INVALID: no sampler set, n_cand differs from
+ * the sampler's, cum decreases, W == 0. */
+int spfm_psgd_pairs_set_proposal(spfm_handle h, const uint32_t* cum, int64_t n_cand);
+/* One weight per positive, in the canonical CSR order of the sampler's positives; NULL clears;
+ * dropped with the sampler.  Once set, both sample entries write a weight per triple beside the
+ * list (spfm_psgd_pairs_sample: the positive's weight; _sample_warp: times its rank weight) and
+ * spfm_psgd_pairs_epoch_sampled reads it.  SPFM_ERR_INVALID: no sampler set, nnz differs from the
+ * sampler's positives, a weight negative or not finite. */
+int spfm_psgd_pairs_set_positive_weights(spfm_handle h, const double* wq, int64_t nnz);
+/* WARP: the layout, draws, admission, score, `order` and resident-list bookkeeping of
+ * spfm_psgd_pairs_sample.  For triple r of positive q = (b, c+): s+ = score(b, c+); the admitted
+ * draws with t < max_draws are tried in the order of t, at most max_trials of them; the first
+ * a_N with score(b, a_N) > s+ - margin (the violator) is the negative, trials = N and
+ *   weight = posw_q * log(max(1, floor(A_b / N))),   A_b = n_cand - |forbidden(b)|
+ * (posw_q = 1 without positive weights; under a proposal table A_b / N estimates the rank under
+ * that proposal).  No violator among those tried: the highest-scored of them (ties to the earliest),
+ * trials = 0, weight = 0.  No draw admitted: the fallback walk's candidate, trials = 0, weight = 0.
+ * scores holds the negative's score.  weights_out (m) / trials_out (m): optional host copies, by
+ * slot, like triples_out / scores_out.  The weights stay on the device for
+ * spfm_psgd_pairs_epoch_sampled; spfm_psgd_lists_epoch_sampled after a sample call that wrote
+ * weights is SPFM_ERR_INVALID.  SPFM_ERR_INVALID: max_trials < 1 or > max_draws, a margin that is
+ * not finite, and everything spfm_psgd_pairs_sample rejects. */
+int spfm_psgd_pairs_sample_warp(spfm_handle h, int degree, int64_t n_negatives,
+                                int64_t max_trials, int64_t max_draws, double margin,
+                                int64_t seed, int64_t epoch, const int32_t* order,
+                                int32_t* triples_out, double* scores_out, double* weights_out,
+                                int32_t* trials_out);
+
 /* Listwise ranking fit: the training item is a LIST, a positive
  * (anchor, plus) with its n_negatives = M negatives.  `triples` (m, 3) is GROUPED: rows
  * q M .. q M + M - 1 share anchor and plus and hold the M negatives of list q -- the layout

@@ -92,6 +92,8 @@ SYMBOLS = [
     "spfm_pcd_epoch", "spfm_pbcd_epoch", "spfm_psgd_epoch", "spfm_psgd_epoch_sharded",
     "spfm_psgd_pairs_epoch", "spfm_psgd_pairs_eval",
     "spfm_psgd_pairs_set_sampler", "spfm_psgd_pairs_sample", "spfm_psgd_pairs_epoch_sampled",
+    "spfm_psgd_pairs_epoch_weighted", "spfm_psgd_pairs_set_proposal",
+    "spfm_psgd_pairs_set_positive_weights", "spfm_psgd_pairs_sample_warp",
     "spfm_psgd_lists_epoch", "spfm_psgd_lists_epoch_sampled", "spfm_psgd_lists_eval",
     "spfm_host_epoch_begin",
     "spfm_host_pass_begin", "spfm_host_step_sums", "spfm_host_step_apply", "spfm_host_epoch_end", "spfm_comm_unique_id", "spfm_comm_init", "spfm_comm_init_shm", "spfm_peer_alloc", "spfm_peer_connect",
@@ -137,6 +139,7 @@ LIST_MAX_NEG = 63  # SPFM_LIST_MAX_NEG
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _lp = C.POINTER(C.c_int64)
+_up = C.POINTER(C.c_uint32)
 _h = C.c_void_p
 
 _lib = None
@@ -197,6 +200,14 @@ def load():
     L.spfm_psgd_pairs_epoch_sampled.argtypes = [_h, C.c_int, C.c_double, C.c_double, C.c_double,
                                                 C.c_double, C.c_int, C.c_double, C.c_int64,
                                                 C.c_int, _lp, _dp]
+    L.spfm_psgd_pairs_epoch_weighted.argtypes = [_h, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                 C.c_double, C.c_int, C.c_double, C.c_int64, _ip,
+                                                 _dp, C.c_int64, C.c_int, _lp, _dp]
+    L.spfm_psgd_pairs_set_proposal.argtypes = [_h, _up, C.c_int64]
+    L.spfm_psgd_pairs_set_positive_weights.argtypes = [_h, _dp, C.c_int64]
+    L.spfm_psgd_pairs_sample_warp.argtypes = [_h, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                              C.c_double, C.c_int64, C.c_int64, _ip, _ip, _dp, _dp,
+                                              _ip]
     L.spfm_psgd_lists_epoch.argtypes = [_h, C.c_int, C.c_double, C.c_double, C.c_double,
                                         C.c_double, C.c_int, C.c_double, C.c_int64, _ip,
                                         C.c_int64, C.c_int64, C.c_int, C.c_int, _lp, _dp]

@@ -1043,13 +1043,20 @@ struct spfm_engine {
     DevBuf sg_triples, sg_lossrow, sg_ordered;
     int psgd_pairs_check(const char* what, int degree, const int32_t* triples, int64_t m);
     int pairs_reserve(int64_t m);  // sg_triples / sg_lossrow; a moved buffer clears the graphs
-    template <typename T, int L>
+    template <typename T, int L, bool WT>
     int psgd_pairs_epoch_tl(const PsgdStep& st, int64_t m);
     int psgd_pairs_epoch(const PsgdStep& st, const int32_t* triples, int64_t m, double* sum_loss);
+    // weighted triples: one double per slot of sg_triples, read by the
+    // WT instances of the gradient kernel; a moved sg_weights clears the graphs
+    DevBuf sg_weights;
+    int weights_reserve(int64_t m);
+    int psgd_pairs_epoch_weighted(const PsgdStep& st, const int32_t* triples,
+                                  const double* weights, int64_t m, double* sum_loss);
     int psgd_pairs_eval(int degree, int fit_linear, const int32_t* triples, int64_t m,
                         double* sum_loss, int64_t* n_ordered);
     // what follows the checks and the filling of sg_triples: the batches and the loss sum
-    int psgd_pairs_run(const PsgdStep& st, int64_t m, double* sum_loss);
+    // (weighted: the kernel reads sg_weights)
+    int psgd_pairs_run(const PsgdStep& st, int64_t m, double* sum_loss, bool weighted = false);
 
     // negatives drawn on the device: the positives (context and
     // candidate of each, canonical CSR order) and the forbidden CSR, uploaded once per data set;
@@ -1064,6 +1071,18 @@ struct spfm_engine {
                           int64_t max_draws, int64_t seed, int64_t epoch, const int32_t* order,
                           int32_t* triples_out, double* scores_out);
     int psgd_pairs_epoch_sampled(const PsgdStep& st, double* sum_loss);
+    // the proposal table and the positives' weights live and die with the
+    // sampler; `sampled_weighted`: the last sample call wrote sg_weights (positive weights, WARP)
+    DevBuf sm_cum, sm_posw, sg_trials;
+    uint32_t sm_cumW = 0;
+    bool have_proposal = false, have_posw = false, sampled_weighted = false;
+    int psgd_pairs_set_proposal(const uint32_t* cum, int64_t n_cand);
+    int psgd_pairs_set_positive_weights(const double* wq, int64_t nnz);
+    // both sample entries; warp: n_candidates is the number of trials
+    int psgd_pairs_sample_any(bool warp, int degree, int64_t n_negatives, int64_t n_candidates,
+                              int64_t max_draws, double margin, int64_t seed, int64_t epoch,
+                              const int32_t* order, int32_t* triples_out, double* scores_out,
+                              double* weights_out, int32_t* trials_out);
 
     // listwise fit: a positive and its n_negatives negatives are one
     // item, read from the grouped triples in sg_triples; what the last sample call used is

@@ -358,6 +358,7 @@ int spfm_engine::psgd_pairs_check(const char* what, int degree, const int32_t* t
 // whatever list was drawn on the device is about to be overwritten
 int spfm_engine::pairs_reserve(int64_t m) {
     sampled = false;
+    sampled_weighted = false;
     const void *o1 = sg_triples.p, *o2 = sg_lossrow.p;
     HIPC(sg_triples.alloc(sizeof(int32_t) * 3 * (size_t)m));
     HIPC(sg_lossrow.alloc(sizeof(double) * (size_t)m));
@@ -365,19 +366,29 @@ int spfm_engine::pairs_reserve(int64_t m) {
     return SPFM_OK;
 }
 
-template <typename T, int L>
+// room for m weights beside the triples
+int spfm_engine::weights_reserve(int64_t m) {
+    const void* old = sg_weights.p;
+    HIPC(sg_weights.alloc(sizeof(double) * (size_t)m));
+    if (sg_weights.p != old) clear_graphs();
+    return SPFM_OK;
+}
+
+// WT: the weighted instance, reading sg_weights (the graph tag says which was recorded)
+template <typename T, int L, bool WT>
 int spfm_engine::psgd_pairs_epoch_tl(const PsgdStep& st, int64_t m) {
     auto grad = [&](int64_t pos, int B, int grid, bool table) {
-        hipLaunchKernelGGL((psgd_pair_grad_kernel<T, L, false>), dim3(grid), dim3(kBlock), 0,
+        hipLaunchKernelGGL((psgd_pair_grad_kernel<T, L, false, WT>), dim3(grid), dim3(kBlock), 0,
                            stream, sg_triples.as<int32_t>() + 3 * pos, B, rptr.as<int64_t>(),
                            ridx.as<int32_t>(), rval.as<T>(), Pt.as<double>(), w.as<double>(),
                            lams.as<double>(), n_orders, k, d, st.degree, loss, st.fit_linear,
                            sg_gradP.as<double>(), sg_gradw.as<double>(),
                            sg_lossrow.as<double>() + pos, (int*)nullptr,
                            table ? sg_sched.as<PsgdBatch>() : (const PsgdBatch*)nullptr,
-                           table ? sg_idx.as<int>() : (int*)nullptr);
+                           table ? sg_idx.as<int>() : (int*)nullptr,
+                           WT ? sg_weights.as<double>() + pos : (const double*)nullptr);
     };
-    return psgd_batches_tl<L>(grad, "psgd_pairs", (int64_t)sizeof(T), m, st);
+    return psgd_batches_tl<L>(grad, WT ? "psgd_pairs_w" : "psgd_pairs", (int64_t)sizeof(T), m, st);
 }
 
 int spfm_engine::psgd_pairs_epoch(const PsgdStep& st, const int32_t* triples, int64_t m,
@@ -396,11 +407,39 @@ int spfm_engine::psgd_pairs_epoch(const PsgdStep& st, const int32_t* triples, in
     return psgd_pairs_run(st, m, sum_loss);
 }
 
+// uploaded triples with a weight each: sum_loss is the sum of wt * loss
+int spfm_engine::psgd_pairs_epoch_weighted(const PsgdStep& st, const int32_t* triples,
+                                           const double* weights, int64_t m, double* sum_loss) {
+    if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs: several ranks are not supported");
+    SPFM_TRY(psgd_pairs_check("psgd pairs", st.degree, triples, m));
+    if (const std::string e = st.check("psgd pairs"); !e.empty()) FAIL(SPFM_ERR_INVALID, e);
+    if (m > 0 && !weights) FAIL(SPFM_ERR_INVALID, "psgd pairs: weights must hold m values");
+    for (int64_t q = 0; q < m; ++q)
+        if (!(weights[q] >= 0.0) || !std::isfinite(weights[q]))
+            FAIL(SPFM_ERR_INVALID, "psgd pairs: weight " + std::to_string(q) +
+                                       " is negative or not finite");
+    if (m == 0) {
+        if (sum_loss) *sum_loss = 0.0;
+        return SPFM_OK;
+    }
+    SPFM_TRY(ensure_pt());
+    SPFM_TRY(pairs_reserve(m));
+    SPFM_TRY(weights_reserve(m));
+    SPFM_TRY(upload_to(sg_triples.p, triples, 3 * (size_t)m));
+    SPFM_TRY(upload_to(sg_weights.p, weights, (size_t)m));
+    HIPC(hipStreamSynchronize(stream));  // caller may reuse triples and weights
+    return psgd_pairs_run(st, m, sum_loss, true);
+}
+
 // the batches over the resident triple list sg_triples[0, m) and the sum of the triples' losses
-int spfm_engine::psgd_pairs_run(const PsgdStep& st, int64_t m, double* sum_loss) {
+int spfm_engine::psgd_pairs_run(const PsgdStep& st, int64_t m, double* sum_loss, bool weighted) {
     p_valid = false;
-    SPFM_TRY(SPFM_DISPATCH(dtype,
-                           return SPFM_DISPATCH_L(k, return psgd_pairs_epoch_tl<T, L>(st, m))));
+    if (weighted)
+        SPFM_TRY(SPFM_DISPATCH(dtype, return SPFM_DISPATCH_L(
+                                          k, return psgd_pairs_epoch_tl<T, L, true>(st, m))));
+    else
+        SPFM_TRY(SPFM_DISPATCH(dtype, return SPFM_DISPATCH_L(
+                                          k, return psgd_pairs_epoch_tl<T, L, false>(st, m))));
     return psgd_epoch_end(sg_lossrow.as<double>(), m, sum_loss);
 }
 
@@ -422,7 +461,7 @@ int spfm_engine::psgd_pairs_eval(int degree, int fit_linear, const int32_t* trip
         sg_triples.as<int32_t>(), (int)m, rptr.as<int64_t>(), ridx.as<int32_t>(), rval.as<T>(),
         Pt.as<double>(), w.as<double>(), lams.as<double>(), n_orders, k, d, degree, loss, 0,
         (double*)nullptr, (double*)nullptr, sg_lossrow.as<double>(), sg_ordered.as<int>(),
-        (const PsgdBatch*)nullptr, (int*)nullptr)));
+        (const PsgdBatch*)nullptr, (int*)nullptr, (const double*)nullptr)));
     loss_sum(sg_lossrow.as<double>(), m, 0);
     loss_sum(sg_ordered.as<int>(), m, 1);
     HIPC(hipGetLastError());
@@ -441,6 +480,7 @@ int spfm_engine::psgd_pairs_set_sampler(int64_t n_ctx, int64_t n_cand, const int
                                         const int32_t* forb_idx) {
     have_sampler = false;
     sampled = false;
+    have_proposal = have_posw = sampled_weighted = false;  // they go with the sampler
     if (!have_data) FAIL(SPFM_ERR_INVALID, "set_sampler: data is required");
     if (n_ctx < 1 || n_cand < 1 || n_ctx + n_cand != n)
         FAIL(SPFM_ERR_INVALID, "set_sampler: n_ctx + n_cand must be the handle's row count");
@@ -487,10 +527,56 @@ int spfm_engine::psgd_pairs_set_sampler(int64_t n_ctx, int64_t n_cand, const int
     return SPFM_OK;
 }
 
-int spfm_engine::psgd_pairs_sample(int degree, int64_t n_negatives, int64_t n_candidates,
-                                   int64_t max_draws, int64_t seed, int64_t epoch,
-                                   const int32_t* order, int32_t* triples_out,
-                                   double* scores_out) {
+// The proposal distribution of every device sampler: inclusive cumulative sums of non-negative
+// integer weights (non-decreasing, 1 <= cum[n_cand - 1] < 2^32); NULL: uniform again.
+int spfm_engine::psgd_pairs_set_proposal(const uint32_t* cum, int64_t n_cand) {
+    if (!have_sampler)
+        FAIL(SPFM_ERR_INVALID, "set_proposal: call spfm_psgd_pairs_set_sampler first");
+    if (!cum) {
+        have_proposal = false;
+        return SPFM_OK;
+    }
+    if (n_cand != sm_ncand)
+        FAIL(SPFM_ERR_INVALID, "set_proposal: n_cand differs from the sampler's");
+    for (int64_t c = 1; c < n_cand; ++c)
+        if (cum[c] < cum[c - 1])
+            FAIL(SPFM_ERR_INVALID, "set_proposal: cum decreases at candidate " + std::to_string(c));
+    if (cum[n_cand - 1] < 1) FAIL(SPFM_ERR_INVALID, "set_proposal: every weight is zero");
+    have_proposal = false;
+    SPFM_TRY(upload(sm_cum, cum, (size_t)n_cand));
+    HIPC(hipStreamSynchronize(stream));  // the caller may reuse cum
+    sm_cumW = cum[n_cand - 1];
+    have_proposal = true;
+    return SPFM_OK;
+}
+
+// One weight per positive, canonical CSR order; NULL clears.  Once set, both sample entries write
+// sg_weights.
+int spfm_engine::psgd_pairs_set_positive_weights(const double* wq, int64_t nnz) {
+    if (!have_sampler)
+        FAIL(SPFM_ERR_INVALID, "set_positive_weights: call spfm_psgd_pairs_set_sampler first");
+    if (!wq) {
+        have_posw = false;
+        return SPFM_OK;
+    }
+    if (nnz != sm_npos)
+        FAIL(SPFM_ERR_INVALID, "set_positive_weights: nnz differs from the sampler's positives");
+    for (int64_t q = 0; q < nnz; ++q)
+        if (!(wq[q] >= 0.0) || !std::isfinite(wq[q]))
+            FAIL(SPFM_ERR_INVALID, "set_positive_weights: weight " + std::to_string(q) +
+                                       " is negative or not finite");
+    have_posw = false;
+    SPFM_TRY(upload(sm_posw, wq, (size_t)nnz));
+    HIPC(hipStreamSynchronize(stream));  // the caller may reuse wq
+    have_posw = true;
+    return SPFM_OK;
+}
+
+int spfm_engine::psgd_pairs_sample_any(bool warp, int degree, int64_t n_negatives,
+                                       int64_t n_candidates, int64_t max_draws, double margin,
+                                       int64_t seed, int64_t epoch, const int32_t* order,
+                                       int32_t* triples_out, double* scores_out,
+                                       double* weights_out, int32_t* trials_out) {
     if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs sample: several ranks are not supported");
     SPFM_TRY(psgd_ready("psgd pairs sample", degree));
     if (!have_sampler)
@@ -503,30 +589,58 @@ int spfm_engine::psgd_pairs_sample(int degree, int64_t n_negatives, int64_t n_ca
         FAIL(SPFM_ERR_INVALID, "psgd pairs sample: the triple list is limited to 2^31 - 1 rows");
     if (seed < 0 || epoch < 0)
         FAIL(SPFM_ERR_INVALID, "psgd pairs sample: seed and epoch must be >= 0");
+    if (warp && n_candidates > max_draws)
+        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: 1 <= max_trials <= max_draws is required");
+    if (warp && !std::isfinite(margin))
+        FAIL(SPFM_ERR_INVALID, "psgd pairs sample: margin must be finite");
     const int64_t m = sm_npos * n_negatives;
     if (order && !is_permutation(order, m))
         FAIL(SPFM_ERR_INVALID, "psgd pairs sample: order is not a permutation of 0..m-1");
+    const bool wr = warp || have_posw;  // this call writes sg_weights
     SPFM_TRY(ensure_pt());
     SPFM_TRY(pairs_reserve(m));
     HIPC(sg_scores.alloc(sizeof(double) * (size_t)m));
+    if (wr) SPFM_TRY(weights_reserve(m));
+    if (warp) HIPC(sg_trials.alloc(sizeof(int32_t) * (size_t)m));
     if (order) SPFM_TRY(upload(sg_order, order, (size_t)m));
-    SPFM_DISPATCH(dtype, SPFM_DISPATCH_L(k, hipLaunchKernelGGL(
-        (psgd_pair_sample_kernel<T, L>), dim3(cdiv(m, kBlock / L)), dim3(kBlock), 0, stream,
-        (int)m, (int)n_negatives, (int)n_candidates, (int)max_draws, (uint64_t)seed,
-        (uint64_t)epoch, (int)sm_nctx, (int)sm_ncand, sm_posrow.as<int32_t>(),
-        sm_posidx.as<int32_t>(), sm_fptr.as<int64_t>(), sm_fidx.as<int32_t>(),
-        order ? sg_order.as<int32_t>() : (const int32_t*)nullptr, rptr.as<int64_t>(),
-        ridx.as<int32_t>(), rval.as<T>(), Pt.as<double>(), w.as<double>(), lams.as<double>(),
-        n_orders, k, d, degree, sg_triples.as<int32_t>(), sg_scores.as<double>())));
+#define SPFM_SAMPLE_LAUNCH(WARP)                                                                 \
+    SPFM_DISPATCH(dtype, SPFM_DISPATCH_L(k, hipLaunchKernelGGL(                                  \
+        (psgd_pair_sample_kernel<T, L, WARP>), dim3(cdiv(m, kBlock / L)), dim3(kBlock), 0,       \
+        stream, (int)m, (int)n_negatives, (int)n_candidates, (int)max_draws, (uint64_t)seed,     \
+        (uint64_t)epoch, (int)sm_nctx, (int)sm_ncand, sm_posrow.as<int32_t>(),                   \
+        sm_posidx.as<int32_t>(), sm_fptr.as<int64_t>(), sm_fidx.as<int32_t>(),                   \
+        order ? sg_order.as<int32_t>() : (const int32_t*)nullptr, rptr.as<int64_t>(),            \
+        ridx.as<int32_t>(), rval.as<T>(), Pt.as<double>(), w.as<double>(), lams.as<double>(),    \
+        n_orders, k, d, degree, sg_triples.as<int32_t>(), sg_scores.as<double>(),                \
+        have_proposal ? sm_cum.as<uint32_t>() : (const uint32_t*)nullptr, sm_cumW,               \
+        have_posw ? sm_posw.as<double>() : (const double*)nullptr, margin,                       \
+        wr ? sg_weights.as<double>() : (double*)nullptr,                                         \
+        WARP ? sg_trials.as<int32_t>() : (int32_t*)nullptr)))
+    if (warp)
+        SPFM_SAMPLE_LAUNCH(true);
+    else
+        SPFM_SAMPLE_LAUNCH(false);
+#undef SPFM_SAMPLE_LAUNCH
     HIPC(hipGetLastError());
     if (triples_out) SPFM_TRY(download(triples_out, sg_triples.p, 3 * (size_t)m));
     if (scores_out) SPFM_TRY(download(scores_out, sg_scores.p, (size_t)m));
+    if (weights_out && wr) SPFM_TRY(download(weights_out, sg_weights.p, (size_t)m));
+    if (trials_out && warp) SPFM_TRY(download(trials_out, sg_trials.p, (size_t)m));
     HIPC(hipStreamSynchronize(stream));  // order may be reused; the copies have landed
     sampled = true;
+    sampled_weighted = wr;
     sampled_m = m;
     sampled_nneg = n_negatives;
     sampled_slots = order != nullptr;
     return SPFM_OK;
+}
+
+int spfm_engine::psgd_pairs_sample(int degree, int64_t n_negatives, int64_t n_candidates,
+                                   int64_t max_draws, int64_t seed, int64_t epoch,
+                                   const int32_t* order, int32_t* triples_out,
+                                   double* scores_out) {
+    return psgd_pairs_sample_any(false, degree, n_negatives, n_candidates, max_draws, 0.0, seed,
+                                 epoch, order, triples_out, scores_out, nullptr, nullptr);
 }
 
 // the epoch of psgd_pairs_epoch over the list the sample call left on the device: nothing is
@@ -539,7 +653,7 @@ int spfm_engine::psgd_pairs_epoch_sampled(const PsgdStep& st, double* sum_loss) 
                                "spfm_psgd_pairs_sample");
     if (const std::string e = st.check("psgd pairs"); !e.empty()) FAIL(SPFM_ERR_INVALID, e);
     SPFM_TRY(ensure_pt());
-    return psgd_pairs_run(st, sampled_m, sum_loss);
+    return psgd_pairs_run(st, sampled_m, sum_loss, sampled_weighted);
 }
 
 // ============================================================ listwise ranking fit
@@ -636,6 +750,9 @@ int spfm_engine::psgd_lists_epoch_sampled(const PsgdStep& st, int64_t n_negative
                                "spfm_psgd_pairs_sample");
     if (const std::string e = lists_args_error("psgd lists", n_negatives, list_loss); !e.empty())
         FAIL(SPFM_ERR_INVALID, e);
+    if (sampled_weighted)
+        FAIL(SPFM_ERR_INVALID, "psgd lists: the sample call wrote weights (positive weights or "
+                               "WARP); the list objectives take none");
     if (sampled_slots)
         FAIL(SPFM_ERR_INVALID, "psgd lists: the sample call scattered its triples by `order`; "
                                "lists need order == NULL");
@@ -730,6 +847,38 @@ int spfm_psgd_pairs_sample(spfm_handle h, int degree, int64_t n_negatives, int64
     SPFM_GUARD(h);
     return h->psgd_pairs_sample(degree, n_negatives, n_candidates, max_draws, seed, epoch, order,
                                 triples_out, scores_out);
+}
+
+int spfm_psgd_pairs_set_proposal(spfm_handle h, const uint32_t* cum, int64_t n_cand) {
+    SPFM_GUARD(h);
+    return h->psgd_pairs_set_proposal(cum, n_cand);
+}
+
+int spfm_psgd_pairs_set_positive_weights(spfm_handle h, const double* wq, int64_t nnz) {
+    SPFM_GUARD(h);
+    return h->psgd_pairs_set_positive_weights(wq, nnz);
+}
+
+int spfm_psgd_pairs_sample_warp(spfm_handle h, int degree, int64_t n_negatives,
+                                int64_t max_trials, int64_t max_draws, double margin,
+                                int64_t seed, int64_t epoch, const int32_t* order,
+                                int32_t* triples_out, double* scores_out, double* weights_out,
+                                int32_t* trials_out) {
+    SPFM_GUARD(h);
+    return h->psgd_pairs_sample_any(true, degree, n_negatives, max_trials, max_draws, margin, seed,
+                                    epoch, order, triples_out, scores_out, weights_out,
+                                    trials_out);
+}
+
+int spfm_psgd_pairs_epoch_weighted(spfm_handle h, int degree, double alpha, double beta,
+                                   double gamma, double eta0, int learning_rate, double power_t,
+                                   int64_t batch_size, const int32_t* triples,
+                                   const double* weights, int64_t m, int fit_linear, int64_t* it,
+                                   double* sum_loss) {
+    SPFM_GUARD(h);
+    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
+                      fit_linear, it};
+    return h->psgd_pairs_epoch_weighted(st, triples, weights, m, sum_loss);
 }
 
 int spfm_psgd_pairs_epoch_sampled(spfm_handle h, int degree, double alpha, double beta,

@@ -16,6 +16,12 @@
 // x = 0: its DP update is a no-op and its D is 0, so no case distinction is left in the loops.
 // What follows the gradient (psgd_update_kernel, the psgd_mich_* passes) is the pointwise
 // solver's, unchanged.
+//
+// Weighted triples: the instances with WT read one double per triple,
+// wt = weights[r] >= 0, write loss_row = wt * loss and scatter with dL = wt * dloss; a triple of
+// weight 0 writes loss_row = 0 and leaves before any other load.  WT is a template parameter, not
+// a null check at run time: the training instances fill the register file, and the instances
+// without WT are the code of a build without weights.
 #pragma once
 #include "spfm_psgd.hip.h"
 
@@ -140,22 +146,28 @@ __device__ __forceinline__ double pair_top_diff(const double* ap, const double* 
 
 // The margin's way out, shared by both forms of the kernel: reduce it over the group, write the
 // triple's loss (EVAL: and the 0/1 flag m > 0), scatter the candidates' part of grad_w (no
-// atomic ever touches a context column).  Returns dL.
-template <typename T, int L, bool EVAL>
+// atomic ever touches a context column).  Returns dL.  WT: loss and dL times weights[r], read
+// here and not carried through the DP.
+template <typename T, int L, bool EVAL, bool WT>
 __device__ __forceinline__ double pair_margin_out(double m, int64_t l1, int64_t h1, int64_t l2,
                                                   int64_t h2, int ln, int r, int loss,
                                                   int fit_linear, const int32_t* __restrict__ ridx,
                                                   const T* __restrict__ rval,
                                                   double* __restrict__ grad_w,
                                                   double* __restrict__ loss_row,
-                                                  int* __restrict__ ordered) {
+                                                  int* __restrict__ ordered,
+                                                  const double* __restrict__ weights) {
     m = group_sum(m, L);
-    if (ln == 0) loss_row[r] = loss_dev(loss, m, 1.0);
+    if (WT) {
+        if (ln == 0) loss_row[r] = weights[r] * loss_dev(loss, m, 1.0);
+    } else {
+        if (ln == 0) loss_row[r] = loss_dev(loss, m, 1.0);
+    }
     if (EVAL) {
         if (ln == 0) ordered[r] = m > 0.0 ? 1 : 0;
         return 0.0;
     }
-    const double dL = dloss_dev(loss, m, 1.0);
+    const double dL = WT ? weights[r] * dloss_dev(loss, m, 1.0) : dloss_dev(loss, m, 1.0);
     if (fit_linear) {
         for (int64_t e = l1 + ln; e < h1; e += L)
             unsafeAtomicAdd(&grad_w[ridx[e]], dL * (double)rval[e]);
@@ -167,7 +179,7 @@ __device__ __forceinline__ double pair_margin_out(double m, int64_t l1, int64_t 
 
 // The register-resident form of one triple at degree DEG: the packed chunk -- entries and P
 // values -- stays in registers between the margin and the gradient.
-template <typename T, int L, bool EVAL, int DEG>
+template <typename T, int L, bool EVAL, int DEG, bool WT>
 __device__ __forceinline__ void pair_keep(int64_t l0, int nb, int64_t l1, int np, int64_t l2,
                                           int nm, double m, int ln, int r, int k, int loss,
                                           int fit_linear, const int32_t* __restrict__ ridx,
@@ -176,7 +188,8 @@ __device__ __forceinline__ void pair_keep(int64_t l0, int nb, int64_t l1, int np
                                           const double* __restrict__ lams,
                                           double* __restrict__ grad_P, double* __restrict__ grad_w,
                                           double* __restrict__ loss_row,
-                                          int* __restrict__ ordered) {
+                                          int* __restrict__ ordered,
+                                          const double* __restrict__ weights) {
     const bool act = ln < k;
     PsgdChunk<T, L> ch;
     PairX<L> px;
@@ -187,23 +200,26 @@ __device__ __forceinline__ void pair_keep(int64_t l0, int nb, int64_t l1, int np
     psgd_a_init(am);
     pair_dp_packed<T, L, DEG>(ch, px, ap, am);
     if (act) m += lams[ln] * (ap[DEG] - am[DEG]);
-    const double dL = pair_margin_out<T, L, EVAL>(m, l1, l1 + np, l2, l2 + nm, ln, r, loss,
-                                                  fit_linear, ridx, rval, grad_w, loss_row,
-                                                  ordered);
+    const double dL = pair_margin_out<T, L, EVAL, WT>(m, l1, l1 + np, l2, l2 + nm, ln, r, loss,
+                                                      fit_linear, ridx, rval, grad_w, loss_row,
+                                                      ordered, weights);
     if (EVAL) return;
     pair_grad<T, L, DEG>(ch, px, ap, am, DEG, act ? dL * lams[ln] : 0.0, grad_P + (act ? ln : 0),
                          k, act);
 }
 
 // One L-lane group per triple.  EVAL: no gradient; loss_row[r] and ordered[r] = (m > 0).
-template <typename T, int L, bool EVAL>
+// WT: `weights` holds one double per slot of `triples` (else it is not read).
+template <typename T, int L, bool EVAL, bool WT = false>
 __global__ __launch_bounds__(kBlock) void psgd_pair_grad_kernel(
     const int32_t* __restrict__ triples, int B, const int64_t* __restrict__ rptr,
     const int32_t* __restrict__ ridx, const T* __restrict__ rval, const double* __restrict__ Pt,
     const double* __restrict__ w, const double* __restrict__ lams, int n_orders, int k, int d,
     int degree, int loss, int fit_linear, double* __restrict__ grad_P,
     double* __restrict__ grad_w, double* __restrict__ loss_row, int* __restrict__ ordered,
-    const PsgdBatch* __restrict__ sched, int* __restrict__ idx) {
+    const PsgdBatch* __restrict__ sched, int* __restrict__ idx,
+    const double* __restrict__ weights) {
+    static_assert(!(EVAL && WT), "the evaluation is unweighted");
     constexpr int gpb = kBlock / L;
     const int grp = threadIdx.x / L, ln = threadIdx.x % L;
     const int r = blockIdx.x * gpb + grp;
@@ -212,8 +228,15 @@ __global__ __launch_bounds__(kBlock) void psgd_pair_grad_kernel(
         psgd_table_batch(sched, idx, B, pos);
         triples += 3 * pos;
         loss_row += pos;
+        if (WT) weights += pos;
     }
     if (r >= B) return;  // whole groups leave; no block-level synchronisation below
+    if (WT) {
+        if (weights[r] == 0.0) {  // the same r in all lanes of the group: it leaves as a whole
+            if (ln == 0) loss_row[r] = 0.0;
+            return;
+        }
+    }
     const int ib = triples[3 * (size_t)r], ip = triples[3 * (size_t)r + 1],
               im = triples[3 * (size_t)r + 2];
     const int64_t l0 = rptr[ib], h0 = rptr[ib + 1];  // the context's entries
@@ -230,9 +253,10 @@ __global__ __launch_bounds__(kBlock) void psgd_pair_grad_kernel(
     if (n_orders == 1 && C == 1 && (h0 - l0) + (h1 - l1) + (h2 - l2) <= kPsgdRC) {
 #define SPFM_PAIR_KEEP(DEG)                                                                    \
     case DEG:                                                                                  \
-        pair_keep<T, L, EVAL, DEG>(l0, (int)(h0 - l0), l1, (int)(h1 - l1), l2, (int)(h2 - l2), \
-                                   m, ln, r, k, loss, fit_linear, ridx, rval, Pt, lams,        \
-                                   grad_P, grad_w, loss_row, ordered);                         \
+        pair_keep<T, L, EVAL, DEG, WT>(l0, (int)(h0 - l0), l1, (int)(h1 - l1), l2,             \
+                                       (int)(h2 - l2), m, ln, r, k, loss, fit_linear, ridx,    \
+                                       rval, Pt, lams, grad_P, grad_w, loss_row, ordered,      \
+                                       weights);                                               \
         break
         switch (degree) {
             SPFM_PAIR_KEEP(2);
@@ -256,8 +280,9 @@ __global__ __launch_bounds__(kBlock) void psgd_pair_grad_kernel(
             if (act) m += lams[s] * pair_top_diff(ap, am, deg);
         }
     }
-    const double dL = pair_margin_out<T, L, EVAL>(m, l1, h1, l2, h2, ln, r, loss, fit_linear, ridx,
-                                                  rval, grad_w, loss_row, ordered);
+    const double dL = pair_margin_out<T, L, EVAL, WT>(m, l1, h1, l2, h2, ln, r, loss, fit_linear,
+                                                      ridx, rval, grad_w, loss_row, ordered,
+                                                      weights);
     if (EVAL) return;
     PairX<L> px;
     for (int o = 0; o < n_orders; ++o) {

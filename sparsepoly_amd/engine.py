@@ -1214,6 +1214,26 @@ class HipEngine(object):
             int(bool(fit_linear)), C.byref(itc), C.byref(sl)))
         return sl.value, itc.value
 
+    def psgd_pairs_epoch_weighted(self, degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                                  batch_size, triples, weights, fit_linear, it):
+        """``psgd_pairs_epoch`` with one weight ``>= 0`` per triple, which multiplies its loss
+        and its gradient (``spfm_psgd_pairs_epoch_weighted``).  Returns
+        (sum of weight * loss, it)."""
+        t = self._triples(triples)
+        wt = np.ascontiguousarray(weights, dtype=np.float64)
+        if wt.shape != (t.shape[0],):
+            raise ValueError("weights must have shape (%d,), got %r" % (t.shape[0], wt.shape))
+        itc = C.c_int64(int(it))
+        sl = C.c_double()
+        lr = (_capi.LEARNING_RATE[learning_rate] if isinstance(learning_rate, str)
+              else int(learning_rate))
+        self._check(self._lib.spfm_psgd_pairs_epoch_weighted(
+            self._h, int(degree), float(alpha), float(beta), float(gamma), float(eta0), lr,
+            float(power_t), int(batch_size), t.ctypes.data_as(_capi._ip),
+            wt.ctypes.data_as(_capi._dp), t.shape[0], int(bool(fit_linear)), C.byref(itc),
+            C.byref(sl)))
+        return sl.value, itc.value
+
     def psgd_pairs_eval(self, degree, fit_linear, triples):
         """(sum of the triples' losses, number of triples with margin > 0) at the live device
         parameters; nothing is updated (``spfm_psgd_pairs_eval``)."""
@@ -1269,6 +1289,53 @@ class HipEngine(object):
             None if t is None else t.ctypes.data_as(_capi._ip),
             None if sc is None else sc.ctypes.data_as(_capi._dp)))
         return m, t, sc
+
+    def psgd_pairs_set_proposal(self, cum):
+        """The proposal distribution of the device samplers: ``cum`` (n_cand,) uint32, the
+        inclusive cumulative sums of integer weights (``pairwise.quantise_proposal``), or ``None``
+        for the uniform draw (``spfm_psgd_pairs_set_proposal``)."""
+        if cum is None:
+            self._check(self._lib.spfm_psgd_pairs_set_proposal(self._h, None, 0))
+            return
+        c = np.ascontiguousarray(cum, dtype=np.uint32)
+        self._check(self._lib.spfm_psgd_pairs_set_proposal(
+            self._h, c.ctypes.data_as(_capi._up), c.size))
+
+    def psgd_pairs_set_positive_weights(self, weights):
+        """One weight ``>= 0`` per positive of the sampler, canonical CSR order, or ``None`` to
+        clear (``spfm_psgd_pairs_set_positive_weights``)."""
+        if weights is None:
+            self._check(self._lib.spfm_psgd_pairs_set_positive_weights(self._h, None, 0))
+            return
+        wq = np.ascontiguousarray(weights, dtype=np.float64)
+        self._check(self._lib.spfm_psgd_pairs_set_positive_weights(
+            self._h, wq.ctypes.data_as(_capi._dp), wq.size))
+
+    def psgd_pairs_sample_warp(self, degree, n_negatives, max_trials, max_draws, margin, seed,
+                               epoch, order=None, want=True):
+        """WARP negatives at the live parameters, left resident with their weights
+        (``spfm_psgd_pairs_sample_warp``).  Returns
+        ``(m, triples, scores, weights, trials)`` by slot; the four copies are ``None`` without
+        ``want``."""
+        m = getattr(self, "_sampler_npos", 0) * max(int(n_negatives), 0)
+        o = None
+        if order is not None:
+            o = np.ascontiguousarray(order, dtype=np.int32)
+            if o.shape != (m,):
+                raise ValueError("order must have shape (%d,), got %r" % (m, o.shape))
+        t = np.empty((m, 3), dtype=np.int32) if want else None
+        sc = np.empty(m, dtype=np.float64) if want else None
+        wt = np.empty(m, dtype=np.float64) if want else None
+        tr = np.empty(m, dtype=np.int32) if want else None
+        self._check(self._lib.spfm_psgd_pairs_sample_warp(
+            self._h, int(degree), int(n_negatives), int(max_trials), int(max_draws),
+            float(margin), int(seed), int(epoch),
+            None if o is None else o.ctypes.data_as(_capi._ip),
+            None if t is None else t.ctypes.data_as(_capi._ip),
+            None if sc is None else sc.ctypes.data_as(_capi._dp),
+            None if wt is None else wt.ctypes.data_as(_capi._dp),
+            None if tr is None else tr.ctypes.data_as(_capi._ip)))
+        return m, t, sc, wt, tr
 
     def psgd_pairs_epoch_sampled(self, degree, alpha, beta, gamma, eta0, learning_rate, power_t,
                                  batch_size, fit_linear, it):

@@ -20,6 +20,9 @@ restate that in NumPy).  ``restate_margins`` / ``restate_pair_gradient`` /
 ``objective='list'`` and ``'softmax'`` make a positive with its ``n_negatives`` negatives ONE
 training item (``restate_list_scores`` / ``restate_list_gradient`` /
 ``restate_list_epoch`` restate it).
+``sampler='warp'``, ``proposal=`` and ``sample_weight=`` are DESIGN.md section 19c: a weight per
+triple, a weighted integer draw (``quantise_proposal`` / ``proposal_cum``) and the rank-weighted
+sampler (``restate_warp``).
 There is no CPU path of the fit: without the library or a GPU it raises.
 """
 import numpy as np
@@ -81,20 +84,29 @@ def sample_triples(interactions, n_negatives=1, random_state=None, exclude=None)
 
 
 def epoch_triples(rng, n_epochs, interactions=None, triples=None, n_negatives=1, resample=True,
-                  shuffle=False, exclude=None):
+                  shuffle=False, exclude=None, weights=None):
     """The triple list of every epoch of ``SparseFactorizationMachineRanker.fit``, in the order
     the device visits it, as the fit draws it from ``rng`` (a ``RandomState``): negatives are
     drawn before the first epoch and, with ``resample``, before every later one; with ``shuffle``
     the list is then permuted.  A generator of ``(m, 3)`` int32 arrays in context / candidate
-    numbering."""
+    numbering.  ``weights`` (one per positive with ``interactions``, one per triple with
+    ``triples``): ``(triples, weights per triple)`` pairs are generated instead, permuted
+    together; the draws from ``rng`` do not change."""
     cur = None if triples is None else np.asarray(triples, dtype=np.int32)
+    wcur = None
+    if weights is not None:
+        wcur = np.asarray(weights, dtype=np.double)
+        if interactions is not None:
+            wcur = np.repeat(wcur, int(n_negatives))
     for ep in range(n_epochs):
         if interactions is not None and (cur is None or resample):
             cur = sample_triples(interactions, n_negatives, rng, exclude)
-        out = cur
+        out, wout = cur, wcur
         if shuffle:
-            out = cur[rng.permutation(cur.shape[0])]
-        yield out
+            perm = rng.permutation(cur.shape[0])
+            out = cur[perm]
+            wout = None if wcur is None else wcur[perm]
+        yield out if wcur is None else (out, wout)
 
 
 def check_triples(triples, B, C):
@@ -122,7 +134,7 @@ def check_triples(triples, B, C):
     return np.ascontiguousarray(t, dtype=np.int32)
 
 
-SAMPLERS = ("host", "uniform", "dynamic")
+SAMPLERS = ("host", "uniform", "dynamic", "warp")
 _MASK64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
@@ -153,11 +165,51 @@ def draw_u64(seed, epoch, r, t):
         return _mix64(key + (t + np.uint64(1)) * g)
 
 
-def draw_candidates(u, C):
+def draw_candidates(u, C, cum=None):
     """``((u >> 32) * C) >> 32`` on uint64 arrays: a candidate in ``[0, C)``; no floating point,
-    no modulo"""
-    return (((np.asarray(u, dtype=np.uint64) >> np.uint64(32)) * np.uint64(C))
-            >> np.uint64(32)).astype(np.int64)
+    no modulo.  With a proposal table ``cum`` (``proposal_cum``; ``W = cum[-1]``): the smallest
+    ``c`` with ``cum[c] > ((u >> 32) * W) >> 32`` -- the same multiply-shift, then a search."""
+    hi = np.asarray(u, dtype=np.uint64) >> np.uint64(32)
+    if cum is None:
+        return ((hi * np.uint64(C)) >> np.uint64(32)).astype(np.int64)
+    cum = np.asarray(cum, dtype=np.uint64)
+    if cum.shape != (C,):
+        raise ValueError("cum must have shape (%d,), got %r" % (C, cum.shape))
+    x = (hi * cum[-1]) >> np.uint64(32)
+    return np.searchsorted(cum, x, side="right").astype(np.int64)
+
+
+def quantise_proposal(weights, C=None):
+    """Integer weights of a proposal distribution over the candidates, as the fit hands them to
+    the device: ``q_c = max(floor(w_c / sum(w) * 2**31), 1 if w_c > 0 else 0)`` (int64).  A
+    positive weight never becomes 0, a zero weight stays 0, and the total is at most
+    ``2**31 + C < 2**32`` for every admissible ``C``.  ``ValueError`` for a negative or non-finite
+    weight, a vector that is not ``(C,)``, and an all-zero vector."""
+    w = np.asarray(weights, dtype=np.double)
+    if w.ndim != 1 or (C is not None and w.shape[0] != C):
+        raise ValueError("proposal must hold one weight per candidate%s, got shape %r"
+                         % ("" if C is None else " (%d)" % C, w.shape))
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError("proposal: the weights must be finite and >= 0")
+    if not (w > 0).any():
+        raise ValueError("proposal: every weight is zero")
+    q = np.floor(w / w.sum() * float(2 ** 31)).astype(np.int64)
+    return np.maximum(q, (w > 0).astype(np.int64))
+
+
+def proposal_cum(q):
+    """the inclusive cumulative sums of the integer weights ``q`` as uint32
+    (``spfm_psgd_pairs_set_proposal``)"""
+    cum = np.cumsum(np.asarray(q, dtype=np.int64))
+    if (np.asarray(q) < 0).any() or cum[-1] < 1 or cum[-1] >= 2 ** 32:
+        raise ValueError("proposal: the integer weights must be >= 0 with a total in [1, 2**32)")
+    return cum.astype(np.uint32)
+
+
+def popularity_weights(interactions, power=0.75):
+    """``(stored entries of the candidate's column of interactions + 1) ** power``"""
+    I = sp.csr_matrix(interactions)
+    return (np.bincount(I.indices, minlength=I.shape[1]) + 1.0) ** float(power)
 
 
 def _forbidden(interactions, exclude, B, C):
@@ -174,7 +226,7 @@ def _forbidden(interactions, exclude, B, C):
     return I, F
 
 
-def _admitted_sets(I, F, n_negatives, n_candidates, max_draws, seed, epoch):
+def _admitted_sets(I, F, n_negatives, n_candidates, max_draws, seed, epoch, cum=None):
     """per output triple r: (b, c+, the admitted candidates in the order of their draws); the
     fallback candidate alone where no draw with t < max_draws is admitted"""
     B, C = I.shape
@@ -185,21 +237,22 @@ def _admitted_sets(I, F, n_negatives, n_candidates, max_draws, seed, epoch):
         q = r // n_negatives
         b = int(rows[q])
         forb = F.indices[F.indptr[b]:F.indptr[b + 1]]
-        cand = draw_candidates(draw_u64(seed, epoch, r, t), C)
+        cand = draw_candidates(draw_u64(seed, epoch, r, t), C, cum)
         adm = cand[~np.isin(cand, forb)][:n_candidates]
-        if adm.size == 0:  # upwards, cyclically, from the last drawn candidate
+        walked = adm.size == 0
+        if walked:  # upwards, cyclically, from the last drawn candidate
             c = int(cand[-1])
             for _ in range(C):
                 c = 0 if c + 1 == C else c + 1
                 if c not in forb:
                     break
             adm = np.array([c], dtype=np.int64)
-        out.append((b, int(I.indices[q]), adm))
+        out.append((b, int(I.indices[q]), adm, walked))
     return out
 
 
 def restate_sample(P, w, lams, X, Z, interactions, degree, n_negatives, n_candidates, max_draws,
-                   seed, epoch, exclude=None, order=None, wide=False, details=False):
+                   seed, epoch, exclude=None, order=None, wide=False, details=False, cum=None):
     """Test aid, NumPy only: what ``spfm_psgd_pairs_sample`` leaves on the device.  For output
     triple ``r = q * n_negatives + i`` (positive ``q`` of ``interactions`` in canonical CSR order)
     the first ``n_candidates`` admitted draws among ``t < max_draws`` (admitted: the candidate is
@@ -211,7 +264,7 @@ def restate_sample(P, w, lams, X, Z, interactions, degree, n_negatives, n_candid
     scores (zeros for ``n_candidates == 1``, which scores nothing) and the distance between the
     best score and the best score of a *different* candidate of the set (``inf`` without one).
     ``details``: a fourth item, per ``r`` (not slot) the pair (admitted candidates, their
-    scores)."""
+    scores).  ``cum``: the proposal table of the draws (``draw_candidates``)."""
     dtype = np.longdouble if wide else np.double
     P, w, lams = _as(dtype, P, w, lams)
     P = P[None] if P.ndim == 2 else P
@@ -219,23 +272,16 @@ def restate_sample(P, w, lams, X, Z, interactions, degree, n_negatives, n_candid
     if not sp.issparse(interactions):
         interactions = sp.csr_matrix(np.asarray(interactions))
     I, F = _forbidden(interactions, exclude, B, C)
-    sets = _admitted_sets(I, F, int(n_negatives), int(n_candidates), int(max_draws), seed, epoch)
+    sets = _admitted_sets(I, F, int(n_negatives), int(n_candidates), int(max_draws), seed, epoch,
+                          cum)
     m = len(sets)
-    Xd, Zd = _dense_sides(X, Z, dtype)
-    lin = Zd @ w
-    cache = {}
-
-    def row_scores(b):
-        if b not in cache:
-            cache[b] = _rows_output(P, lams, Xd[b][None, :] + Zd, degree)[0] + lin
-        return cache[b]
-
+    row_scores = _row_scorer(P, w, lams, X, Z, degree, dtype)
     slots = np.arange(m) if order is None else np.asarray(order, dtype=np.int64)
     triples = np.empty((m, 3), dtype=np.int32)
     scores = np.zeros(m, dtype=dtype)
     gap = np.full(m, np.inf)
     det = []
-    for r, (b, cp, adm) in enumerate(sets):
+    for r, (b, cp, adm, _) in enumerate(sets):
         sc = row_scores(b)[adm]
         best = int(np.argmax(sc))  # the first maximum: the earliest admitted draw
         other = sc[adm != adm[best]]
@@ -250,6 +296,84 @@ def restate_sample(P, w, lams, X, Z, interactions, degree, n_negatives, n_candid
     return triples, scores, gap
 
 
+def _row_scorer(P, w, lams, X, Z, degree, dtype):
+    """b -> the scores s(b, .) of every candidate by dense evaluation, cached per context"""
+    Xd, Zd = _dense_sides(X, Z, dtype)
+    lin = Zd @ w
+    cache = {}
+
+    def row_scores(b):
+        if b not in cache:
+            cache[b] = _rows_output(P, lams, Xd[b][None, :] + Zd, degree)[0] + lin
+        return cache[b]
+
+    return row_scores
+
+
+def restate_warp(P, w, lams, X, Z, interactions, degree, n_negatives, max_trials, max_draws,
+                 margin, seed, epoch, exclude=None, order=None, wide=False, cum=None,
+                 positive_weights=None, details=False):
+    """Test aid, NumPy only: what ``spfm_psgd_pairs_sample_warp`` leaves on the device (DESIGN.md
+    section 19c).  The draws, the admission, the score and the slots are ``restate_sample``'s.
+    For output triple ``r`` of positive ``q = (b, c+)`` the admitted draws with ``t < max_draws``
+    are tried in the order of ``t``, at most ``max_trials`` of them; the first ``a_N`` with
+    ``s(b, a_N) > s(b, c+) - margin`` is the negative, ``trials = N`` and ``weight = posw_q *
+    log(max(1, A_b // N))`` with ``A_b = C - |forbidden(b)|``.  No violator: the highest-scored of
+    those tried (ties to the earliest), ``trials = 0``, ``weight = 0``; no draw admitted: the
+    fallback walk's candidate, ``trials = 0``, ``weight = 0``.  Returns ``(triples, scores,
+    weights, trials, near)`` by slot; ``near`` is the smallest ``|s - (s+ - margin)|`` over the
+    candidates that were tried (``inf`` for the fallback).  ``details``: a sixth item, per ``r``
+    (not slot) ``(tried candidates, their scores, s+ - margin)``."""
+    dtype = np.longdouble if wide else np.double
+    P, w, lams = _as(dtype, P, w, lams)
+    P = P[None] if P.ndim == 2 else P
+    B, C = X.shape[0], Z.shape[0]
+    if not sp.issparse(interactions):
+        interactions = sp.csr_matrix(np.asarray(interactions))
+    I, F = _forbidden(interactions, exclude, B, C)
+    if max_trials < 1 or max_trials > max_draws:
+        raise ValueError("1 <= max_trials <= max_draws is required")
+    sets = _admitted_sets(I, F, int(n_negatives), int(max_trials), int(max_draws), seed, epoch,
+                          cum)
+    m = len(sets)
+    posw = (np.ones(I.nnz) if positive_weights is None
+            else np.asarray(positive_weights, dtype=np.double))
+    if posw.shape != (I.nnz,):
+        raise ValueError("positive_weights must have shape (%d,)" % I.nnz)
+    row_scores = _row_scorer(P, w, lams, X, Z, degree, dtype)
+    free = C - np.diff(F.indptr)
+    slots = np.arange(m) if order is None else np.asarray(order, dtype=np.int64)
+    triples = np.empty((m, 3), dtype=np.int32)
+    scores = np.zeros(m, dtype=dtype)
+    weights = np.zeros(m)
+    trials = np.zeros(m, dtype=np.int32)
+    near = np.full(m, np.inf)
+    det = []
+    for r, (b, cp, adm, walked) in enumerate(sets):
+        s_all = row_scores(b)
+        thr = s_all[cp] - dtype(margin)
+        sc = s_all[adm]
+        viol = np.flatnonzero(sc > thr)
+        if walked:
+            pick, n_tried = 0, 0
+        elif viol.size:
+            pick = int(viol[0])
+            n_tried = pick + 1
+            trials[slots[r]] = n_tried
+            rank = max(1, int(free[b]) // n_tried)
+            weights[slots[r]] = posw[r // int(n_negatives)] * np.log(float(rank))
+        else:
+            pick, n_tried = int(np.argmax(sc)), adm.size
+        if n_tried:
+            near[slots[r]] = float(np.abs(sc[:n_tried] - thr).min())
+        triples[slots[r]] = (b, cp, adm[pick])
+        scores[slots[r]] = sc[pick]
+        det.append((adm[:n_tried], sc[:n_tried], thr))
+    if details:
+        return triples, scores, weights, trials, near, det
+    return triples, scores, weights, trials, near
+
+
 def _prepare_pairs(est, X, Z):
     """Canonical, checked, widened (X, Z) of one width, for an estimator that need not be fitted;
     every argument error is raised here, before a handle exists."""
@@ -261,6 +385,19 @@ def _prepare_pairs(est, X, Z):
         raise ValueError("a pairwise fit needs a context row and two candidate rows")
     _check_disjoint(X, Z)
     return _widen(est, X, Z)
+
+
+def _check_weights(weights, count, what):
+    """``None``, or ``count`` finite weights ``>= 0`` as float64 (one per ``what``)"""
+    if weights is None:
+        return None
+    wt = np.asarray(weights, dtype=np.double)
+    if wt.shape != (count,):
+        raise ValueError("sample_weight must hold one value per %s (%d), got shape %r"
+                         % (what, count, wt.shape))
+    if not np.isfinite(wt).all() or (wt < 0).any():
+        raise ValueError("sample_weight: the weights must be finite and >= 0")
+    return np.ascontiguousarray(wt)
 
 
 # ------------------------------------------------------------------ NumPy restatement (test aid)
@@ -329,11 +466,12 @@ def restate_margins(P, w, lams, X, Z, triples, degree, wide=False):
     return (fp - fm) + (Zd[t[:, 1]] - Zd[t[:, 2]]) @ w
 
 
-def restate_pair_gradient(P, w, lams, X, Z, triples, degree, loss, wide=False):
+def restate_pair_gradient(P, w, lams, X, Z, triples, degree, loss, wide=False, weights=None):
     """Test aid, NumPy only: ``(losses (m,), grad_P (n_orders, k, d), grad_w (d,))`` of the
     summed loss of the triples at ``(P, w)`` -- the sums one minibatch scatters.  ``grad_w`` is
     formed from ``z_c+ - z_c-`` alone: the context's term cancels and its columns are exactly
-    zero."""
+    zero.  ``weights`` (m,): triple ``q`` enters with ``weights[q]`` times its loss (the returned
+    losses are weighted too)."""
     dtype = np.longdouble if wide else np.double
     P, w, lams = _as(dtype, P, w, lams)
     P = P[None] if P.ndim == 2 else P
@@ -344,6 +482,9 @@ def restate_pair_gradient(P, w, lams, X, Z, triples, degree, loss, wide=False):
     fm, dpm = _rows_output(P, lams, Vm, degree)
     dz = Zd[t[:, 1]] - Zd[t[:, 2]]
     val, dL = _loss_pos(loss, (fp - fm) + dz @ w)
+    if weights is not None:
+        wt = np.asarray(weights, dtype=dtype)
+        val, dL = wt * val, wt * dL
     gP = np.zeros_like(P)
     for o in range(P.shape[0]):
         deg = degree - o
@@ -409,12 +550,15 @@ def _prox(regularizer, Po, c):
 
 def restate_pairwise_epoch(P, w, lams, X, Z, triples, degree, loss="logistic", regularizer="l1",
                            alpha=1.0, beta=1.0, gamma=1.0, eta0=1.0, learning_rate="optimal",
-                           power_t=1.0, batch_size=1, fit_linear=True, it=1, wide=False):
+                           power_t=1.0, batch_size=1, fit_linear=True, it=1, wide=False,
+                           weights=None):
     """Test aid, NumPy only: one epoch of the pairwise fit over ``triples`` (context / candidate
     numbering, visited in the order given) from ``P`` (n_orders, k, d) and ``w``.  Minibatch
     ``bi`` covers the triples ``[bi * batch_size, ...)``, the last one may be shorter; per batch
     the gradient sums, the step ``eta / B`` with ``psgd_eta`` at ``it``, the shrink and the prox of
-    the minibatch solver.  Returns ``(P, w, sum_loss, it)`` (new arrays)."""
+    the minibatch solver.  ``weights`` (m,): one per triple, visited with it; the step stays
+    ``eta / B`` with ``B`` the triple count and ``sum_loss`` is the sum of weight times loss.
+    Returns ``(P, w, sum_loss, it)`` (new arrays)."""
     dtype = np.longdouble if wide else np.double
     P, w, lams = _as(dtype, P, w, lams)
     P = (P[None] if P.ndim == 2 else P).copy()
@@ -423,7 +567,8 @@ def restate_pairwise_epoch(P, w, lams, X, Z, triples, degree, loss="logistic", r
     sum_loss = dtype(0)
     for pos in range(0, t.shape[0], int(batch_size)):
         tb = t[pos:pos + int(batch_size)]
-        val, gP, gw = restate_pair_gradient(P, w, lams, X, Z, tb, degree, loss, wide)
+        wb = None if weights is None else np.asarray(weights)[pos:pos + int(batch_size)]
+        val, gP, gw = restate_pair_gradient(P, w, lams, X, Z, tb, degree, loss, wide, wb)
         sum_loss += val.sum()
         eta_P, eta_w = _psgd_eta(learning_rate, eta0, alpha, beta, power_t, it)
         if fit_linear:
@@ -655,7 +800,8 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                                       % MAX_DEGREE)
 
     def fit(self, X, Z, interactions=None, triples=None, n_negatives=1, resample=True,
-            sampler="host", n_candidates=8, exclude=None, objective="pairwise"):
+            sampler="host", n_candidates=8, exclude=None, objective="pairwise", margin=1.0,
+            proposal=None, proposal_power=0.75, sample_weight=None):
         """Fit on contexts ``X`` (B, d) and candidates ``Z`` (C, d) with disjoint column sets.
         Exactly one of ``interactions`` -- a sparse (B, C) matrix whose stored entries are the
         positives; ``n_negatives`` negatives per positive are drawn, again before every epoch
@@ -682,7 +828,24 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
         mean of the ``n_negatives`` pairwise losses (the pairwise fit's arithmetic with
         ``batch_size`` counted in positives).  ``batch_size``, the shuffle and the mean loss of
         the stopping rule count lists; explicit ``triples`` must arrive grouped, ``n_negatives``
-        rows per positive."""
+        rows per positive.
+
+        DESIGN.md section 19c, ``objective='pairwise'`` only:
+
+        * ``sampler='warp'``: per triple the device tries up to ``n_candidates`` admissible draws
+          and trains against the first whose score exceeds ``s+ - margin``, weighted by
+          ``log(max(1, A_b // N))`` (``N`` trials, ``A_b`` admissible candidates of the context);
+          a triple without a violator has weight 0 for that epoch.
+        * ``proposal``: the distribution of the device samplers' draws -- ``None`` (uniform),
+          ``'popularity'`` (``(stored count of the candidate's column of interactions + 1) **
+          proposal_power``) or ``C`` weights; quantised by ``quantise_proposal``.  Not with
+          ``sampler='host'``.
+        * ``sample_weight``: a confidence weight ``>= 0`` per positive -- with ``interactions``
+          ``'data'`` (its stored values) or ``nnz`` values in canonical CSR order; with
+          ``triples`` one value per triple.  It multiplies the triple's loss and gradient.
+
+        The mean loss of the stopping rule stays ``sum_loss / m`` with ``m`` the number of
+        triples, not the weight sum."""
         self._check_config()
         if objective not in OBJECTIVES:
             raise ValueError("objective %r is not supported. Choose from %s."
@@ -700,14 +863,41 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                              "not triples" % (sampler,))
         if int(n_candidates) != n_candidates or n_candidates < 1:
             raise ValueError("n_candidates must be an integer >= 1, got %r" % (n_candidates,))
+        if listwise and (sampler == "warp" or sample_weight is not None):
+            raise ValueError("sampler='warp' and sample_weight need objective='pairwise', got %r"
+                             % (objective,))
+        if sampler == "host" and proposal is not None:
+            raise ValueError("proposal applies to the device samplers ('uniform', 'dynamic', "
+                             "'warp'), not to sampler='host'")
+        if sampler == "warp" and not np.isfinite(margin):
+            raise ValueError("margin must be finite, got %r" % (margin,))
         Xa, Za = _prepare_pairs(self, X, Z)
         B, C = Xa.shape[0], Za.shape[0]
         n_features = Xa.shape[1]
         forbidden = None
+        cum = None
         if interactions is not None:
             if not sp.issparse(interactions):
                 interactions = sp.csr_matrix(np.asarray(interactions))
+            stored = interactions
             interactions = _pattern(interactions, B, C, "interactions")
+            if isinstance(sample_weight, str):
+                if sample_weight != "data":
+                    raise ValueError("sample_weight %r is not supported: 'data' or an array"
+                                     % (sample_weight,))
+                stored = sp.csr_matrix(stored, dtype=np.double, copy=True)
+                stored.sum_duplicates()
+                stored.sort_indices()
+                sample_weight = stored.data
+            if isinstance(proposal, str):
+                if proposal != "popularity":
+                    raise ValueError("proposal %r is not supported: None, 'popularity' or %d "
+                                     "weights" % (proposal, C))
+                proposal = popularity_weights(interactions, proposal_power)
+            if proposal is not None:
+                cum = proposal_cum(quantise_proposal(proposal, C))
+            sample_weight = _check_weights(sample_weight, interactions.nnz, "stored entry of "
+                                           "interactions")
             if interactions.nnz == 0:
                 raise ValueError("interactions has no stored entry")
             if exclude is not None:
@@ -724,6 +914,7 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
             triples = check_triples(triples, B, C)
             if triples.shape[0] == 0:
                 raise ValueError("triples is empty")
+            sample_weight = _check_weights(sample_weight, triples.shape[0], "triple")
         rng = check_random_state(self.random_state)
         if not (self.warm_start and hasattr(self, "w_")):
             self.w_ = np.zeros(n_features, dtype=np.double)
@@ -758,16 +949,24 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
             self.w_ = np.ascontiguousarray(self.w_, dtype=np.double)
             engine.set_params(self.P_, self.w_, self.lams_)
             engine.configure("psgd", self.loss, self.regularizer, self.degree)
-            if sampler == "host":
+            if sampler == "host" and sample_weight is not None:
+                lists = epoch_triples(rng, self.max_iter, interactions, triples, n_negatives,
+                                      resample, self.shuffle, exclude, weights=sample_weight)
+            elif sampler == "host":
                 lists = (epoch_lists if listwise else epoch_triples)(
                     rng, self.max_iter, interactions, triples, n_negatives, resample,
                     self.shuffle, exclude)
             else:
                 engine.psgd_pairs_set_sampler(B, C, interactions, forbidden)
+                if cum is not None:
+                    engine.psgd_pairs_set_proposal(cum)
+                if sample_weight is not None:
+                    engine.psgd_pairs_set_positive_weights(sample_weight)
                 lists = self._device_lists(engine, rng, interactions.nnz * int(n_negatives),
                                            int(n_negatives),
                                            1 if sampler == "uniform" else int(n_candidates),
-                                           resample, listwise)
+                                           resample, listwise,
+                                           float(margin) if sampler == "warp" else None)
             converged, self.n_iter_ = self._fit_pairs(engine, B, batch_size, lists,
                                                       objective, int(n_negatives))
         finally:
@@ -775,11 +974,12 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
         return self._finish_fit(converged)
 
     def _device_lists(self, engine, rng, m, n_negatives, n_candidates, resample,
-                      listwise=False):
+                      listwise=False, warp_margin=None):
         """per epoch: have the device draw the epoch's negatives (before the first epoch and,
         with ``resample``, before every later one) and yield the number of resident triples;
         ``listwise``: the triples stay grouped and ``(m, visiting order of the lists or None)``
-        is yielded"""
+        is yielded; ``warp_margin``: the WARP sampler with that margin and ``n_candidates``
+        trials"""
         seed = rng.randint(0, 2 ** 31 - 1)
         list_order = None
         for ep in range(self.max_iter):
@@ -793,9 +993,14 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                 continue
             if ep == 0 or resample:
                 order = rng.permutation(m) if self.shuffle else None
-                engine.psgd_pairs_sample(self.degree, n_negatives, n_candidates,
-                                         64 * n_candidates, seed, ep, order,
-                                         want_triples=False, want_scores=False)
+                if warp_margin is not None:
+                    engine.psgd_pairs_sample_warp(self.degree, n_negatives, n_candidates,
+                                                  64 * n_candidates, warp_margin, seed, ep,
+                                                  order, want=False)
+                else:
+                    engine.psgd_pairs_sample(self.degree, n_negatives, n_candidates,
+                                             64 * n_candidates, seed, ep, order,
+                                             want_triples=False, want_scores=False)
             yield m
 
     def _fit_pairs(self, engine, B, batch_size, lists, objective="pairwise", n_negatives=1):
@@ -818,6 +1023,11 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                 m = t[0] // n_negatives
                 sum_loss, self.it_ = engine.psgd_lists_epoch_sampled(
                     *step, n_negatives, objective, self.fit_linear, self.it_, list_order=t[1])
+            elif isinstance(t, tuple):  # (triples, a weight per triple)
+                m = t[0].shape[0]
+                stacked = t[0] + np.array([0, B, B], dtype=np.int32)  # rows of [X; Z]
+                sum_loss, self.it_ = engine.psgd_pairs_epoch_weighted(
+                    *step, stacked, t[1], self.fit_linear, self.it_)
             elif isinstance(t, np.ndarray):
                 m = t.shape[0]
                 stacked = t + np.array([0, B, B], dtype=np.int32)  # rows of [X; Z]
