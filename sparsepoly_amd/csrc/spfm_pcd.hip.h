@@ -814,21 +814,50 @@ __device__ __forceinline__ void pcd_sync_entry(size_t i, double x, double p_old,
     yy[2 * i] = (T)(yh - lam * upd * dprev);
 }
 
+// Layout of a row block held in LDS (pcd_prb_kernel, LR 1 / 2).  One cache value per row
+// (AS == 1: degree 2, all-subsets): ONE 8-byte record {A[i], word} per row at lds_a (lds_r is
+// not used) -- both words of a row are always read together and written together, so every row
+// access is a single ds_read_b64 / ds_write_b64 instead of two 4-byte accesses with two
+// independent bank patterns.  Two cache values (AS == 2): arrays lds_a[rows][AS], lds_r[rows].
+// Either way 4 * (AS + 1) bytes per row behind the same base.
+// (a compile-time trait: a run-time switch in this kernel once cost 9 %)
+template <int AS>
+constexpr bool kPrbRowRec = (AS == 1);
+
+template <typename T, int AS>
+__device__ __forceinline__ void prb_row_load(const T* lds_a, const T* lds_r, int il, T& word,
+                                             T* a) {
+    if constexpr (kPrbRowRec<AS>) {
+        const typename Vec2<T>::type v = reinterpret_cast<const typename Vec2<T>::type*>(lds_a)[il];
+        a[0] = v.x;
+        word = v.y;
+    } else {
+        word = lds_r[il];
+#pragma unroll
+        for (int t = 0; t < AS; ++t) a[t] = lds_a[il * AS + t];
+    }
+}
+template <typename T, int AS>
+__device__ __forceinline__ void prb_row_store(T* lds_a, T* lds_r, int il, T word, const T* a) {
+    if constexpr (kPrbRowRec<AS>) {
+        typename Vec2<T>::type v;
+        v.x = a[0];
+        v.y = word;
+        reinterpret_cast<typename Vec2<T>::type*>(lds_a)[il] = v;
+    } else {
+#pragma unroll
+        for (int t = 0; t < AS; ++t) lds_a[il * AS + t] = a[t];
+        lds_r[il] = word;
+    }
+}
+
 // the same update on a row block held in LDS as (A[i, 1..AS], r_i = yhat_i - y_i)
 template <typename T, int M>
 __device__ __forceinline__ void pcd_sync_entry_lds(int il, double x, double p_old, double upd,
                                                    double lam, T* lds_a, T* lds_r) {
     constexpr int AS = Kind<M>::AS;
-    double yh = (double)lds_r[il];
-    if constexpr (M == 0) {
-        const double a0 = (double)lds_a[il];
-        yh -= lam * a0;
-        double a1 = a0 / (1.0 + x * p_old);
-        a1 *= 1.0 + x * (p_old - upd);
-        yh += lam * a1;
-        lds_a[il] = (T)a1;
-        lds_r[il] = (T)yh;
-    } else {
+    if constexpr (!kPrbRowRec<AS>) {  // two cache values per row: the arrays, word by word
+        const double yh = (double)lds_r[il];
         double dprev = x;
 #pragma unroll
         for (int t = 0; t < AS; ++t) {
@@ -838,6 +867,29 @@ __device__ __forceinline__ void pcd_sync_entry_lds(int il, double x, double p_ol
             dprev = dcur;
         }
         lds_r[il] = (T)(yh - lam * upd * dprev);
+        return;
+    }
+    T wd, ar[AS], an[AS];
+    prb_row_load<T, AS>(lds_a, lds_r, il, wd, ar);
+    double yh = (double)wd;
+    if constexpr (M == 0) {
+        const double a0 = (double)ar[0];
+        yh -= lam * a0;
+        double a1 = a0 / (1.0 + x * p_old);
+        a1 *= 1.0 + x * (p_old - upd);
+        yh += lam * a1;
+        an[0] = (T)a1;
+        prb_row_store<T, AS>(lds_a, lds_r, il, (T)yh, an);
+    } else {
+        double dprev = x;
+#pragma unroll
+        for (int t = 0; t < AS; ++t) {
+            const double a = (double)ar[t];
+            const double dcur = x * (a - p_old * dprev);
+            an[t] = (T)(a - upd * dprev);
+            dprev = dcur;
+        }
+        prb_row_store<T, AS>(lds_a, lds_r, il, (T)(yh - lam * upd * dprev), an);
     }
 }
 

@@ -352,14 +352,10 @@ __device__ __forceinline__ void prb_fill_lds(const T* __restrict__ A,
         for (int u = 0; u < kPrbFillU; ++u) {
             const int il = base + u * kPrbThreads;
             if (il < nr) {
-#pragma unroll
-                for (int t = 0; t < AS; ++t) lds_a[il * AS + t] = ar[u][t];
-                if constexpr (LR == 1) {
-                    lds_r[il] = (T)((double)yv[u].x - (double)yv[u].y);
-                } else {
-                    lds_r[il] = yv[u].x;
-                    lds_s[il] = yv[u].y > (T)0 ? 1 : 0;
-                }
+                const T wd = (LR == 1) ? (T)((double)yv[u].x - (double)yv[u].y) : yv[u].x;
+                if constexpr (AS > 0) prb_row_store<T, AS>(lds_a, lds_r, il, wd, ar[u]);
+                else lds_r[il] = wd;
+                if constexpr (LR != 1) lds_s[il] = yv[u].y > (T)0 ? 1 : 0;
             }
         }
     }
@@ -380,12 +376,19 @@ __device__ __forceinline__ void prb_writeback_lds(T* __restrict__ A, T* __restri
             const int il = base + u * kPrbThreads;
             if (il < nr) {
                 const size_t i = (size_t)(row0 + il);
+                T wd;
+                if constexpr (AS > 0) {
+                    T ar[AS];
+                    prb_row_load<T, AS>(lds_a, lds_r, il, wd, ar);
 #pragma unroll
-                for (int t = 0; t < AS; ++t) A[i * AS + t] = lds_a[il * AS + t];
+                    for (int t = 0; t < AS; ++t) A[i * AS + t] = ar[t];
+                } else {
+                    wd = lds_r[il];
+                }
                 if constexpr (LR == 1)
-                    yy[2 * i] = (T)((double)lds_r[il] + (double)yt[u]);
+                    yy[2 * i] = (T)((double)wd + (double)yt[u]);
                 else
-                    yy[2 * i] = lds_r[il];
+                    yy[2 * i] = wd;
             }
         }
     }
@@ -522,8 +525,10 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
     // CR: per-conflict contributions of the step, behind the fixed block
     double* sh_ce = dyn_lds + kPrbLdsFixed;  // [64][2] of a row's EARLIER column (constant)
     double* sh_cv = sh_ce + 128;             // [64][2] of its LATER column (per round)
-    T* lds_a = reinterpret_cast<T*>(dyn_lds + kPrbLdsFixed + (CR ? kPrbLdsCR : 0));  // [rows_per][AS] A[i, 1..AS]
-    T* lds_r = lds_a + (size_t)a.rows_per * AS;                // [rows_per] residual or yhat
+    // rows: AS == 1: [rows_per] records {A[i], word}; AS == 2: [rows_per][AS] A[i, 1..AS], then
+    // [rows_per] words (word = residual or yhat; prb_row_load / prb_row_store, spfm_pcd.hip.h)
+    T* lds_a = reinterpret_cast<T*>(dyn_lds + kPrbLdsFixed + (CR ? kPrbLdsCR : 0));
+    T* lds_r = lds_a + (size_t)a.rows_per * AS;
     unsigned char* lds_s = reinterpret_cast<unsigned char*>(lds_r + a.rows_per);  // y > 0
     if constexpr (LDSR) {
         const int nr = min(a.rows_per, a.n_rows - row0);
@@ -636,10 +641,12 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
                     if (i / a.rows_per == g) {
                         double st[CSN];
                         if constexpr (LDSR) {
-                            st[0] = (double)lds_r[i - row0];
+                            T wd, ar[AS];
+                            prb_row_load<T, AS>(lds_a, lds_r, i - row0, wd, ar);
+                            st[0] = (double)wd;
                             st[1] = (LR == 1) ? 0.0 : (lds_s[i - row0] ? 1.0 : -1.0);
 #pragma unroll
-                            for (int t = 0; t < AS; ++t) st[2 + t] = (double)lds_a[(i - row0) * AS + t];
+                            for (int t = 0; t < AS; ++t) st[2 + t] = (double)ar[t];
                         } else if constexpr (PK) {
                             const float4 r = rec[(size_t)i];
                             st[0] = (double)r.x;
@@ -666,10 +673,12 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
             for (int u = 0; u < PRB_PF; ++u) {  // all gathers in flight before any use
                 if constexpr (LDSR) {
                     const int il = cur.row[u] - row0;
-                    yh[u] = (double)lds_r[il];
+                    T wd, ar[AS];
+                    prb_row_load<T, AS>(lds_a, lds_r, il, wd, ar);
+                    yh[u] = (double)wd;
                     yt[u] = (LR == 1) ? 0.0 : (lds_s[il] ? 1.0 : -1.0);
 #pragma unroll
-                    for (int t = 0; t < AS; ++t) av[u][t] = (double)lds_a[il * AS + t];
+                    for (int t = 0; t < AS; ++t) av[u][t] = (double)ar[t];
                 } else if constexpr (PK) {
                     const float4 r = rec[(size_t)cur.row[u]];
                     yh[u] = (double)r.x;
@@ -702,10 +711,12 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
                 const double x = (double)eval[e];
                 double a1[AS], y0, y1;
                 if constexpr (LDSR) {
-                    y0 = (double)lds_r[i - row0];
+                    T wd, ar[AS];
+                    prb_row_load<T, AS>(lds_a, lds_r, i - row0, wd, ar);
+                    y0 = (double)wd;
                     y1 = (LR == 1) ? 0.0 : (lds_s[i - row0] ? 1.0 : -1.0);
 #pragma unroll
-                    for (int t = 0; t < AS; ++t) a1[t] = (double)lds_a[(i - row0) * AS + t];
+                    for (int t = 0; t < AS; ++t) a1[t] = (double)ar[t];
                 } else if constexpr (PK) {
                     const float4 r = rec[(size_t)i];
                     y0 = (double)r.x;
@@ -761,11 +772,12 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
                         const double x = (double)eval[e];
                         double a1[Kind<M>::AS], y0, y1;
                         if constexpr (LDSR) {
-                            y0 = (double)lds_r[i - row0];
+                            T wd, ar[Kind<M>::AS];
+                            prb_row_load<T, Kind<M>::AS>(lds_a, lds_r, i - row0, wd, ar);
+                            y0 = (double)wd;
                             y1 = (LR == 1) ? 0.0 : (lds_s[i - row0] ? 1.0 : -1.0);
 #pragma unroll
-                            for (int t = 0; t < Kind<M>::AS; ++t)
-                                a1[t] = (double)lds_a[(i - row0) * Kind<M>::AS + t];
+                            for (int t = 0; t < Kind<M>::AS; ++t) a1[t] = (double)ar[t];
                         } else if constexpr (PK) {
                             const float4 r = rec[(size_t)i];
                             y0 = (double)r.x;
@@ -1020,9 +1032,7 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
                         }
                         const T y0f = (T)(y0n - lam * Db * db);
                         if constexpr (LDSR) {
-#pragma unroll
-                            for (int t = 0; t < AS; ++t) lds_a[(i - row0) * AS + t] = a2[t];
-                            lds_r[i - row0] = y0f;
+                            prb_row_store<T, AS>(lds_a, lds_r, i - row0, y0f, a2);
                         } else if constexpr (PK) {
                             float4 o;
                             o.x = (float)y0f;
@@ -1060,8 +1070,8 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
                             an *= 1.0 + x * (p_old - upd);
                             yn += lam * an;
                             if constexpr (LDSR) {
-                                lds_a[i - row0] = (T)an;
-                                lds_r[i - row0] = (T)yn;
+                                const T a2 = (T)an;
+                                prb_row_store<T, AS>(lds_a, lds_r, (int)i - row0, (T)yn, &a2);
                             } else {
                                 A[i] = (T)an;
                                 yy[2 * i] = (T)yn;
@@ -1069,14 +1079,16 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
                         } else if constexpr (LDSR) {
                             const int il = (int)i - row0;
                             double dprev = x;
+                            T a2[AS];
 #pragma unroll
                             for (int t = 0; t < AS; ++t) {
                                 const double a1 = av[u][t];
                                 const double dcur = x * (a1 - p_old * dprev);
-                                lds_a[il * AS + t] = (T)(a1 - upd * dprev);
+                                a2[t] = (T)(a1 - upd * dprev);
                                 dprev = dcur;
                             }
-                            lds_r[il] = (T)(yh[u] - lam * upd * dlast[u]);
+                            prb_row_store<T, AS>(lds_a, lds_r, il, (T)(yh[u] - lam * upd * dlast[u]),
+                                                 a2);
                         } else if constexpr (PK) {
                             const double d1 = x * (av[u][0] - p_old * x);
                             float4 o;
