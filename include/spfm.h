@@ -253,6 +253,36 @@ int spfm_psgd_epoch_sharded(spfm_handle h, int degree, double alpha, double beta
                             const int32_t* indices_samples, int64_t n_global, int64_t row_lo,
                             int fit_linear, int64_t* it, double* sum_loss);
 
+/* Per-feature AdaGrad steps for every epoch entry of the minibatch unit -- spfm_psgd_epoch and the
+ * spfm_psgd_pairs_* / spfm_psgd_lists_* epochs.  The mode is handle
+ * state: the epoch entries keep their signatures, and their learning_rate / power_t give the BASE
+ * rates eta_P, eta_w of a minibatch.  State: A_P (n_orders, d), one f64 accumulator per order and
+ * column shared by the column's k components, and A_w (d).  With gbar the minibatch's summed
+ * gradient over its B items, per column j of order o
+ *   A_P[o,j] += sum_s gbar[o,j,s]^2              (accumulated first)
+ *   e         = eta_P / sqrt(initial_accumulator + A_P[o,j])
+ *   p[o,j,:]  = (p[o,j,:] - e gbar[o,j,:]) / (1 + e beta), then the l1 / l21 prox of the column
+ *               with strength gamma e / (1 + e beta)
+ * and, with fit_linear, w[j] likewise with A_w[j], eta_w and alpha.  Every column is shrunk and
+ * proxed every minibatch as before; a column that never saw a gradient keeps the rate
+ * eta / sqrt(initial_accumulator), the plain rule's for the default 1.0.  `it` advances as before.
+ *   mode                 0 off (the plain rules) | 1 per-feature AdaGrad
+ *   initial_accumulator  G0 > 0, finite
+ *   acc_P, acc_w         n_orders*d and d values >= 0 to start from (a warm start); NULL: zeros
+ * The call always (re)sets both accumulators; they survive spfm_set_params and epochs and are
+ * cleared by this call or spfm_destroy alone.  SPFM_ERR_INVALID: a mode other than 0 / 1,
+ * initial_accumulator <= 0 or not finite, a negative or non-finite accumulator value, a handle
+ * without parameters.  In mode 1 every epoch entry returns SPFM_ERR_INVALID before anything is
+ * launched (the parameters stay as they were) when the handle is configured with squaredl12 /
+ * squaredl21 -- their prox couples columns that now carry different steps, which the support
+ * search of the plain rule does not solve --, when it has a communicator (several ranks), or when
+ * the parameters' n_orders / d changed since this call. */
+int spfm_psgd_set_adaptive(spfm_handle h, int mode, double initial_accumulator,
+                           const double* acc_P, const double* acc_w);
+/* The accumulators as they stand (either pointer may be NULL).  SPFM_ERR_INVALID before the first
+ * spfm_psgd_set_adaptive. */
+int spfm_psgd_get_adaptive(spfm_handle h, double* acc_P, double* acc_w);
+
 /* Pairwise ranking fit: one pass of minibatch psgd over triples.  The
  * handle's data is the stacked matrix [X; Z] (contexts, then candidates; the targets are not
  * read).  Row k of `triples` (m, 3) is (anchor, plus, minus), three row indices into that matrix:

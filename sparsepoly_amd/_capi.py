@@ -95,6 +95,7 @@ SYMBOLS = [
     "spfm_psgd_pairs_epoch_weighted", "spfm_psgd_pairs_set_proposal",
     "spfm_psgd_pairs_set_positive_weights", "spfm_psgd_pairs_sample_warp",
     "spfm_psgd_lists_epoch", "spfm_psgd_lists_epoch_sampled", "spfm_psgd_lists_eval",
+    "spfm_psgd_set_adaptive", "spfm_psgd_get_adaptive",
     "spfm_host_epoch_begin",
     "spfm_host_pass_begin", "spfm_host_step_sums", "spfm_host_step_apply", "spfm_host_epoch_end", "spfm_comm_unique_id", "spfm_comm_init", "spfm_comm_init_shm", "spfm_peer_alloc", "spfm_peer_connect",
     "spfm_profile_enable", "spfm_profile_get", "spfm_profile_reset", "spfm_set_use_graph",
@@ -216,6 +217,8 @@ def load():
                                                 C.c_int64, C.c_int, _ip, C.c_int, _lp, _dp]
     L.spfm_psgd_lists_eval.argtypes = [_h, C.c_int, C.c_int, _ip, C.c_int64, C.c_int64, C.c_int,
                                        _dp, _lp]
+    L.spfm_psgd_set_adaptive.argtypes = [_h, C.c_int, C.c_double, _dp, _dp]
+    L.spfm_psgd_get_adaptive.argtypes = [_h, _dp, _dp]
     L.spfm_host_epoch_begin.argtypes = [_h, C.c_int, C.c_int]
     L.spfm_host_pass_begin.argtypes = [_h, C.c_int]
     L.spfm_host_step_sums.argtypes = [_h, C.c_int, _dp]

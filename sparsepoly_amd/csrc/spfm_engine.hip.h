@@ -1037,6 +1037,18 @@ struct spfm_engine {
     template <int L, typename GradFn>
     int psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_, int64_t n_items,
                         const PsgdStep& st);
+    // per-feature AdaGrad steps: handle state.  A_P (n_orders, d) and
+    // A_w (d), sized at the setter (acc_orders, acc_d) and cleared by it alone; every epoch entry
+    // of the unit takes the mode, G0 and the reason it cannot run through its PsgdStep
+    DevBuf sg_accP, sg_accw;
+    int psgd_adaptive = 0;
+    double psgd_g0 = 1.0;
+    int acc_orders = 0;
+    int32_t acc_d = 0;
+    PsgdStep psgd_step(int degree, double alpha, double beta, double gamma, double eta0, int lr,
+                       double power_t, int64_t batch_size, int fit_linear, int64_t* it) const;
+    int psgd_set_adaptive(int mode, double g0, const double* acc_P, const double* acc_w);
+    int psgd_get_adaptive(double* acc_P, double* acc_w);
 
     // pairwise ranking fit: triples (anchor, plus, minus) of rows of the
     // handle's data [X; Z]; buffers of their own (sg_samples and pred_tmp are sized by n)

@@ -57,6 +57,63 @@ int spfm_engine::psgd_ready(const char* what, int degree) {
     return SPFM_OK;
 }
 
+// ================================================== per-feature AdaGrad steps
+// the step of an epoch entry with the handle's adaptive state beside the entry's arguments
+PsgdStep spfm_engine::psgd_step(int degree, double alpha, double beta, double gamma, double eta0,
+                                int lr, double power_t, int64_t batch_size, int fit_linear,
+                                int64_t* it) const {
+    PsgdStep st{degree, alpha, beta, gamma, eta0, lr, power_t, batch_size, fit_linear, it};
+    st.adaptive = psgd_adaptive;
+    st.g0 = psgd_g0;
+    if (psgd_adaptive)
+        st.adaptive_err = psgd_adaptive_error(
+            reg == SPFM_REG_SQUAREDL12 || reg == SPFM_REG_SQUAREDL21, dist(),
+            acc_orders == n_orders && acc_d == d);
+    return st;
+}
+
+// NULL: the accumulator starts from zero.  A moved buffer changes the recorded kernel arguments.
+int spfm_engine::psgd_set_adaptive(int mode, double g0, const double* acc_P, const double* acc_w) {
+    if (mode != 0 && mode != 1)
+        FAIL(SPFM_ERR_INVALID, "set_adaptive: mode must be 0 (off) or 1 (per-feature AdaGrad)");
+    if (!(g0 > 0.0) || !std::isfinite(g0))
+        FAIL(SPFM_ERR_INVALID, "set_adaptive: initial_accumulator must be positive and finite");
+    if (!have_params) FAIL(SPFM_ERR_INVALID, "set_adaptive: set the parameters first");
+    const size_t nP = (size_t)n_orders * d, nw = (size_t)d;
+    for (size_t i = 0; acc_P && i < nP; ++i)
+        if (!(acc_P[i] >= 0.0) || !std::isfinite(acc_P[i]))
+            FAIL(SPFM_ERR_INVALID, "set_adaptive: acc_P holds a negative or non-finite value");
+    for (size_t i = 0; acc_w && i < nw; ++i)
+        if (!(acc_w[i] >= 0.0) || !std::isfinite(acc_w[i]))
+            FAIL(SPFM_ERR_INVALID, "set_adaptive: acc_w holds a negative or non-finite value");
+    const void *o1 = sg_accP.p, *o2 = sg_accw.p;
+    HIPC(sg_accP.alloc(sizeof(double) * nP));
+    HIPC(sg_accw.alloc(sizeof(double) * nw));
+    if (sg_accP.p != o1 || sg_accw.p != o2) clear_graphs();
+    if (acc_P)
+        SPFM_TRY(upload_to(sg_accP.p, acc_P, nP));
+    else
+        HIPC(hipMemsetAsync(sg_accP.p, 0, sizeof(double) * nP, stream));
+    if (acc_w)
+        SPFM_TRY(upload_to(sg_accw.p, acc_w, nw));
+    else
+        HIPC(hipMemsetAsync(sg_accw.p, 0, sizeof(double) * nw, stream));
+    HIPC(hipStreamSynchronize(stream));  // the caller may reuse its arrays
+    acc_orders = n_orders;
+    acc_d = d;
+    psgd_adaptive = mode;
+    psgd_g0 = g0;
+    return SPFM_OK;
+}
+
+int spfm_engine::psgd_get_adaptive(double* acc_P, double* acc_w) {
+    if (acc_d == 0) FAIL(SPFM_ERR_INVALID, "get_adaptive: spfm_psgd_set_adaptive was not called");
+    if (acc_P) SPFM_TRY(download(acc_P, sg_accP.p, (size_t)acc_orders * acc_d));
+    if (acc_w) SPFM_TRY(download(acc_w, sg_accw.p, (size_t)acc_d));
+    HIPC(hipStreamSynchronize(stream));
+    return SPFM_OK;
+}
+
 // first stage of a count: out[block] = number of set flags in the block's contiguous slice
 static __global__ __launch_bounds__(kBlock) void pair_count_partial_kernel(
     const int* __restrict__ v, int64_t n, double* __restrict__ out) {
@@ -122,12 +179,19 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
     int* h_done = reinterpret_cast<int*>(h_scalar + 4);
     // what follows a gradient, for both routes below: with a table (graph replay) the kernels
     // read the minibatch's scalars from sched[idx[1]] and the ones passed here are placeholders
-    auto update = [&](double cp, double denp, double strength, double cw, double denw,
-                      const PsgdBatch* sched, int* idx) {
-        hipLaunchKernelGGL((psgd_update_kernel<L>), dim3(nb_dense), dim3(kBlock), 0, stream,
-                           Pt.as<double>(), sg_gradP.as<double>(), w.as<double>(),
-                           sg_gradw.as<double>(), n_orders, k, d, reg, cp, denp, strength,
-                           st.fit_linear, cw, denw, sg_norms.as<double>(), ms, sched, idx);
+    // (adaptive steps: the kernel of DESIGN.md section 19d takes the update's place on both routes)
+    auto update = [&](const PsgdBatch& b, const PsgdBatch* sched, int* idx) {
+        if (st.adaptive)
+            hipLaunchKernelGGL((psgd_update_adaptive_kernel<L>), dim3(nb_dense), dim3(kBlock), 0,
+                               stream, Pt.as<double>(), sg_gradP.as<double>(), w.as<double>(),
+                               sg_gradw.as<double>(), sg_accP.as<double>(), sg_accw.as<double>(),
+                               n_orders, k, d, reg, st.fit_linear, b, sched, idx);
+        else
+            hipLaunchKernelGGL((psgd_update_kernel<L>), dim3(nb_dense), dim3(kBlock), 0, stream,
+                               Pt.as<double>(), sg_gradP.as<double>(), w.as<double>(),
+                               sg_gradw.as<double>(), n_orders, k, d, reg, b.cp, b.denp,
+                               b.strength, st.fit_linear, b.cw, b.denw, sg_norms.as<double>(), ms,
+                               sched, idx);
     };
     auto mich_finish = [&](double strength, const PsgdBatch* sched, const int* idx) {
         hipLaunchKernelGGL(psgd_mich_finish_kernel, dim3(nb_fin), dim3(kBlock), 0, stream, ms,
@@ -180,9 +244,12 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
         const int gridg = cdiv(std::min<int64_t>(st.batch_size, n_items), gpb);
         const PsgdBatch* sched = sg_sched.as<PsgdBatch>();
         int* idx = sg_idx.as<int>();
+        PsgdBatch none{};  // placeholders: the kernels read sched[idx[1]]
+        none.B = 1;
+        none.denp = none.denw = 1.0;
         auto pair = [&]() {
             grad((int64_t)0, 0, gridg, true);
-            update(0.0, 1.0, 0.0, 0.0, 1.0, sched, idx);
+            update(none, sched, idx);
             if (!mich) return;
             mich_finish(0.0, sched, idx);
             mich_sweeps(kMichSweeps, 0.0, sched, idx);
@@ -192,7 +259,8 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
         };
         const std::string key = fkey(tag, {}, {st.degree, loss, reg, st.fit_linear, gridg, L,
                                                   tsize_, (int64_t)mich,
-                                                  (int64_t)psgd_graph_sweeps});
+                                                  (int64_t)psgd_graph_sweeps,
+                                                  (int64_t)st.adaptive});
         int64_t done_b = 0;
         for (; done_b + kPsgdRun <= nbat; done_b += kPsgdRun) {
             int rc = run_cached(key, [&]() {
@@ -244,7 +312,7 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
         }
         const PsgdBatch b = st.batch(*st.it, B);
         prof_begin(1, 0);
-        update(b.cp, b.denp, b.strength, b.cw, b.denw, nullptr, nullptr);
+        update(b, nullptr, nullptr);
         prof_end(1);
         if (mich) {
             prof_begin(2, 0);
@@ -819,8 +887,8 @@ int spfm_psgd_epoch(spfm_handle h, int degree, double alpha, double beta, double
         h->err = "psgd: several ranks share this handle's communicator -- use spfm_psgd_epoch_sharded";
         return SPFM_ERR_INVALID;
     }
-    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
-                      fit_linear, it};
+    const PsgdStep st = h->psgd_step(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                                      batch_size, fit_linear, it);
     return h->psgd_epoch(st, indices_samples, n_samples, 0, sum_loss);
 }
 
@@ -829,9 +897,20 @@ int spfm_psgd_epoch_sharded(spfm_handle h, int degree, double alpha, double beta
                             const int32_t* indices_samples, int64_t n_global, int64_t row_lo,
                             int fit_linear, int64_t* it, double* sum_loss) {
     SPFM_GUARD(h);
-    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
-                      fit_linear, it};
+    const PsgdStep st = h->psgd_step(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                                      batch_size, fit_linear, it);
     return h->psgd_epoch(st, indices_samples, n_global, row_lo, sum_loss);
+}
+
+int spfm_psgd_set_adaptive(spfm_handle h, int mode, double initial_accumulator,
+                           const double* acc_P, const double* acc_w) {
+    SPFM_GUARD(h);
+    return h->psgd_set_adaptive(mode, initial_accumulator, acc_P, acc_w);
+}
+
+int spfm_psgd_get_adaptive(spfm_handle h, double* acc_P, double* acc_w) {
+    SPFM_GUARD(h);
+    return h->psgd_get_adaptive(acc_P, acc_w);
 }
 
 int spfm_psgd_pairs_set_sampler(spfm_handle h, int64_t n_ctx, int64_t n_cand,
@@ -876,8 +955,8 @@ int spfm_psgd_pairs_epoch_weighted(spfm_handle h, int degree, double alpha, doub
                                    const double* weights, int64_t m, int fit_linear, int64_t* it,
                                    double* sum_loss) {
     SPFM_GUARD(h);
-    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
-                      fit_linear, it};
+    const PsgdStep st = h->psgd_step(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                                      batch_size, fit_linear, it);
     return h->psgd_pairs_epoch_weighted(st, triples, weights, m, sum_loss);
 }
 
@@ -886,8 +965,8 @@ int spfm_psgd_pairs_epoch_sampled(spfm_handle h, int degree, double alpha, doubl
                                   int64_t batch_size, int fit_linear, int64_t* it,
                                   double* sum_loss) {
     SPFM_GUARD(h);
-    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
-                      fit_linear, it};
+    const PsgdStep st = h->psgd_step(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                                      batch_size, fit_linear, it);
     return h->psgd_pairs_epoch_sampled(st, sum_loss);
 }
 
@@ -896,8 +975,8 @@ int spfm_psgd_pairs_epoch(spfm_handle h, int degree, double alpha, double beta, 
                           const int32_t* triples, int64_t m, int fit_linear, int64_t* it,
                           double* sum_loss) {
     SPFM_GUARD(h);
-    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
-                      fit_linear, it};
+    const PsgdStep st = h->psgd_step(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                                      batch_size, fit_linear, it);
     return h->psgd_pairs_epoch(st, triples, m, sum_loss);
 }
 
@@ -912,8 +991,8 @@ int spfm_psgd_lists_epoch(spfm_handle h, int degree, double alpha, double beta, 
                           const int32_t* triples, int64_t m, int64_t n_negatives, int list_loss,
                           int fit_linear, int64_t* it, double* sum_loss) {
     SPFM_GUARD(h);
-    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
-                      fit_linear, it};
+    const PsgdStep st = h->psgd_step(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                                      batch_size, fit_linear, it);
     return h->psgd_lists_epoch(st, triples, m, n_negatives, list_loss, sum_loss);
 }
 
@@ -923,8 +1002,8 @@ int spfm_psgd_lists_epoch_sampled(spfm_handle h, int degree, double alpha, doubl
                                   const int32_t* list_order, int fit_linear, int64_t* it,
                                   double* sum_loss) {
     SPFM_GUARD(h);
-    const PsgdStep st{degree, alpha, beta, gamma, eta0, learning_rate, power_t, batch_size,
-                      fit_linear, it};
+    const PsgdStep st = h->psgd_step(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                                      batch_size, fit_linear, it);
     return h->psgd_lists_epoch_sampled(st, n_negatives, list_loss, list_order, sum_loss);
 }
 

@@ -7,6 +7,8 @@
 //                       hardware f64 atomics into grad_P (n_orders, d, k) / grad_w (d)
 //   psgd_update_kernel  one dense HBM pass over P: SGD step, shrink, grad reset and -- for
 //                       l1 / l21 -- the prox, fused (psgd.py:94-122)
+//   psgd_update_adaptive_kernel  the same pass with per-feature AdaGrad steps (l1 / l21 only;
+//                       spfm_psgd_set_adaptive)
 // and, for squaredl12 / squaredl21, whose prox needs the support of a whole vector
 // (regularizer/utils.py:27-70), a few psgd_mich_* passes: the reference's randomised
 // pivot search is replaced by the monotone fixed-point iteration
@@ -381,6 +383,86 @@ __global__ __launch_bounds__(kBlock) void psgd_update_kernel(
                 double* dst = ms.part + ((size_t)o * ms.NB + blockIdx.x) * 2;
                 dst[0] = sa;
                 dst[1] = sc;
+            }
+        }
+    }
+}
+
+// psgd_update_kernel with per-feature AdaGrad steps: column j of order o
+// steps with e = eta_P / sqrt(G0 + A_P[o, j]), A_P[o, j] the running sum over the minibatches of
+// the squared norm of the column's MEAN gradient (this minibatch's included), and w[j] likewise
+// with A_w[j].  The step is one scalar inside every group l1 and l21 prox over, so both stay
+// closed-form with strength gamma * e / (1 + e * beta).  Same decomposition as above; per column
+// one f64 load and one f64 store more.  l1, l21 or no penalty only (the engine refuses the rest).
+// `b`: the minibatch's scalars; table-driven, sched[idx[1]] replaces it.
+template <int L>
+__global__ __launch_bounds__(kBlock) void psgd_update_adaptive_kernel(
+    double* __restrict__ Pt, double* __restrict__ grad_P, double* __restrict__ w,
+    double* __restrict__ grad_w, double* __restrict__ acc_P, double* __restrict__ acc_w,
+    int n_orders, int k, int d, int reg, int fit_linear, PsgdBatch b,
+    const PsgdBatch* __restrict__ sched, int* __restrict__ idx) {
+    constexpr int gpb = kBlock / L;
+    if (sched) {  // table-driven (graph replay): batch idx[1], then hand idx[0] on
+        const int bi = idx[1];
+        b = sched[bi];
+        if (blockIdx.x == 0 && threadIdx.x == 0) idx[0] = bi + 1;
+    }
+    const int grp = threadIdx.x / L, ln = threadIdx.x % L;
+    const int C = (k + L - 1) / L;
+    const double rB = 1.0 / (double)b.B;  // (f64 divisions are what this pass computes: one per
+                                          // thread here, two per column below)
+    if (fit_linear) {
+        for (int j = blockIdx.x * kBlock + threadIdx.x; j < d; j += gridDim.x * kBlock) {
+            const double g = grad_w[j] * rB;
+            grad_w[j] = 0.0;
+            const double a = acc_w[j] + g * g;
+            acc_w[j] = a;
+            const double e = b.eta_w / sqrt(b.g0 + a);
+            w[j] = (w[j] - e * g) / (1.0 + e * b.alpha);
+        }
+    }
+    for (int o = 0; o < n_orders; ++o) {
+        for (int j = blockIdx.x * gpb + grp; j < d; j += gridDim.x * gpb) {
+            const size_t base = ((size_t)o * d + j) * k;
+            double p[kPsgdMaxC], g[kPsgdMaxC];
+            double q = 0.0;
+#pragma unroll
+            for (int c = 0; c < kPsgdMaxC; ++c) {
+                const int s = c * L + ln;
+                p[c] = 0.0;
+                g[c] = 0.0;
+                if (c < C && s < k) {
+                    g[c] = grad_P[base + s] * rB;
+                    grad_P[base + s] = 0.0;
+                    p[c] = Pt[base + s];
+                    q += g[c] * g[c];
+                }
+            }
+            const double a = acc_P[(size_t)o * d + j] + group_sum(q, L);
+            if (ln == 0) acc_P[(size_t)o * d + j] = a;
+            const double e = b.eta_P / sqrt(b.g0 + a);
+            const double rden = 1.0 / (1.0 + e * b.beta);
+            const double strength = b.gamma * e * rden;
+            q = 0.0;
+#pragma unroll
+            for (int c = 0; c < kPsgdMaxC; ++c) {
+                p[c] = (p[c] - e * g[c]) * rden;
+                q += fabs(p[c]) * fabs(p[c]);
+            }
+            if (reg == REG_L1) {
+#pragma unroll
+                for (int c = 0; c < kPsgdMaxC; ++c) p[c] = soft_thr(p[c], strength);
+            } else if (reg == REG_L21) {  // l21.py:43-48
+                double nr = sqrt(group_sum(q, L));
+                if (nr <= strength) nr = INFINITY;
+                const double f = 1.0 - strength / nr;
+#pragma unroll
+                for (int c = 0; c < kPsgdMaxC; ++c) p[c] *= f;
+            }
+#pragma unroll
+            for (int c = 0; c < kPsgdMaxC; ++c) {
+                const int s = c * L + ln;
+                if (c < C && s < k) Pt[base + s] = p[c];
             }
         }
     }

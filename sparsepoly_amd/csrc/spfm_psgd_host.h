@@ -22,6 +22,10 @@ struct PsgdBatch {
     int B;          // rows in the batch
     int pad;
     double cp, denp, strength, cw, denw;  // eta_P/B, 1+eta_P*beta, prox strength, eta_w/B, 1+eta_w*alpha
+    // adaptive steps only (zero otherwise): what psgd_update_adaptive_kernel forms a column's
+    // step from -- the base rates of this minibatch, the penalties as given, the accumulators'
+    // offset G0.  They travel in the table so that a replayed graph never holds a stale one.
+    double eta_P, eta_w, alpha, beta, gamma, g0;
 };
 
 // psgd.py:9-22
@@ -44,6 +48,19 @@ inline void psgd_eta(int lr, double eta0, double alpha, double beta, double powe
     }
 }
 
+// Per-feature AdaGrad steps (spfm_psgd_set_adaptive): why a handle in
+// adaptive mode cannot run an epoch, in the order the checks are made; nullptr: it can.
+inline const char* psgd_adaptive_error(bool squared_norm, bool ranks, bool acc_fit) {
+    if (squared_norm)
+        return "adaptive steps cannot be combined with squaredl12 / squaredl21: their prox "
+               "couples columns that now carry different steps";
+    if (ranks) return "adaptive steps are not supported with several ranks";
+    if (!acc_fit)
+        return "the adaptive accumulators do not fit the parameters: call "
+               "spfm_psgd_set_adaptive again";
+    return nullptr;
+}
+
 // What an epoch entry passes down to the minibatches: filled once in the extern "C" entry.
 struct PsgdStep {
     int degree;
@@ -53,6 +70,10 @@ struct PsgdStep {
     int64_t batch_size;
     int fit_linear;
     int64_t* it;
+    // the handle's adaptive mode (0: off), its G0, and psgd_adaptive_error() of its state
+    int adaptive = 0;
+    double g0 = 0.0;
+    const char* adaptive_err = nullptr;
 
     // the step-argument checks in `what`'s words; empty: none failed
     std::string check(const char* what) const {
@@ -60,6 +81,7 @@ struct PsgdStep {
                         : batch_size < 1   ? "batch_size must be >= 1"
                         : lr < 0 || lr > 3 ? "learning_rate is not supported."
                         : *it < 1          ? "it must be >= 1"
+                        : adaptive         ? adaptive_err
                                            : nullptr;
         return e ? std::string(what) + ": " + e : std::string();
     }
@@ -76,6 +98,12 @@ struct PsgdStep {
         e.strength = gamma * eta_P / (1 + eta_P * beta);
         e.cw = eta_w / (double)B;
         e.denw = 1 + eta_w * alpha;
+        e.eta_P = adaptive ? eta_P : 0.0;
+        e.eta_w = adaptive ? eta_w : 0.0;
+        e.alpha = adaptive ? alpha : 0.0;
+        e.beta = adaptive ? beta : 0.0;
+        e.gamma = adaptive ? gamma : 0.0;
+        e.g0 = adaptive ? g0 : 0.0;
         return e;
     }
 };

@@ -1191,6 +1191,33 @@ class HipEngine(object):
             int(bool(fit_linear)), C.byref(itc), C.byref(sl)))
         return sl.value, itc.value
 
+    def psgd_set_adaptive(self, mode, initial_accumulator=1.0, acc_P=None, acc_w=None):
+        """Per-feature AdaGrad steps for every psgd / pairs / lists epoch of this handle
+        (``spfm_psgd_set_adaptive``).  ``mode``: 0 off, 1 (or
+        ``'adagrad'``) on; ``acc_P`` (n_orders, d) / ``acc_w`` (d): accumulators to start from,
+        ``None``: zeros.  The epoch calls' ``learning_rate`` then gives the base rate."""
+        mode = 1 if mode == "adagrad" else int(mode)
+        Pp = wp = None
+        if acc_P is not None:
+            Pa, Pp = _capi.f64(acc_P)
+            if Pa.size != self.n_orders * self.d:
+                raise ValueError("acc_P must hold n_orders * d values")
+        if acc_w is not None:
+            wa, wp = _capi.f64(acc_w)
+            if wa.size != self.d:
+                raise ValueError("acc_w must hold d values")
+        self._check(self._lib.spfm_psgd_set_adaptive(self._h, mode, float(initial_accumulator),
+                                                     Pp, wp))
+
+    def psgd_get_adaptive(self):
+        """``(A_P (n_orders, d), A_w (d,))``: the accumulators of the adaptive steps as they
+        stand (``spfm_psgd_get_adaptive``)."""
+        aP = np.empty((self.n_orders, self.d))
+        aw = np.empty(self.d)
+        self._check(self._lib.spfm_psgd_get_adaptive(
+            self._h, aP.ctypes.data_as(_capi._dp), aw.ctypes.data_as(_capi._dp)))
+        return aP, aw
+
     @staticmethod
     def _triples(triples):
         t = np.ascontiguousarray(triples, dtype=np.int32)

@@ -221,6 +221,10 @@ class FoldInMixin(object):
         at = int(real[-1]) + 1 if d else 0
         self.P_ = np.ascontiguousarray(np.insert(self.P_, [at] * n_new, 0.0, axis=2))
         self.w_ = np.ascontiguousarray(np.insert(self.w_, [at] * n_new, 0.0))
+        if hasattr(self, "adagrad_P_"):  # learning_rate='adagrad': new features start from zero
+            self.adagrad_P_ = np.ascontiguousarray(
+                np.insert(self.adagrad_P_, [at] * n_new, 0.0, axis=1))
+            self.adagrad_w_ = np.ascontiguousarray(np.insert(self.adagrad_w_, [at] * n_new, 0.0))
         new_real, _ = _columns(self, d + n_new)
         assert (new_real[d:] == at + np.arange(n_new)).all()
         return np.arange(d, d + n_new)

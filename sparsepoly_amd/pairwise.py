@@ -548,35 +548,90 @@ def _prox(regularizer, Po, c):
     raise ValueError("regularizer %r cannot be used with a pairwise fit" % (regularizer,))
 
 
+def _adaptive_step(P, w, gP, gw, B, eta_P, eta_w, alpha, beta, gamma, regularizer, fit_linear,
+                   G0, acc):
+    """one minibatch of the per-feature AdaGrad rule from the summed
+    gradients; ``acc = (A_P (n_orders, d), A_w (d,))`` is updated in place.  -> (P, w)"""
+    if regularizer not in ("l1", "l21"):
+        raise ValueError("adaptive steps cannot be combined with regularizer %r: its prox couples "
+                         "features that carry different steps" % (regularizer,))
+    dtype = P.dtype.type
+    A_P, A_w = acc
+    if fit_linear:
+        gb = gw / B
+        A_w += gb ** 2
+        ew = eta_w / np.sqrt(dtype(G0) + A_w)
+        w = (w - ew * gb) / (1 + ew * alpha)
+    gb = gP / B
+    A_P += (gb ** 2).sum(axis=1)
+    e = (eta_P / np.sqrt(dtype(G0) + A_P))[:, None, :]  # one step per (order, feature)
+    P = (P - e * gb) / (1 + e * beta)
+    c = gamma * e / (1 + e * beta)
+    if regularizer == "l1":
+        return _soft(P, c), w
+    nr = np.sqrt((np.abs(P) ** 2).sum(axis=1, keepdims=True))
+    nr = np.where(nr <= c, np.inf, nr)
+    return P * (1 - c / nr), w
+
+
+def _adaptive_state(adaptive, acc, P, dtype):
+    """(G0 or None, (A_P, A_w) copies in ``dtype``) of the restatements' ``adaptive`` / ``acc``"""
+    if adaptive is None:
+        return None, acc
+    if adaptive is True or adaptive == "adagrad":
+        G0 = 1.0
+    else:
+        G0 = float(adaptive)
+    if not (G0 > 0 and np.isfinite(G0)):
+        raise ValueError("adaptive: the initial accumulator must be positive and finite")
+    if acc is None:
+        return G0, (np.zeros((P.shape[0], P.shape[2]), dtype=dtype),
+                    np.zeros(P.shape[2], dtype=dtype))
+    return G0, (np.array(acc[0], dtype=dtype), np.array(acc[1], dtype=dtype))
+
+
 def restate_pairwise_epoch(P, w, lams, X, Z, triples, degree, loss="logistic", regularizer="l1",
                            alpha=1.0, beta=1.0, gamma=1.0, eta0=1.0, learning_rate="optimal",
                            power_t=1.0, batch_size=1, fit_linear=True, it=1, wide=False,
-                           weights=None):
+                           weights=None, adaptive=None, acc=None):
     """Test aid, NumPy only: one epoch of the pairwise fit over ``triples`` (context / candidate
     numbering, visited in the order given) from ``P`` (n_orders, k, d) and ``w``.  Minibatch
     ``bi`` covers the triples ``[bi * batch_size, ...)``, the last one may be shorter; per batch
     the gradient sums, the step ``eta / B`` with ``psgd_eta`` at ``it``, the shrink and the prox of
     the minibatch solver.  ``weights`` (m,): one per triple, visited with it; the step stays
     ``eta / B`` with ``B`` the triple count and ``sum_loss`` is the sum of weight times loss.
-    Returns ``(P, w, sum_loss, it)`` (new arrays)."""
+    Returns ``(P, w, sum_loss, it)`` (new arrays).
+
+    ``adaptive``: ``None`` is the above; ``True`` / ``'adagrad'`` (G0 = 1)
+    or a positive G0 steps every feature with ``eta / sqrt(G0 + A)`` -- ``learning_rate`` gives
+    the base rate ``eta``, ``acc = (A_P (n_orders, d), A_w (d,))`` the accumulators to start from
+    (``None``: zeros) -- and the return value is ``(P, w, sum_loss, it, (A_P, A_w))``."""
     dtype = np.longdouble if wide else np.double
     P, w, lams = _as(dtype, P, w, lams)
     P = (P[None] if P.ndim == 2 else P).copy()
     w = w.copy()
     t = np.asarray(triples, dtype=np.int64)
     sum_loss = dtype(0)
+    G0, acc = _adaptive_state(adaptive, acc, P, dtype)
     for pos in range(0, t.shape[0], int(batch_size)):
         tb = t[pos:pos + int(batch_size)]
         wb = None if weights is None else np.asarray(weights)[pos:pos + int(batch_size)]
         val, gP, gw = restate_pair_gradient(P, w, lams, X, Z, tb, degree, loss, wide, wb)
         sum_loss += val.sum()
         eta_P, eta_w = _psgd_eta(learning_rate, eta0, alpha, beta, power_t, it)
+        if G0 is not None:
+            P, w = _adaptive_step(P, w, gP, gw, tb.shape[0], eta_P, eta_w, alpha, beta, gamma,
+                                  regularizer, fit_linear, G0, acc)
+            it += 1
+            continue
         if fit_linear:
             w = (w - gw * (eta_w / tb.shape[0])) / (1 + eta_w * alpha)
         P = (P - gP * (eta_P / tb.shape[0])) / (1 + eta_P * beta)
         strength = gamma * eta_P / (1 + eta_P * beta)
         P = np.stack([_prox(regularizer, P[o], dtype(strength)) for o in range(P.shape[0])])
         it += 1
+    if G0 is not None:
+        return P, w, sum_loss, it, acc
     return P, w, sum_loss, it
 
 
@@ -689,11 +744,12 @@ def restate_list_gradient(P, w, lams, X, Z, triples, n_negatives, degree, object
 def restate_list_epoch(P, w, lams, X, Z, triples, n_negatives, degree, objective="softmax",
                        loss="logistic", regularizer="l1", alpha=1.0, beta=1.0, gamma=1.0,
                        eta0=1.0, learning_rate="optimal", power_t=1.0, batch_size=1,
-                       fit_linear=True, it=1, wide=False):
+                       fit_linear=True, it=1, wide=False, adaptive=None, acc=None):
     """Test aid, NumPy only: one epoch of the list fit over the grouped ``triples`` (lists
     visited in the order given).  ``restate_pairwise_epoch`` with lists as items: minibatch ``bi``
     covers the lists ``[bi * batch_size, ...)``, the step is ``eta / B`` with ``B`` lists.
-    Returns ``(P, w, sum_loss over the lists, it)`` (new arrays)."""
+    Returns ``(P, w, sum_loss over the lists, it)`` (new arrays); with ``adaptive`` / ``acc`` as in
+    ``restate_pairwise_epoch``, ``(P, w, sum_loss, it, (A_P, A_w))``."""
     dtype = np.longdouble if wide else np.double
     P, w, lams = _as(dtype, P, w, lams)
     P = (P[None] if P.ndim == 2 else P).copy()
@@ -701,6 +757,7 @@ def restate_list_epoch(P, w, lams, X, Z, triples, n_negatives, degree, objective
     M = int(n_negatives)
     t = np.asarray(triples, dtype=np.int64)
     sum_loss = dtype(0)
+    G0, acc = _adaptive_state(adaptive, acc, P, dtype)
     for pos in range(0, t.shape[0] // M, int(batch_size)):
         tb = t[pos * M:(pos + int(batch_size)) * M]
         B = tb.shape[0] // M
@@ -708,12 +765,19 @@ def restate_list_epoch(P, w, lams, X, Z, triples, n_negatives, degree, objective
                                             wide)
         sum_loss += val.sum()
         eta_P, eta_w = _psgd_eta(learning_rate, eta0, alpha, beta, power_t, it)
+        if G0 is not None:
+            P, w = _adaptive_step(P, w, gP, gw, B, eta_P, eta_w, alpha, beta, gamma, regularizer,
+                                  fit_linear, G0, acc)
+            it += 1
+            continue
         if fit_linear:
             w = (w - gw * (eta_w / B)) / (1 + eta_w * alpha)
         P = (P - gP * (eta_P / B)) / (1 + eta_P * beta)
         strength = gamma * eta_P / (1 + eta_P * beta)
         P = np.stack([_prox(regularizer, P[o], dtype(strength)) for o in range(P.shape[0])])
         it += 1
+    if G0 is not None:
+        return P, w, sum_loss, it, acc
     return P, w, sum_loss, it
 
 
@@ -792,7 +856,8 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
         if self.distributed:
             raise ValueError("the pairwise fit runs on one GPU (distributed=False).")
         self._get_loss(self.loss)
-        if self.learning_rate not in _capi.LEARNING_RATE:
+        self._check_adagrad(self.regularizer, False)
+        if self._base_rate() not in _capi.LEARNING_RATE:
             raise ValueError("learning_rate %s is not supported. Choose from %s."
                              % (self.learning_rate, _capi.LEARNING_RATE))
         if self.degree > MAX_DEGREE:
@@ -949,6 +1014,7 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
             self.w_ = np.ascontiguousarray(self.w_, dtype=np.double)
             engine.set_params(self.P_, self.w_, self.lams_)
             engine.configure("psgd", self.loss, self.regularizer, self.degree)
+            self._adagrad_begin(engine, self.P_.shape)
             if sampler == "host" and sample_weight is not None:
                 lists = epoch_triples(rng, self.max_iter, interactions, triples, n_negatives,
                                       resample, self.shuffle, exclude, weights=sample_weight)
@@ -1011,7 +1077,7 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
         no_improvement_count = 0
         best_loss = np.inf
         epoch = 0
-        step = (self.degree, self.alpha, self.beta, self.gamma, self.eta0, self.learning_rate,
+        step = (self.degree, self.alpha, self.beta, self.gamma, self.eta0, self._base_rate(),
                 self.power_t, batch_size)
         for epoch, t in enumerate(lists):
             if objective != "pairwise" and isinstance(t, np.ndarray):
@@ -1033,13 +1099,13 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                 stacked = t + np.array([0, B, B], dtype=np.int32)  # rows of [X; Z]
                 sum_loss, self.it_ = engine.psgd_pairs_epoch(
                     self.degree, self.alpha, self.beta, self.gamma, self.eta0,
-                    self.learning_rate, self.power_t, batch_size, stacked, self.fit_linear,
+                    self._base_rate(), self.power_t, batch_size, stacked, self.fit_linear,
                     self.it_)
             else:
                 m = t
                 sum_loss, self.it_ = engine.psgd_pairs_epoch_sampled(
                     self.degree, self.alpha, self.beta, self.gamma, self.eta0,
-                    self.learning_rate, self.power_t, batch_size, self.fit_linear, self.it_)
+                    self._base_rate(), self.power_t, batch_size, self.fit_linear, self.it_)
             if (self.callback is not None) and epoch % self.n_calls == 0:
                 if callback_needs_params(self.callback):
                     self._sync_params(engine)  # P_ and w_ as they stand after this epoch
@@ -1060,6 +1126,7 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                 converged = True
                 break
         self._sync_params(engine)
+        self._adagrad_end(engine)
         return converged, epoch
 
     def sample_negatives(self, X, Z, interactions, n_negatives=1, n_candidates=8, exclude=None,

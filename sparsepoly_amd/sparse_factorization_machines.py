@@ -166,7 +166,58 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
         self.device = device
         self.distributed = distributed
 
+    # ``learning_rate='adagrad'`` (solver='psgd' and the ranker): G0 of the
+    # per-feature steps.  A plain class attribute, not a constructor keyword: ``get_params()`` and
+    # the signatures stay the reference's.
+    adagrad_init = 1.0
+
     # ------------------------------------------------------------------ helpers
+    def _adagrad(self):
+        return self.solver == "psgd" and self.learning_rate == "adagrad"
+
+    def _base_rate(self):
+        """the rule the epoch entries tabulate: 'adagrad' scales the constant rate per feature"""
+        return "constant" if self._adagrad() else self.learning_rate
+
+    def _check_adagrad(self, reg_obj, plugin):
+        """what ``learning_rate='adagrad'`` cannot be combined with, before any device work"""
+        if not self._adagrad():
+            return
+        from . import regularizer as _r
+
+        if plugin:
+            raise ValueError("learning_rate='adagrad' needs one of the built-in regularizers "
+                             "'l1', 'l21' (the per-feature prox runs on the device).")
+        if isinstance(reg_obj, (_r.SquaredL12, _r.SquaredL21)) or \
+                reg_obj in ("squaredl12", "squaredl21"):
+            raise ValueError("learning_rate='adagrad' cannot be combined with the squaredl12 / "
+                             "squaredl21 regularizers: their prox couples features that now "
+                             "carry different steps; choose 'l1' or 'l21'.")
+        if self.distributed:
+            raise ValueError("learning_rate='adagrad' runs on one GPU (distributed=False).")
+
+    def _adagrad_begin(self, engine, shape):
+        """after set_params: switch the handle's mode; ``warm_start`` uploads the accumulators of
+        the previous fit again, like ``it_``"""
+        if not self._adagrad():
+            if getattr(engine, "_adaptive", False):  # a kept session of an earlier adagrad fit
+                engine.psgd_set_adaptive(0)
+                engine._adaptive = False
+            return
+        aP = aw = None
+        if self.warm_start and hasattr(self, "adagrad_P_") and hasattr(self, "adagrad_w_"):
+            aP = np.ascontiguousarray(self.adagrad_P_, dtype=np.double)
+            aw = np.ascontiguousarray(self.adagrad_w_, dtype=np.double)
+            if aP.shape != (shape[0], shape[2]) or aw.shape != (shape[2],):
+                raise ValueError("warm_start: adagrad_P_ / adagrad_w_ do not fit this data and "
+                                 "configuration")
+        engine.psgd_set_adaptive(1, self.adagrad_init, aP, aw)
+        engine._adaptive = True
+
+    def _adagrad_end(self, engine):
+        if self._adagrad():
+            self.adagrad_P_, self.adagrad_w_ = engine.psgd_get_adaptive()
+
     def _augment(self, X):
         """sparse_factorization_machines.py:86-92"""
         if self.fit_lower == "augment":
@@ -351,7 +402,7 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
             batch_size = int(n_samples * n_features / nnz)
         else:
             batch_size = self.batch_size
-        if self.learning_rate not in LEARNING_RATE:
+        if self._base_rate() not in LEARNING_RATE:
             msg = f"learning_rate {self.learning_rate} is not supported."
             msg += f" Choose from {LEARNING_RATE}."
             raise ValueError(msg)
@@ -362,7 +413,7 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
             # (distributed: the global order on every rank; each forms the gradient of its own
             # rows of a minibatch, the sums are all-reduced -- spfm_psgd_epoch_sharded)
             sum_loss, self.it_ = engine.psgd_epoch(
-                self.degree, self.alpha, self.beta, self.gamma, self.eta0, self.learning_rate,
+                self.degree, self.alpha, self.beta, self.gamma, self.eta0, self._base_rate(),
                 self.power_t, batch_size, indices_samples, self.fit_linear, self.it_,
                 row_lo=self._row_lo if self.distributed else None)
             if (self.callback is not None) and epoch % self.n_calls == 0:
@@ -385,6 +436,7 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
                 converged = True
                 break
         self._sync_params(engine)
+        self._adagrad_end(engine)
         return converged, epoch
 
     # ---------------------------------------------------------------------- fit
@@ -406,6 +458,7 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
         # device chains: its epochs are stepped from the host, calling the object's own prox and
         # cache hooks (include/spfm.h "host-stepped epochs")
         self._plugin_reg = None if self._is_builtin_regularizer(reg_obj) else reg_obj
+        self._check_adagrad(reg_obj, self._plugin_reg is not None)
         # deviation: the reference takes any degree; the device kernels stop at SPFM_MAX_DEGREE.
         # Raised before w_ / P_ exist, so a refused fit leaves the estimator unfitted.
         if self.degree > MAX_DEGREE:
@@ -514,6 +567,7 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
             self._upload_validation(engine)
             self._live = (engine, n_samples)
             if self.solver == "psgd":
+                self._adagrad_begin(engine, self.P_.shape)
                 # X.count_nonzero() (dataset.py:32,84): stored entries, n*d when dense
                 nnz = X.nnz if sp.issparse(X) else n_samples * n_features
                 converged, self.n_iter_ = self._fit_psgd(engine, n_samples, n_features,

@@ -72,6 +72,9 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"),
                     help="directory of pairwise_<build tag>.json")
     ap.add_argument("--profile-only", action="store_true")
+    ap.add_argument("--learning-rate", default="optimal",
+                    help="step rule of both routes; 'adagrad': per-feature AdaGrad steps on the "
+                         "constant rate (DESIGN.md section 19d)")
     a = ap.parse_args()
 
     B, C, m, k = a.contexts, a.candidates, a.triples, a.k
@@ -87,7 +90,8 @@ def main():
     build_s = time.perf_counter() - t0
 
     P0 = 0.01 * np.random.RandomState(a.seed + 3).randn(1, k, d)
-    hyper = (2, 1e-3, 1e-3, 1e-4, 0.05, "optimal", 1.0)
+    adagrad = a.learning_rate == "adagrad"
+    hyper = (2, 1e-3, 1e-3, 1e-4, 0.05, "constant" if adagrad else a.learning_rate, 1.0)
     pair = HipEngine(0, "f32")
     S1 = sp.vstack([X, Z], format="csr")
     S1.sort_indices()
@@ -100,6 +104,9 @@ def main():
     point.set_params(P0, np.zeros(d), np.ones(k))
     point.configure("psgd", "logistic", "l1", 2)
     idx = np.arange(2 * m, dtype=np.int32)
+    if adagrad:
+        pair.psgd_set_adaptive(1)
+        point.psgd_set_adaptive(1)
 
     state = {"pair": 1, "point": 1}
 
@@ -130,6 +137,7 @@ def main():
     med = {r: float(np.median(v)) for r, v in times.items()}
     out = dict(
         tool="bench_pairwise", build_tag=tag, device=pair.device_name,
+        learning_rate=a.learning_rate,
         contexts=B, candidates=C, features=d, k=k, triples=m, batch_size=a.batch,
         updates_per_epoch=-(-m // a.batch), warmup=a.warmup, runs=a.runs,
         context_entries_mean=round(X.nnz / B, 2), candidate_entries_mean=round(Z.nnz / C, 2),
@@ -145,7 +153,7 @@ def main():
         timing="host clock around an epoch call that ends in a device synchronise; both routes "
                "include the upload of their visiting order (12 m / 8 m bytes)")
     os.makedirs(a.out, exist_ok=True)
-    path = os.path.join(a.out, "pairwise_%s.json" % tag)
+    path = os.path.join(a.out, "pairwise_%s%s.json" % ("adagrad_" if adagrad else "", tag))
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
