@@ -103,6 +103,28 @@ int spfm_set_data_csr(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr
  * spfm_set_data_* on either handle detaches that handle only. */
 int spfm_share_data(spfm_handle dst, spfm_handle src, const double* y);
 
+/* -- row weights ---------------------------------------
+ * weights[n] for the rows of the handle's training data; NULL clears.  n must equal the data's.
+ * Every loss term becomes w_i * loss(yhat_i, y_i): the column sums of pcd / pbcd / cd_linear
+ * are g = sum_i (w_i dloss_i) dA_ij and h = sum_i (w_i dA_ij) dA_ij (cd_linear: the weighted
+ * column norm sum_i w_i x_ij^2, formed here, once), psgd's row gradient and row loss are scaled
+ * by w_i while the minibatch gradient is still divided by the number of rows of the minibatch,
+ * and spfm_loss_sum returns sum_i w_i loss_i.  Integer weights are row replication (up to
+ * summation order); a zero-weight row keeps its prediction maintained and enters no sum.
+ * Weights belong to the handle, like the targets: co-tenants of one image (spfm_share_data) carry
+ * their own, and spfm_set_data_* / spfm_share_data on the handle clear them.  While weights are
+ * set the epochs run on the multi-kernel engine and the psgd kernels -- the persistent passes
+ * are not used ("persistent_active" reads 0) -- and an installed schedule stays valid.  Memory:
+ * 8 n + 8 d bytes.
+ * SPFM_ERR_INVALID: no data, n differs, a negative or non-finite weight, all weights zero.
+ * SPFM_ERR_UNSUPPORTED: a communicator is attached.  On a weighted handle the triple and list
+ * entries (spfm_psgd_pairs_*, spfm_psgd_lists_*), spfm_psgd_epoch_sharded and the host-stepped
+ * epochs (spfm_host_*) return SPFM_ERR_UNSUPPORTED; spfm_eval_loss, spfm_foldin_csr and the
+ * bank entries do not read the weights. */
+int spfm_set_sample_weight(spfm_handle h, const double* weights, int64_t n);
+/* set_out: 0/1; sum_out: sum of the weights (n when none are set).  Either may be NULL. */
+int spfm_get_sample_weight(spfm_handle h, int* set_out, double* sum_out);
+
 /* -- parameters -------------------------------------------------------------
  * P is (n_orders, k, d) row-major as self.P_ (sparse_factorization_machines.py
  * :383-389), w (d), lams (k, each +-1: :403-404).  d must equal the data's
@@ -128,7 +150,8 @@ int spfm_configure(spfm_handle h, int solver, int loss, int regularizer, int top
  * + the order-2 term on P[1] if add_lower_deg2 (fit_lower='explicit', degree 3). */
 int spfm_init_pred(spfm_handle h, int degree, int fit_linear, int add_lower_deg2);
 int spfm_get_y_pred(spfm_handle h, double* out);
-/* sum_i loss(y_pred_i, y_i) (loss.py:20-21,34-42,61-65) of the local shard */
+/* sum_i loss(y_pred_i, y_i) (loss.py:20-21,34-42,61-65) of the local shard; with sample weights
+ * set, sum_i w_i loss(y_pred_i, y_i) */
 int spfm_loss_sum(spfm_handle h, double* out);
 
 /* Same computation on a caller-supplied CSR matrix (predict(),

@@ -36,7 +36,7 @@ def visible_devices():
 
 
 def fit_concurrently(estimators, X, y, max_concurrent=None, devices=None, share_data=True, *,
-                     targets=None):
+                     targets=None, sample_weights=None):
     """Fit every estimator of ``estimators`` on ``(X, y)``, up to ``max_concurrent`` at a time
     PER DEVICE (default: four, two when all of them use ``solver='pbcd'``).  ``X`` / ``y`` may be
     one data set for all of them or sequences with one entry per estimator (cross-validation
@@ -51,7 +51,10 @@ def fit_concurrently(estimators, X, y, max_concurrent=None, devices=None, share_
     streams (``share_data``; ``spfm_share_data``), and the first fit to reach the colouring
     computes it for everybody.  ``targets`` (keyword only): one target per estimator over the ONE
     ``X`` -- the per-class targets of a one-vs-rest fit, say; ``y`` is not used then, and the image
-    and the schedule are shared as for one ``y``.  Returns the list of fitted estimators (the same
+    and the schedule are shared as for one ``y``.  ``sample_weights`` (keyword only): one
+    ``sample_weight`` vector (or ``None``) per estimator over the ONE ``X`` -- weights belong to a
+    fit's own handle like its targets, so K cross-validation folds are K 0/1 masks over one image
+    and one colouring; compatible with ``targets``.  Returns the list of fitted estimators (the same
     objects); the first exception raised by a fit is re-raised after all fits have ended."""
     ests = list(estimators)
     if not ests:
@@ -69,6 +72,13 @@ def fit_concurrently(estimators, X, y, max_concurrent=None, devices=None, share_
         targets = list(targets)
         if len(targets) != len(ests):
             raise ValueError("targets must hold one entry per estimator.")
+    if sample_weights is not None:
+        if per_fit_data:
+            raise ValueError("sample_weights= gives one weight vector per estimator over a single "
+                             "X.")
+        sample_weights = list(sample_weights)
+        if len(sample_weights) != len(ests):
+            raise ValueError("sample_weights must hold one entry per estimator.")
     if per_fit_data:
         if not isinstance(y, (list, tuple)) or len(X) != len(ests) or len(y) != len(ests):
             raise ValueError("X and y must hold one entry per estimator.")
@@ -106,10 +116,13 @@ def fit_concurrently(estimators, X, y, max_concurrent=None, devices=None, share_
                         return
                     i, est = todo.pop()
                 try:
+                    kw = {}
+                    if sample_weights is not None and sample_weights[i] is not None:
+                        kw["sample_weight"] = sample_weights[i]
                     if targets is not None:
-                        est.fit(X, targets[i])
+                        est.fit(X, targets[i], **kw)
                     else:
-                        est.fit(X[i] if per_fit_data else X, y[i] if per_fit_data else y)
+                        est.fit(X[i] if per_fit_data else X, y[i] if per_fit_data else y, **kw)
                 except BaseException as exc:  # re-raised by the caller's thread
                     with lock:
                         errors.append(exc)

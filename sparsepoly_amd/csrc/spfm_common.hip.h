@@ -155,6 +155,20 @@ struct Vec2<double> {
     using type = double2;
 };
 
+// Row weights of a weighted fit as a compile-time property of the kernels
+// that form dloss / loss sums: a kernel body takes one of these accessors.  NoRowWeight is what
+// every unweighted instantiation gets -- `on` is false, the body keeps its unweighted expression
+// under `if constexpr`, nothing is loaded.  RowWeight gathers w_i from the handle's f64[n] vector.
+struct NoRowWeight {
+    static constexpr bool on = false;
+    __device__ __forceinline__ double operator()(size_t) const { return 1.0; }
+};
+struct RowWeight {
+    static constexpr bool on = true;
+    const double* __restrict__ w;
+    __device__ __forceinline__ double operator()(size_t i) const { return w[i]; }
+};
+
 // Model kind by template parameter M: M >= 2 = factorization machine of degree M (ANOVA
 // kernel, caches A[i, 1..M-1]); M == 0 = all-subsets model (kernel prod_j (1 + p_j x_j),
 // one cache value A[i] per component; reference optimizer/pcd_all.py, pbcd_all.py,

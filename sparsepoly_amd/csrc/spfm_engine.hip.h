@@ -319,6 +319,22 @@ struct spfm_engine {
     uint64_t sched_hash = 0;  // of (order, batch_ptr): names a schedule in `scache`
     int share_data_from(spfm_engine* src, const double* y);
 
+    // Row weights: per handle like `yy` -- w_i as f64[n] and the weighted
+    // column norms cn_j = sum_i w_i x_ij^2 as f64[d] (col_norm belongs to the shared image).
+    // While set, the epochs run on the multi-kernel engine and the psgd kernels (the *_usable
+    // predicates below); new data clears them (data_installed).
+    DevBuf wrow, wcn;
+    bool weighted = false;
+    double wsum = 0.0;
+    int set_sample_weight(const double* weights, int64_t n_);
+    void clear_sample_weight();
+    int refuse_weighted(const char* what) {
+        if (weighted)
+            FAIL(SPFM_ERR_UNSUPPORTED, std::string(what) + ": not on a handle with sample weights "
+                                                           "(spfm_set_sample_weight)");
+        return SPFM_OK;
+    }
+
     // params
     int n_orders = 0, k = 0;
     bool have_params = false;
@@ -854,7 +870,7 @@ struct spfm_engine {
     // (several ranks: the persistent passes need the peer-mapped exchange slabs)
     bool prb_usable() const {
         return persistent && !pers_failed && (!dist() || peer_ready) && max_batch_cols <= 64 &&
-               nnz < ((int64_t)1 << 31) && n > 0;
+               nnz < ((int64_t)1 << 31) && n > 0 && !weighted;
     }
 
     bool resident_ok(const void* fn, int threads, size_t lds, int G);
@@ -881,7 +897,7 @@ struct spfm_engine {
     // worth trying: the persistent 64-column pass is in use and the strict steps are narrow
     bool relax_candidate() const {
         return relax_on && prb_usable() && !dist() && n_batches() > 0 &&
-               (double)d / (double)n_batches() < 12.0;
+               (double)d / (double)n_batches() < 12.0 && !weighted;
     }
     template <typename T>
     int ensure_relax();
@@ -902,7 +918,8 @@ struct spfm_engine {
     // ------------------------------------------------------ wide persistent passes
     bool wide_usable() const {
         return persistent && !pers_failed && wide_on && (!dist() || peer_ready) &&
-               max_batch_cols > 64 && max_batch_cols <= 512 && nnz < ((int64_t)1 << 31) && n > 0;
+               max_batch_cols > 64 && max_batch_cols <= 512 && nnz < ((int64_t)1 << 31) && n > 0 &&
+               !weighted;
     }
 
     int wide_groups(int ncu, size_t lds_max) const;
@@ -946,7 +963,7 @@ struct spfm_engine {
     bool pbprb_usable(int M) const {
         return persistent && !pers_failed && pb_persistent && (!dist() || peer_ready) &&
                max_batch_cols <= 64 && nnz < ((int64_t)1 << 31) && n > 0 && k <= 62 &&
-               pbprb_degree_ok(M);
+               pbprb_degree_ok(M) && !weighted;
     }
 
     const char* validate_pb_stream(int G, int NG, const std::vector<int32_t>& gsp,

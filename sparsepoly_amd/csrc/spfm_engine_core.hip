@@ -240,6 +240,7 @@ int spfm_engine::data_installed(const double* y) {
     }
     have_data = true;
     configured = false;
+    clear_sample_weight();  // they named rows of the old data
     have_sampler = false;  // the positives and the drawn triples named rows of the old data
     sampled = false;
     col_norm_reduced = false;
@@ -401,6 +402,50 @@ int spfm_engine::share_data_from(spfm_engine* src, const double* y_) {
         scache = src->scache;
     }
     return data_installed(y_);
+}
+
+// ========================================================== row weights
+//   The captured graphs of the multi-kernel passes hold kernel arguments and
+// the choice of kernel: setting or clearing weights drops them.  An installed schedule stays (a
+// valid batch partition is valid on any engine), and so do the entry streams.
+void spfm_engine::clear_sample_weight() {
+    if (weighted) invalidate(kInvGraphs);
+    weighted = false;
+    wsum = 0.0;
+    wrow.release();
+    wcn.release();
+}
+
+int spfm_engine::set_sample_weight(const double* weights, int64_t n_) {
+    if (!weights) {
+        clear_sample_weight();
+        return SPFM_OK;
+    }
+    if (!have_data) FAIL(SPFM_ERR_INVALID, "set_sample_weight: set the data first");
+    if (dist())
+        FAIL(SPFM_ERR_UNSUPPORTED, "set_sample_weight: not with a communicator attached");
+    if (n_ != n) FAIL(SPFM_ERR_INVALID, "set_sample_weight: n differs from the data's rows");
+    double sum = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!(weights[i] >= 0.0) || !std::isfinite(weights[i]))
+            FAIL(SPFM_ERR_INVALID, "set_sample_weight: weight " + std::to_string(i) +
+                                       " is negative or not finite");
+        sum += weights[i];
+    }
+    if (!(sum > 0.0)) FAIL(SPFM_ERR_INVALID, "set_sample_weight: all weights are zero");
+    if (!std::isfinite(sum)) FAIL(SPFM_ERR_INVALID, "set_sample_weight: the weights' sum is not finite");
+    invalidate(kInvGraphs);
+    SPFM_TRY(upload(wrow, weights, (size_t)n));
+    HIPC(wcn.alloc(sizeof(double) * (size_t)d));
+    SPFM_DISPATCH(dtype, hipLaunchKernelGGL((col_norm_w_kernel<T>),
+                                            dim3(cdiv((int64_t)d * 64, kBlock)), dim3(kBlock), 0,
+                                            stream, d, cptr.as<int64_t>(), cidx.as<int32_t>(),
+                                            cval.as<T>(), wrow.as<double>(), wcn.as<double>()));
+    HIPC(hipGetLastError());
+    SPFM_TRY(sync());  // the caller may reuse its array
+    weighted = true;
+    wsum = sum;
+    return SPFM_OK;
 }
 
 // ================================================================= params
@@ -804,8 +849,13 @@ int spfm_engine::get_y_pred_t(double* out) {
 template <typename T>
 int spfm_engine::loss_sum_t(double* out) {
     const int nb = 512;
-    hipLaunchKernelGGL((loss_partial_kernel<T>), dim3(nb), dim3(kBlock), 0, stream, n,
-                       yy.as<typename Vec2<T>::type>(), loss, partial.as<double>());
+    if (weighted)
+        hipLaunchKernelGGL((loss_partial_w_kernel<T>), dim3(nb), dim3(kBlock), 0, stream, n,
+                           yy.as<typename Vec2<T>::type>(), loss, wrow.as<double>(),
+                           partial.as<double>());
+    else
+        hipLaunchKernelGGL((loss_partial_kernel<T>), dim3(nb), dim3(kBlock), 0, stream, n,
+                           yy.as<typename Vec2<T>::type>(), loss, partial.as<double>());
     hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(kBlock), 0, stream,
                        partial.as<double>(), nb, scalar.as<double>());
     HIPC(hipGetLastError());
@@ -842,6 +892,8 @@ int spfm_engine::epoch_prologue() {
     if (!have_data || !have_params || !configured)
         FAIL(SPFM_ERR_INVALID, "epoch: data, parameters and configuration are required");
     if (!have_schedule) FAIL(SPFM_ERR_INVALID, "epoch: call spfm_set_schedule first");
+    if (weighted && dist())
+        FAIL(SPFM_ERR_UNSUPPORTED, "epoch: sample weights with a communicator attached");
     int rc = ensure_col_norm();
     if (rc) return rc;
     HIPC(hipMemsetAsync(viol_col.p, 0, sizeof(double) * (size_t)d, stream));
@@ -1053,6 +1105,18 @@ int spfm_set_data_csr(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr
 int spfm_share_data(spfm_handle dst, spfm_handle src, const double* y) {
     SPFM_GUARD(dst);
     return dst->share_data_from(src, y);
+}
+
+int spfm_set_sample_weight(spfm_handle h, const double* weights, int64_t n) {
+    SPFM_GUARD(h);
+    return h->set_sample_weight(weights, n);
+}
+
+int spfm_get_sample_weight(spfm_handle h, int* set_out, double* sum_out) {
+    if (!h) return SPFM_ERR_INVALID;
+    if (set_out) *set_out = h->weighted ? 1 : 0;
+    if (sum_out) *sum_out = h->weighted ? h->wsum : (double)h->n;
+    return SPFM_OK;
 }
 
 int spfm_set_params(spfm_handle h, int n_orders, int k, int32_t d, const double* P,

@@ -31,9 +31,16 @@ int spfm_engine::pbcd_body_lc(int order_idx, double beta, double gamma, double e
         const ColDesc* desc = d_desc.as<ColDesc>() + c0;
         const int64_t bn = prof_on ? batch_nnz(b) : 0;
         prof_begin(2, bn);
-        hipLaunchKernelGGL((pbcd_grad_kernel<T, M, L, C>), dim3(nc * kPbW), dim3(kBlock), shm,
-                           stream, desc, cidx.as<int32_t>(), cval.as<T>(), A.as<T>(),
-                           yy.as<typename Vec2<T>::type>(), Po, k, loss, part.as<double>());
+        if (weighted)
+            hipLaunchKernelGGL((pbcd_grad_kernel<T, M, L, C, RowWeight>), dim3(nc * kPbW),
+                               dim3(kBlock), shm, stream, desc, cidx.as<int32_t>(), cval.as<T>(),
+                               A.as<T>(), yy.as<typename Vec2<T>::type>(), Po, k, loss,
+                               part.as<double>(), RowWeight{wrow.as<double>()});
+        else
+            hipLaunchKernelGGL((pbcd_grad_kernel<T, M, L, C>), dim3(nc * kPbW), dim3(kBlock),
+                               shm, stream, desc, cidx.as<int32_t>(), cval.as<T>(), A.as<T>(),
+                               yy.as<typename Vec2<T>::type>(), Po, k, loss, part.as<double>(),
+                               NoRowWeight{});
         prof_end(2);
         int rc = allreduce(part.as<double>(), (size_t)nc * kPbW * (k + 1));
         if (rc) return rc;
@@ -223,7 +230,8 @@ int spfm_engine::host_sums_pbcd(int b, double* out) {
     const size_t shm = sizeof(double) * ((size_t)(kBlock / L) * k + 16);
     hipLaunchKernelGGL((pbcd_grad_kernel<T, M, L, C>), dim3(nc * kPbW), dim3(kBlock), shm, stream,
                        d_desc.as<ColDesc>() + c0, cidx.as<int32_t>(), cval.as<T>(), A.as<T>(),
-                       yy.as<typename Vec2<T>::type>(), Po, k, loss, part.as<double>());
+                       yy.as<typename Vec2<T>::type>(), Po, k, loss, part.as<double>(),
+                       NoRowWeight{});
     HIPC(hipGetLastError());
     const size_t np = (size_t)nc * kPbW * (k + 1);
     int rc = allreduce(part.as<double>(), np);

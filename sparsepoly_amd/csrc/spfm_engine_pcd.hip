@@ -16,11 +16,16 @@ int spfm_engine::lin_body(double alpha) {
         if (nc == 0) continue;
         const int32_t* cols = d_order.as<int32_t>() + c0;
         prof_begin(4, prof_on ? batch_nnz(b) : 0);
-        if (!dist()) {
+        if (weighted) {  // (never with a communicator: epoch_prologue)
+            hipLaunchKernelGGL((lin_fused_kernel<T, RowWeight>), dim3(nc), dim3(kBlock), 0,
+                               stream, d_desc.as<ColDesc>() + c0, cidx.as<int32_t>(),
+                               cval.as<T>(), yy.as<T>(), loss, w.as<double>(), wcn.as<double>(),
+                               alpha, mu, viol_col.as<double>(), RowWeight{wrow.as<double>()});
+        } else if (!dist()) {
             hipLaunchKernelGGL((lin_fused_kernel<T>), dim3(nc), dim3(kBlock), 0, stream,
                                d_desc.as<ColDesc>() + c0, cidx.as<int32_t>(), cval.as<T>(),
                                yy.as<T>(), loss, w.as<double>(), col_norm.as<double>(), alpha,
-                               mu, viol_col.as<double>());
+                               mu, viol_col.as<double>(), NoRowWeight{});
         } else {
             hipLaunchKernelGGL((lin_grad_kernel<T>), dim3(nc), dim3(kBlock), 0, stream, cols,
                                cptr.as<int64_t>(), cidx.as<int32_t>(), cval.as<T>(),
@@ -97,10 +102,17 @@ int spfm_engine::pcd_pass_body(int order_idx, double beta, double gamma, double 
         const ColDesc* desc = d_desc.as<ColDesc>() + c0;
         const int64_t bn = prof_on ? batch_nnz(b) : 0;
         prof_begin(0, bn);
-        hipLaunchKernelGGL((pcd_grad_kernel<T, M>), dim3(nc), dim3(kBlock), 0, stream, c, desc,
-                           cidx.as<int32_t>(), cval.as<T>(), A.as<T>(), a_stride,
-                           yy.as<typename Vec2<T>::type>(), Po, d, loss, part.as<double>(),
-                           pold.as<double>());
+        if (weighted)
+            hipLaunchKernelGGL((pcd_grad_kernel<T, M, RowWeight>), dim3(nc), dim3(kBlock), 0,
+                               stream, c, desc, cidx.as<int32_t>(), cval.as<T>(), A.as<T>(),
+                               a_stride, yy.as<typename Vec2<T>::type>(), Po, d, loss,
+                               part.as<double>(), pold.as<double>(),
+                               RowWeight{wrow.as<double>()});
+        else
+            hipLaunchKernelGGL((pcd_grad_kernel<T, M>), dim3(nc), dim3(kBlock), 0, stream, c,
+                               desc, cidx.as<int32_t>(), cval.as<T>(), A.as<T>(), a_stride,
+                               yy.as<typename Vec2<T>::type>(), Po, d, loss, part.as<double>(),
+                               pold.as<double>(), NoRowWeight{});
         prof_end(0);
         int rc = allreduce(part.as<double>(), (size_t)2 * nc);
         if (rc) return rc;
@@ -288,6 +300,7 @@ int spfm_engine::pcd_epoch(int order_idx, int degree, double beta, double gamma,
 }
 
 int spfm_engine::host_epoch_begin(int order_idx, int degree) {
+    SPFM_TRY(refuse_weighted("host-stepped epochs"));
     int rc = epoch_prologue();
     if (rc) return rc;
     if (solver != SPFM_SOLVER_PCD && solver != SPFM_SOLVER_PBCD)
@@ -335,7 +348,7 @@ int spfm_engine::host_sums_pcd(int b, double* out) {
     hipLaunchKernelGGL((pcd_grad_kernel<T, M>), dim3(nc), dim3(kBlock), 0, stream, ctl.as<Ctl>(),
                        d_desc.as<ColDesc>() + c0, cidx.as<int32_t>(), cval.as<T>(), A.as<T>(),
                        (size_t)n * Kind<M>::AS, yy.as<typename Vec2<T>::type>(), Po, d, loss,
-                       part.as<double>(), pold.as<double>());
+                       part.as<double>(), pold.as<double>(), NoRowWeight{});
     HIPC(hipGetLastError());
     int rc = allreduce(part.as<double>(), (size_t)2 * nc);
     if (rc) return rc;

@@ -54,7 +54,7 @@ int spfm_engine::psgd_ready(const char* what, int degree) {
         FAIL(SPFM_ERR_INVALID, w + "data, parameters and configuration are required");
     if (solver != SPFM_SOLVER_PSGD) FAIL(SPFM_ERR_INVALID, w + "engine is not configured for psgd");
     if (degree != top_degree) FAIL(SPFM_ERR_INVALID, w + "degree differs from configure()");
-    return SPFM_OK;
+    return refuse_weighted(what);  // the triple and list kernels know no row weights
 }
 
 // ================================================== per-feature AdaGrad steps
@@ -341,6 +341,18 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
 template <typename T, int L>
 int spfm_engine::psgd_epoch_tl(const PsgdStep& st) {
     auto grad = [&](int64_t pos, int B, int grid, bool table) {
+        if (weighted) {
+            hipLaunchKernelGGL((psgd_grad_kernel<T, L, RowWeight>), dim3(grid), dim3(kBlock), 0,
+                               stream, sg_samples.as<int32_t>() + pos, B, rptr.as<int64_t>(),
+                               ridx.as<int32_t>(), rval.as<T>(), yy.as<T>(), Pt.as<double>(),
+                               w.as<double>(), lams.as<double>(), n_orders, k, d, st.degree,
+                               loss, st.fit_linear, sg_gradP.as<double>(),
+                               sg_gradw.as<double>(), pred_tmp.as<double>() + pos,
+                               table ? sg_sched.as<PsgdBatch>() : (const PsgdBatch*)nullptr,
+                               table ? sg_idx.as<int>() : (int*)nullptr,
+                               RowWeight{wrow.as<double>()});
+            return;
+        }
         hipLaunchKernelGGL((psgd_grad_kernel<T, L>), dim3(grid), dim3(kBlock), 0, stream,
                            sg_samples.as<int32_t>() + pos, B, rptr.as<int64_t>(),
                            ridx.as<int32_t>(), rval.as<T>(), yy.as<T>(), Pt.as<double>(),
@@ -348,9 +360,10 @@ int spfm_engine::psgd_epoch_tl(const PsgdStep& st) {
                            st.fit_linear, sg_gradP.as<double>(), sg_gradw.as<double>(),
                            pred_tmp.as<double>() + pos,
                            table ? sg_sched.as<PsgdBatch>() : (const PsgdBatch*)nullptr,
-                           table ? sg_idx.as<int>() : (int*)nullptr);
+                           table ? sg_idx.as<int>() : (int*)nullptr, NoRowWeight{});
     };
-    return psgd_batches_tl<L>(grad, "psgd", (int64_t)sizeof(T), n, st);
+    // (the graph tag says which gradient kernel was recorded)
+    return psgd_batches_tl<L>(grad, weighted ? "psgd_w" : "psgd", (int64_t)sizeof(T), n, st);
 }
 
 // optimizer/psgd.py:125-199: one pass over indices_samples
@@ -897,6 +910,7 @@ int spfm_psgd_epoch_sharded(spfm_handle h, int degree, double alpha, double beta
                             const int32_t* indices_samples, int64_t n_global, int64_t row_lo,
                             int fit_linear, int64_t* it, double* sum_loss) {
     SPFM_GUARD(h);
+    SPFM_TRY(h->refuse_weighted("psgd (sharded)"));
     const PsgdStep st = h->psgd_step(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
                                       batch_size, fit_linear, it);
     return h->psgd_epoch(st, indices_samples, n_global, row_lo, sum_loss);

@@ -60,12 +60,14 @@ __global__ __launch_bounds__(kBlock) void lin_sync_kernel(
 // Single-GPU fused form of the two kernels above (no exchange between the gradient
 // and the update): one launch per step, column found through its descriptor, the
 // first two entries per thread stay in registers between the two halves.
-template <typename T>
+// WA (spfm_common.hip.h): NoRowWeight, or RowWeight for a weighted handle -- g = sum_i (w_i *
+// dloss_i) * x_ij, and col_norm_sq is then the handle's weighted norm cn_j = sum_i w_i x_ij^2.
+template <typename T, typename WA = NoRowWeight>
 __global__ __launch_bounds__(kBlock) void lin_fused_kernel(
     const ColDesc* __restrict__ desc, const int32_t* __restrict__ cidx,
     const T* __restrict__ cval, T* __restrict__ yy, int loss, double* __restrict__ w,
     const double* __restrict__ col_norm_sq, double alpha, double mu,
-    double* __restrict__ viol_col) {
+    double* __restrict__ viol_col, WA wt) {
     __shared__ double red[16];
     constexpr int PF = 2;
     const ColDesc cd = desc[blockIdx.x];
@@ -89,11 +91,21 @@ __global__ __launch_bounds__(kBlock) void lin_fused_kernel(
     for (int u = 0; u < PF; ++u) {
         const typename Vec2<T>::type yv = yy2[ri[u]];
         ryh[u] = (double)yv.x;
-        g += rv[u] ? dloss_dev(loss, (double)yv.x, (double)yv.y) * rx[u] : 0.0;
+        if constexpr (WA::on)
+            g += rv[u] ? (wt((size_t)ri[u]) * dloss_dev(loss, (double)yv.x, (double)yv.y)) * rx[u]
+                       : 0.0;
+        else
+            g += rv[u] ? dloss_dev(loss, (double)yv.x, (double)yv.y) * rx[u] : 0.0;
     }
     for (int64_t ii = cd.start + tid + PF * kBlock; ii < cd.start + cd.len; ii += kBlock) {
-        const typename Vec2<T>::type yv = yy2[cidx[ii]];
-        g += dloss_dev(loss, (double)yv.x, (double)yv.y) * (double)cval[ii];
+        if constexpr (WA::on) {
+            const int i = cidx[ii];
+            const typename Vec2<T>::type yv = yy2[i];
+            g += (wt((size_t)i) * dloss_dev(loss, (double)yv.x, (double)yv.y)) * (double)cval[ii];
+        } else {
+            const typename Vec2<T>::type yv = yy2[cidx[ii]];
+            g += dloss_dev(loss, (double)yv.x, (double)yv.y) * (double)cval[ii];
+        }
     }
     block_sum2(g, h, red);
     double upd = g;
@@ -126,6 +138,25 @@ __global__ __launch_bounds__(kBlock) void col_norm_kernel(int d, const int64_t* 
     for (int64_t ii = cptr[wave] + lane; ii < cptr[wave + 1]; ii += kWave) {
         const double x = (double)cval[ii];
         a += x * x;
+    }
+    a = wave_sum(a);
+    if (lane == 0) out[wave] = a;
+}
+
+// the weighted column norm cn_j = sum_i w_i x_ij^2 of a weighted handle,
+// formed once when the weights are set
+template <typename T>
+__global__ __launch_bounds__(kBlock) void col_norm_w_kernel(int d, const int64_t* __restrict__ cptr,
+                                                            const int32_t* __restrict__ cidx,
+                                                            const T* __restrict__ cval,
+                                                            const double* __restrict__ wrow,
+                                                            double* __restrict__ out) {
+    const int wave = (blockIdx.x * kBlock + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+    if (wave >= d) return;
+    double a = 0.0;
+    for (int64_t ii = cptr[wave] + lane; ii < cptr[wave + 1]; ii += kWave) {
+        const double x = (double)cval[ii];
+        a += (wrow[cidx[ii]] * x) * x;
     }
     a = wave_sum(a);
     if (lane == 0) out[wave] = a;

@@ -150,12 +150,14 @@ __device__ __forceinline__ void pb_st(double* p, double v) {
 
 constexpr int kPbW = 32;  // workgroups per column in the gather / scatter kernels
 
-template <typename T, int M, int L, int C>
+// Weighted (WA = RowWeight): grad_s = sum_i (w_i * dloss_i) * dA_ijs and
+// the scalar sum_s sum_i (w_i * dA_ijs) * dA_ijs -- with w == 1 the unweighted sums bit for bit.
+template <typename T, int M, int L, int C, typename WA = NoRowWeight>
 __global__ __launch_bounds__(kBlock) void pbcd_grad_kernel(
     const ColDesc* __restrict__ desc, const int32_t* __restrict__ cidx,
     const T* __restrict__ cval, const T* __restrict__ A,
     const typename Vec2<T>::type* __restrict__ yy, const double* __restrict__ P /* (d,k) */,
-    int k, int loss, double* __restrict__ part /* [ncols][kPbW][k+1] */) {
+    int k, int loss, double* __restrict__ part /* [ncols][kPbW][k+1] */, WA wt) {
     constexpr int G = kBlock / L;  // entry groups per workgroup
     constexpr int U = 4;           // entries per group in flight
     extern __shared__ double shm[];  // G * k + 16
@@ -177,6 +179,7 @@ __global__ __launch_bounds__(kBlock) void pbcd_grad_kernel(
     for (int64_t ii0 = cd.start + (int64_t)w * G + grp; ii0 < e; ii0 += (int64_t)U * G * kPbW) {
         int iu[U];
         double xu[U], dlu[U];
+        double wu[WA::on ? U : 1];  // (weighted instantiation only)
         double au[U][C][AS];
 #pragma unroll
         for (int u = 0; u < U; ++u) {  // all loads of U entries in flight together
@@ -189,7 +192,12 @@ __global__ __launch_bounds__(kBlock) void pbcd_grad_kernel(
         for (int u = 0; u < U; ++u) {
             if (iu[u] >= 0) {
                 const typename Vec2<T>::type yv = yy[iu[u]];
-                dlu[u] = dloss_dev(loss, (double)yv.x, (double)yv.y);
+                if constexpr (WA::on) {
+                    wu[u] = wt((size_t)iu[u]);
+                    dlu[u] = wu[u] * dloss_dev(loss, (double)yv.x, (double)yv.y);
+                } else {
+                    dlu[u] = dloss_dev(loss, (double)yv.x, (double)yv.y);
+                }
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
                     const int s = lane + c * L;
@@ -209,7 +217,8 @@ __global__ __launch_bounds__(kBlock) void pbcd_grad_kernel(
                     if (s < k) {
                         const double dprev = grad_factor<M>(au[u][c], xu[u], p[c]);
                         grad[c] += dlu[u] * dprev;
-                        hs += dprev * dprev;
+                        if constexpr (WA::on) hs += (wu[u] * dprev) * dprev;
+                        else hs += dprev * dprev;
                     }
                 }
             }

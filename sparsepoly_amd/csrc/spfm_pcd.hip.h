@@ -239,12 +239,14 @@ __global__ void pcd_cache_combine_kernel(int reg, int nblk, const double* __rest
 // batch: part[2q] = sum_i dloss(yhat_i, y_i) * dA_i[M-1], part[2q+1] = sum_i
 // dA_i[M-1]^2 with dA from _grad_anova (pcd.py:8-12); pold[q] = P[s, j] (the
 // snapshot every workgroup of the following chain reads).  One workgroup per column.
-template <typename T, int M>
+// Weighted (WA = RowWeight): g = sum_i (w_i * dloss_i) * dA_i and
+// h = sum_i (w_i * dA_i) * dA_i -- with w == 1 the unweighted sums bit for bit.
+template <typename T, int M, typename WA = NoRowWeight>
 __global__ __launch_bounds__(kBlock) void pcd_grad_kernel(
     const Ctl* __restrict__ ctl, const ColDesc* __restrict__ desc,
     const int32_t* __restrict__ cidx, const T* __restrict__ cval, const T* __restrict__ A_all,
     size_t a_stride, const typename Vec2<T>::type* __restrict__ yy, const double* __restrict__ P,
-    int d, int loss, double* __restrict__ part, double* __restrict__ pold) {
+    int d, int loss, double* __restrict__ part, double* __restrict__ pold, WA wt) {
     __shared__ double red[16];
     const int q = blockIdx.x;
     const ColDesc cd = desc[q];
@@ -261,8 +263,14 @@ __global__ __launch_bounds__(kBlock) void pcd_grad_kernel(
 #pragma unroll
         for (int t = 0; t < AS; ++t) a[t] = (double)A[(size_t)i * AS + t];
         const double dprev = grad_factor<M>(a, x, p);
-        g += dloss_dev(loss, (double)yv.x, (double)yv.y) * dprev;
-        h += dprev * dprev;
+        if constexpr (WA::on) {
+            const double wi = wt((size_t)i);
+            g += (wi * dloss_dev(loss, (double)yv.x, (double)yv.y)) * dprev;
+            h += (wi * dprev) * dprev;
+        } else {
+            g += dloss_dev(loss, (double)yv.x, (double)yv.y) * dprev;
+            h += dprev * dprev;
+        }
     }
     block_sum2(g, h, red);
     if (threadIdx.x == 0) {

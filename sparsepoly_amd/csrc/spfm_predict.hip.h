@@ -98,5 +98,21 @@ __global__ __launch_bounds__(kBlock) void loss_partial_kernel(
     if (threadIdx.x == 0) partial[blockIdx.x] = a;
 }
 
+// ... of w_i * loss(yhat_i, y_i): the loss sum of a weighted handle
+template <typename T>
+__global__ __launch_bounds__(kBlock) void loss_partial_w_kernel(
+    int64_t n, const typename Vec2<T>::type* __restrict__ yy, int loss,
+    const double* __restrict__ wrow, double* __restrict__ partial) {
+    __shared__ double red[16];
+    double a = 0.0, b = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * kBlock) {
+        const typename Vec2<T>::type yv = yy[i];
+        a += wrow[i] * loss_dev(loss, (double)yv.x, (double)yv.y);
+    }
+    block_sum2(a, b, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = a;
+}
+
 
 }  // namespace spfm

@@ -135,15 +135,18 @@ __device__ __forceinline__ void psgd_table_batch(const PsgdBatch* __restrict__ s
     pos = sched[bi].pos;
 }
 
-// One L-lane group per row of the minibatch.
-template <typename T, int L>
+// One L-lane group per row of the minibatch.  WA (spfm_common.hip.h): NoRowWeight, or RowWeight
+// for a weighted handle (dL = w_i * dloss, loss_row = w_i * loss; the
+// update kernels still divide by the batch's row count).
+template <typename T, int L, typename WA = NoRowWeight>
 __global__ __launch_bounds__(kBlock) void psgd_grad_kernel(
     const int32_t* __restrict__ samples, int B, const int64_t* __restrict__ rptr,
     const int32_t* __restrict__ ridx, const T* __restrict__ rval, const T* __restrict__ yy,
     const double* __restrict__ Pt, const double* __restrict__ w,
     const double* __restrict__ lams, int n_orders, int k, int d, int degree, int loss,
     int fit_linear, double* __restrict__ grad_P, double* __restrict__ grad_w,
-    double* __restrict__ loss_row, const PsgdBatch* __restrict__ sched, int* __restrict__ idx) {
+    double* __restrict__ loss_row, const PsgdBatch* __restrict__ sched, int* __restrict__ idx,
+    WA wt) {
     constexpr int gpb = kBlock / L;
     const int grp = threadIdx.x / L, ln = threadIdx.x % L;
     const int r = blockIdx.x * gpb + grp;
@@ -188,8 +191,15 @@ __global__ __launch_bounds__(kBlock) void psgd_grad_kernel(
         }
     }
     yp = group_sum(yp, L);
-    const double dL = dloss_dev(loss, yp, yi);
-    if (ln == 0) loss_row[r] = loss_dev(loss, yp, yi);
+    double dL;
+    if constexpr (WA::on) {
+        const double wi = wt((size_t)i);
+        dL = wi * dloss_dev(loss, yp, yi);
+        if (ln == 0) loss_row[r] = wi * loss_dev(loss, yp, yi);
+    } else {
+        dL = dloss_dev(loss, yp, yi);
+        if (ln == 0) loss_row[r] = loss_dev(loss, yp, yi);
+    }
     // _update_grads (psgd.py:60-91)
     if (fit_linear)
         for (int64_t e = lo + ln; e < hi; e += L)

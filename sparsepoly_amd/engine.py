@@ -315,6 +315,27 @@ class HipEngine(object):
         self._check(self._lib.spfm_share_data(self._h, src._h, yp))
         self.n, self.d = src.n, src.d
 
+    def set_sample_weight(self, sample_weight):
+        """One weight per row of this engine's training data (``spfm_set_sample_weight``,
+        DESIGN.md section 20); ``None`` clears.  New data (``set_data`` / ``share_data``) clears
+        them too."""
+        if sample_weight is None:
+            self._check(self._lib.spfm_set_sample_weight(self._h, None, 0))
+            return
+        wa, wp = _capi.f64(sample_weight)
+        self._check(self._lib.spfm_set_sample_weight(self._h, wp, wa.shape[0]))
+
+    def sample_weight_set(self):
+        flag = C.c_int()
+        self._check(self._lib.spfm_get_sample_weight(self._h, C.byref(flag), None))
+        return bool(flag.value)
+
+    def sample_weight_sum(self):
+        """Sum of the weights; the row count when none are set."""
+        out = C.c_double()
+        self._check(self._lib.spfm_get_sample_weight(self._h, None, C.byref(out)))
+        return out.value
+
     def set_params(self, P, w, lams):
         P = np.ascontiguousarray(P, dtype=np.float64)
         if P.ndim != 3:

@@ -83,6 +83,8 @@ class ObjectiveMixin(object):
             cached = getattr(self, "_device_session", None)
             if cached is not None:
                 live = (cached[1], int(cached[0][0][0][0]))
+                if getattr(live[0], "_h", None) is not None and live[0].sample_weight_set():
+                    live = (live[0], live[0].sample_weight_sum())  # mean=True scales by sum(w)
         if live is None or getattr(live[0], "_h", None) is None:
             raise SpfmError(_NO_SESSION % what)
         return live

@@ -30,7 +30,10 @@ class OneVsRestClassifier(ClassifierMixin, BaseEstimator):
     are by default fitted one after the other (still on the one shared image): a pbcd fit that
     shares the CUs with another adds its partial sums in another order than a solo fit, and the
     members are meant to equal solo fits bit for bit; ``max_concurrent=2`` trades that for two
-    fits at a time.  Fitted attributes:
+    fits at a time.  ``class_weight`` (a plain attribute, default ``None``): ``'balanced'`` is
+    handed to the clones, each of which balances its own one-against-the-rest problem (1 : C-1 by
+    construction); a dict label -> weight over the multiclass labels becomes a per-sample vector
+    that multiplies into every clone's ``sample_weight``.  Fitted attributes:
     ``estimators_``, ``classes_``, ``n_features_in_``.  The bank of the fitted clones is built on
     first use and kept; ``release_device()`` drops it (pickling does too)."""
 
@@ -39,9 +42,12 @@ class OneVsRestClassifier(ClassifierMixin, BaseEstimator):
         self.max_concurrent = max_concurrent
         self.devices = devices
 
+    class_weight = None
+
     # ------------------------------------------------------------------ fit
-    def fit(self, X, y):
+    def fit(self, X, y, sample_weight=None):
         from .concurrent import fit_concurrently
+        from .weights import check_sample_weight, class_weight_vector
 
         if not isinstance(self.estimator, (SparseFactorizationMachineClassifier,
                                            SparseAllSubsetsClassifier)):
@@ -60,11 +66,21 @@ class OneVsRestClassifier(ClassifierMixin, BaseEstimator):
             raise ValueError("y holds a single class")
         self.release_device()
         ests = [clone(self.estimator) for _ in range(Y.shape[1])]
+        cw = self.class_weight
+        if cw is None:  # (clone() copies constructor parameters only)
+            cw = getattr(self.estimator, "class_weight", None)
+        sw = None if sample_weight is None else check_sample_weight(sample_weight, n_rows)
+        if isinstance(cw, dict):
+            sw = class_weight_vector(cw, y) * (1.0 if sw is None else sw)
+            cw = None
+        for e in ests:
+            e.class_weight = cw
         max_concurrent = self.max_concurrent
         if max_concurrent is None and self.estimator.solver == "pbcd":
             max_concurrent = 1  # the whole GPU each, as a solo fit has it (see the class docstring)
         fit_concurrently(ests, X, None, max_concurrent=max_concurrent, devices=self.devices,
-                         targets=[Y[:, c] for c in range(Y.shape[1])])
+                         targets=[Y[:, c] for c in range(Y.shape[1])],
+                         sample_weights=None if sw is None else [sw] * len(ests))
         self.estimators_ = ests
         self.classes_ = binarizer.classes_
         self.label_binarizer_ = binarizer

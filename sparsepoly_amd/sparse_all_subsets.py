@@ -28,6 +28,7 @@ from .ranking import RankingMixin
 from .monitor import ObjectiveMixin, callback_needs_params
 from .regularizer import L1, L21, OmegaCS, OmegaTI
 from .schedule import Schedule
+from .weights import combine_weights
 
 
 class _BaseSparseAllSubsets(ObjectiveMixin, InteractionMixin, RankingMixin, BaseSparsePoly, metaclass=ABCMeta):
@@ -71,9 +72,16 @@ class _BaseSparseAllSubsets(ObjectiveMixin, InteractionMixin, RankingMixin, Base
         else:
             self.feature_order_ = engine.set_schedule(self.schedule, indices_feature)
 
-    def fit(self, X, y):
-        """sparse_all_subsets.py:203-258 with _fit_pcd (:80-138) / _fit_pbcd (:140-201)."""
+    def fit(self, X, y, sample_weight=None):
+        """sparse_all_subsets.py:203-258 with _fit_pcd (:80-138) / _fit_pbcd (:140-201).
+
+        ``sample_weight`` (n_samples, >= 0): every loss term becomes ``w_i * loss_i`` (DESIGN.md
+        section 20); a classifier's ``class_weight`` attribute multiplies into it.  ``mean=True``
+        then scales the penalties by ``sum(w)``, kept as ``sample_weight_sum_``."""
+        y_raw = y
         X, y = self._check_X_y(X, y)
+        sample_weight = combine_weights(sample_weight, getattr(self, "class_weight", None),
+                                        y_raw, X.shape[0])
         self._check_validation(X.shape[1])
         n_samples, n_features = X.shape
         rng = check_random_state(self.random_state)
@@ -100,8 +108,9 @@ class _BaseSparseAllSubsets(ObjectiveMixin, InteractionMixin, RankingMixin, Base
                              "object.")
         if isinstance(self.schedule, Schedule) and self.shuffle:
             raise ValueError("a fixed Schedule cannot be combined with shuffle=True.")
-        beta = self.beta * n_samples if self.mean else self.beta
-        gamma = self.gamma * n_samples if self.mean else self.gamma
+        scale = n_samples if sample_weight is None else float(sample_weight.sum())
+        beta = self.beta * scale if self.mean else self.beta
+        gamma = self.gamma * scale if self.mean else self.gamma
 
         self.P_ = np.ascontiguousarray(self.P_, dtype=np.double)
         engine = self._new_engine()
@@ -111,12 +120,14 @@ class _BaseSparseAllSubsets(ObjectiveMixin, InteractionMixin, RankingMixin, Base
             from . import engine as _engine_mod
 
             _engine_mod.shared_set_data(engine, X if csr_direct else canonical_csc(X), y)
+            engine.set_sample_weight(sample_weight)
+            self.sample_weight_sum_ = float(scale)
             engine.set_params(self.P_[None], np.zeros(n_features), self.lams_)
             engine.configure(self.solver, self.loss, self.regularizer, -1)
             engine.init_pred(-1, False, False)  # y_pred = self._get_output(X) (:241)
             # objective_terms() / validation_loss() read this session while the loop runs
             self._upload_validation(engine)
-            self._live = (engine, n_samples)
+            self._live = (engine, scale)
             indices_feature = np.arange(n_features, dtype=np.int32)
             indices_component = np.arange(self.n_components, dtype=np.int32)
             if not self.shuffle:
@@ -227,6 +238,11 @@ class SparseAllSubsetsClassifier(_BaseSparseAllSubsets, SparsePolyClassifierMixi
     Reference: sparse_all_subsets.py:393-519."""
 
     _LOSSES = CLASSIFICATION_LOSSES
+
+    # None, 'balanced' or a dict label -> weight; multiplies into ``fit``'s ``sample_weight``
+    # (sparsepoly_amd/weights.py).  A plain class attribute: ``get_params()`` and the
+    # constructor signature stay the reference's.
+    class_weight = None
 
     def __init__(self, loss="squared_hinge", n_components=2, solver="pcd", beta=1, gamma=1,
                  eta0=0.1, mean=False, regularizer="omegati", tol=1e-6, warm_start=False,

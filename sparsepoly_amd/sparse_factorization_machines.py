@@ -58,6 +58,7 @@ from .ranking import RankingMixin
 from .explain import ExplainMixin
 from .foldin import FoldInMixin
 from .monitor import ObjectiveMixin, callback_needs_params
+from .weights import combine_weights
 
 MAX_DEGREE = 6  # include/spfm.h SPFM_MAX_DEGREE
 
@@ -388,10 +389,12 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
         self._sync_params(engine)
         return converged, it
 
-    def _fit_psgd(self, engine, n_samples, n_features, nnz, rng):
+    def _fit_psgd(self, engine, n_samples, n_features, nnz, rng, loss_scale=None):
         """Restates _fit_psgd, sparse_factorization_machines.py:94-173.  Like pbcd the
         reference trains a transposed copy of P_ (:113) and writes it back after the loop
-        (:172), while w_ is updated in place: callbacks see the initial P_ and the live w_."""
+        (:172), while w_ is updated in place: callbacks see the initial P_ and the live w_.
+        ``loss_scale``: what the epoch's loss sum is divided by for the stopping rule -- the sum
+        of the sample weights of a weighted fit, else ``n_samples``."""
         from ._capi import LEARNING_RATE
 
         indices_samples = np.arange(n_samples, dtype=np.int32)
@@ -421,7 +424,7 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
                     self._sync_params(engine, with_P=False)
                 if self.callback(self) is not None:
                     break
-            sum_loss /= n_samples
+            sum_loss /= n_samples if loss_scale is None else loss_scale
             if self.verbose:
                 print(f"Epoch {epoch+1} loss {sum_loss}")
             if sum_loss > (best_loss - self.tol):
@@ -440,14 +443,23 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
         return converged, epoch
 
     # ---------------------------------------------------------------------- fit
-    def fit(self, X, y):
+    def fit(self, X, y, sample_weight=None):
         """Fit factorization machine to training data
         (sparse_factorization_machines.py:355-435).
 
         With ``distributed=True`` every rank passes the same global ``X, y``; each
         rank trains on its contiguous block of rows.
+
+        ``sample_weight`` (n_samples, >= 0): every loss term becomes ``w_i * loss_i`` (DESIGN.md
+        section 20; integer weights are row replication), for all three solvers; a classifier's
+        ``class_weight`` attribute multiplies into it.  ``mean=True`` then scales the penalties
+        by ``sum(w)``, kept as ``sample_weight_sum_``.  Not with ``distributed=True`` or a
+        plug-in regularizer object (ValueError).
         """
+        y_raw = y
         X, y = self._check_X_y(X, y)
+        sample_weight = combine_weights(sample_weight, getattr(self, "class_weight", None),
+                                        y_raw, X.shape[0])
         self._check_validation(X.shape[1])
         X = self._augment(X)
         n_samples, n_features = X.shape
@@ -459,6 +471,15 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
         # cache hooks (include/spfm.h "host-stepped epochs")
         self._plugin_reg = None if self._is_builtin_regularizer(reg_obj) else reg_obj
         self._check_adagrad(reg_obj, self._plugin_reg is not None)
+        if sample_weight is not None:
+            if self.distributed:
+                raise ValueError("sample_weight / class_weight run on one GPU "
+                                 "(distributed=False).")
+            if self._plugin_reg is not None:
+                raise ValueError("sample_weight / class_weight need one of the built-in "
+                                 "regularizers (host-stepped epochs take no weights).")
+        # what mean=True scales the penalties by, and psgd's stopping rule divides by
+        scale = n_samples if sample_weight is None else float(sample_weight.sum())
         # deviation: the reference takes any degree; the device kernels stop at SPFM_MAX_DEGREE.
         # Raised before w_ / P_ exist, so a refused fit leaves the estimator unfitted.
         if self.degree > MAX_DEGREE:
@@ -547,6 +568,9 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
             else:
                 # (concurrent fits on one data set attach to ONE device image of it)
                 self.shared_image_ = _engine_mod.shared_set_data(engine, X if csr_direct else Xc, y)
+            # every fit sets or clears: a kept session may hold the previous fit's weights
+            engine.set_sample_weight(sample_weight)
+            self.sample_weight_sum_ = float(scale)
             self.P_ = np.ascontiguousarray(self.P_, dtype=np.double)
             self.w_ = np.ascontiguousarray(self.w_, dtype=np.double)
             engine.set_params(self.P_, self.w_, self.lams_)
@@ -565,23 +589,23 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
                 engine.configure(self.solver, self.loss, self.regularizer, self.degree)
             # objective_terms() / validation_loss() read this session while the loops run
             self._upload_validation(engine)
-            self._live = (engine, n_samples)
+            self._live = (engine, scale)
             if self.solver == "psgd":
                 self._adagrad_begin(engine, self.P_.shape)
                 # X.count_nonzero() (dataset.py:32,84): stored entries, n*d when dense
                 nnz = X.nnz if sp.issparse(X) else n_samples * n_features
                 converged, self.n_iter_ = self._fit_psgd(engine, n_samples, n_features,
-                                                         nnz, rng)
+                                                         nnz, rng, loss_scale=scale)
                 self._end_live(engine)
                 keep = key is not None
                 return self._finish_fit(converged)
             # y_pred = self._get_output(X) (:408)
             engine.init_pred(self.degree, self.fit_linear, self._add_lower_deg2())
             if self.solver == "pcd":
-                converged, self.n_iter_ = self._fit_pcd(engine, n_samples, n_features, rng,
+                converged, self.n_iter_ = self._fit_pcd(engine, scale, n_features, rng,
                                                         conflict_csc)
             else:
-                converged, self.n_iter_ = self._fit_pbcd(engine, n_samples, n_features, rng,
+                converged, self.n_iter_ = self._fit_pbcd(engine, scale, n_features, rng,
                                                          conflict_csc)
             self.n_steps_per_sweep_ = engine.n_batches
             self.__dict__.pop("_Pt_host", None)
@@ -733,6 +757,11 @@ class SparseFactorizationMachineClassifier(_BaseSparseFactorizationMachine,
     """
 
     _LOSSES = CLASSIFICATION_LOSSES
+
+    # None, 'balanced' or a dict label -> weight; multiplies into ``fit``'s ``sample_weight``
+    # (sparsepoly_amd/weights.py).  A plain class attribute like ``adagrad_init``:
+    # ``get_params()`` and the constructor signature stay the reference's.
+    class_weight = None
 
     def __init__(
         self,
