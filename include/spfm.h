@@ -625,6 +625,15 @@ int spfm_debug_hop_latency(spfm_handle h, int partner, int rounds, double* ns_pe
  * totals on to the rest).  ncols = slots actually read. */
 int spfm_debug_exchange_cost(spfm_handle h, int groups, int ncols, int readers_mod, int rounds,
                              double* ns_per_round);
+/* diagnostic: the sums of one step's sweep, with an exact answer.  vals[groups][64][nv] (nv = 1:
+ * lin_prb_kernel's granules, 2: pcd_prb_kernel's pairs) are uploaded as the tagged granules of step
+ * `step` into a slab of the production layout; ONE workgroup then runs the persistent passes' own
+ * sweep -- every wave its part, wave 0 the sum of the eight part sums -- and out[64][nv] receives
+ * the totals (slots >= ncols: 0).  Nothing is published or waited for.  The contract it pins: a
+ * value loses its two lowest mantissa bits, a part's workgroups are added in ascending order from
+ * 0.0, then the parts in ascending order.  groups <= 256, ncols in [1, 64]. */
+int spfm_debug_sweep_sums(spfm_handle h, int groups, int ncols, int nv, int step,
+                          const double* vals, double* out);
 
 /* Diagnostic for the counter calibration (profiles/r03_fetch_calibration.txt): one launch that
  * reads the persistent pass's entry stream (slot bounds, rows, values of every step, with the

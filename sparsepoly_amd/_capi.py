@@ -101,6 +101,7 @@ SYMBOLS = [
     "spfm_host_pass_begin", "spfm_host_step_sums", "spfm_host_step_apply", "spfm_host_epoch_end", "spfm_comm_unique_id", "spfm_comm_init", "spfm_comm_init_shm", "spfm_peer_alloc", "spfm_peer_connect",
     "spfm_profile_enable", "spfm_profile_get", "spfm_profile_reset", "spfm_set_use_graph",
     "spfm_set_option", "spfm_get_option", "spfm_debug_prb_stamps", "spfm_debug_hop_latency", "spfm_debug_exchange_cost",
+    "spfm_debug_sweep_sums",
     "spfm_debug_branch_counts", "spfm_debug_stream_probe", "spfm_debug_write_probe",
     "spfm_gram_csr_dense", "spfm_gram_csr_csr",
     "spfm_objective_terms", "spfm_set_eval_csr", "spfm_eval_loss",
@@ -239,6 +240,7 @@ def load():
     L.spfm_debug_prb_stamps.argtypes = [_h, _lp, C.c_int]
     L.spfm_debug_hop_latency.argtypes = [_h, C.c_int, C.c_int, _dp, _ip]
     L.spfm_debug_exchange_cost.argtypes = [_h, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
+    L.spfm_debug_sweep_sums.argtypes = [_h, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp]
     L.spfm_peer_alloc.argtypes = [_h, C.c_char_p]
     L.spfm_peer_connect.argtypes = [_h, C.c_int, C.c_int, C.c_char_p]
     L.spfm_debug_branch_counts.argtypes = [_h, C.POINTER(C.c_uint32), C.c_int]

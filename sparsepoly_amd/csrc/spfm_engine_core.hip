@@ -1627,6 +1627,55 @@ int spfm_debug_exchange_cost(spfm_handle h, int groups, int ncols, int readers_m
     return SPFM_OK;
 }
 
+int spfm_debug_sweep_sums(spfm_handle h, int groups, int ncols, int nv, int step,
+                          const double* vals, double* out) {
+    SPFM_GUARD(h);
+    if (groups < 1 || groups > 256 || ncols < 1 || ncols > 64 || (nv != 1 && nv != 2) || step < 0 ||
+        !vals || !out)
+        return SPFM_ERR_INVALID;
+    // the slab as the publishing workgroups leave it: [2][groups][64][2] words, parity step & 1
+    // filled with the values' bits, the two lowest replaced by the step's tag
+    const size_t words = (size_t)2 * groups * 64 * 2;
+    const unsigned long long tag = (unsigned long long)(((step >> 1) % 3) + 1);
+    std::vector<unsigned long long> host(words, 0ull);
+    for (int g = 0; g < groups; ++g)
+        for (int q = 0; q < 64; ++q)
+            for (int v = 0; v < nv; ++v) {
+                unsigned long long u;
+                memcpy(&u, vals + ((size_t)g * 64 + q) * nv + v, sizeof u);
+                host[(((size_t)(step & 1) * groups + g) * 64 + q) * 2 + v] = (u & ~3ull) | tag;
+            }
+    DevBuf slab, abortw, dout;
+    if (slab.alloc(words * sizeof(double)) != hipSuccess || abortw.alloc(16) != hipSuccess ||
+        dout.alloc(sizeof(double) * 64 * 2) != hipSuccess)
+        return SPFM_ERR_RUNTIME;
+    if (hipMemcpyAsync(slab.p, host.data(), words * sizeof(double), hipMemcpyHostToDevice,
+                       h->stream) != hipSuccess)
+        return SPFM_ERR_RUNTIME;
+    (void)hipMemsetAsync(abortw.p, 0, 16, h->stream);
+    (void)hipMemsetAsync(dout.p, 0, sizeof(double) * 64 * 2, h->stream);
+    PrbArgs a{};
+    a.G = groups;
+    a.slab = slab.as<double>();
+    a.abort_flag = abortw.as<unsigned>();
+    a.spin_max = 1u << 10;  // every tag is there: the sweep cannot spin
+    hipLaunchKernelGGL(sweep_probe_kernel, dim3(1), dim3(kPrbThreads), 0, h->stream, a, ncols, nv,
+                       step, dout.as<double>());
+    if (hipStreamSynchronize(h->stream) != hipSuccess) {
+        h->err = "sweep_probe_kernel failed";
+        return SPFM_ERR_RUNTIME;
+    }
+    unsigned aborted = 0;
+    (void)hipMemcpy(&aborted, abortw.p, sizeof(unsigned), hipMemcpyDeviceToHost);
+    if (aborted) {
+        h->err = "sweep probe: a granule did not carry the step's tag";
+        return SPFM_ERR_RUNTIME;
+    }
+    if (hipMemcpy(out, dout.p, sizeof(double) * 64 * nv, hipMemcpyDeviceToHost) != hipSuccess)
+        return SPFM_ERR_RUNTIME;
+    return SPFM_OK;
+}
+
 int spfm_debug_stream_probe(spfm_handle h, int64_t* bytes_out) {
     SPFM_GUARD(h);
     return h->debug_stream_probe(bytes_out);

@@ -202,18 +202,101 @@ __device__ __forceinline__ void prb_load_pairs8(const double* const* p, prb_u4* 
         : "memory");
 }
 
+// What a sweeping wave's part looks like, fixed for the launch: its workgroups, and whether they
+// are a whole number of groups of eight (G = 64 with eight parts: exactly one group), which takes
+// prb_collect_quarter's straight-line form.
+struct PrbSweep {
+    int g0, g1;   // the part's workgroups
+    int groups8;  // wave-uniform; > 0: the part is groups8 whole groups of eight
+};
+__device__ __forceinline__ PrbSweep prb_sweep_init(const PrbArgs& a, int w, int nparts) {
+    PrbSweep s;
+    s.g0 = (a.G * w) / nparts;
+    s.g1 = (a.G * (w + 1)) / nparts;
+    const int len = s.g1 - s.g0;
+    s.groups8 = __builtin_amdgcn_readfirstlane((len & 7) == 0 ? len >> 3 : 0);
+    return s;
+}
+
+typedef unsigned __attribute__((ext_vector_type(2))) prb_u2;
+template <int NV> struct PrbRec { typedef prb_u2 type; };
+template <> struct PrbRec<2> { typedef prb_u4 type; };
+
 template <int NV>
-__device__ __forceinline__ bool prb_collect_quarter(const PrbArgs& a, int b, int w, int lane,
-                                                    int ncols, double* out /* [nparts][64][2] LDS */,
-                                                    int nparts = 4) {
-    const double* slab = a.slab + (size_t)(b & 1) * a.G * 64 * 2;
+__device__ __forceinline__ bool prb_collect_quarter(const PrbArgs& a, const PrbSweep& sw, int b,
+                                                    int w, int lane, int ncols,
+                                                    double* out /* [nparts][64][2] LDS */) {
     const unsigned long long tag = prb_tag(b);
-    const int g0 = (a.G * w) / nparts, g1 = (a.G * (w + 1)) / nparts;
+    const int g0 = sw.g0, g1 = sw.g1;
     double tot[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) tot[v] = 0.0;
     bool ok = true;
-    if (lane < ncols) {
+    if (sw.groups8 > 0) {
+        // Whole groups of eight: nothing behind the loads' wait is clamped or masked.  The tags
+        // are tested on the sixteen (eight) low words at once, and a wrong one anywhere in the wave
+        // makes the whole wave load again -- which changes no lane's words: a slab word of step b
+        // is rewritten at step b + 2 at the earliest, and no workgroup gets there while this one
+        // is in step b.  Spin count and abort check are the wave's.  The sums are the general
+        // code's: from 0.0, workgroups ascending.  In FRONT of the loads everything is the general
+        // code's on purpose, the eight clamped addresses formed per step included: with one
+        // address per lane, immediate offsets and the step-invariant part formed before the step
+        // loop the polls start ~70 instructions earlier, and config 2 ran 5.5 % SLOWER than the
+        // parent (alone) and 1.5 % slower than this form (together with it); profiles/prb_sweep_*.
+        if (lane < ncols) {
+            typedef typename PrbRec<NV>::type Rec;
+            const double* sl = a.slab + (size_t)(b & 1) * a.G * 64 * 2 + (size_t)lane * 2;
+            for (int k = 0; k < sw.groups8; ++k) {
+                const int gg = g0 + 8 * k;
+                Rec r[8];
+                unsigned spins = 0;
+                for (;;) {
+                    if constexpr (NV == 2) {
+                        const double* ptr[8];
+#pragma unroll
+                        for (int u = 0; u < 8; ++u)
+                            ptr[u] = sl + (size_t)((gg + u < g1) ? gg + u : g1 - 1) * 128;
+                        prb_load_pairs8(ptr, r);
+                    } else {
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) {
+                            const unsigned long long t = prb_load_granule(sl + (size_t)(gg + u) * 128);
+                            r[u].x = (unsigned)t;
+                            r[u].y = (unsigned)(t >> 32);
+                        }
+                    }
+                    const unsigned tg = (unsigned)tag;
+                    unsigned x = 0u;
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        x |= r[u].x ^ tg;
+                        if constexpr (NV == 2) x |= r[u].z ^ tg;
+                    }
+                    if (__ballot((x & 3u) != 0u) == 0ull) break;
+                    if ((++spins & 63u) == 0) {
+                        if (__hip_atomic_load(a.abort_flag, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT) ||
+                            spins > a.spin_max) {
+                            __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+                            ok = false;
+                            break;
+                        }
+                    }
+                }
+                if (!ok) break;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    tot[0] += __longlong_as_double(
+                        (long long)(((unsigned long long)r[u].y << 32) | (r[u].x & ~3u)));
+                    if constexpr (NV == 2)
+                        tot[1] += __longlong_as_double(
+                            (long long)(((unsigned long long)r[u].w << 32) | (r[u].z & ~3u)));
+                }
+            }
+        }
+    } else if (lane < ncols) {
+        const double* slab = a.slab + (size_t)(b & 1) * a.G * 64 * 2;
         const double* sl = slab + (size_t)lane * 2;
         constexpr int GU = 8;  // granule pairs polled together per lane
         for (int gg = g0; gg < g1; gg += GU) {
@@ -267,6 +350,12 @@ __device__ __forceinline__ bool prb_collect_quarter(const PrbArgs& a, int b, int
 #pragma unroll
     for (int v = 0; v < NV; ++v) out[((size_t)w * 64 + lane) * 2 + v] = tot[v];
     return ok;
+}
+// (one-off callers, the diagnostic kernels: the part is worked out at the call)
+template <int NV>
+__device__ __forceinline__ bool prb_collect_quarter(const PrbArgs& a, int b, int w, int lane,
+                                                    int ncols, double* out, int nparts = 4) {
+    return prb_collect_quarter<NV>(a, prb_sweep_init(a, w, nparts), b, w, lane, ncols, out);
 }
 
 // The entries one thread owns in one step: 4 lanes share a slot, each keeps up to
@@ -605,6 +694,7 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
     // during it -- i.e. as a scalar load: as a vector load at the top of the step it stood,
     // with its s_waitcnt vmcnt(0), in front of every step's gather
     int c4n = (4 <= a.nb) ? prb_const_load(a.bptr + 4) : c3;
+    const PrbSweep sw = prb_sweep_init(a, part, kPrbParts);  // this wave's part of the sweep
     for (int b = 0; b < a.nb; ++b) {
         const int ncols = c1 - c0;
         const int c4 = c4n;  // used two steps from now; loaded during the previous step
@@ -840,7 +930,7 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
             }
             {
                 const bool ok =
-                    prb_collect_quarter<2>(a, b, part, lane, ncols, sh_quart, kPrbParts);
+                    prb_collect_quarter<2>(a, sw, b, part, lane, ncols, sh_quart);
                 if (!ok) *sh_ok = 0;
             }
             PRB_WSTAMP(2)  // granule sweep until every workgroup's partials are in
@@ -860,7 +950,7 @@ __global__ __launch_bounds__(kPrbThreads) void pcd_prb_kernel(
                    ++spins < (1u << 24))
                 __builtin_amdgcn_s_sleep(1);
             PRB_HSTAMP(1)  // helper wave 5: from the end of the previous step to "go"
-            const bool ok = prb_collect_quarter<2>(a, b, part, lane, ncols, sh_quart, kPrbParts);
+            const bool ok = prb_collect_quarter<2>(a, sw, b, part, lane, ncols, sh_quart);
             if (!ok) *sh_ok = 0;
             PRB_HSTAMP(2)  // its part of the sweep
             if constexpr (CR) {
@@ -1289,6 +1379,7 @@ __global__ __launch_bounds__(kPrbThreads) void lin_prb_kernel(
             if (lane < c1 - c0) clq = reinterpret_cast<const prb_u4*>(a.clist)[c0 + lane];
         }
     }
+    const PrbSweep sw = prb_sweep_init(a, part, kPrbParts);  // see pcd_prb_kernel
     for (int b = 0; b < a.nb; ++b) {
         const int ncols = c1 - c0;
         // (a scalar load, see pcd_prb_kernel: as a vector load its wait stood in front of the step)
@@ -1376,7 +1467,7 @@ __global__ __launch_bounds__(kPrbThreads) void lin_prb_kernel(
             if (b + 2 < a.nb) prb_load_sp(a, g, b + 2, slot, c3 - c2, n2e0, n2e1, lm2);
             {
                 const bool ok =
-                    prb_collect_quarter<1>(a, b, part, lane, ncols, sh_quart, kPrbParts);
+                    prb_collect_quarter<1>(a, sw, b, part, lane, ncols, sh_quart);
                 if (!ok) *sh_ok = 0;
             }
             if (b + 1 < a.nb) {
@@ -1389,7 +1480,7 @@ __global__ __launch_bounds__(kPrbThreads) void lin_prb_kernel(
                        b + 1 &&
                    ++spins < (1u << 24))
                 __builtin_amdgcn_s_sleep(1);
-            const bool ok = prb_collect_quarter<1>(a, b, part, lane, ncols, sh_quart, kPrbParts);
+            const bool ok = prb_collect_quarter<1>(a, sw, b, part, lane, ncols, sh_quart);
             if (!ok) *sh_ok = 0;
         }
         if (control) {
@@ -1401,7 +1492,7 @@ __global__ __launch_bounds__(kPrbThreads) void lin_prb_kernel(
                        ++spins < (1u << 24))
                     __builtin_amdgcn_s_sleep(1);
                 const bool ok =
-                    prb_collect_quarter<1>(a, b, part, lane, ncols, sh_quart, kPrbParts);
+                    prb_collect_quarter<1>(a, sw, b, part, lane, ncols, sh_quart);
                 if (!ok) *sh_ok = 0;
             }
             if constexpr (CR) {
@@ -1722,6 +1813,33 @@ static __global__ __launch_bounds__(768) void exchange_probe_kernel(PrbArgs a, i
         }
         __syncthreads();
         if (!ok_flag) break;
+    }
+}
+
+// ---- diagnostic: the sweep's sums with an exact answer ---------------------------------
+// One workgroup; the slab of step `step` already holds every workgroup's tagged granules (written
+// by the host), so nothing is published and nothing waited for.  Every wave runs the sweep of its
+// part exactly as in pcd_prb_kernel / lin_prb_kernel (same wave -> part mapping), wave 0 then adds
+// the part sums in order.  out[64][nv]; lanes >= ncols come back as 0.
+static __global__ __launch_bounds__(kPrbThreads) void sweep_probe_kernel(PrbArgs a, int ncols,
+                                                                         int nv, int step,
+                                                                         double* __restrict__ out) {
+    __shared__ double quart[kPrbParts * 64 * 2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool control = wave == 0;
+    const bool worker = wave >= 1 && wave <= 4;
+    const int part = worker ? wave - 1 : (control ? 4 : wave);
+    const PrbSweep sw = prb_sweep_init(a, part, kPrbParts);
+    if (nv == 2) prb_collect_quarter<2>(a, sw, step, part, lane, ncols, quart);
+    else prb_collect_quarter<1>(a, sw, step, part, lane, ncols, quart);
+    __syncthreads();
+    if (control) {
+        for (int v = 0; v < nv; ++v) {
+            double tot = quart[lane * 2 + v];
+#pragma unroll
+            for (int w = 1; w < kPrbParts; ++w) tot += quart[(w * 64 + lane) * 2 + v];
+            out[lane * nv + v] = tot;
+        }
     }
 }
 

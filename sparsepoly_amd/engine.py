@@ -1524,6 +1524,18 @@ class HipEngine(object):
                                                        C.byref(ns)))
         return ns.value
 
+    def debug_sweep_sums(self, vals, ncols=64, step=0):
+        """Totals of one step's granule sweep over vals[groups, 64, nv] (nv = 1 or 2), as the
+        persistent passes form them: array [64, nv]; see spfm.h."""
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        assert vals.ndim == 3 and vals.shape[1] == 64, vals.shape
+        groups, _, nv = vals.shape
+        out = np.zeros((64, nv), dtype=np.float64)
+        self._check(self._lib.spfm_debug_sweep_sums(
+            self._h, int(groups), int(ncols), int(nv), int(step),
+            vals.ctypes.data_as(_capi._dp), out.ctypes.data_as(_capi._dp)))
+        return out
+
     def debug_prb_stamps(self):
         buf = np.zeros(16 * 512, dtype=np.int64)
         nv = self._lib.spfm_debug_prb_stamps(self._h, buf.ctypes.data_as(_capi._lp), buf.size)
