@@ -1192,6 +1192,37 @@ int spfm_bank_losses(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
 int spfm_bank_mean(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
                    const int32_t* indices, const double* data, const double* weights,
                    double* out);
+/* spfm_bank_group_sums: grouped, weighted per-member sums behind the same scoring pass (DESIGN.md
+ * section 21) -- what cross-validation needs from F fitted clones: every member's metric on the
+ * rows of every fold, in one pass over X.
+ *   out[q][f][g] = sum over rows i with group[i] == g of weight[i] * metric_q(score_if, y_if)
+ * out is (Q x F x G) row-major; y_if = y[i] (per_model = 0) or y[i * F + f] (per_model = 1);
+ * weight (n) or NULL = 1.0; group (n) ids in [0, G) or NULL = all 0; metrics (Q) distinct ids: one
+ * of SPFM_LOSS_* (that loss of (score, y)), SPFM_METRIC_ABS_ERROR (|score - y|) or
+ * SPFM_METRIC_SIGN_ERROR (1.0 where (score > 0) != (y > 0), else 0.0: a score of 0 is the negative
+ * class).  The term is weight[i] * value in this bracketing, so a weight of 1.0 changes no bit of
+ * it and weight = NULL equals a vector of ones.  A group without rows gives exact zeros; n = 0 is
+ * valid and gives all zeros.
+ * Deterministic, no float atomics: the rows go in blocks of 256 (a slab starts a new block), wave
+ * w of a block adds its 64 rows' terms one after the other in row order, the four waves are added
+ * in wave order, the blocks of the call in block order.  Column f depends neither on the other
+ * members nor on f's position nor on F; the sums are the same from run to run for one slab size
+ * (spfm_bank_set_partition).  spfm_bank_losses keeps its own kernels and its own order.
+ * Errors, each before the first write to out: NULL y (with n > 0), out or metrics, G < 1, Q < 1,
+ * an unknown metric id or the same id twice, a group id outside [0, G), a negative or non-finite
+ * weight and everything the other passes refuse -> SPFM_ERR_INVALID; G above SPFM_BANK_MAX_GROUPS
+ * or Q above SPFM_BANK_MAX_METRICS -> SPFM_ERR_UNSUPPORTED (the message names the cap; the request
+ * is never split or truncated).  The caps bound the LDS table of a workgroup, 4 waves x G x F
+ * doubles with the metrics taken one after the other: 64 KB at G = 32, F = 64. */
+#define SPFM_BANK_MAX_GROUPS 32
+#define SPFM_BANK_MAX_METRICS 4
+#define SPFM_METRIC_ABS_ERROR 16
+#define SPFM_METRIC_SIGN_ERROR 17
+int spfm_bank_group_sums(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
+                         const int32_t* indices, const double* data, const double* y,
+                         int per_model, const double* weight /* n, or NULL = 1.0 */,
+                         const int32_t* group /* n ids in [0, G), or NULL = all 0 */, int G, int Q,
+                         const int32_t* metrics, double* out /* Q x F x G, row-major */);
 int spfm_bank_set_partition(spfm_handle h, int64_t slab_nnz);
 int spfm_bank_info(spfm_handle h, int64_t* out4);
 int spfm_bank_release(spfm_handle h);

@@ -3,6 +3,7 @@ factorization machines; drop-in for the pcd / pbcd path of neonnnnn/sparsepoly
 (reference ``sparsepoly/__init__.py:1-19`` exports the same estimator and
 regularizer names)."""
 from .bank import ModelBank
+from .model_selection import CVResult, cross_validate_path, fold_ids
 from .pairwise import (SparseFactorizationMachineRanker, draw_u64, restate_sample,
                        sample_triples)
 from .regularizer import L1, L21, OmegaCS, OmegaTI, SquaredL12, SquaredL21
@@ -13,6 +14,7 @@ from .sparse_factorization_machines import (
 )
 
 __all__ = [
+    "CVResult",
     "L1",
     "L21",
     "ModelBank",
@@ -28,4 +30,6 @@ __all__ = [
     "sample_triples",
     "draw_u64",
     "restate_sample",
+    "cross_validate_path",
+    "fold_ids",
 ]

@@ -6,8 +6,9 @@ one-vs-rest classifier are F fitted models over the same features.  Their own
 parameters.  A ``ModelBank`` stacks the models along the component axis into one resident image
 (``spfm_bank_*``, ``include/spfm.h``): ``X`` goes up once per call, a stored
 entry costs one contiguous read of ``sum_f k_f`` doubles, and what users reduce the (n, F) scores
-to -- the best model per row, a loss per model, a weighted mean -- is formed on the device, so
-only that leaves it.  There is no CPU path: without the library or a GPU the device calls raise.
+to -- the best model per row, a loss per model, a weighted mean, per member and fold of the rows
+the weighted sums of a few metrics (``group_sums``: the scoring half of cross-validation, see
+``model_selection.py``) -- is formed on the device, so only that leaves it.  There is no CPU path: without the library or a GPU the device calls raise.
 
 The members are all factorization machines of one ``degree``, ``fit_lower`` and ``fit_linear``,
 or all all-subsets models, over the same features; they may differ in ``n_components``.  The score
@@ -124,11 +125,8 @@ class ModelBank(object):
         one-member bank).  The scores stay on the device."""
         return self._engine.bank_argmax(self._X(X))
 
-    def losses(self, X, y, loss=None, mean=False):
-        """(F,) ``sum_i loss(score_if, y_i)`` for a shared target ``y`` (n,), or
-        ``sum_i loss(score_if, y_if)`` for per-member targets ``y`` (n, F); ``mean``: divided by
-        n.  ``loss`` defaults to the members' common ``loss``.  Classifier members take their
-        targets already as -1 / +1.  F doubles leave the device."""
+    def _loss_name(self, loss):
+        """``loss``, or the members' common one"""
         if loss is None:
             found = {getattr(e, "loss", None) for e in self.estimators}
             if len(found) != 1:
@@ -137,6 +135,20 @@ class ModelBank(object):
             loss = found.pop()
         if loss not in _capi.LOSSES:
             raise ValueError("loss must be one of %s, got %r" % (sorted(_capi.LOSSES), loss))
+        return loss
+
+    def losses(self, X, y, loss=None, mean=False, sample_weight=None):
+        """(F,) ``sum_i loss(score_if, y_i)`` for a shared target ``y`` (n,), or
+        ``sum_i loss(score_if, y_if)`` for per-member targets ``y`` (n, F); ``mean``: divided by
+        n.  ``loss`` defaults to the members' common ``loss``.  Classifier members take their
+        targets already as -1 / +1.  F doubles leave the device.
+
+        ``sample_weight`` (n,): ``sum_i w_i loss(...)``, the one-group table of ``group_sums``
+        (its summation order, not this call's); ``mean`` then divides by ``sum(w)``."""
+        if sample_weight is not None:
+            tab = self.group_sums(X, y, sample_weight=sample_weight, metrics=("loss",), loss=loss)
+            return tab["loss"][:, 0] / tab["weight"][0] if mean else tab["loss"][:, 0]
+        loss = self._loss_name(loss)
         Xa = self._X(X)
         y = np.asarray(y, dtype=np.double)
         n = Xa.shape[0]
@@ -145,6 +157,29 @@ class ModelBank(object):
                              % (n, n, self.n_models, y.shape))
         out = self._engine.bank_losses(Xa, y, loss)
         return out / n if mean else out
+
+    def group_sums(self, X, y, groups=None, n_groups=None, sample_weight=None, metrics=("loss",),
+                   loss=None):
+        """Per member and group of rows, the weighted sum of each metric, in one pass over ``X``:
+        dict metric name -> float64 (F, G), cell [f, g] ``sum_{i: groups_i = g} w_i
+        metric(score_if, y_if)``, plus ``"weight"`` -> (G,), the groups' total weights
+        (``np.bincount(groups, weights=w, minlength=G)``).  ``y`` (n,) or (n, F) as for ``losses``;
+        ``groups`` (n,) integers in [0, G) (``None``: one group), ``n_groups`` = G (default:
+        ``groups.max() + 1``, at most %d); ``sample_weight`` (n,) >= 0 (``None``: 1.0, the same
+        bits as a vector of ones).  ``metrics``: up to %d distinct names among ``"loss"`` (``loss``,
+        or the members' common one), ``"squared"``, ``"squared_hinge"``, ``"logistic"``,
+        ``"abs_error"`` (``|score - y|``) and ``"sign_error"`` (1 where ``(score > 0) != (y >
+        0)``).  A group without rows gives zeros.  Every argument error is a ValueError raised
+        before the device is touched.  Only the tables leave the device."""
+        Xa = self._X(X)
+        ya, ga, G, wa, names, ids = _group_args(Xa.shape[0], self.n_models, y, groups, n_groups,
+                                                sample_weight, metrics,
+                                                lambda: self._loss_name(loss))
+        tab = self._engine.bank_group_sums(Xa, ya, wa, ga, G, ids)
+        out = {name: tab[q] for q, name in enumerate(names)}
+        out["weight"] = np.bincount(np.zeros(Xa.shape[0], dtype=np.intp) if ga is None else ga,
+                                    weights=wa, minlength=G).astype(np.double)
+        return out
 
     def mean(self, X, weights=None):
         """(n,) ``sum_f weights[f] score_if``, the weights applied in member order; default
@@ -187,6 +222,73 @@ class ModelBank(object):
         raise TypeError("a ModelBank holds a device handle and cannot be pickled")
 
 
+ModelBank.group_sums.__doc__ %= (_capi.BANK_MAX_GROUPS, _capi.BANK_MAX_METRICS)
+
+METRICS = ("loss",) + tuple(sorted(_capi.BANK_METRICS))
+
+
+def _group_args(n, F, y, groups, n_groups, sample_weight, metrics, default_loss):
+    """The checked arguments of ``group_sums``: ``(y, groups int32 or None, G, weights or None,
+    the metrics' names as given, their library names)``.  Every error is a ValueError; nothing
+    here needs the library.  ``default_loss()`` resolves ``"loss"``."""
+    y = np.asarray(y, dtype=np.double)
+    if y.shape not in ((n,), (n, F)):
+        raise ValueError("y must be (%d,) or (%d, %d), got %r" % (n, n, F, y.shape))
+    if isinstance(metrics, str):
+        metrics = (metrics,)
+    names = list(metrics)
+    if not names:
+        raise ValueError("metrics must name at least one of %s" % (METRICS,))
+    ids = []
+    for m in names:
+        if not isinstance(m, str) or m not in METRICS:
+            raise ValueError("unknown metric %r: metrics must be among %s" % (m, METRICS))
+        ids.append(default_loss() if m == "loss" else m)
+    if len(set(ids)) != len(ids):
+        raise ValueError("metrics %r name the same metric twice" % (names,))
+    if len(ids) > _capi.BANK_MAX_METRICS:
+        raise ValueError("%d metrics exceed the cap of %d (SPFM_BANK_MAX_METRICS); a longer list "
+                         "is refused, never split silently" % (len(ids), _capi.BANK_MAX_METRICS))
+    ga = None
+    if groups is not None:
+        g = np.asarray(groups)
+        if g.shape != (n,):
+            raise ValueError("groups must be (%d,), got %r" % (n, g.shape))
+        if g.dtype.kind not in "iu":
+            if g.dtype.kind != "f" or not np.all(np.isfinite(g)) or np.any(g != np.rint(g)):
+                raise ValueError("groups must hold integers")
+        if g.size and g.min() < 0:
+            raise ValueError("groups holds a negative id")
+        top = int(g.max()) + 1 if g.size else 1
+        if n_groups is None:
+            n_groups = top
+        elif top > int(n_groups):
+            raise ValueError("groups holds the id %d, n_groups is %d" % (top - 1, int(n_groups)))
+    elif n_groups is None:
+        n_groups = 1
+    if int(n_groups) != n_groups or int(n_groups) < 1:
+        raise ValueError("n_groups must be an integer >= 1, got %r" % (n_groups,))
+    G = int(n_groups)
+    if G > _capi.BANK_MAX_GROUPS:
+        raise ValueError("%d groups exceed the cap of %d (SPFM_BANK_MAX_GROUPS); a larger table is "
+                         "refused, never split silently" % (G, _capi.BANK_MAX_GROUPS))
+    if groups is not None:
+        ga = np.ascontiguousarray(g, dtype=np.int32)
+    wa = None
+    if sample_weight is not None:
+        try:
+            wa = np.ascontiguousarray(sample_weight, dtype=np.double)
+        except (TypeError, ValueError):
+            raise ValueError("sample_weight must be numeric.")
+        if wa.shape != (n,):
+            raise ValueError("sample_weight has shape %s, expected (%d,)" % (wa.shape, n))
+        if not np.all(np.isfinite(wa)):
+            raise ValueError("sample_weight holds a NaN or an infinite value.")
+        if np.any(wa < 0):
+            raise ValueError("sample_weight holds a negative value.")
+    return y, ga, G, wa, names, ids
+
+
 # ------------------------------------------------------------------ NumPy restatement (test aid)
 def restate_bank_scores(estimators, X, wide=False):
     """Test aid, NumPy only, never touches the device: the (n, F) scores, column f what
@@ -202,4 +304,44 @@ def restate_bank_scores(estimators, X, wide=False):
     for f, (_, _, _, P, w, lams) in enumerate(specs):
         out[:, f] = _restate_output(V[:, used], degree, lin, lower, P[:, :, used], w[used], lams,
                                     dtype)
+    return out
+
+
+def _metric(name, p, y, dtype):
+    """one metric of (score, target), elementwise, by the project's piecewise definitions
+    (``loss_dev`` of the device code; ``loss.py``)"""
+    p, y = np.asarray(p, dtype=dtype), np.asarray(y, dtype=dtype)
+    if name == "squared":
+        return 0.5 * (p - y) ** 2
+    if name == "squared_hinge":
+        return np.maximum(1 - p * y, 0) ** 2
+    if name == "logistic":
+        z = p * y
+        zc = np.clip(z, -18, 18)
+        return np.where(z > 18, np.exp(-z), np.where(z < -18, -z, np.log1p(np.exp(-zc))))
+    if name == "abs_error":
+        return np.abs(p - y)
+    if name == "sign_error":
+        return ((p > 0) != (y > 0)).astype(dtype)
+    raise ValueError("unknown metric %r" % (name,))
+
+
+def restate_group_sums(scores, y, w, groups, G, metrics, wide=False):
+    """Test aid, NumPy only, never touches the device: what ``group_sums`` sums, from given
+    ``scores`` (n, F).  ``y`` (n,) or (n, F); ``w`` (n,) or ``None`` (ones); ``groups`` (n,) or
+    ``None`` (all 0); ``metrics`` library names (``"squared"`` ..., not ``"loss"``).  Returns
+    (Q, F, G), cell [q, f, g] ``sum_{i: groups_i = g} w_i metric_q(scores_if, y_if)``; ``wide``: in
+    ``np.longdouble``."""
+    dtype = np.longdouble if wide else np.double
+    scores = np.asarray(scores, dtype=dtype)
+    n, F = scores.shape
+    y = np.asarray(y, dtype=dtype)
+    y2 = y[:, None] if y.ndim == 1 else y
+    w = np.ones(n, dtype=dtype) if w is None else np.asarray(w, dtype=dtype)
+    groups = np.zeros(n, dtype=np.intp) if groups is None else np.asarray(groups, dtype=np.intp)
+    out = np.zeros((len(metrics), F, G), dtype=dtype)
+    for q, name in enumerate(metrics):
+        terms = w[:, None] * _metric(name, scores, y2, dtype)
+        for g in range(G):
+            out[q, :, g] = terms[groups == g].sum(axis=0)
     return out

@@ -165,4 +165,87 @@ static __global__ __launch_bounds__(kBlock) void bank_loss_finish_kernel(
     if (threadIdx.x == 0) out[f] = a;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Grouped, weighted per-member sums (spfm_bank_group_sums):
+//   out[q][f][g] = sum over rows i with group[i] == g of weight[i] * metric_q(score_if, y_if).
+constexpr int kBankMaxGroups = 32;
+constexpr int kBankMaxMetrics = 4;
+enum { METRIC_ABS_ERROR = 16, METRIC_SIGN_ERROR = 17 };  // beside the three LOSS_* ids
+
+// the value of one metric on one (score, target); the three losses are loss_dev itself
+__device__ __forceinline__ double bank_metric_dev(int metric, double p, double y) {
+    if (metric == METRIC_ABS_ERROR) return fabs(p - y);
+    if (metric == METRIC_SIGN_ERROR) return ((p > 0) != (y > 0)) ? 1.0 : 0.0;  // base.py's predict
+    return loss_dev(metric, p, y);
+}
+
+// partial[block][q][g][f] for the block's 256 rows (the same blocks, and the same part0 indexing,
+// as bank_loss_partial_kernel).  One workgroup per block of 256 rows, four waves.
+//
+// Work split.  Wave w of the block owns its rows 64 w .. 64 w + 63 -- a function of the row number
+// alone, never of F.  Lane f < F is member f: the loads sc[i * F + f] of a row are coalesced, the
+// row's group id and weight are wave-uniform.  The metrics are taken one after the other, so that
+// the table in LDS is tab[wave][g][f], 4 G F doubles: 64 KB at the caps (G = 32, F = 64), 3.2 KB
+// for five folds of twenty members.  Lane f alone reads and writes column f of its wave's table.
+//
+// Summation order (what the error bound of tests/test_hip_bank_groups.py is derived from).  For
+// metric q, member f and group g, with t_i = weight[i] * metric_q(score_if, y_if) (this bracketing:
+// a weight of 1.0 changes no bit of the term; weight NULL multiplies by 1.0 all the same):
+//   W_w = ((0 + t_i1) + t_i2) + ...   the rows of wave w that belong to g, IN ROW ORDER: a row's
+//                                     term goes through at most 64 additions;
+//   B   = (((0 + W_0) + W_1) + W_2) + W_3   the four waves in wave order: 4 additions;
+//   out = ((0 + B_0) + B_1) + ... + B_{P-1}  bank_group_finish_kernel, the P blocks of the call
+//                                     IN BLOCK ORDER across all slabs: P additions.
+// So a term goes through at most 64 + 4 + P additions, P = the call's blocks of 256 rows (every
+// slab starts a new block).  No butterfly, no atomics, every operand is member f's own: the value
+// depends neither on the other members nor on f's position nor on F, and for one slab size it is
+// the same from run to run.  A group without rows sums nothing: exact zeros.
+static __global__ __launch_bounds__(kBlock) void bank_group_partial_kernel(
+    int64_t rows, int F, const double* __restrict__ sc, const double* __restrict__ y, int ys_row,
+    int ys_f, const double* __restrict__ weight /* rows or NULL */,
+    const int32_t* __restrict__ group /* rows or NULL */, int G, int Q, int4 metrics,
+    double* __restrict__ partial /* blocks x Q x G x F */) {
+    extern __shared__ double bank_group_tab[];  // [kBlock / kWave][G][F]
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int GF = G * F;
+    double* const tab = bank_group_tab + (size_t)wave * GF;
+    const int64_t i0 = (int64_t)blockIdx.x * kBlock + (int64_t)wave * kWave;
+    const int len = (int)max((int64_t)0, min((int64_t)kWave, rows - i0));
+    for (int q = 0; q < Q; ++q) {
+        const int metric = q == 0 ? metrics.x : q == 1 ? metrics.y : q == 2 ? metrics.z : metrics.w;
+        if (lane < F) {
+            for (int g = 0; g < G; ++g) tab[g * F + lane] = 0.0;
+            for (int r = 0; r < len; ++r) {
+                const int64_t i = i0 + r;
+                const int g = group ? group[i] : 0;  // in [0, G): checked on the host
+                const double w = weight ? weight[i] : 1.0;
+                const double v = bank_metric_dev(metric, sc[(size_t)i * F + lane],
+                                                 y[(size_t)i * ys_row + (size_t)lane * ys_f]);
+                tab[g * F + lane] += w * v;
+            }
+        }
+        __syncthreads();
+        double* const o = partial + ((size_t)blockIdx.x * Q + q) * GF;
+        for (int c = threadIdx.x; c < GF; c += kBlock) {
+            double a = 0.0;
+            for (int w = 0; w < kBlock / kWave; ++w) a += bank_group_tab[(size_t)w * GF + c];
+            o[c] = a;
+        }
+        __syncthreads();  // the tables are zeroed again for the next metric
+    }
+}
+
+// acc[q][g][f] += the slab's partials one after the other in block order: thread c owns cell c of
+// the Q G F cells.  Run once per slab on the same accumulator (zeroed before the first slab), so
+// the call's blocks are added in block order whatever the slabs are.
+static __global__ __launch_bounds__(kBlock) void bank_group_finish_kernel(
+    int64_t P, int cells, const double* __restrict__ partial, double* __restrict__ acc) {
+    const int c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= cells) return;
+    double a = acc[c];
+#pragma unroll 8  // (the loads of eight blocks in flight; the additions stay in block order)
+    for (int64_t p = 0; p < P; ++p) a += partial[(size_t)p * cells + c];
+    acc[c] = a;
+}
+
 }  // namespace spfm

@@ -1367,6 +1367,8 @@ struct spfm_engine {
     DevBuf bk_sc;                          // its scores (rows x F)
     DevBuf bk_y, bk_wt, bk_part, bk_fin;   // targets of one slab, mean weights, loss partials, sums
     DevBuf bk_oi, bk_o0, bk_o1;            // per-row results of one slab
+    DevBuf bk_gw, bk_gg, bk_gpart, bk_gacc;  // group sums: weights and ids of one slab, its partial
+                                             // tables, the call's running Q x G x F table
     bool bk_have = false, bk_lin = false;
     int bk_F = 0, bk_S = 0, bk_d = 0, bk_blocks = 0, bk_degree[2] = {0, 0};
     int64_t bk_slab_nnz = 0;               // spfm_bank_set_partition: stored entries per slab (0 = default)
@@ -1377,7 +1379,7 @@ struct spfm_engine {
     void bank_release();
     int bank_set(int32_t d_, int F, const int32_t* koff, int n_blocks, const int32_t* degree,
                  const double* Pt_bank, const double* lams_bank, const double* w_bank);
-    struct BankCall {  // the arguments of spfm_bank_scores / _argmax / _losses / _mean
+    struct BankCall {  // the arguments of spfm_bank_scores / _argmax / _losses / _mean / _group_sums
         int what;  // BANK_SCORES ...
         int64_t n;
         int32_t d;
@@ -1391,6 +1393,10 @@ struct spfm_engine {
         const double* y;     // losses: (n) or (n x F)
         int per_model;       // losses
         const double* wt;    // mean: (F) or NULL = 1 / F
+        const double* weight;    // group sums: (n) or NULL = 1.0
+        const int32_t* group;    // group sums: (n) ids in [0, G) or NULL = all 0
+        int G, Q;                // group sums
+        const int32_t* metrics;  // group sums: (Q) SPFM_LOSS_* / SPFM_METRIC_* ids
     };
     int bank_check(const char* what, const BankCall& c);
     template <typename T, int M>

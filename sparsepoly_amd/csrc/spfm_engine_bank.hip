@@ -1,7 +1,8 @@
-// spfm_engine_bank.hip -- spfm_bank_set / _scores / _argmax / _losses / _mean / _set_partition /
-// _info / _release (include/spfm.h): F fitted models, stacked along the component axis and
-// resident on the handle, scored in one pass over the rows of a CSR matrix; the argmax, the loss
-// sums and the weighted mean are formed on the device behind that pass (spfm_bank.hip.h).
+// spfm_engine_bank.hip -- spfm_bank_set / _scores / _argmax / _losses / _mean / _group_sums /
+// _set_partition / _info / _release (include/spfm.h): F fitted models, stacked along the component
+// axis and resident on the handle, scored in one pass over the rows of a CSR matrix; the argmax,
+// the loss sums, the weighted mean and the grouped weighted sums are formed
+// on the device behind that pass (spfm_bank.hip.h).
 // Read-only like predict and independent of spfm_set_params: the bank brings its own parameters.
 // Rows go through in slabs bounded by stored entries.  See DESIGN.md section 17.
 #include "spfm_engine.hip.h"
@@ -16,6 +17,12 @@ static_assert(kBankMaxModels <= kWave, "one model per lane of the wave that owns
 static_assert(LOSS_SQUARED == SPFM_LOSS_SQUARED && LOSS_SQUARED_HINGE == SPFM_LOSS_SQUARED_HINGE &&
                   LOSS_LOGISTIC == SPFM_LOSS_LOGISTIC,
               "header and device agree on the losses");
+static_assert(kBankMaxGroups == SPFM_BANK_MAX_GROUPS && kBankMaxMetrics == SPFM_BANK_MAX_METRICS &&
+                  METRIC_ABS_ERROR == SPFM_METRIC_ABS_ERROR &&
+                  METRIC_SIGN_ERROR == SPFM_METRIC_SIGN_ERROR && kBankMaxMetrics == 4,
+              "header and device agree on the group sums (the metric ids travel in an int4)");
+static_assert(sizeof(double) * (kBlock / kWave) * kBankMaxGroups * kBankMaxModels <= (64u << 10),
+              "the group table of a workgroup stays within 64 KB of LDS at the caps");
 
 namespace {
 // One slab's scratch: 4 (column) + at most 8 (value) bytes per stored entry and 8 F (scores) + up
@@ -23,11 +30,13 @@ namespace {
 // at most 96 MiB, the rows of a slab are capped so that scores and targets stay within 128 MiB.
 constexpr int64_t kBankRowBudget = 128ll << 20;
 constexpr int64_t kBankSlabMax = 1ll << 23;  // stored entries per slab: default and largest
+enum { BANK_GROUPS = 4 };                    // beside BANK_SCORES ... BANK_MEAN
 }  // namespace
 
 void spfm_engine::bank_release() {
     for (DevBuf* b : {&bk_pt, &bk_lams, &bk_w, &bk_koff, &bk_rp, &bk_ri, &bk_rv, &bk_sc, &bk_y,
-                      &bk_wt, &bk_part, &bk_fin, &bk_oi, &bk_o0, &bk_o1})
+                      &bk_wt, &bk_part, &bk_fin, &bk_oi, &bk_o0, &bk_o1, &bk_gw, &bk_gg, &bk_gpart,
+                      &bk_gacc})
         b->release();
     bk_have = false;
     bk_F = bk_S = bk_d = bk_blocks = 0;
@@ -88,7 +97,7 @@ int spfm_engine::bank_set(int32_t d_, int F, const int32_t* koff, int n_blocks,
     return SPFM_OK;
 }
 
-// every check of the four passes, before any device work and before any output is written
+// every check of the five passes, before any device work and before any output is written
 int spfm_engine::bank_check(const char* what, const BankCall& c) {
     const std::string w(what);
     if (!bk_have) FAIL(SPFM_ERR_INVALID, w + ": no bank set (spfm_bank_set)");
@@ -105,6 +114,42 @@ int spfm_engine::bank_check(const char* what, const BankCall& c) {
             c.loss != SPFM_LOSS_LOGISTIC)
             FAIL(SPFM_ERR_INVALID, w + ": unknown loss");
         if (!c.out || (c.n > 0 && !c.y)) FAIL(SPFM_ERR_INVALID, w + ": NULL array");
+    } else if (c.what == BANK_GROUPS) {
+        char buf[160];
+        if (!c.out || !c.metrics || (c.n > 0 && !c.y)) FAIL(SPFM_ERR_INVALID, w + ": NULL array");
+        if (c.G < 1 || c.Q < 1) FAIL(SPFM_ERR_INVALID, w + ": G and Q must be >= 1");
+        if (c.G > SPFM_BANK_MAX_GROUPS) {
+            snprintf(buf, sizeof buf, "%s: %d groups exceed SPFM_BANK_MAX_GROUPS = %d", what, c.G,
+                     (int)SPFM_BANK_MAX_GROUPS);
+            FAIL(SPFM_ERR_UNSUPPORTED, buf);
+        }
+        if (c.Q > SPFM_BANK_MAX_METRICS) {
+            snprintf(buf, sizeof buf, "%s: %d metrics exceed SPFM_BANK_MAX_METRICS = %d", what, c.Q,
+                     (int)SPFM_BANK_MAX_METRICS);
+            FAIL(SPFM_ERR_UNSUPPORTED, buf);
+        }
+        for (int q = 0; q < c.Q; ++q) {
+            const int m = c.metrics[q];
+            if (m != SPFM_LOSS_SQUARED && m != SPFM_LOSS_SQUARED_HINGE && m != SPFM_LOSS_LOGISTIC &&
+                m != SPFM_METRIC_ABS_ERROR && m != SPFM_METRIC_SIGN_ERROR)
+                FAIL(SPFM_ERR_INVALID, w + ": unknown metric");
+            for (int p = 0; p < q; ++p)
+                if (c.metrics[p] == m) FAIL(SPFM_ERR_INVALID, w + ": the same metric twice");
+        }
+        if (c.group)
+            for (int64_t i = 0; i < c.n; ++i)
+                if (c.group[i] < 0 || c.group[i] >= c.G) {
+                    snprintf(buf, sizeof buf, "%s: group id %d of row %lld outside [0, %d)", what,
+                             (int)c.group[i], (long long)i, c.G);
+                    FAIL(SPFM_ERR_INVALID, buf);
+                }
+        if (c.weight)
+            for (int64_t i = 0; i < c.n; ++i)
+                if (!(c.weight[i] >= 0.0) || !std::isfinite(c.weight[i])) {
+                    snprintf(buf, sizeof buf, "%s: the weight of row %lld is negative or not finite",
+                             what, (long long)i);
+                    FAIL(SPFM_ERR_INVALID, buf);
+                }
     } else if (c.n > 0) {
         if (!c.out) FAIL(SPFM_ERR_INVALID, w + ": NULL output");
         if (c.what == BANK_ARGMAX && (!c.idx || !c.runner))
@@ -137,19 +182,29 @@ int spfm_engine::bank_slab(const BankCall& c, int64_t r0, int64_t r1, int64_t pa
         HIPC(bk_o1.alloc(sizeof(double) * (size_t)rows));
     }
     if (c.what == BANK_MEAN) HIPC(bk_o0.alloc(sizeof(double) * (size_t)rows));
-    if (c.what == BANK_LOSSES)
+    if (c.what == BANK_LOSSES || c.what == BANK_GROUPS)
         HIPC(bk_y.alloc(sizeof(double) * (size_t)rows * (c.per_model ? F : 1)));
+    const unsigned row_blocks = cdiv(rows, kBlock);
+    const int cells = c.Q * c.G * F;  // group sums: the cells of one table
+    if (c.what == BANK_GROUPS) {
+        if (c.weight) HIPC(bk_gw.alloc(sizeof(double) * (size_t)rows));
+        if (c.group) HIPC(bk_gg.alloc(sizeof(int32_t) * (size_t)rows));
+        HIPC(bk_gpart.alloc(sizeof(double) * (size_t)row_blocks * cells));
+    }
     std::vector<T> hv;  // staging of the values
     return run_staged([&]() -> int {
         SPFM_TRY(stage_csr_rows<T>(bk_rp, bk_ri, bk_rv, hv, c.indptr, c.indices, c.data, r0, r1));
-        if (c.what == BANK_LOSSES)
+        if (c.what == BANK_LOSSES || c.what == BANK_GROUPS)
             SPFM_TRY(upload_to(bk_y.p, c.y + (size_t)r0 * (c.per_model ? F : 1),
                                (size_t)rows * (c.per_model ? F : 1)));
+        if (c.what == BANK_GROUPS && c.weight)
+            SPFM_TRY(upload_to(bk_gw.p, c.weight + r0, (size_t)rows));
+        if (c.what == BANK_GROUPS && c.group)
+            SPFM_TRY(upload_to(bk_gg.p, c.group + r0, (size_t)rows));
         for (int q = 0; q < bk_blocks; ++q) {
             (void)SPFM_DISPATCH_KIND(kind_of(bk_degree[q]), true,  // (2..6 or -1: bank_set)
                                      bank_launch_block<T, M>(rows, e0, q, q == 0));
         }
-        const unsigned row_blocks = cdiv(rows, kBlock);
         const double* sc = bk_sc.as<double>();
         if (c.what == BANK_ARGMAX)
             hipLaunchKernelGGL(bank_argmax_kernel, dim3(row_blocks), dim3(kBlock), 0, stream, rows,
@@ -162,6 +217,21 @@ int spfm_engine::bank_slab(const BankCall& c, int64_t r0, int64_t r1, int64_t pa
                                rows, F, sc, bk_y.as<double>(), c.per_model ? F : 1,
                                c.per_model ? 1 : 0, c.loss,
                                bk_part.as<double>() + (size_t)part0 * F);
+        if (c.what == BANK_GROUPS) {
+            // the slab's blocks (part0 .. part0 + row_blocks - 1 of the call) into partial tables,
+            // then onto the call's running table in block order
+            const int4 ids = {c.metrics[0], c.Q > 1 ? c.metrics[1] : 0, c.Q > 2 ? c.metrics[2] : 0,
+                              c.Q > 3 ? c.metrics[3] : 0};
+            hipLaunchKernelGGL(bank_group_partial_kernel, dim3(row_blocks), dim3(kBlock),
+                               sizeof(double) * (kBlock / kWave) * c.G * F, stream, rows, F, sc,
+                               bk_y.as<double>(), c.per_model ? F : 1, c.per_model ? 1 : 0,
+                               c.weight ? bk_gw.as<double>() : (const double*)nullptr,
+                               c.group ? bk_gg.as<int32_t>() : (const int32_t*)nullptr, c.G, c.Q,
+                               ids, bk_gpart.as<double>());
+            hipLaunchKernelGGL(bank_group_finish_kernel, dim3(cdiv(cells, kBlock)), dim3(kBlock), 0,
+                               stream, (int64_t)row_blocks, cells, bk_gpart.as<double>(),
+                               bk_gacc.as<double>());
+        }
         HIPC(hipGetLastError());
         if (c.what == BANK_SCORES) SPFM_TRY(download(c.out + (size_t)r0 * F, sc, (size_t)rows * F));
         if (c.what == BANK_ARGMAX) {
@@ -181,6 +251,7 @@ int spfm_engine::bank_run(const char* what, const BankCall& c) {
     const int F = bk_F;
     if (c.n == 0) {
         if (c.what == BANK_LOSSES) std::fill(c.out, c.out + F, 0.0);
+        if (c.what == BANK_GROUPS) std::fill(c.out, c.out + (size_t)c.Q * F * c.G, 0.0);
         return SPFM_OK;
     }
     const int64_t slab_nnz = bk_slab_nnz > 0 ? bk_slab_nnz : kBankSlabMax;
@@ -195,6 +266,10 @@ int spfm_engine::bank_run(const char* what, const BankCall& c) {
     if (c.what == BANK_LOSSES) {
         HIPC(bk_part.alloc(sizeof(double) * (size_t)part.back() * F));
         HIPC(bk_fin.alloc(sizeof(double) * (size_t)F));
+    }
+    if (c.what == BANK_GROUPS) {
+        HIPC(bk_gacc.alloc(sizeof(double) * (size_t)c.Q * c.G * F));
+        HIPC(hipMemsetAsync(bk_gacc.p, 0, sizeof(double) * (size_t)c.Q * c.G * F, stream));
     }
     if (c.what == BANK_MEAN) {
         const std::vector<double> hw((size_t)F, 1.0 / (double)F);  // staging of the default
@@ -212,6 +287,15 @@ int spfm_engine::bank_run(const char* what, const BankCall& c) {
         HIPC(hipGetLastError());
         SPFM_TRY(download(c.out, bk_fin.p, (size_t)F));
         SPFM_TRY(sync());
+    }
+    if (c.what == BANK_GROUPS) {  // the device table is [q][g][f] (lane = member), out is [q][f][g]
+        std::vector<double> tab((size_t)c.Q * c.G * F);
+        SPFM_TRY(download(tab.data(), bk_gacc.p, tab.size()));
+        SPFM_TRY(sync());
+        for (int q = 0; q < c.Q; ++q)
+            for (int g = 0; g < c.G; ++g)
+                for (int f = 0; f < F; ++f)
+                    c.out[((size_t)q * F + f) * c.G + g] = tab[((size_t)q * c.G + g) * F + f];
     }
     return SPFM_OK;
 }
@@ -258,6 +342,17 @@ int spfm_bank_mean(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
     const spfm_engine::BankCall c = {BANK_MEAN, n, d, indptr, indices, data, out, nullptr,
                                      nullptr, 0, nullptr, 0, weights};
     return SPFM_DISPATCH(h->dtype, return h->bank_run<T>("bank_mean", c));
+}
+
+int spfm_bank_group_sums(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
+                         const int32_t* indices, const double* data, const double* y,
+                         int per_model, const double* weight, const int32_t* group, int G, int Q,
+                         const int32_t* metrics, double* out) {
+    SPFM_GUARD(h);
+    const spfm_engine::BankCall c = {BANK_GROUPS, n, d, indptr, indices, data, out, nullptr,
+                                     nullptr, 0, y, per_model ? 1 : 0, nullptr, weight, group, G,
+                                     Q, metrics};
+    return SPFM_DISPATCH(h->dtype, return h->bank_run<T>("bank_group_sums", c));
 }
 
 int spfm_bank_set_partition(spfm_handle h, int64_t slab_nnz) {

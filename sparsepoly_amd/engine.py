@@ -916,6 +916,37 @@ class HipEngine(object):
                                                out.ctypes.data_as(_capi._dp)))
         return out
 
+    def bank_group_sums(self, X, y, weight, group, G, metrics):
+        """``spfm_bank_group_sums``: float64 (Q, F, G), cell [q, f, g] the sum over the rows of
+        group ``g`` of ``weight_i * metric_q(score_if, y_if)``.  ``y`` (n,) or (n, F); ``weight``
+        (n,) float64 or ``None`` (1.0); ``group`` (n,) int32 or ``None`` (all 0); ``metrics`` a
+        sequence of names from ``_capi.BANK_METRICS``."""
+        for m in metrics:
+            if m not in _capi.BANK_METRICS:
+                raise ValueError("bank_group_sums: metrics must be among %s, got %r"
+                                 % (sorted(_capi.BANK_METRICS), m))
+        n, args, keep = self._bank_args(X, "bank_group_sums")
+        ya, yp = _capi.f64(y)
+        F = self.bank_shape[0]
+        if ya.shape not in ((n,), (n, F)):
+            raise ValueError("bank_group_sums: y must be (%d,) or (%d, %d), got %r"
+                             % (n, n, F, ya.shape))
+        wp = gp = None
+        if weight is not None:
+            wa, wp = _capi.f64(weight)
+            if wa.shape != (n,):
+                raise ValueError("bank_group_sums: weight must be (%d,), got %r" % (n, wa.shape))
+        if group is not None:
+            ga, gp = _capi.i32(group)
+            if ga.shape != (n,):
+                raise ValueError("bank_group_sums: group must be (%d,), got %r" % (n, ga.shape))
+        ma, mp = _capi.i32([_capi.BANK_METRICS[m] for m in metrics])
+        out = np.zeros((len(metrics), F, max(int(G), 1)))
+        self._check(self._lib.spfm_bank_group_sums(*args, yp, int(ya.ndim == 2), wp, gp, int(G),
+                                                   len(metrics), mp,
+                                                   out.ctypes.data_as(_capi._dp)))
+        return out
+
     def bank_mean(self, X, weights=None):
         """``spfm_bank_mean``: (n,) ``sum_f weights[f] score_if``, added in model order;
         ``weights`` ``None``: ``1 / F``."""

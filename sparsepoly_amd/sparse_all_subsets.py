@@ -199,6 +199,13 @@ class _BaseSparseAllSubsets(ObjectiveMixin, InteractionMixin, RankingMixin, Base
 
         return fit_path(self, X, y, max_concurrent=max_concurrent, **grid)
 
+    def cross_validate_path(self, X, y, cv=5, **kw):
+        """K-fold cross-validation of a parameter grid (``gamma=[...]``, ...) on one device image:
+        ``sparsepoly_amd.model_selection.cross_validate_path(self, X, y, cv, ...)``."""
+        from .model_selection import cross_validate_path
+
+        return cross_validate_path(self, X, y, cv=cv, **kw)
+
     def _get_output(self, X):
         """sparse_all_subsets.py:260-263 (poly_predict(..., 'all-subsets')), on the device."""
         engine = self._new_engine()

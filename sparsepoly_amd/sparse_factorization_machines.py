@@ -660,6 +660,13 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
 
         return fit_path(self, X, y, max_concurrent=max_concurrent, **grid)
 
+    def cross_validate_path(self, X, y, cv=5, **kw):
+        """K-fold cross-validation of a parameter grid (``gamma=[...]``, ...) on one device image:
+        ``sparsepoly_amd.model_selection.cross_validate_path(self, X, y, cv, ...)``."""
+        from .model_selection import cross_validate_path
+
+        return cross_validate_path(self, X, y, cv=cv, **kw)
+
     def release_device(self):
         """Free the device session kept by ``warm_start=True`` (data, schedule, stream)."""
         cached = getattr(self, "_device_session", None)

@@ -6,8 +6,8 @@ Pure Python and numpy -- nothing here needs the library or a device.  The semant
 restatement, in the tradition of the ``restate_*`` functions: the tests fit the CPU oracle on the
 replicated matrix and compare the weighted device fit against it.
 
-Out of scope: ``objective(X, y)``, ``set_validation`` / ``validation_loss``, ``fold_in`` and
-``ModelBank.losses`` take no weights; the ranker keeps its own per-positive ``sample_weight``.
+Out of scope: ``objective(X, y)``, ``set_validation`` / ``validation_loss`` and ``fold_in`` take no
+weights; the ranker keeps its own per-positive ``sample_weight``.
 """
 import numpy as np
 import scipy.sparse as sp
