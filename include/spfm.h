@@ -1223,6 +1223,46 @@ int spfm_bank_group_sums(spfm_handle h, int64_t n, int32_t d, const int64_t* ind
                          int per_model, const double* weight /* n, or NULL = 1.0 */,
                          const int32_t* group /* n ids in [0, G), or NULL = all 0 */, int G, int Q,
                          const int32_t* metrics, double* out /* Q x F x G, row-major */);
+/* spfm_bank_group_auc: the exact ROC-AUC of every member on sets of rows, behind the same scoring
+ * pass.  Row i belongs to set u of member f when bit group[i] of
+ * sets[f * U + u] is set (group NULL: every row is in group 0); sets NULL: U = G and set u = {u}
+ * for every member.  A row is positive for member f when y_if > 0 (y as for spfm_bank_group_sums).
+ * Over the rows of a set, P its positives, N its negatives, s the member's scores:
+ *   weight == NULL (integers only): pairs[f][u] = {U2, n_pos, n_neg} with
+ *     U2 = 2 #{(p, q): s_q < s_p} + #{(p, q): s_q == s_p},
+ *     out[f][u] = {(double)U2 / (2.0 * (double)n_pos * (double)n_neg), n_pos, n_neg};
+ *   weighted: out[f][u] = {sum_p w_p (sum_{q: s_q < s_p} w_q + 1/2 sum_{q: s_q == s_p} w_q)
+ *     / (W_pos W_neg), W_pos, W_neg}; pairs is not written.
+ * -0.0 and +0.0 are equal scores; the scores are taken to be finite.  A set that lacks a class
+ * (the product of the two counts or weights is 0) has auc = NaN, the counts and weights are
+ * reported all the same; an empty set gives NaN and zeros; n = 0 is valid.
+ * The scores of a slab become order-preserving 64-bit keys in a member-major image that lives
+ * until the call returns; after the last slab every member's keys are sorted (stable radix sort,
+ * the row number as payload: equal scores sit in row order) and walked in blocks of
+ * SPFM_BANK_RANK_BLOCK sorted positions (spfm_bank_rank.hip.h: no atomics, every addend
+ * non-negative, the order of the additions a function of the sorted position alone).  The integers
+ * depend on nothing but the scores; the weighted values have the same bits from run to run, for
+ * every slab size (spfm_bank_set_partition), every F and every position of the member.
+ * Errors, each before the first write to out and before any device work: everything
+ * spfm_bank_group_sums refuses for y, weight, group, G and the matrix; U < 1, NULL out, a set bit
+ * at or above G -> SPFM_ERR_INVALID; G above SPFM_BANK_MAX_GROUPS, U above SPFM_BANK_MAX_SETS, or
+ * a scratch (8 n F bytes of keys, n F of class and group, 4 n of row numbers, 8 n of weights where
+ * given, and with Fb = min(F, max(1, 128 MiB / 12 n)) the members of a sort batch and nb = ceil(n /
+ * SPFM_BANK_RANK_BLOCK): 12 n Fb of sorted pairs, 40 nb U Fb of the walk's block records, and the
+ * sort's own storage) above SPFM_BANK_AUC_MAX_BYTES -> SPFM_ERR_UNSUPPORTED (the message names the
+ * cap or the bytes; the request is never split or truncated).  The scratch is freed before the
+ * call returns, whatever it returns.  Test hook: the environment variable SPFM_BANK_AUC_BATCH = m
+ * >= 1, read at every call, makes Fb = min(Fb, m); no result bit depends on it. */
+#define SPFM_BANK_MAX_SETS 32
+#define SPFM_BANK_RANK_BLOCK 256
+#define SPFM_BANK_AUC_MAX_BYTES (1ll << 30)
+int spfm_bank_group_auc(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
+                        const int32_t* indices, const double* data, const double* y,
+                        int per_model, const double* weight /* n, or NULL: integer path */,
+                        const int32_t* group /* n ids in [0, G), or NULL = all 0 */, int G,
+                        const uint32_t* sets /* F x U bitmasks over groups, or NULL */, int U,
+                        double* out /* F x U x 3: auc, pos_weight, neg_weight */,
+                        int64_t* pairs /* F x U x 3 or NULL; only when weight == NULL */);
 int spfm_bank_set_partition(spfm_handle h, int64_t slab_nnz);
 int spfm_bank_info(spfm_handle h, int64_t* out4);
 int spfm_bank_release(spfm_handle h);

@@ -8,14 +8,17 @@ parameters.  A ``ModelBank`` stacks the models along the component axis into one
 entry costs one contiguous read of ``sum_f k_f`` doubles, and what users reduce the (n, F) scores
 to -- the best model per row, a loss per model, a weighted mean, per member and fold of the rows
 the weighted sums of a few metrics (``group_sums``: the scoring half of cross-validation, see
-``model_selection.py``) -- is formed on the device, so only that leaves it.  There is no CPU path: without the library or a GPU the device calls raise.
+``model_selection.py``), per member and set of rows the exact ROC-AUC (``group_auc``: a sort per
+member on the device) -- is formed on the device, so only that leaves it.
+There is no CPU path: without the library or a GPU the device calls raise.
 
 The members are all factorization machines of one ``degree``, ``fit_lower`` and ``fit_linear``,
 or all all-subsets models, over the same features; they may differ in ``n_components``.  The score
 of a member does not depend on the other members or on its position: column f of a bank equals
 the one-model bank of that member bit for bit.
 
-``restate_bank_scores`` is the plain NumPy restatement, a test aid that never touches the device.
+``restate_bank_scores`` is the plain NumPy restatement, a test aid that never touches the device;
+``restate_group_sums`` and ``restate_group_auc`` restate the reductions from given scores.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -181,6 +184,29 @@ class ModelBank(object):
                                     weights=wa, minlength=G).astype(np.double)
         return out
 
+    def group_auc(self, X, y, groups=None, n_groups=None, sample_weight=None, sets=None):
+        """Per member and set of rows the exact ROC-AUC, in one pass over ``X`` and one sort per
+        member on the device: dict with ``"auc"``, ``"pos_weight"``, ``"neg_weight"``, float64
+        (F, U) each, and for unweighted calls ``"pairs"`` int64 (F, U, 3): ``U2 = 2 #{s_neg <
+        s_pos} + #{s_neg == s_pos}``, the positives, the negatives; ``auc = U2 / (2 n_pos
+        n_neg)``.  Weighted: ``auc = sum_p w_p (sum_{q: s_q < s_p} w_q + 1/2 sum_{q: s_q = s_p}
+        w_q) / (W_pos W_neg)`` over the positives ``p`` and negatives ``q`` of the set.  A row is
+        positive where ``y > 0``; ``y``, ``groups``, ``n_groups`` and ``sample_weight`` as for
+        ``group_sums``.  ``sets``: ``None`` (one set per group), boolean (U, G) -- set ``u`` holds
+        the rows of the groups ``g`` with ``sets[u, g]``, the same for every member -- or
+        (F, U, G), at most %d sets.  A set that lacks a class has ``auc`` NaN, its weights are
+        reported all the same.  Every argument error is a ValueError raised before the device is
+        touched.  Only the tables leave the device."""
+        Xa = self._X(X)
+        ya, ga, G, wa, _, _ = _group_args(Xa.shape[0], self.n_models, y, groups, n_groups,
+                                          sample_weight, ("sign_error",), None)
+        masks = _set_masks(sets, self.n_models, G)
+        tab, pairs = self._engine.bank_group_auc(Xa, ya, wa, ga, G, masks)
+        out = {"auc": tab[:, :, 0], "pos_weight": tab[:, :, 1], "neg_weight": tab[:, :, 2]}
+        if pairs is not None:
+            out["pairs"] = pairs
+        return out
+
     def mean(self, X, weights=None):
         """(n,) ``sum_f weights[f] score_if``, the weights applied in member order; default
         ``1 / F``."""
@@ -223,6 +249,7 @@ class ModelBank(object):
 
 
 ModelBank.group_sums.__doc__ %= (_capi.BANK_MAX_GROUPS, _capi.BANK_MAX_METRICS)
+ModelBank.group_auc.__doc__ %= (_capi.BANK_MAX_SETS,)
 
 METRICS = ("loss",) + tuple(sorted(_capi.BANK_METRICS))
 
@@ -289,6 +316,38 @@ def _group_args(n, F, y, groups, n_groups, sample_weight, metrics, default_loss)
     return y, ga, G, wa, names, ids
 
 
+def _sets_array(sets, F, G):
+    """``sets`` of ``group_auc`` as boolean (F, U, G); ``None``: one set per group.  Every error is
+    a ValueError; nothing here needs the library."""
+    if sets is None:
+        return np.broadcast_to(np.eye(G, dtype=bool), (F, G, G))
+    a = np.asarray(sets)
+    if a.dtype != bool:
+        if a.dtype.kind not in "iuf" or np.any((a != 0) & (a != 1)):
+            raise ValueError("sets must be boolean")
+        a = a.astype(bool)
+    if a.ndim == 2:
+        a = np.broadcast_to(a, (F,) + a.shape)
+    if a.ndim != 3 or a.shape[0] != F or a.shape[2] != G:
+        raise ValueError("sets must be (U, %d) or (%d, U, %d) for %d groups and %d members, got %r"
+                         % (G, F, G, G, F, np.shape(sets)))
+    if a.shape[1] < 1:
+        raise ValueError("sets must name at least one set")
+    if a.shape[1] > _capi.BANK_MAX_SETS:
+        raise ValueError("%d sets exceed the cap of %d (SPFM_BANK_MAX_SETS); a larger table is "
+                         "refused, never split silently" % (a.shape[1], _capi.BANK_MAX_SETS))
+    return a
+
+
+def _set_masks(sets, F, G):
+    """uint32 (F, U) bitmasks over the groups, or ``None`` for ``sets=None``"""
+    if sets is None:
+        return None
+    a = _sets_array(sets, F, G)
+    bits = np.left_shift(np.uint64(1), np.arange(G, dtype=np.uint64))
+    return (a.astype(np.uint64) * bits).sum(axis=2).astype(np.uint32)
+
+
 # ------------------------------------------------------------------ NumPy restatement (test aid)
 def restate_bank_scores(estimators, X, wide=False):
     """Test aid, NumPy only, never touches the device: the (n, F) scores, column f what
@@ -344,4 +403,53 @@ def restate_group_sums(scores, y, w, groups, G, metrics, wide=False):
         terms = w[:, None] * _metric(name, scores, y2, dtype)
         for g in range(G):
             out[q, :, g] = terms[groups == g].sum(axis=0)
+    return out
+
+
+def restate_group_auc(scores, y, w, groups, G, sets, wide=False):
+    """Test aid, NumPy only, never touches the device: what ``group_auc`` gives, from given
+    ``scores`` (n, F).  ``y`` (n,) or (n, F), positive where ``> 0``; ``w`` (n,) or ``None``;
+    ``groups`` (n,) or ``None`` (all 0); ``sets`` as for ``group_auc``.  Returns the same dict.
+    Unweighted (``w`` ``None``) the pairs are counted in Python integers; weighted the sums run in
+    double, or in ``np.longdouble`` with ``wide``.  Per positive the negatives below it and those
+    tied with it are read off the sorted negatives: ``w_p (C[lo] + C[hi]) / 2`` with ``C`` the
+    running weights of the negatives -- every addend is non-negative, there is no subtraction."""
+    dtype = np.longdouble if wide else np.double
+    scores = np.asarray(scores, dtype=np.double) + 0.0  # (-0.0 + 0.0 = +0.0: one zero)
+    n, F = scores.shape
+    y = np.asarray(y, dtype=np.double)
+    pos_all = np.broadcast_to((y[:, None] if y.ndim == 1 else y) > 0, (n, F))
+    groups = np.zeros(n, dtype=np.intp) if groups is None else np.asarray(groups, dtype=np.intp)
+    S = _sets_array(sets, F, G)
+    U = S.shape[1]
+    auc = np.full((F, U), np.nan)
+    wpos = np.zeros((F, U), dtype=dtype)
+    wneg = np.zeros((F, U), dtype=dtype)
+    pairs = np.zeros((F, U, 3), dtype=np.int64)
+    for f in range(F):
+        for u in range(U):
+            rows = S[f, u][groups]
+            p = rows & pos_all[:, f]
+            q = rows & ~pos_all[:, f]
+            order = np.argsort(scores[q, f], kind="stable")
+            sq = scores[q, f][order]
+            lo = np.searchsorted(sq, scores[p, f], side="left")
+            hi = np.searchsorted(sq, scores[p, f], side="right")
+            if w is None:
+                u2, npos, nneg = int(lo.sum()) + int(hi.sum()), int(p.sum()), int(q.sum())
+                pairs[f, u] = (u2, npos, nneg)
+                wpos[f, u], wneg[f, u] = npos, nneg
+                if npos * nneg:
+                    auc[f, u] = float(u2) / (2.0 * float(npos) * float(nneg))
+                continue
+            wv = np.asarray(w, dtype=dtype)
+            C = np.concatenate([np.zeros(1, dtype=dtype), np.cumsum(wv[q][order], dtype=dtype)])
+            num = (wv[p] * (C[lo] + C[hi])).sum(dtype=dtype) / 2
+            wpos[f, u] = wv[p].sum(dtype=dtype)
+            wneg[f, u] = C[-1]
+            if wpos[f, u] * wneg[f, u] > 0:
+                auc[f, u] = num / (wpos[f, u] * wneg[f, u])
+    out = {"auc": auc, "pos_weight": wpos.astype(np.double), "neg_weight": wneg.astype(np.double)}
+    if w is None:
+        out["pairs"] = pairs
     return out

@@ -84,6 +84,25 @@ class SparsePolyClassifierMixin(ClassifierMixin):
         """Class labels as seen in ``fit`` (``base.py:86-100``)."""
         return self.label_binarizer_.inverse_transform(self.decision_function(X) > 0)
 
+    def roc_auc(self, X, y, sample_weight=None):
+        """The exact ROC-AUC of ``decision_function(X)`` against the labels ``y`` (as seen in
+        ``fit``), ties counted half, optionally weighted: scored, sorted and counted on the device
+        (``ModelBank.group_auc`` of the one-member bank).  NaN where ``y``
+        lacks a class."""
+        from sklearn.exceptions import NotFittedError
+
+        from .bank import ModelBank
+
+        if not hasattr(self, "label_binarizer_"):
+            raise NotFittedError("%s is not fitted yet." % type(self).__name__)
+        labels = np.asarray(y).ravel()
+        unknown = np.setdiff1d(labels, self.label_binarizer_.classes_)
+        if unknown.size:
+            raise ValueError("y holds labels unseen in fit: %r" % (unknown.tolist(),))
+        target = self.label_binarizer_.transform(labels).ravel().astype(np.double)  # -1 / +1
+        with ModelBank([self]) as bank:
+            return float(bank.group_auc(X, target, sample_weight=sample_weight)["auc"][0, 0])
+
     def predict_proba(self, X):
         """P(y = +1 | x) under the logistic loss (``base.py:102-124``)."""
         if self.loss != "logistic":

@@ -13,7 +13,7 @@ JOBS="${SPFM_BUILD_JOBS:-$(nproc)}"
 TAG="$(cat "$HERE"/*.hip "$HERE"/*.h "$HERE"/*.cpp "$HERE/../../include/spfm.h" | sha256sum | cut -c1-12)"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -DSPFM_BUILD_TAG=\"$TAG\""
 # heaviest units first
-UNITS="spfm_engine_prb_f32 spfm_engine_prb_f64 spfm_engine_pbprb_f32 spfm_engine_pbprb_f64 spfm_engine_pcd spfm_engine_pbcd spfm_engine_wide spfm_engine_psgd spfm_engine_core spfm_ingest spfm_colour spfm_engine_gram spfm_engine_objective spfm_engine_interactions spfm_engine_partners spfm_engine_rank spfm_engine_explain spfm_engine_pairs spfm_engine_bank spfm_engine_foldin"
+UNITS="spfm_engine_prb_f32 spfm_engine_prb_f64 spfm_engine_pbprb_f32 spfm_engine_pbprb_f64 spfm_engine_pcd spfm_engine_pbcd spfm_engine_wide spfm_engine_psgd spfm_engine_core spfm_ingest spfm_colour spfm_engine_gram spfm_engine_objective spfm_engine_interactions spfm_engine_partners spfm_engine_rank spfm_engine_explain spfm_engine_pairs spfm_engine_bank spfm_engine_bank_auc spfm_engine_foldin"
 # a unit is rebuilt when its source, any header or the flags changed (hash kept beside the object)
 HDRHASH="$(cat "$HERE"/*.h "$HERE/../../include/spfm.h" | sha256sum | cut -c1-16)"
 compile() {

@@ -1369,6 +1369,13 @@ struct spfm_engine {
     DevBuf bk_oi, bk_o0, bk_o1;            // per-row results of one slab
     DevBuf bk_gw, bk_gg, bk_gpart, bk_gacc;  // group sums: weights and ids of one slab, its partial
                                              // tables, the call's running Q x G x F table
+    // spfm_bank_group_auc (spfm_engine_bank_auc.hip): allocated by
+    // auc_begin, freed by auc_release when the call returns
+    DevBuf bk_akey, bk_ameta, bk_arow, bk_aw;  // keys (F x n), class and group (F x n), 0..n-1, weights
+    DevBuf bk_askey, bk_asrow, bk_atmp;        // sorted keys and rows of one batch, the sort's storage
+    DevBuf bk_asets, bk_ablk, bk_aout;         // set masks, the walk's block records, its results
+    int bk_abatch = 0;                         // members per sort batch of the call
+    size_t bk_atmp_bytes = 0;                  // the sort's storage for n pairs
     bool bk_have = false, bk_lin = false;
     int bk_F = 0, bk_S = 0, bk_d = 0, bk_blocks = 0, bk_degree[2] = {0, 0};
     int64_t bk_slab_nnz = 0;               // spfm_bank_set_partition: stored entries per slab (0 = default)
@@ -1397,6 +1404,9 @@ struct spfm_engine {
         const int32_t* group;    // group sums: (n) ids in [0, G) or NULL = all 0
         int G, Q;                // group sums
         const int32_t* metrics;  // group sums: (Q) SPFM_LOSS_* / SPFM_METRIC_* ids
+        const uint32_t* sets;    // group auc: (F x U) bitmasks over the groups or NULL
+        int U;                   // group auc
+        int64_t* pairs;          // group auc: (F x U x 3) or NULL
     };
     int bank_check(const char* what, const BankCall& c);
     template <typename T, int M>
@@ -1405,6 +1415,14 @@ struct spfm_engine {
     int bank_slab(const BankCall& c, int64_t r0, int64_t r1, int64_t part0);
     template <typename T>
     int bank_run(const char* what, const BankCall& c);
+    // group auc: the checks beyond bank_check and the call's scratch; the keys of one slab behind
+    // its predict launches (enqueued, inside run_staged); sorts, walk and results after the last
+    int auc_check(const char* what, const BankCall& c);
+    int auc_begin(const BankCall& c);
+    void auc_slab(const BankCall& c, int64_t r0, int64_t rows);
+    int auc_finish(const BankCall& c);
+    void auc_empty(const BankCall& c);
+    void auc_release();
 
     // ------------------------------- fold-in of new columns (spfm_engine_foldin.hip)
     // With every other column fixed the model output is affine in the parameters of one column j:

@@ -947,6 +947,41 @@ class HipEngine(object):
                                                    out.ctypes.data_as(_capi._dp)))
         return out
 
+    def bank_group_auc(self, X, y, weight, group, G, sets):
+        """``spfm_bank_group_auc``: ``(out float64 (F, U, 3), pairs int64 (F, U, 3) or None)``:
+        per member and set ``auc, pos_weight, neg_weight`` and, unweighted, ``U2, n_pos, n_neg``.
+        ``y`` (n,) or (n, F); ``weight`` (n,) float64 or ``None`` (the integer path); ``group`` (n,)
+        int32 or ``None`` (all 0); ``sets`` uint32 (F, U) bitmasks over the groups or ``None`` (one
+        set per group)."""
+        n, args, keep = self._bank_args(X, "bank_group_auc")
+        ya, yp = _capi.f64(y)
+        F = self.bank_shape[0]
+        if ya.shape not in ((n,), (n, F)):
+            raise ValueError("bank_group_auc: y must be (%d,) or (%d, %d), got %r"
+                             % (n, n, F, ya.shape))
+        wp = gp = sp_ = None
+        if weight is not None:
+            wa, wp = _capi.f64(weight)
+            if wa.shape != (n,):
+                raise ValueError("bank_group_auc: weight must be (%d,), got %r" % (n, wa.shape))
+        if group is not None:
+            ga, gp = _capi.i32(group)
+            if ga.shape != (n,):
+                raise ValueError("bank_group_auc: group must be (%d,), got %r" % (n, ga.shape))
+        U = max(int(G), 1)
+        if sets is not None:
+            sa = np.ascontiguousarray(sets, dtype=np.uint32)
+            if sa.ndim != 2 or sa.shape[0] != F:
+                raise ValueError("bank_group_auc: sets must be (%d, U), got %r" % (F, sa.shape))
+            U, sp_ = sa.shape[1], sa.ctypes.data_as(_capi._up)
+        out = np.zeros((F, max(U, 1), 3))
+        pairs = np.zeros((F, max(U, 1), 3), dtype=np.int64) if weight is None else None
+        self._check(self._lib.spfm_bank_group_auc(
+            *args, yp, int(ya.ndim == 2), wp, gp, int(G), sp_, int(U),
+            out.ctypes.data_as(_capi._dp),
+            None if pairs is None else pairs.ctypes.data_as(_capi._lp)))
+        return out, pairs
+
     def bank_mean(self, X, weights=None):
         """``spfm_bank_mean``: (n,) ``sum_f weights[f] score_if``, added in model order;
         ``weights`` ``None``: ``1 / F``."""

@@ -5,11 +5,15 @@ fits one clone per (grid point, fold) side by side -- K folds are K 0/1 masks ov
 and one colouring (``fit_concurrently(..., sample_weights=masks)``) -- stacks
 the fitted clones into ``ModelBank``s and scores every clone on every fold in one pass over ``X``
 per bank (``ModelBank.group_sums``).  Only the small (member, fold) tables
-leave the device; the held-out and the training scores are read off them on the host.
+leave the device; the held-out and the training scores are read off them on the host.  With
+``rank_metrics=("auc",)`` every bank makes one more pass, ``ModelBank.group_auc`` (DESIGN.md section
+22): the exact ROC-AUC of every clone on its held-out fold and on the union of the other folds --
+the latter is no function of per-fold values, so each clone asks for both sets of rows by name.
 
 ``fold_ids`` and the assembly of the result (``assemble_cv``) are pure NumPy.
 
-Out of scope: AUC per fold (a sort per member and fold), the ranker, nested cross-validation.
+Out of scope: average precision and other curve metrics (``rank_metrics`` leaves room for them),
+the ranker, nested cross-validation.
 """
 import numpy as np
 
@@ -203,16 +207,56 @@ def _check_weighted_fit(est):
     est._get_loss(est.loss)
 
 
+RANK_METRICS = ("auc",)
+
+
+def _rank_args(rank_metrics, select, metrics, classifier, refit):
+    """the checked ``rank_metrics`` (a tuple) of ``cross_validate_path``; every error is a
+    ValueError"""
+    if isinstance(rank_metrics, str):
+        rank_metrics = (rank_metrics,)
+    rank_metrics = tuple(rank_metrics)
+    for m in rank_metrics:
+        if not isinstance(m, str) or m not in RANK_METRICS:
+            raise ValueError("unknown rank metric %r: rank_metrics must be among %s"
+                             % (m, RANK_METRICS))
+    if len(set(rank_metrics)) != len(rank_metrics):
+        raise ValueError("rank_metrics %r name the same metric twice" % (rank_metrics,))
+    if rank_metrics and not classifier:
+        raise ValueError("rank_metrics need a classifier: the ROC-AUC of a regressor's targets is "
+                         "not defined")
+    if select is not None and select != "loss" and select not in rank_metrics:
+        raise ValueError("select must be None, 'loss' or one of rank_metrics %r, got %r"
+                         % (rank_metrics, select))
+    if select == "loss" and "loss" not in metrics:
+        raise ValueError("select='loss' picks the smallest mean test 'loss': add it to metrics")
+    if refit and select not in rank_metrics and "loss" not in metrics:
+        raise ValueError("refit=True picks the smallest mean test 'loss': add it to metrics")
+    return rank_metrics
+
+
+def _check_rank_folds(y_score, w, fold, K):
+    """every held-out fold holds weight of both classes -- and with it every training complement,
+    which is a union of at least one such fold"""
+    pos = np.bincount(fold, weights=w * (y_score > 0), minlength=K)
+    neg = np.bincount(fold, weights=w * ~(y_score > 0), minlength=K)
+    for f in range(K):
+        if not (pos[f] > 0 and neg[f] > 0):
+            raise ValueError("rank_metrics: fold %d holds no %s weight"
+                             % (f, "positive" if not pos[f] > 0 else "negative"))
+
+
 class CVResult(object):
     """What ``cross_validate_path`` returns.  ``params``: the grid points; ``fold_`` (n,) the fold
     ids; ``test_[metric]`` / ``train_[metric]`` (n_params, K): column f the clone that held fold f
     out, scored on that fold / on the other folds; ``mean_test_[metric]`` / ``std_test_[metric]``
     (n_params,) over the folds; ``best_index_`` / ``best_params_``: the smallest mean test
-    ``"loss"`` (ties: the lowest index; ``None`` without that metric); ``estimators_``
+    ``"loss"`` (ties: the lowest index; ``None`` without that metric) or, where a rank metric was
+    named by ``select``, the largest mean test value of it (ties: the lowest index); ``estimators_``
     ``[p][f]`` the fitted clones or ``None``; ``best_estimator_`` (``refit=True``) fitted on all
     rows; ``info_``: ``banks``, ``passes`` over ``X`` and ``members`` per bank."""
 
-    def __init__(self, params, fold, K, scores, estimators, info):
+    def __init__(self, params, fold, K, scores, estimators, info, select=None):
         self.params = params
         self.fold_ = fold
         self.n_folds_ = K
@@ -222,7 +266,10 @@ class CVResult(object):
         self.mean_test_ = {m: t.mean(axis=1) for m, t in self.test_.items()}
         self.std_test_ = {m: t.std(axis=1) for m, t in self.test_.items()}
         self.best_index_ = self.best_params_ = None
-        if "loss" in self.mean_test_:
+        if select in RANK_METRICS:
+            self.best_index_ = int(np.argmax(self.mean_test_[select]))  # first of the largest
+            self.best_params_ = params[self.best_index_]
+        elif "loss" in self.mean_test_:
             self.best_index_ = int(np.argmin(self.mean_test_["loss"]))  # first of the smallest
             self.best_params_ = params[self.best_index_]
         self.estimators_ = estimators
@@ -231,7 +278,8 @@ class CVResult(object):
 
 
 def cross_validate_path(estimator, X, y, cv=5, sample_weight=None, metrics=None, refit=False,
-                        keep_estimators=True, max_concurrent=None, devices=None, **grid):
+                        keep_estimators=True, max_concurrent=None, devices=None, rank_metrics=(),
+                        select=None, **grid):
     """K-fold cross-validation of a parameter grid: ``grid`` as for ``fit_path`` (keyword ->
     sequence, all of one length).  For every grid point ``p`` and fold ``f`` a clone is fitted with
     ``sample_weight = (fold != f) * w`` -- all of them side by side over one device image per
@@ -242,9 +290,15 @@ def cross_validate_path(estimator, X, y, cv=5, sample_weight=None, metrics=None,
     ``estimator.random_state``), an (n,) array of fold ids, or an object with ``.split(X, y)``
     whose test sets partition the rows.  ``metrics``: names of ``ModelBank.group_sums``; default
     ``("loss",)``, classifiers ``("loss", "sign_error")``.  ``refit``: fit the best grid point on
-    all rows.  Returns a ``CVResult``.  Every argument error, and whatever a weighted ``fit``
-    refuses (``distributed=True``, plug-in regularizer objects, the ranker), is a ValueError raised
-    before any device work."""
+    all rows.  ``rank_metrics``: names among ``("auc",)``, classifiers only: one more pass per
+    bank (``ModelBank.group_auc``) gives every clone's exact ROC-AUC on its held-out fold
+    (``test_["auc"]``) and on the union of the other folds (``train_["auc"]``), weighted by
+    ``sample_weight``; a fold or a training complement without positive or without negative weight
+    is refused.  ``select``: what ``best_index_``, ``best_params_`` and ``refit`` go by: ``None`` /
+    ``"loss"`` the smallest mean test ``"loss"``, a rank metric the largest mean test value (ties:
+    the lowest index).  Returns a ``CVResult``.  Every argument error, and whatever a weighted
+    ``fit`` refuses (``distributed=True``, plug-in regularizer objects, the ranker), is a
+    ValueError raised before any device work."""
     from .bank import ModelBank, _group_args
     from .concurrent import fit_concurrently
 
@@ -272,8 +326,9 @@ def cross_validate_path(estimator, X, y, cv=5, sample_weight=None, metrics=None,
         raise ValueError("the grid varies loss (%s): name the metrics explicitly instead of 'loss'"
                          % ", ".join(sorted(map(str, losses))))
     _group_args(n, 1, y_score, fold, K, sample_weight, metrics, lambda: next(iter(losses)))
-    if refit and "loss" not in metrics:
-        raise ValueError("refit=True picks the smallest mean test 'loss': add it to metrics")
+    rank_metrics = _rank_args(rank_metrics, select, metrics, classifier, refit)
+    if rank_metrics:
+        _check_rank_folds(y_score, w, fold, K)
 
     clones = [make(p) for p in params for _ in range(K)]  # member p * K + f holds fold f out
     held = np.tile(np.arange(K), len(params))
@@ -284,17 +339,28 @@ def cross_validate_path(estimator, X, y, cv=5, sample_weight=None, metrics=None,
     chunks = bank_chunks([_kind(e) for e in clones], [e.n_components for e in clones])
     tables = {m: np.zeros((len(clones), K)) for m in metrics}
     weight = None
+    ranks = {m: (np.zeros(len(clones)), np.zeros(len(clones))) for m in rank_metrics}
     for members in chunks:
         with ModelBank([clones[i] for i in members]) as bank:
             tab = bank.group_sums(X, y_score, groups=fold, n_groups=K, sample_weight=sample_weight,
                                   metrics=metrics)
+            if rank_metrics:  # per member: its held-out fold, and every other fold
+                own = held[members][:, None] == np.arange(K)[None, :]
+                auc = bank.group_auc(X, y_score, groups=fold, n_groups=K,
+                                     sample_weight=sample_weight,
+                                     sets=np.stack([own, ~own], axis=1))["auc"]
+                ranks["auc"][0][members] = auc[:, 0]
+                ranks["auc"][1][members] = auc[:, 1]
         weight = tab["weight"]
         for m in metrics:
             tables[m][members] = tab[m]
-    info = dict(banks=len(chunks), passes=len(chunks), members=[len(c) for c in chunks])
+    info = dict(banks=len(chunks), passes=len(chunks) * (2 if rank_metrics else 1),
+                members=[len(c) for c in chunks])
     estimators = [clones[p * K:(p + 1) * K] for p in range(len(params))] if keep_estimators \
         else None
-    result = CVResult(params, fold, K, assemble_cv(tables, weight, held), estimators, info)
+    scores = assemble_cv(tables, weight, held)
+    scores.update(ranks)
+    result = CVResult(params, fold, K, scores, estimators, info, select)
     if refit:
         best = make(result.best_params_)
         kw = {} if sample_weight is None else {"sample_weight": sample_weight}
