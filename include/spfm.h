@@ -1263,6 +1263,56 @@ int spfm_bank_group_auc(spfm_handle h, int64_t n, int32_t d, const int64_t* indp
                         const uint32_t* sets /* F x U bitmasks over groups, or NULL */, int U,
                         double* out /* F x U x 3: auc, pos_weight, neg_weight */,
                         int64_t* pairs /* F x U x 3 or NULL; only when weight == NULL */);
+/* spfm_bank_group_curve: average precision, the best F1 and the KS distance of every member on sets
+ * of rows, with the thresholds of the two maxima, behind the scoring pass, the key images and the
+ * sorts of spfm_bank_group_auc.  Rows, sets, groups, positives (y_if > 0),
+ * weights and -0.0 == +0.0 are exactly as there.  For one member and one set, w_p the weight of a
+ * row of the set (1 unweighted) and 0 of any other row, go through the member's tie runs from the
+ * highest score down; for run r
+ *   Prun(r), Nrun(r) = the positive / negative weight of the run,
+ *   TP(r), FP(r)     = the positive / negative weight of all runs down to and including r,
+ * and r is a candidate when Prun(r) + Nrun(r) > 0 (it holds a row of the set of non-zero weight: a
+ * row of weight 0 is the same as an absent row).  Then
+ *   average_precision = (1 / W_pos) sum over the candidates of Prun(r) * (TP(r) / (TP(r) + FP(r))),
+ *   best_f1           = max over the candidates of 2 TP(r) / ((TP(r) + FP(r)) + W_pos),
+ *   ks                = max over the candidates of |TP(r) / W_pos - FP(r) / W_neg|.
+ * Of several candidates that reach a maximum the one with the highest score wins.  Each maximum
+ * reports its threshold -- the run's score, the zero run as +0.0: predict positive where
+ * decision_function >= threshold -- and its TP and FP.
+ *   out[f][u]    = {ap, f1, f1_thr, f1_tp, f1_fp, ks, ks_thr, ks_tp, ks_fp, W_pos, W_neg};
+ *   counts[f][u] = {n_pos, n_neg, f1_tp, f1_fp, ks_tp, ks_fp}, written only for weight == NULL.
+ * weight == NULL (integers only): the two maxima are chosen by exact integer comparison (F1 by
+ * cross-multiplication in unsigned 64 bit, KS by |TP n_neg - FP n_pos|), then
+ *   f1 = (double)(2 TP) / (double)(TP + FP + n_pos),
+ *   ks = (double)|TP n_neg - FP n_pos| / ((double)n_pos * (double)n_neg):
+ * counts, thresholds, f1 and ks depend on nothing but the scores and labels.  Weighted, the doubles
+ * above are compared as written; the winning ks is then reported in the integer form,
+ * |TP W_neg - FP W_pos| / (W_pos W_neg) in doubles, so that integer weights give the bits that
+ * replicated rows give.  The terms of ap, Prun * (TP / (TP + FP)) in double, are added in
+ * blocks of SPFM_BANK_RANK_BLOCK sorted positions from the top, the blocks in order
+ * (spfm_bank_curve.hip.h: no atomics, every addend non-negative): every value has the same bits
+ * from run to run, for every slab size, every F, every position of the member and every batch.
+ * ap and f1 need W_pos > 0 (with W_neg == 0 they are 1.0 by the formulas), ks needs both class
+ * weights; what is undefined is NaN, its threshold NaN and its TP / FP 0; the weights are reported
+ * all the same.  An empty set gives NaN and zeros; n = 0 is valid.
+ * auc_out (F x U x 3) and auc_pairs (F x U x 3, weight == NULL only), where given, receive what
+ * spfm_bank_group_auc gives for the same arguments, bit for bit, from the same sorted copies: one
+ * scoring pass and one sort per member for both tables.
+ * Errors: those of spfm_bank_group_auc, each before the first write to an output and before any
+ * device work; NULL out -> SPFM_ERR_INVALID.  The scratch is that call's plus 96 nb U Fb bytes of
+ * this walk's block records, inside the same SPFM_BANK_AUC_MAX_BYTES; SPFM_BANK_AUC_BATCH applies
+ * unchanged. */
+#define SPFM_BANK_CURVE_VALUES 11  /* ap, f1, f1_thr, f1_tp, f1_fp, ks, ks_thr, ks_tp, ks_fp, W_pos, W_neg */
+#define SPFM_BANK_CURVE_COUNTS 6   /* n_pos, n_neg, f1_tp, f1_fp, ks_tp, ks_fp */
+int spfm_bank_group_curve(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
+                          const int32_t* indices, const double* data, const double* y,
+                          int per_model, const double* weight /* n, or NULL: integer path */,
+                          const int32_t* group /* n ids in [0, G), or NULL = all 0 */, int G,
+                          const uint32_t* sets /* F x U bitmasks over groups, or NULL */, int U,
+                          double* out /* F x U x 11 */,
+                          int64_t* counts /* F x U x 6, written only for weight == NULL; may be NULL */,
+                          double* auc_out /* F x U x 3 as spfm_bank_group_auc's out, or NULL */,
+                          int64_t* auc_pairs /* as spfm_bank_group_auc's pairs, or NULL */);
 int spfm_bank_set_partition(spfm_handle h, int64_t slab_nnz);
 int spfm_bank_info(spfm_handle h, int64_t* out4);
 int spfm_bank_release(spfm_handle h);

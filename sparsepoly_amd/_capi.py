@@ -117,7 +117,7 @@ SYMBOLS = [
     "spfm_explain_info",
     "spfm_explain_pairs_csr", "spfm_explain_pairs_topk_csr", "spfm_explain_pairs_grouped_csr",
     "spfm_bank_set", "spfm_bank_scores", "spfm_bank_argmax", "spfm_bank_losses", "spfm_bank_mean",
-    "spfm_bank_group_sums", "spfm_bank_group_auc",
+    "spfm_bank_group_sums", "spfm_bank_group_auc", "spfm_bank_group_curve",
     "spfm_bank_set_partition", "spfm_bank_info", "spfm_bank_release",
     "spfm_foldin_csr", "spfm_foldin_set_partition", "spfm_foldin_info",
 ]
@@ -141,6 +141,8 @@ BANK_MAX_METRICS = 4  # SPFM_BANK_MAX_METRICS
 BANK_MAX_SETS = 32  # SPFM_BANK_MAX_SETS
 BANK_RANK_BLOCK = 256  # SPFM_BANK_RANK_BLOCK
 BANK_AUC_MAX_BYTES = 1 << 30  # SPFM_BANK_AUC_MAX_BYTES
+BANK_CURVE_VALUES = 11  # SPFM_BANK_CURVE_VALUES
+BANK_CURVE_COUNTS = 6  # SPFM_BANK_CURVE_COUNTS
 # metric ids of spfm_bank_group_sums: the SPFM_LOSS_* ids, SPFM_METRIC_ABS_ERROR / _SIGN_ERROR
 BANK_METRICS = dict(LOSSES, abs_error=16, sign_error=17)
 FOLDIN_MAX_UNKNOWNS = 128  # SPFM_FOLDIN_MAX_UNKNOWNS
@@ -301,6 +303,8 @@ def load():
     L.spfm_bank_group_sums.argtypes = _bank + [_dp, C.c_int, _dp, _ip, C.c_int, C.c_int, _ip, _dp]
     L.spfm_bank_group_auc.argtypes = _bank + [_dp, C.c_int, _dp, _ip, C.c_int, _up, C.c_int, _dp,
                                               _lp]
+    L.spfm_bank_group_curve.argtypes = _bank + [_dp, C.c_int, _dp, _ip, C.c_int, _up, C.c_int, _dp,
+                                                _lp, _dp, _lp]
     L.spfm_bank_set_partition.argtypes = [_h, C.c_int64]
     L.spfm_bank_info.argtypes = [_h, _lp]
     L.spfm_bank_release.argtypes = [_h]

@@ -9,7 +9,9 @@ entry costs one contiguous read of ``sum_f k_f`` doubles, and what users reduce 
 to -- the best model per row, a loss per model, a weighted mean, per member and fold of the rows
 the weighted sums of a few metrics (``group_sums``: the scoring half of cross-validation, see
 ``model_selection.py``), per member and set of rows the exact ROC-AUC (``group_auc``: a sort per
-member on the device) -- is formed on the device, so only that leaves it.
+member on the device), average precision, the best F1 and the KS distance
+with their thresholds (``group_curve``: a second walk over the same sorted scores, section 23) -- is
+formed on the device, so only that leaves it.
 There is no CPU path: without the library or a GPU the device calls raise.
 
 The members are all factorization machines of one ``degree``, ``fit_lower`` and ``fit_linear``,
@@ -18,7 +20,8 @@ of a member does not depend on the other members or on its position: column f of
 the one-model bank of that member bit for bit.
 
 ``restate_bank_scores`` is the plain NumPy restatement, a test aid that never touches the device;
-``restate_group_sums`` and ``restate_group_auc`` restate the reductions from given scores.
+``restate_group_sums``, ``restate_group_auc`` and ``restate_group_curve`` restate the reductions
+from given scores.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -207,6 +210,41 @@ class ModelBank(object):
             out["pairs"] = pairs
         return out
 
+    def group_curve(self, X, y, groups=None, n_groups=None, sample_weight=None, sets=None,
+                    auc=False):
+        """Per member and set of rows the average precision, the best F1 and the KS distance of
+        the scores, with the thresholds of the two maxima, in one pass over ``X`` and one sort per
+        member on the device.  The arguments are ``group_auc``'s.  Going through a member's tie
+        runs from the highest score down, with ``TP`` / ``FP`` the positive / negative weight of
+        all runs down to and including a run and ``Prun`` its own positive weight, over the runs
+        that hold weight of the set: ``average_precision = sum Prun TP / (TP + FP) / W_pos``,
+        ``best_f1 = max 2 TP / (TP + FP + W_pos)``, ``ks = max |TP / W_pos - FP / W_neg|``; of
+        several runs that reach a maximum the highest score wins.  Returns a dict of float64
+        (F, U) arrays: ``"average_precision"``, ``"pos_weight"``, ``"neg_weight"``; ``"best_f1"``,
+        ``"f1_threshold"``, ``"f1_tp"``, ``"f1_fp"``; ``"ks"``, ``"ks_threshold"``, ``"ks_tp"``,
+        ``"ks_fp"``.  A threshold is the run's score (a zero as ``+0.0``): predict positive where
+        ``decision_function >= threshold``.  Unweighted the maxima are chosen by exact integer
+        comparison and ``"counts"``, int64 (F, U, 6), holds ``n_pos, n_neg, f1_tp, f1_fp, ks_tp,
+        ks_fp``.  ``auc=True`` adds ``"auc"`` and, unweighted, ``"pairs"`` -- the very values of
+        ``group_auc`` -- from the same pass and sorts.  ``average_precision`` and ``best_f1`` are
+        NaN without positive weight (1.0 without negative weight), ``ks`` without either; a NaN
+        value has a NaN threshold and ``tp = fp = 0``.  Every argument error is a ValueError raised
+        before the device is touched.  Only the tables leave the device."""
+        Xa = self._X(X)
+        ya, ga, G, wa, _, _ = _group_args(Xa.shape[0], self.n_models, y, groups, n_groups,
+                                          sample_weight, ("sign_error",), None)
+        masks = _set_masks(sets, self.n_models, G)
+        tab, counts, auc_tab, pairs = self._engine.bank_group_curve(Xa, ya, wa, ga, G, masks,
+                                                                    auc=bool(auc))
+        out = {name: tab[:, :, k] for k, name in enumerate(CURVE_FIELDS)}
+        if counts is not None:
+            out["counts"] = counts
+        if auc_tab is not None:
+            out["auc"] = auc_tab[:, :, 0]
+        if pairs is not None:
+            out["pairs"] = pairs
+        return out
+
     def mean(self, X, weights=None):
         """(n,) ``sum_f weights[f] score_if``, the weights applied in member order; default
         ``1 / F``."""
@@ -252,6 +290,9 @@ ModelBank.group_sums.__doc__ %= (_capi.BANK_MAX_GROUPS, _capi.BANK_MAX_METRICS)
 ModelBank.group_auc.__doc__ %= (_capi.BANK_MAX_SETS,)
 
 METRICS = ("loss",) + tuple(sorted(_capi.BANK_METRICS))
+# the SPFM_BANK_CURVE_VALUES values of one (member, set) of spfm_bank_group_curve, in its order
+CURVE_FIELDS = ("average_precision", "best_f1", "f1_threshold", "f1_tp", "f1_fp", "ks",
+                "ks_threshold", "ks_tp", "ks_fp", "pos_weight", "neg_weight")
 
 
 def _group_args(n, F, y, groups, n_groups, sample_weight, metrics, default_loss):
@@ -452,4 +493,100 @@ def restate_group_auc(scores, y, w, groups, G, sets, wide=False):
     out = {"auc": auc, "pos_weight": wpos.astype(np.double), "neg_weight": wneg.astype(np.double)}
     if w is None:
         out["pairs"] = pairs
+    return out
+
+
+def restate_group_curve(scores, y, w, groups, G, sets, wide=False):
+    """Test aid, NumPy only, never touches the device: what ``group_curve`` gives (without
+    ``auc``), from given ``scores`` (n, F).  The arguments are ``restate_group_auc``'s.  The rows of
+    a set that carry weight are gathered into tie runs from the highest score down; ``TP`` / ``FP``
+    are running sums over the runs.  Unweighted (``w`` ``None``) everything is counted and compared
+    in Python integers: F1 by cross-multiplication, KS by ``|TP n_neg - FP n_pos|``, a later run
+    replacing the held one only when strictly greater.  Weighted the quotients ``2 TP / ((TP + FP)
+    + W_pos)`` and ``|TP / W_pos - FP / W_neg|`` are compared in double, or in ``np.longdouble``
+    with ``wide``; ``np.argmax`` keeps the first, the highest score.  The winning ``ks`` is reported
+    as ``|TP W_neg - FP W_pos| / (W_pos W_neg)``, the integer form, so that integer weights give
+    the bits of replicated rows."""
+    dtype = np.longdouble if wide else np.double
+    scores = np.asarray(scores, dtype=np.double) + 0.0  # (-0.0 + 0.0 = +0.0: one zero)
+    n, F = scores.shape
+    y = np.asarray(y, dtype=np.double)
+    pos_all = np.broadcast_to((y[:, None] if y.ndim == 1 else y) > 0, (n, F))
+    groups = np.zeros(n, dtype=np.intp) if groups is None else np.asarray(groups, dtype=np.intp)
+    S = _sets_array(sets, F, G)
+    U = S.shape[1]
+    out = {name: np.zeros((F, U)) for name in CURVE_FIELDS}
+    for name in ("average_precision", "best_f1", "f1_threshold", "ks", "ks_threshold"):
+        out[name][:] = np.nan
+    counts = np.zeros((F, U, 6), dtype=np.int64)
+    wv = None if w is None else np.asarray(w, dtype=dtype)
+    for f in range(F):
+        for u in range(U):
+            rows = S[f, u][groups]
+            if wv is not None:
+                rows = rows & (wv > 0)  # a row of weight 0 is the same as an absent row
+            if not rows.any():
+                continue
+            s = scores[rows, f]
+            pos = pos_all[rows, f]
+            thr, inv = np.unique(-s, return_inverse=True)  # ascending in -s: the top run first
+            thr = -thr + 0.0
+            inv = inv.ravel()
+            R = thr.shape[0]
+            cell = {}
+            if wv is None:
+                prun = np.bincount(inv, weights=pos, minlength=R).astype(np.int64).tolist()
+                nrun = np.bincount(inv, weights=~pos, minlength=R).astype(np.int64).tolist()
+                npos, nneg = sum(prun), sum(nrun)
+                tp = fp = 0
+                ap = 0.0
+                f1 = ks = None  # (tp, fp, run) held; ks with its value in front
+                for r in range(R):
+                    tp += prun[r]
+                    fp += nrun[r]
+                    ap += float(prun[r]) * (float(tp) / float(tp + fp))
+                    if f1 is None or tp * (f1[0] + f1[1] + npos) > f1[0] * (tp + fp + npos):
+                        f1 = (tp, fp, r)
+                    v = abs(tp * nneg - fp * npos)
+                    if ks is None or v > ks[0]:
+                        ks = (v, tp, fp, r)
+                cell["pos_weight"], cell["neg_weight"] = npos, nneg
+                counts[f, u, :2] = (npos, nneg)
+                if npos > 0:
+                    cell["average_precision"] = ap / float(npos)
+                    cell["best_f1"] = float(2 * f1[0]) / float(f1[0] + f1[1] + npos)
+                    cell["f1_threshold"], cell["f1_tp"], cell["f1_fp"] = thr[f1[2]], f1[0], f1[1]
+                    counts[f, u, 2:4] = f1[:2]
+                if npos > 0 and nneg > 0:
+                    cell["ks"] = float(ks[0]) / (float(npos) * float(nneg))
+                    cell["ks_threshold"], cell["ks_tp"], cell["ks_fp"] = thr[ks[3]], ks[1], ks[2]
+                    counts[f, u, 4:6] = ks[1:3]
+            else:
+                ws = wv[rows]
+                prun = np.zeros(R, dtype=dtype)
+                nrun = np.zeros(R, dtype=dtype)
+                np.add.at(prun, inv[pos], ws[pos])
+                np.add.at(nrun, inv[~pos], ws[~pos])
+                tp, fp = np.cumsum(prun, dtype=dtype), np.cumsum(nrun, dtype=dtype)
+                wpos, wneg = tp[-1], fp[-1]
+                cell["pos_weight"], cell["neg_weight"] = wpos, wneg
+                if wpos > 0:
+                    # (cumsum adds one after the other, as the integer loop above does)
+                    cell["average_precision"] = np.cumsum(prun * (tp / (tp + fp)),
+                                                          dtype=dtype)[-1] / wpos
+                    val = 2 * tp / ((tp + fp) + wpos)
+                    r = int(np.argmax(val))
+                    cell["best_f1"], cell["f1_threshold"] = val[r], thr[r]
+                    cell["f1_tp"], cell["f1_fp"] = tp[r], fp[r]
+                if wpos > 0 and wneg > 0:
+                    val = np.abs(tp / wpos - fp / wneg)
+                    r = int(np.argmax(val))
+                    # chosen by the quotients, reported in the integer form
+                    cell["ks"] = abs(tp[r] * wneg - fp[r] * wpos) / (wpos * wneg)
+                    cell["ks_threshold"] = thr[r]
+                    cell["ks_tp"], cell["ks_fp"] = tp[r], fp[r]
+            for name, v in cell.items():
+                out[name][f, u] = float(v)
+    if w is None:
+        out["counts"] = counts
     return out

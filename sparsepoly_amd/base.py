@@ -89,9 +89,15 @@ class SparsePolyClassifierMixin(ClassifierMixin):
         ``fit``), ties counted half, optionally weighted: scored, sorted and counted on the device
         (``ModelBank.group_auc`` of the one-member bank).  NaN where ``y``
         lacks a class."""
-        from sklearn.exceptions import NotFittedError
-
         from .bank import ModelBank
+
+        target = self._rank_target(y)
+        with ModelBank([self]) as bank:
+            return float(bank.group_auc(X, target, sample_weight=sample_weight)["auc"][0, 0])
+
+    def _rank_target(self, y):
+        """the labels ``y`` (as seen in ``fit``) as -1 / +1, for the rank statistics"""
+        from sklearn.exceptions import NotFittedError
 
         if not hasattr(self, "label_binarizer_"):
             raise NotFittedError("%s is not fitted yet." % type(self).__name__)
@@ -99,9 +105,39 @@ class SparsePolyClassifierMixin(ClassifierMixin):
         unknown = np.setdiff1d(labels, self.label_binarizer_.classes_)
         if unknown.size:
             raise ValueError("y holds labels unseen in fit: %r" % (unknown.tolist(),))
-        target = self.label_binarizer_.transform(labels).ravel().astype(np.double)  # -1 / +1
+        return self.label_binarizer_.transform(labels).ravel().astype(np.double)
+
+    def average_precision(self, X, y, sample_weight=None):
+        """The average precision of ``decision_function(X)`` against the labels ``y`` (as seen in
+        ``fit``), the step-wise sum over the distinct scores as in scikit-learn, optionally
+        weighted: scored, sorted and walked on the device (``ModelBank.group_curve`` of the
+        one-member bank).  NaN where ``y`` holds no positive."""
+        from .bank import ModelBank
+
+        target = self._rank_target(y)
         with ModelBank([self]) as bank:
-            return float(bank.group_auc(X, target, sample_weight=sample_weight)["auc"][0, 0])
+            tab = bank.group_curve(X, target, sample_weight=sample_weight)
+        return float(tab["average_precision"][0, 0])
+
+    def operating_point(self, X, y, by="f1", sample_weight=None):
+        """A decision threshold from the rows ``X``, ``y``: the score at which F1 (``by="f1"``) or
+        the KS distance ``|TPR - FPR|`` (``by="ks"``) is largest, the highest such score where
+        several reach it (``ModelBank.group_curve`` of the one-member bank).
+        Returns a dict: ``threshold`` (predict positive where ``decision_function >= threshold``;
+        ``predict`` itself keeps cutting at ``> 0``), ``value``, ``tp`` and ``fp`` (the positive and
+        negative weight at or above the threshold), ``pos_weight``, ``neg_weight``.  NaN where the
+        quantity is undefined (F1: no positive; KS: a class is missing)."""
+        from .bank import ModelBank
+
+        if by not in ("f1", "ks"):
+            raise ValueError("by must be 'f1' or 'ks', got %r" % (by,))
+        target = self._rank_target(y)
+        with ModelBank([self]) as bank:
+            tab = bank.group_curve(X, target, sample_weight=sample_weight)
+        names = dict(threshold=by + "_threshold", value="best_f1" if by == "f1" else "ks",
+                     tp=by + "_tp", fp=by + "_fp", pos_weight="pos_weight",
+                     neg_weight="neg_weight")
+        return {k: float(tab[v][0, 0]) for k, v in names.items()}
 
     def predict_proba(self, X):
         """P(y = +1 | x) under the logistic loss (``base.py:102-124``)."""

@@ -1374,6 +1374,8 @@ struct spfm_engine {
     DevBuf bk_akey, bk_ameta, bk_arow, bk_aw;  // keys (F x n), class and group (F x n), 0..n-1, weights
     DevBuf bk_askey, bk_asrow, bk_atmp;        // sorted keys and rows of one batch, the sort's storage
     DevBuf bk_asets, bk_ablk, bk_aout;         // set masks, the walk's block records, its results
+    DevBuf bk_cblk, bk_cout;  // spfm_bank_group_curve: its walk's block
+                              // records and results, beside the scratch above
     int bk_abatch = 0;                         // members per sort batch of the call
     size_t bk_atmp_bytes = 0;                  // the sort's storage for n pairs
     bool bk_have = false, bk_lin = false;
@@ -1407,6 +1409,8 @@ struct spfm_engine {
         const uint32_t* sets;    // group auc: (F x U) bitmasks over the groups or NULL
         int U;                   // group auc
         int64_t* pairs;          // group auc: (F x U x 3) or NULL
+        double* curve;           // group curve: (F x U x SPFM_BANK_CURVE_VALUES); out is its auc_out
+        int64_t* counts;         // group curve: (F x U x SPFM_BANK_CURVE_COUNTS) or NULL
     };
     int bank_check(const char* what, const BankCall& c);
     template <typename T, int M>
@@ -1415,8 +1419,9 @@ struct spfm_engine {
     int bank_slab(const BankCall& c, int64_t r0, int64_t r1, int64_t part0);
     template <typename T>
     int bank_run(const char* what, const BankCall& c);
-    // group auc: the checks beyond bank_check and the call's scratch; the keys of one slab behind
-    // its predict launches (enqueued, inside run_staged); sorts, walk and results after the last
+    // group auc and group curve: the checks beyond bank_check and the call's scratch; the keys of
+    // one slab behind its predict launches (enqueued, inside run_staged); sorts, walks and results
+    // after the last.  A call is the curve's when c.curve is set; its c.out (the AUC table) may be NULL
     int auc_check(const char* what, const BankCall& c);
     int auc_begin(const BankCall& c);
     void auc_slab(const BankCall& c, int64_t r0, int64_t rows);

@@ -1,9 +1,10 @@
 // spfm_engine_bank.hip -- spfm_bank_set / _scores / _argmax / _losses / _mean / _group_sums /
-// _group_auc / _set_partition / _info / _release (include/spfm.h): F fitted models, stacked along the component
+// _group_auc / _group_curve / _set_partition / _info / _release (include/spfm.h): F fitted models, stacked along the component
 // axis and resident on the handle, scored in one pass over the rows of a CSR matrix; the argmax,
 // the loss sums, the weighted mean and the grouped weighted sums are formed
 // on the device behind that pass (spfm_bank.hip.h); the rank statistic of spfm_bank_group_auc hangs
-// its own steps on the same slabs (spfm_engine_bank_auc.hip).
+// its own steps on the same slabs (spfm_engine_bank_auc.hip), and so do the
+// curve statistics of spfm_bank_group_curve (section 23).
 // Read-only like predict and independent of spfm_set_params: the bank brings its own parameters.
 // Rows go through in slabs bounded by stored entries.  See DESIGN.md section 17.
 #include "spfm_engine.hip.h"
@@ -31,14 +32,16 @@ namespace {
 // at most 96 MiB, the rows of a slab are capped so that scores and targets stay within 128 MiB.
 constexpr int64_t kBankRowBudget = 128ll << 20;
 constexpr int64_t kBankSlabMax = 1ll << 23;  // stored entries per slab: default and largest
-enum { BANK_GROUPS = 4, BANK_AUC = 5 };      // beside BANK_SCORES ... BANK_MEAN
+enum { BANK_GROUPS = 4, BANK_AUC = 5, BANK_CURVE = 6 };  // beside BANK_SCORES ... BANK_MEAN
+// the two calls that keep the keys of every slab and sort them (spfm_engine_bank_auc.hip)
+inline bool bank_sorts(int what) { return what == BANK_AUC || what == BANK_CURVE; }
 }  // namespace
 
 void spfm_engine::bank_release() {
     for (DevBuf* b : {&bk_pt, &bk_lams, &bk_w, &bk_koff, &bk_rp, &bk_ri, &bk_rv, &bk_sc, &bk_y,
                       &bk_wt, &bk_part, &bk_fin, &bk_oi, &bk_o0, &bk_o1, &bk_gw, &bk_gg, &bk_gpart,
                       &bk_gacc, &bk_akey, &bk_ameta, &bk_arow, &bk_aw, &bk_askey, &bk_asrow,
-                      &bk_atmp, &bk_asets, &bk_ablk, &bk_aout})
+                      &bk_atmp, &bk_asets, &bk_ablk, &bk_aout, &bk_cblk, &bk_cout})
         b->release();
     bk_have = false;
     bk_F = bk_S = bk_d = bk_blocks = 0;
@@ -116,9 +119,10 @@ int spfm_engine::bank_check(const char* what, const BankCall& c) {
             c.loss != SPFM_LOSS_LOGISTIC)
             FAIL(SPFM_ERR_INVALID, w + ": unknown loss");
         if (!c.out || (c.n > 0 && !c.y)) FAIL(SPFM_ERR_INVALID, w + ": NULL array");
-    } else if (c.what == BANK_GROUPS || c.what == BANK_AUC) {  // (auc: Q = 1, a metric of its own)
+    } else if (c.what == BANK_GROUPS || bank_sorts(c.what)) {  // (auc: Q = 1, a metric of its own)
         char buf[160];
-        if (!c.out || !c.metrics || (c.n > 0 && !c.y)) FAIL(SPFM_ERR_INVALID, w + ": NULL array");
+        const double* out = c.what == BANK_CURVE ? c.curve : c.out;  // (the curve's c.out may be NULL)
+        if (!out || !c.metrics || (c.n > 0 && !c.y)) FAIL(SPFM_ERR_INVALID, w + ": NULL array");
         if (c.G < 1 || c.Q < 1) FAIL(SPFM_ERR_INVALID, w + ": G and Q must be >= 1");
         if (c.G > SPFM_BANK_MAX_GROUPS) {
             snprintf(buf, sizeof buf, "%s: %d groups exceed SPFM_BANK_MAX_GROUPS = %d", what, c.G,
@@ -184,7 +188,7 @@ int spfm_engine::bank_slab(const BankCall& c, int64_t r0, int64_t r1, int64_t pa
         HIPC(bk_o1.alloc(sizeof(double) * (size_t)rows));
     }
     if (c.what == BANK_MEAN) HIPC(bk_o0.alloc(sizeof(double) * (size_t)rows));
-    if (c.what == BANK_LOSSES || c.what == BANK_GROUPS || c.what == BANK_AUC)
+    if (c.what == BANK_LOSSES || c.what == BANK_GROUPS || bank_sorts(c.what))
         HIPC(bk_y.alloc(sizeof(double) * (size_t)rows * (c.per_model ? F : 1)));
     const unsigned row_blocks = cdiv(rows, kBlock);
     const int cells = c.Q * c.G * F;  // group sums: the cells of one table
@@ -193,16 +197,16 @@ int spfm_engine::bank_slab(const BankCall& c, int64_t r0, int64_t r1, int64_t pa
         if (c.group) HIPC(bk_gg.alloc(sizeof(int32_t) * (size_t)rows));
         HIPC(bk_gpart.alloc(sizeof(double) * (size_t)row_blocks * cells));
     }
-    if (c.what == BANK_AUC && c.group) HIPC(bk_gg.alloc(sizeof(int32_t) * (size_t)rows));
+    if (bank_sorts(c.what) && c.group) HIPC(bk_gg.alloc(sizeof(int32_t) * (size_t)rows));
     std::vector<T> hv;  // staging of the values
     return run_staged([&]() -> int {
         SPFM_TRY(stage_csr_rows<T>(bk_rp, bk_ri, bk_rv, hv, c.indptr, c.indices, c.data, r0, r1));
-        if (c.what == BANK_LOSSES || c.what == BANK_GROUPS || c.what == BANK_AUC)
+        if (c.what == BANK_LOSSES || c.what == BANK_GROUPS || bank_sorts(c.what))
             SPFM_TRY(upload_to(bk_y.p, c.y + (size_t)r0 * (c.per_model ? F : 1),
                                (size_t)rows * (c.per_model ? F : 1)));
         if (c.what == BANK_GROUPS && c.weight)
             SPFM_TRY(upload_to(bk_gw.p, c.weight + r0, (size_t)rows));
-        if ((c.what == BANK_GROUPS || c.what == BANK_AUC) && c.group)
+        if ((c.what == BANK_GROUPS || bank_sorts(c.what)) && c.group)
             SPFM_TRY(upload_to(bk_gg.p, c.group + r0, (size_t)rows));
         for (int q = 0; q < bk_blocks; ++q) {
             (void)SPFM_DISPATCH_KIND(kind_of(bk_degree[q]), true,  // (2..6 or -1: bank_set)
@@ -235,7 +239,7 @@ int spfm_engine::bank_slab(const BankCall& c, int64_t r0, int64_t r1, int64_t pa
                                stream, (int64_t)row_blocks, cells, bk_gpart.as<double>(),
                                bk_gacc.as<double>());
         }
-        if (c.what == BANK_AUC) auc_slab(c, r0, rows);
+        if (bank_sorts(c.what)) auc_slab(c, r0, rows);
         HIPC(hipGetLastError());
         if (c.what == BANK_SCORES) SPFM_TRY(download(c.out + (size_t)r0 * F, sc, (size_t)rows * F));
         if (c.what == BANK_ARGMAX) {
@@ -251,17 +255,17 @@ int spfm_engine::bank_slab(const BankCall& c, int64_t r0, int64_t r1, int64_t pa
 template <typename T>
 int spfm_engine::bank_run(const char* what, const BankCall& c) {
     SPFM_TRY(bank_check(what, c));
-    if (c.what == BANK_AUC) SPFM_TRY(auc_check(what, c));
+    if (bank_sorts(c.what)) SPFM_TRY(auc_check(what, c));
     struct AucScratch {  // the rank statistic's scratch does not outlive the call
         spfm_engine* e;
         ~AucScratch() {
             if (e) e->auc_release();
         }
-    } auc_scratch{c.what == BANK_AUC ? this : nullptr};
+    } auc_scratch{bank_sorts(c.what) ? this : nullptr};
     bk_slabs = bk_launches = 0;
     const int F = bk_F;
     if (c.n == 0) {
-        if (c.what == BANK_AUC) auc_empty(c);
+        if (bank_sorts(c.what)) auc_empty(c);
         if (c.what == BANK_LOSSES) std::fill(c.out, c.out + F, 0.0);
         if (c.what == BANK_GROUPS) std::fill(c.out, c.out + (size_t)c.Q * F * c.G, 0.0);
         return SPFM_OK;
@@ -283,7 +287,7 @@ int spfm_engine::bank_run(const char* what, const BankCall& c) {
         HIPC(bk_gacc.alloc(sizeof(double) * (size_t)c.Q * c.G * F));
         HIPC(hipMemsetAsync(bk_gacc.p, 0, sizeof(double) * (size_t)c.Q * c.G * F, stream));
     }
-    if (c.what == BANK_AUC) SPFM_TRY(auc_begin(c));
+    if (bank_sorts(c.what)) SPFM_TRY(auc_begin(c));
     if (c.what == BANK_MEAN) {
         const std::vector<double> hw((size_t)F, 1.0 / (double)F);  // staging of the default
         HIPC(bk_wt.alloc(sizeof(double) * (size_t)F));
@@ -310,7 +314,7 @@ int spfm_engine::bank_run(const char* what, const BankCall& c) {
                 for (int f = 0; f < F; ++f)
                     c.out[((size_t)q * F + f) * c.G + g] = tab[((size_t)q * c.G + g) * F + f];
     }
-    if (c.what == BANK_AUC) SPFM_TRY(auc_finish(c));
+    if (bank_sorts(c.what)) SPFM_TRY(auc_finish(c));
     return SPFM_OK;
 }
 
@@ -379,6 +383,20 @@ int spfm_bank_group_auc(spfm_handle h, int64_t n, int32_t d, const int64_t* indp
                                      nullptr, 0, y, per_model ? 1 : 0, nullptr, weight, group, G,
                                      1, &kMetric, sets, U, pairs};
     return SPFM_DISPATCH(h->dtype, return h->bank_run<T>("bank_group_auc", c));
+}
+
+int spfm_bank_group_curve(spfm_handle h, int64_t n, int32_t d, const int64_t* indptr,
+                          const int32_t* indices, const double* data, const double* y,
+                          int per_model, const double* weight, const int32_t* group, int G,
+                          const uint32_t* sets, int U, double* out, int64_t* counts,
+                          double* auc_out, int64_t* auc_pairs) {
+    SPFM_GUARD(h);
+    static const int32_t kMetric = SPFM_METRIC_SIGN_ERROR;  // (bank_check reads one metric id)
+    const spfm_engine::BankCall c = {BANK_CURVE, n, d, indptr, indices, data, auc_out, nullptr,
+                                     nullptr, 0, y, per_model ? 1 : 0, nullptr, weight, group, G,
+                                     1, &kMetric, sets, U, auc_out ? auc_pairs : nullptr, out,
+                                     counts};
+    return SPFM_DISPATCH(h->dtype, return h->bank_run<T>("bank_group_curve", c));
 }
 
 int spfm_bank_set_partition(spfm_handle h, int64_t slab_nnz) {

@@ -982,6 +982,47 @@ class HipEngine(object):
             None if pairs is None else pairs.ctypes.data_as(_capi._lp)))
         return out, pairs
 
+    def bank_group_curve(self, X, y, weight, group, G, sets, auc=False):
+        """``spfm_bank_group_curve``: ``(out float64 (F, U, 11), counts int64 (F, U, 6) or None,
+        auc_out float64 (F, U, 3) or None, auc_pairs int64 (F, U, 3) or None)``: per member and set
+        ``ap, f1, f1_thr, f1_tp, f1_fp, ks, ks_thr, ks_tp, ks_fp, pos_weight, neg_weight`` and,
+        unweighted, ``n_pos, n_neg, f1_tp, f1_fp, ks_tp, ks_fp``; with ``auc`` the tables of
+        ``bank_group_auc`` from the same pass and sorts.  The arguments are ``bank_group_auc``'s."""
+        n, args, keep = self._bank_args(X, "bank_group_curve")
+        ya, yp = _capi.f64(y)
+        F = self.bank_shape[0]
+        if ya.shape not in ((n,), (n, F)):
+            raise ValueError("bank_group_curve: y must be (%d,) or (%d, %d), got %r"
+                             % (n, n, F, ya.shape))
+        wp = gp = sp_ = None
+        if weight is not None:
+            wa, wp = _capi.f64(weight)
+            if wa.shape != (n,):
+                raise ValueError("bank_group_curve: weight must be (%d,), got %r" % (n, wa.shape))
+        if group is not None:
+            ga, gp = _capi.i32(group)
+            if ga.shape != (n,):
+                raise ValueError("bank_group_curve: group must be (%d,), got %r" % (n, ga.shape))
+        U = max(int(G), 1)
+        if sets is not None:
+            sa = np.ascontiguousarray(sets, dtype=np.uint32)
+            if sa.ndim != 2 or sa.shape[0] != F:
+                raise ValueError("bank_group_curve: sets must be (%d, U), got %r" % (F, sa.shape))
+            U, sp_ = sa.shape[1], sa.ctypes.data_as(_capi._up)
+        U1 = max(U, 1)
+        out = np.zeros((F, U1, _capi.BANK_CURVE_VALUES))
+        ints = weight is None
+        counts = np.zeros((F, U1, _capi.BANK_CURVE_COUNTS), dtype=np.int64) if ints else None
+        auc_out = np.zeros((F, U1, 3)) if auc else None
+        pairs = np.zeros((F, U1, 3), dtype=np.int64) if auc and ints else None
+        self._check(self._lib.spfm_bank_group_curve(
+            *args, yp, int(ya.ndim == 2), wp, gp, int(G), sp_, int(U),
+            out.ctypes.data_as(_capi._dp),
+            None if counts is None else counts.ctypes.data_as(_capi._lp),
+            None if auc_out is None else auc_out.ctypes.data_as(_capi._dp),
+            None if pairs is None else pairs.ctypes.data_as(_capi._lp)))
+        return out, counts, auc_out, pairs
+
     def bank_mean(self, X, weights=None):
         """``spfm_bank_mean``: (n,) ``sum_f weights[f] score_if``, added in model order;
         ``weights`` ``None``: ``1 / F``."""

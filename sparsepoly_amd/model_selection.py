@@ -9,11 +9,13 @@ leave the device; the held-out and the training scores are read off them on the 
 ``rank_metrics=("auc",)`` every bank makes one more pass, ``ModelBank.group_auc`` (DESIGN.md section
 22): the exact ROC-AUC of every clone on its held-out fold and on the union of the other folds --
 the latter is no function of per-fold values, so each clone asks for both sets of rows by name.
+``"average_precision"`` and ``"ks"`` (``ModelBank.group_curve``) come from a
+second walk over the same sorted scores: any subset of the three names is still ONE more pass.
 
 ``fold_ids`` and the assembly of the result (``assemble_cv``) are pure NumPy.
 
-Out of scope: average precision and other curve metrics (``rank_metrics`` leaves room for them),
-the ranker, nested cross-validation.
+Out of scope: partial AUC and TPR at a fixed FPR, thresholds chosen on the training side of a fold
+and scored on the held-out side, the ranker, nested cross-validation.
 """
 import numpy as np
 
@@ -207,7 +209,7 @@ def _check_weighted_fit(est):
     est._get_loss(est.loss)
 
 
-RANK_METRICS = ("auc",)
+RANK_METRICS = ("auc", "average_precision", "ks")
 
 
 def _rank_args(rank_metrics, select, metrics, classifier, refit):
@@ -290,11 +292,14 @@ def cross_validate_path(estimator, X, y, cv=5, sample_weight=None, metrics=None,
     ``estimator.random_state``), an (n,) array of fold ids, or an object with ``.split(X, y)``
     whose test sets partition the rows.  ``metrics``: names of ``ModelBank.group_sums``; default
     ``("loss",)``, classifiers ``("loss", "sign_error")``.  ``refit``: fit the best grid point on
-    all rows.  ``rank_metrics``: names among ``("auc",)``, classifiers only: one more pass per
-    bank (``ModelBank.group_auc``) gives every clone's exact ROC-AUC on its held-out fold
-    (``test_["auc"]``) and on the union of the other folds (``train_["auc"]``), weighted by
-    ``sample_weight``; a fold or a training complement without positive or without negative weight
-    is refused.  ``select``: what ``best_index_``, ``best_params_`` and ``refit`` go by: ``None`` /
+    all rows.  ``rank_metrics``: names among ``("auc", "average_precision", "ks")``, classifiers
+    only: ONE more pass per bank, whatever the subset (``ModelBank.group_auc`` for ``("auc",)``
+    alone, else ``ModelBank.group_curve``), gives every clone's exact ROC-AUC, average precision and
+    KS distance on its held-out fold (``test_[m]``) and on the union of the other folds
+    (``train_[m]``), weighted by ``sample_weight``; a fold or a training complement without
+    positive or without negative weight is refused.  ``"best_f1"`` is not among them: a threshold
+    chosen on the held-out fold and scored on that same fold is optimistic (use
+    ``operating_point`` on rows of its own).  ``select``: what ``best_index_``, ``best_params_`` and ``refit`` go by: ``None`` /
     ``"loss"`` the smallest mean test ``"loss"``, a rank metric the largest mean test value (ties:
     the lowest index).  Returns a ``CVResult``.  Every argument error, and whatever a weighted
     ``fit`` refuses (``distributed=True``, plug-in regularizer objects, the ranker), is a
@@ -346,11 +351,15 @@ def cross_validate_path(estimator, X, y, cv=5, sample_weight=None, metrics=None,
                                   metrics=metrics)
             if rank_metrics:  # per member: its held-out fold, and every other fold
                 own = held[members][:, None] == np.arange(K)[None, :]
-                auc = bank.group_auc(X, y_score, groups=fold, n_groups=K,
-                                     sample_weight=sample_weight,
-                                     sets=np.stack([own, ~own], axis=1))["auc"]
-                ranks["auc"][0][members] = auc[:, 0]
-                ranks["auc"][1][members] = auc[:, 1]
+                kw = dict(groups=fold, n_groups=K, sample_weight=sample_weight,
+                          sets=np.stack([own, ~own], axis=1))
+                if rank_metrics == ("auc",):
+                    rtab = bank.group_auc(X, y_score, **kw)
+                else:  # the curve's walk, and the AUC's where asked, on one pass and one sort
+                    rtab = bank.group_curve(X, y_score, auc="auc" in rank_metrics, **kw)
+                for m in rank_metrics:
+                    ranks[m][0][members] = rtab[m][:, 0]
+                    ranks[m][1][members] = rtab[m][:, 1]
         weight = tab["weight"]
         for m in metrics:
             tables[m][members] = tab[m]
