@@ -561,6 +561,7 @@ int spfm_set_use_graph(spfm_handle h, int on);
  *   "debug_spin_max"          | >= 64 (2^21)   | nothing   | polls of one in-kernel wait before a persistent pass gives up
  *   "debug_drop_group"        | any int (0)    | nothing   | the next N persistent launches lack their last workgroup, i.e. time out
  *   "debug_keep_last_error"   | 0/1 (0)        | nothing   | spfm_comm_init does not clear the thread's stale HIP error before calling RCCL
+ *   "debug_setup_any_size"    | 0/1 (0)        | nothing   | before the schedule; "colour_device" and "stream_device" apply whatever the problem's size (the thresholds of 2^20 entries and 4096 columns are skipped, every other guard stays), and the entry streams keep what spfm_debug_stream_tables reads
  *
  * Read-outs (spfm_get_option only)
  *   "persistent_active"       | 0/1            | -         | the next pcd epoch will use a persistent pass: option on, steps of <= 64 columns or the wide pass
@@ -650,6 +651,57 @@ int spfm_debug_write_probe(spfm_handle h, int bytes_per_record, int64_t* bytes_o
  * omegacs.py:75-76, out[3] squaredl21.py:48-49 (out[4..7] reserved).  reset != 0 clears the
  * counters after reading.  Counters are per process (all handles of the device). */
 int spfm_debug_branch_counts(spfm_handle h, unsigned* out8, int reset);
+
+/* -- the set-up tables: the entry streams of the persistent passes ------------------
+ * What the passes run on is built once per schedule, by device kernels ("stream_device") or by
+ * host threads; the two forms produce the same tables, entry for entry.  The two calls below
+ * make the tables themselves comparable (tests/test_setup_tables_host.py,
+ * tests/test_hip_setup_tables.py).  With G row blocks of rows_per = max(1, ceil(n_rows / G))
+ * rows, nb steps and nnz entries:
+ *   SPFM_STREAM_ROWBLOCK (the 64-column passes), _ROWBLOCK_RELAXED (their relaxed runs: the same
+ *     form over the merged steps, without the entries that `skip` marks).  Entries sorted by
+ *     (row block g, step b, slot q, row): sp[(g*nb + b)*65 + q] = first entry of slot q, src[e] =
+ *     position of entry e in the CSC arrays, lmask[(g*nb + b)*2 + (q >> 5)] bit (q & 31) = the
+ *     slot holds more than long_thresh entries.  sp: G*nb*65 + 1, lmask: G*nb*2.
+ *   SPFM_STREAM_PBCD (the persistent pbcd pass).  Every (g, b) deals its slots to NG groups of at
+ *     most 64 / NG: tab[(g*nb + b)*64 + grp*(64/NG) + t] = the slot group grp handles as its
+ *     t-th, 0xFF = none.  balance = 0: slot q -> (q % NG, q / NG).  balance = 1: slots in
+ *     descending order of their entries in the block, ties by slot, each to the group with the
+ *     fewest entries so far that still has room, ties by group.  Slots exist below min(64,
+ *     max(ncols(b), ncols(b+2))).  Entries sorted by (g, b, grp, t, row): sp[(g*nb + b)*(NG+1) +
+ *     grp] = first entry of the group, flags[e] = t | 0x80 if step b-1 touched the entry's row (a
+ *     skipped entry still marks its row as touched).  sp: G*nb*(NG+1) + 1, tab: G*max(nb,1)*64.
+ *   SPFM_STREAM_WIDE (the wide passes).  Entries sorted by (g, b, q, row); wbase[b] = sum over the
+ *     earlier steps of (ncols + 1), tot = d + nb: sp[g*tot + wbase[b] + q] = first entry of slot
+ *     q, flags[e] = 1 if step b-1 touched the entry's row.  sp: G*tot + 1.
+ * src and flags take nnz elements; the entry count (nnz less the skipped entries) is returned. */
+#define SPFM_STREAM_ROWBLOCK 0
+#define SPFM_STREAM_ROWBLOCK_RELAXED 1
+#define SPFM_STREAM_PBCD 2
+#define SPFM_STREAM_WIDE 3
+/* Host-only form of the stream builders (no handle, no device), on a caller-given canonical CSC
+ * structure (indptr[d+1], indices: ascending rows in [0, n_rows) inside each column), visiting
+ * order and step boundaries batch_ptr[n_batches+1].  groups = G; long_thresh: row-block kinds;
+ * NG (8, 16, 32 or 64) and balance: SPFM_STREAM_PBCD; skip[nnz] or NULL: not for
+ * SPFM_STREAM_WIDE.  Steps of at most 64 columns except for SPFM_STREAM_WIDE.  Outputs are
+ * caller-allocated with the sizes above; lmask / tab may be NULL for the kinds without them. */
+int spfm_stream_build(int kind, int64_t n_rows, int32_t d, const int64_t* indptr,
+                      const int32_t* indices, const int32_t* order, const int32_t* batch_ptr,
+                      int32_t n_batches, int groups, int long_thresh, int NG, int balance,
+                      const uint8_t* skip, int32_t* sp, int32_t* src, uint8_t* flags,
+                      uint32_t* lmask, uint8_t* tab, int64_t* n_entries);
+/* diagnostic: the shape of the stream of `kind` that the handle holds -- streams are built by the
+ * first epoch that needs them -- info8 = {G, n_batches, NG, long_thresh, balance, entries, any
+ * long slot, built on the device}; SPFM_ERR_INVALID if that stream has not been built. */
+int spfm_debug_stream_info(spfm_handle h, int kind, int64_t* info8);
+/* ... and its tables, copied out of device memory into caller-allocated arrays of the sizes
+ * above (any pointer may be NULL).  skip[nnz] and batch_ptr_out[n_batches+1]: the entries left
+ * out and the merged step boundaries of SPFM_STREAM_ROWBLOCK_RELAXED (batch_ptr_out: the
+ * schedule's boundaries for the other kinds).  src, the wide stream's flags and skip are kept
+ * only by a handle with "debug_setup_any_size" = 1: SPFM_ERR_INVALID otherwise. */
+int spfm_debug_stream_tables(spfm_handle h, int kind, int32_t* sp, int32_t* src, uint8_t* flags,
+                             uint32_t* lmask, uint8_t* tab, uint8_t* skip,
+                             int32_t* batch_ptr_out);
 
 /* -- Gram matrices (sparsepoly/kernels.py) -------------------------------------
  * The Gram matrices of kernels.py:51-137 and poly_predict (:140-153) on the device, for

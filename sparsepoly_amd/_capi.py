@@ -80,6 +80,7 @@ SOLVERS = {"pcd": 0, "pbcd": 1, "psgd": 2}
 LEARNING_RATE = {"constant": 0, "optimal": 1, "pegasos": 2, "invscaling": 3}
 SCHEDULES = {"exact": 0, "colored": 1, "colored_rlf": 2}
 GRAM_KINDS = {"anova": 0, "poly": 1, "all-subsets": 2}  # SPFM_GRAM_*
+STREAMS = {"rowblock": 0, "relaxed": 1, "pbcd": 2, "wide": 3}  # SPFM_STREAM_*
 GRAM_MAX_DEGREE = 64  # SPFM_GRAM_MAX_DEGREE
 
 # every symbol include/spfm.h declares (checked by tests/test_capi_symbols.py)
@@ -103,6 +104,7 @@ SYMBOLS = [
     "spfm_set_option", "spfm_get_option", "spfm_debug_prb_stamps", "spfm_debug_hop_latency", "spfm_debug_exchange_cost",
     "spfm_debug_sweep_sums",
     "spfm_debug_branch_counts", "spfm_debug_stream_probe", "spfm_debug_write_probe",
+    "spfm_stream_build", "spfm_debug_stream_info", "spfm_debug_stream_tables",
     "spfm_gram_csr_dense", "spfm_gram_csr_csr",
     "spfm_objective_terms", "spfm_set_eval_csr", "spfm_eval_loss",
     "spfm_interaction_stats", "spfm_interaction_topk", "spfm_interaction_list",
@@ -153,6 +155,7 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _lp = C.POINTER(C.c_int64)
 _up = C.POINTER(C.c_uint32)
+_bp = C.POINTER(C.c_uint8)
 _h = C.c_void_p
 
 _lib = None
@@ -256,6 +259,11 @@ def load():
     L.spfm_debug_branch_counts.argtypes = [_h, C.POINTER(C.c_uint32), C.c_int]
     L.spfm_debug_stream_probe.argtypes = [_h, _lp]
     L.spfm_debug_write_probe.argtypes = [_h, C.c_int, _lp]
+    L.spfm_stream_build.argtypes = [C.c_int, C.c_int64, C.c_int32, _lp, _ip, _ip, _ip, C.c_int32,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, _bp, _ip, _ip, _bp, _up,
+                                    _bp, _lp]
+    L.spfm_debug_stream_info.argtypes = [_h, C.c_int, _lp]
+    L.spfm_debug_stream_tables.argtypes = [_h, C.c_int, _ip, _ip, _bp, _up, _bp, _bp, _ip]
     L.spfm_gram_csr_dense.argtypes = [_h, C.c_int, C.c_int, C.c_int64, C.c_int32, _lp, _ip, _dp,
                                       C.c_int64, _dp, _dp, C.c_int, C.c_int64, _dp]
     L.spfm_gram_csr_csr.argtypes = [_h, C.c_int, C.c_int, C.c_int64, C.c_int32, _lp, _ip, _dp,

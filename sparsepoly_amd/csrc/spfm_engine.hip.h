@@ -786,6 +786,20 @@ struct spfm_engine {
     bool stream_device = true;   // the 64-column pass's entry stream built on the device
     int stream_device_used = 0;
     int pb_stream_device_used = 0, wide_stream_device_used = 0;  // the pbcd / wide entry streams
+    // Test hook "debug_setup_any_size": the device colouring and the device stream builders run
+    // whatever the problem's size (every other guard stays), and the builders keep what the
+    // passes do not need but spfm_debug_stream_tables reads: the entries' CSC positions (and the
+    // wide stream's flags and the relaxed runs' skip mask), which are otherwise freed once the
+    // row / value images are gathered.
+    bool debug_setup_any_size = false;
+    DevBuf dbg_prb_src, dbg_r_src, dbg_pb_src, dbg_w_src, dbg_w_hz;
+    std::vector<uint8_t> dbg_r_skip;
+    int64_t dbg_r_entries = 0;   // entries of the relaxed runs' stream
+    int relax_stream_device_used = 0;  // ... and whether the device built it
+    int pb_stream_balance = 0;   // the slot map the pbcd stream was built with
+    int debug_stream_info(int which, int64_t* info8);
+    int debug_stream_tables(int which, int32_t* sp, int32_t* src, uint8_t* flags, uint32_t* lmask,
+                            uint8_t* tab, uint8_t* skip, int32_t* batch_ptr_out);
     int colour_columns(int mode, int64_t rows, const int64_t* cp, const int32_t* ci, bool own,
                        const int32_t* jf, int max_batch);
 

@@ -587,8 +587,9 @@ int spfm_engine::colour_columns(int mode, int64_t rows, const int64_t* cp, const
         schedule_rlf(rows, d, cp, ci, jf, std::max(1, max_batch), order, batch_ptr);
         return SPFM_OK;
     }
-    if (own && colour_device && d >= 4096 && nnz >= (1 << 20) && nnz < ((int64_t)1 << 31) &&
-        (int64_t)d / std::max(1, max_batch) < 3500 && rptr.p && cptr.p) {
+    // (the test hook "debug_setup_any_size" lifts the size threshold alone)
+    if (own && colour_device && (debug_setup_any_size || (d >= 4096 && nnz >= (1 << 20))) &&
+        nnz < ((int64_t)1 << 31) && (int64_t)d / std::max(1, max_batch) < 3500 && rptr.p && cptr.p) {
         std::vector<int32_t> col((size_t)d);
         int nc = 0, ovf = 0;
         const hipError_t e = device_first_fit(n, d, nnz, cptr.as<int64_t>(), cidx.as<int32_t>(),
@@ -1028,6 +1029,79 @@ int spfm_engine::host_barrier() {
         int rc = allreduce(scalar.as<double>() + 4, 1);
         if (rc) return rc;
         HIPC(hipStreamSynchronize(stream));
+    }
+    return SPFM_OK;
+}
+
+// ===================================================== the set-up tables, read back (spfm.h)
+int spfm_engine::debug_stream_info(int which, int64_t* info) {
+    if (!info) FAIL(SPFM_ERR_INVALID, "stream_info: info8 is NULL");
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    if (!have_schedule) FAIL(SPFM_ERR_INVALID, "stream_info: no schedule installed");
+    switch (which) {
+        case SPFM_STREAM_ROWBLOCK:
+            if (!prb_ready) FAIL(SPFM_ERR_INVALID, "stream_info: the 64-column stream has not been built");
+            info[0] = prb_G, info[1] = n_batches(), info[3] = prb_long, info[5] = nnz;
+            info[6] = prb_has_long, info[7] = stream_device_used;
+            return SPFM_OK;
+        case SPFM_STREAM_ROWBLOCK_RELAXED:
+            if (!prb_ready || relax_state != 1)
+                FAIL(SPFM_ERR_INVALID, "stream_info: the relaxed runs' stream has not been built");
+            info[0] = prb_G, info[1] = (int64_t)r_batch_ptr.size() - 1, info[3] = prb_long;
+            info[5] = dbg_r_entries, info[6] = relax_has_long, info[7] = relax_stream_device_used;
+            return SPFM_OK;
+        case SPFM_STREAM_PBCD:
+            if (!pb_stream_ready) FAIL(SPFM_ERR_INVALID, "stream_info: the pbcd stream has not been built");
+            info[0] = pb_stream_G, info[1] = n_batches(), info[2] = pb_stream_NG;
+            info[4] = pb_stream_balance, info[5] = nnz, info[7] = pb_stream_device_used;
+            return SPFM_OK;
+        case SPFM_STREAM_WIDE:
+            if (!wide_ready) FAIL(SPFM_ERR_INVALID, "stream_info: the wide stream has not been built");
+            info[0] = wide_G, info[1] = n_batches(), info[5] = nnz, info[7] = wide_stream_device_used;
+            return SPFM_OK;
+        default: FAIL(SPFM_ERR_INVALID, "stream_info: unknown kind");
+    }
+}
+
+int spfm_engine::debug_stream_tables(int which, int32_t* sp, int32_t* src, uint8_t* flags,
+                                     uint32_t* lmask, uint8_t* tab, uint8_t* skip,
+                                     int32_t* batch_ptr_out) {
+    int64_t info[8];
+    SPFM_TRY(debug_stream_info(which, info));
+    const size_t G = (size_t)info[0], nb = (size_t)info[1], NG = (size_t)info[2];
+    const size_t ne = (size_t)info[5];
+    const bool relaxed = which == SPFM_STREAM_ROWBLOCK_RELAXED;
+    const DevBuf *b_sp, *b_src, *b_flags = nullptr, *b_lmask = nullptr, *b_tab = nullptr;
+    size_t nsp;
+    if (which == SPFM_STREAM_ROWBLOCK || relaxed) {
+        b_sp = relaxed ? &r_sp : &prb_sp;
+        b_src = relaxed ? &dbg_r_src : &dbg_prb_src;
+        b_lmask = relaxed ? &r_lmask : &prb_lmask;
+        nsp = G * nb * 65 + 1;
+    } else if (which == SPFM_STREAM_PBCD) {
+        b_sp = &pb_sp, b_src = &dbg_pb_src, b_flags = &pb_meta, b_tab = &pb_tab;
+        nsp = G * nb * (NG + 1) + 1;
+    } else {
+        b_sp = &w_wsp, b_src = &dbg_w_src, b_flags = &dbg_w_hz;
+        nsp = G * ((size_t)d + nb) + 1;
+    }
+    if ((lmask && !b_lmask) || (tab && !b_tab) || (flags && !b_flags))
+        FAIL(SPFM_ERR_INVALID, "stream_tables: this kind of stream has no such table");
+    if ((src && !b_src->p) || (flags && !b_flags->p) ||
+        (skip && (!relaxed || dbg_r_skip.size() != (size_t)nnz)))
+        FAIL(SPFM_ERR_INVALID,
+             "stream_tables: kept only by a handle with debug_setup_any_size = 1 (skip: relaxed runs)");
+    HIPC(hipStreamSynchronize(stream));
+    if (sp) SPFM_TRY(download(sp, b_sp->p, nsp));
+    if (src) SPFM_TRY(download(src, b_src->p, ne));
+    if (flags) SPFM_TRY(download(flags, b_flags->p, ne));
+    if (lmask) SPFM_TRY(download(lmask, b_lmask->p, G * nb * 2));
+    if (tab) SPFM_TRY(download(tab, b_tab->p, G * std::max<size_t>(nb, 1) * 64));
+    HIPC(hipStreamSynchronize(stream));
+    if (skip && nnz > 0) std::memcpy(skip, dbg_r_skip.data(), (size_t)nnz);
+    if (batch_ptr_out) {
+        const std::vector<int32_t>& bp = relaxed ? r_batch_ptr : batch_ptr;
+        std::memcpy(batch_ptr_out, bp.data(), sizeof(int32_t) * bp.size());
     }
     return SPFM_OK;
 }
@@ -1699,6 +1773,77 @@ int spfm_debug_branch_counts(spfm_handle h, unsigned* out8, int reset) {
     for (auto unit : units)
         if (unit(out8, reset) != hipSuccess) return SPFM_ERR_RUNTIME;
     return SPFM_OK;
+}
+
+int spfm_stream_build(int kind, int64_t n_rows, int32_t d, const int64_t* indptr,
+                      const int32_t* indices, const int32_t* order_in, const int32_t* batch_ptr_in,
+                      int32_t nb, int groups, int long_thresh, int NG, int balance,
+                      const uint8_t* skip, int32_t* sp_out, int32_t* src_out, uint8_t* flags_out,
+                      uint32_t* lmask_out, uint8_t* tab_out, int64_t* n_entries) {
+    const bool rowblock = kind == SPFM_STREAM_ROWBLOCK || kind == SPFM_STREAM_ROWBLOCK_RELAXED;
+    const bool pb = kind == SPFM_STREAM_PBCD, wide = kind == SPFM_STREAM_WIDE;
+    if (!(rowblock || pb || wide) || n_rows < 0 || d <= 0 || !indptr || !order_in ||
+        !batch_ptr_in || nb < 1 || groups < 1 || !sp_out || !n_entries || (wide && skip))
+        return SPFM_ERR_INVALID;
+    if (pb && NG != 8 && NG != 16 && NG != 32 && NG != 64) return SPFM_ERR_INVALID;
+    // the builders index their arrays with every one of these: check them all first
+    if (indptr[0] != 0) return SPFM_ERR_INVALID;
+    for (int j = 0; j < d; ++j)
+        if (indptr[j + 1] < indptr[j]) return SPFM_ERR_INVALID;
+    const int64_t nz = indptr[d];
+    if (nz >= ((int64_t)1 << 31) || (nz > 0 && (!indices || !src_out)) ||
+        (nz > 0 && !rowblock && !flags_out))
+        return SPFM_ERR_INVALID;
+    for (int j = 0; j < d; ++j)
+        for (int64_t ii = indptr[j]; ii < indptr[j + 1]; ++ii)
+            if (indices[ii] < 0 || indices[ii] >= n_rows ||
+                (ii > indptr[j] && indices[ii] <= indices[ii - 1]))
+                return SPFM_ERR_INVALID;
+    std::vector<char> seen((size_t)d, 0);
+    for (int q = 0; q < d; ++q) {
+        const int j = order_in[q];
+        if (j < 0 || j >= d || seen[(size_t)j]) return SPFM_ERR_INVALID;
+        seen[(size_t)j] = 1;
+    }
+    if (batch_ptr_in[0] != 0 || batch_ptr_in[nb] != d) return SPFM_ERR_INVALID;
+    for (int b = 0; b < nb; ++b) {
+        const int64_t nc = (int64_t)batch_ptr_in[b + 1] - batch_ptr_in[b];
+        if (nc < 0 || (!wide && nc > 64)) return SPFM_ERR_INVALID;
+    }
+    const std::vector<int32_t> order(order_in, order_in + d), bp(batch_ptr_in, batch_ptr_in + nb + 1);
+    std::vector<int32_t> sp, src;
+    std::vector<uint8_t> flags;
+    if (rowblock) {
+        std::vector<uint32_t> lmask;
+        build_rowblock_stream(n_rows, indptr, indices, order, bp, groups, long_thresh, sp, src, lmask,
+                              skip);
+        if (lmask_out) std::memcpy(lmask_out, lmask.data(), sizeof(uint32_t) * lmask.size());
+    } else if (pb) {
+        std::vector<uint8_t> tab;
+        build_pb_stream(n_rows, indptr, indices, order, bp, groups, NG, balance != 0, skip, sp, src,
+                        flags, tab);
+        if (tab_out) std::memcpy(tab_out, tab.data(), tab.size());
+    } else {
+        std::vector<int32_t> wbase;
+        build_wide_stream(n_rows, indptr, indices, order, bp, groups, wbase, sp, src, flags);
+    }
+    std::memcpy(sp_out, sp.data(), sizeof(int32_t) * sp.size());
+    if (!src.empty()) std::memcpy(src_out, src.data(), sizeof(int32_t) * src.size());
+    if (!flags.empty()) std::memcpy(flags_out, flags.data(), flags.size());
+    *n_entries = (int64_t)src.size();
+    return SPFM_OK;
+}
+
+int spfm_debug_stream_info(spfm_handle h, int kind, int64_t* info8) {
+    SPFM_GUARD(h);
+    return h->debug_stream_info(kind, info8);
+}
+
+int spfm_debug_stream_tables(spfm_handle h, int kind, int32_t* sp, int32_t* src, uint8_t* flags,
+                             uint32_t* lmask, uint8_t* tab, uint8_t* skip,
+                             int32_t* batch_ptr_out) {
+    SPFM_GUARD(h);
+    return h->debug_stream_tables(kind, sp, src, flags, lmask, tab, skip, batch_ptr_out);
 }
 
 int spfm_set_use_graph(spfm_handle h, int on) {

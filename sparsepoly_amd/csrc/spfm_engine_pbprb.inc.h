@@ -13,6 +13,8 @@ int spfm_engine::ensure_pb_stream(int NG) {
     HIPC(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
     const int G = std::max(1, std::min(pbprb_G, ncu));
     if (pb_stream_ready && pb_stream_G == G && pb_stream_NG == NG) return SPFM_OK;
+    dbg_pb_src.release();
+    pb_stream_balance = pb_balance ? 1 : 0;
     // handles that share a data image share this stream too (see ensure_prb)
     std::unique_lock<std::mutex> cache_lock;
     std::string ckey;
@@ -59,7 +61,7 @@ int spfm_engine::ensure_pb_stream(int NG) {
     // exactly, tests/test_hip_stream.py), or by the host threads (small problems -- which are
     // audited --, stream_device=0, no room for the scratch)
     pb_stream_device_used = 0;
-    if (stream_device && nnz >= (1 << 20) && !getenv("SPFM_VALIDATE")) {
+    if (stream_device && (debug_setup_any_size || nnz >= (1 << 20)) && !getenv("SPFM_VALIDATE")) {
         const hipError_t e = device_pb_stream(
             n, d, nnz, G, nb_, NG, pb_balance ? 1 : 0, d_order.as<int32_t>(), d_bptr.as<int32_t>(),
             cptr.as<int64_t>(), cidx.as<int32_t>(), rptr.as<int64_t>(), ridx.as<int32_t>(),
@@ -95,6 +97,7 @@ int spfm_engine::ensure_pb_stream(int NG) {
         HIPC(hipGetLastError());
     }
     HIPC(hipStreamSynchronize(stream));
+    if (debug_setup_any_size) dbg_pb_src.share(d_src);  // kept for spfm_debug_stream_tables
     if (scache) {
         auto e = std::make_unique<StreamCache::Pb>();
         e->key = ckey;

@@ -116,6 +116,7 @@ int spfm_engine::lin_prb_loss(double alpha) {
 template <typename T>
 int spfm_engine::ensure_prb() {
     if (prb_ready) return SPFM_OK;
+    dbg_prb_src.release();
     int ncu = 0;
     HIPC(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
     if (prb_G > ncu) prb_G = ncu;
@@ -187,7 +188,7 @@ int spfm_engine::build_prb_stream(int nb_) {
     HIPC(prb_sp.alloc(sizeof(int32_t) * nsp));
     HIPC(prb_lmask.alloc(sizeof(uint32_t) * (size_t)prb_G * nb_ * 2));
     stream_device_used = 0;
-    if (stream_device && nnz >= (1 << 20)) {
+    if (stream_device && (debug_setup_any_size || nnz >= (1 << 20))) {
         int hl = 0;
         const hipError_t e = device_rowblock_stream(
             n, d, nnz, prb_G, nb_, prb_long, d_order.as<int32_t>(), d_bptr.as<int32_t>(),
@@ -222,6 +223,7 @@ int spfm_engine::build_prb_stream(int nb_) {
         HIPC(hipGetLastError());
     }
     HIPC(hipStreamSynchronize(stream));  // the host staging vectors and d_src die here
+    if (debug_setup_any_size) dbg_prb_src.share(d_src);  // ... unless the test hook keeps it
     return SPFM_OK;
 }
 
@@ -229,6 +231,8 @@ template <typename T>
 int spfm_engine::ensure_relax() {
     if (relax_state != 0) return SPFM_OK;
     relax_state = -1;
+    dbg_r_src.release();
+    dbg_r_skip.clear();
     int rc = ensure_prb<T>();  // workgroup count, col_norm / viol buffers, abort word
     if (rc) return rc;
     std::vector<int32_t> cf_ptr, cf_row, cf_qq, sp, src;
@@ -248,7 +252,7 @@ int spfm_engine::ensure_relax() {
     const size_t nsp_r = (size_t)prb_G * nbr * 65 + 1;
     bool dev_stream = false;
     size_t ne = 0;
-    if (stream_device && nnz >= (1 << 20)) {
+    if (stream_device && (debug_setup_any_size || nnz >= (1 << 20))) {
         DevBuf d_skip;
         HIPC(d_skip.alloc((size_t)nnz));
         SPFM_TRY(upload_to(d_skip.p, skip.data(), (size_t)nnz));
@@ -320,6 +324,12 @@ int spfm_engine::ensure_relax() {
         HIPC(hipGetLastError());
     }
     HIPC(hipStreamSynchronize(stream));
+    dbg_r_entries = (int64_t)ne;
+    relax_stream_device_used = dev_stream ? 1 : 0;
+    if (debug_setup_any_size) {  // kept for spfm_debug_stream_tables
+        dbg_r_src.share(d_src);
+        dbg_r_skip = skip;
+    }
     relax_state = 1;
     return SPFM_OK;
 }

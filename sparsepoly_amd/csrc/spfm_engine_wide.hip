@@ -35,6 +35,8 @@ int spfm_engine::ensure_wide() {
     HIPC(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
     const int G = wide_groups(ncu, (size_t)lds_max);
     if (wide_ready && wide_G == G) return SPFM_OK;
+    dbg_w_src.release();
+    dbg_w_hz.release();
     const int nb_ = n_batches();
     const size_t nz = (size_t)(nnz > 0 ? nnz : 1);
     // wbase[b] = columns + steps in front of step b (ncols + 1 boundaries per step)
@@ -60,7 +62,8 @@ int spfm_engine::ensure_wide() {
     // the stream: on the device (spfm_ingest.hip device_wide_stream: the host builder's tables
     // exactly, tests/test_hip_stream.py) or by the host threads
     wide_stream_device_used = 0;
-    if (stream_device && nnz >= (1 << 20) && (int64_t)d + nb_ < ((int64_t)1 << 31) / std::max(G, 1)) {
+    if (stream_device && (debug_setup_any_size || nnz >= (1 << 20)) &&
+        (int64_t)d + nb_ < ((int64_t)1 << 31) / std::max(G, 1)) {
         const hipError_t e = device_wide_stream(
             n, d, nnz, G, nb_, d_order.as<int32_t>(), d_bptr.as<int32_t>(), cptr.as<int64_t>(),
             cidx.as<int32_t>(), rptr.as<int64_t>(), ridx.as<int32_t>(), w_wsp.as<int32_t>(),
@@ -89,6 +92,10 @@ int spfm_engine::ensure_wide() {
                        d_desc.as<ColDesc>(), col_norm.as<double>(), prb_cn.as<double>());
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(stream));
+    if (debug_setup_any_size) {  // kept for spfm_debug_stream_tables
+        dbg_w_src.share(d_src);
+        dbg_w_hz.share(d_hz);
+    }
     wide_G = G;
     wide_tot = (int)tot;
     wide_ready = true;

@@ -156,6 +156,7 @@ const OptRow kOptions[] = {
     {"debug_spin_max", TEST_HOOK, integer(M(spin_max), 64, kMax), G, "polls of one in-kernel wait before a persistent pass gives up"},
     {"debug_drop_group", TEST_HOOK, integer(M(debug_drop), kMin, kMax), G, "the next N persistent launches lack their last workgroup"},
     {"debug_keep_last_error", TEST_HOOK, flag(M(keep_last_error)), G, "spfm_comm_init keeps the thread's stale HIP error"},
+    {"debug_setup_any_size", TEST_HOOK, flag(M(debug_setup_any_size)), SCHED | PRB | PB | WIDE | RELAX | PBRELAX, "device colouring and device entry streams whatever the problem's size"},
     // ---- read-outs
     {"persistent_active", READOUT, custom(nullptr, get_persistent_active), 0, "the next pcd epoch uses a persistent pass"},
     {"wide_active", READOUT, custom(nullptr, get_wide_active), 0, "the next pcd epoch uses the wide pass"},

@@ -41,6 +41,61 @@ def canonical_csc(X):
     return Xc
 
 
+def _stream_arrays(kind, d, nnz, G, nb, NG):
+    """Zeroed arrays of the sizes spfm.h gives for the tables of a stream of ``kind``."""
+    nsp = {"rowblock": G * nb * 65, "relaxed": G * nb * 65, "pbcd": G * nb * (NG + 1),
+           "wide": G * (d + nb)}[kind] + 1
+    out = dict(sp=np.zeros(nsp, dtype=np.int32), src=np.zeros(nnz, dtype=np.int32))
+    if kind in ("rowblock", "relaxed"):
+        out["lmask"] = np.zeros(G * nb * 2, dtype=np.uint32)
+    else:
+        out["flags"] = np.zeros(nnz, dtype=np.uint8)
+    if kind == "pbcd":
+        out["tab"] = np.zeros(G * max(nb, 1) * 64, dtype=np.uint8)
+    return out
+
+
+def _stream_ptrs(t):
+    """The five table pointers of spfm_stream_build / spfm_debug_stream_tables (NULL = none)."""
+    def ptr(name, ctype):
+        return t[name].ctypes.data_as(ctype) if name in t else None
+    return (ptr("sp", _capi._ip), ptr("src", _capi._ip), ptr("flags", _capi._bp),
+            ptr("lmask", _capi._up), ptr("tab", _capi._bp))
+
+
+def stream_build(kind, n_rows, indptr, indices, order, batch_ptr, groups, long_thresh=48, NG=16,
+                 balance=True, skip=None):
+    """``spfm_stream_build``: the host form of the entry-stream builders on a canonical CSC
+    structure -- no handle, no device.  ``kind``: 'rowblock' (``skip``: the relaxed runs' form),
+    'pbcd' or 'wide'.  Returns a dict of the tables (include/spfm.h): ``sp``, ``src`` and
+    ``lmask`` (row-block kinds) or ``flags`` (+ ``tab`` for 'pbcd'), cut to ``n_entries``."""
+    lib = _capi.load()
+    ipa, ipp = _capi.i64(indptr)
+    ixa, ixp = _capi.i32(indices)
+    oa, op = _capi.i32(order)
+    ba, bp = _capi.i32(batch_ptr)
+    d, nb, nnz = oa.shape[0], ba.shape[0] - 1, int(ipa[-1])
+    if ipa.shape[0] != d + 1 or ixa.shape[0] != nnz:
+        raise ValueError("stream_build: indptr / indices / order do not fit together")
+    if skip is not None:
+        skip = np.ascontiguousarray(skip, dtype=np.uint8)
+        if skip.shape[0] != nnz:
+            raise ValueError("stream_build: skip needs one byte per entry")
+    t = _stream_arrays(kind, d, nnz, int(groups), nb, int(NG))
+    ne = C.c_int64()
+    rc = lib.spfm_stream_build(
+        _capi.STREAMS[kind], int(n_rows), d, ipp, ixp, op, bp, nb, int(groups), int(long_thresh),
+        int(NG), int(bool(balance)), None if skip is None else skip.ctypes.data_as(_capi._bp),
+        *(_stream_ptrs(t) + (C.byref(ne),)))
+    if rc != 0:
+        raise ValueError("spfm_stream_build failed (%d): bad arguments" % rc)
+    t["n_entries"] = ne.value
+    for name in ("src", "flags"):
+        if name in t:
+            t[name] = t[name][:ne.value]
+    return t
+
+
 # Engines created inside `co_tenancy(n)` -- or by the worker threads of one
 # `fit_concurrently` call -- announce that n of them train side by side on one GPU
 # (sparsepoly_amd/concurrent.py): every persistent pass keeps to 1/n of the CUs.  The state of
@@ -243,7 +298,7 @@ class HipEngine(object):
             raise SpfmError("spfm_create failed: %s" % msg)
         self._h = h
         self.precision = precision
-        self.n = self.d = self.k = self.n_orders = None
+        self.n = self.d = self.nnz = self.k = self.n_orders = None
         self.order = None
         self.n_batches = None
         self.device = int(device)
@@ -289,7 +344,7 @@ class HipEngine(object):
                 raise ValueError("y has %d entries, X has %d rows" % (keep[3][0].shape[0], n))
             self._check(self._lib.spfm_set_data_csr(self._h, n, d, keep[0][1], keep[1][1],
                                                     keep[2][1], keep[3][1]))
-            self.n, self.d = n, d
+            self.n, self.d, self.nnz = n, d, int(keep[0][0][-1])
             return
         Xc = X if (sp.isspmatrix_csc(X) and X.has_canonical_format) else canonical_csc(X)
         n, d = Xc.shape
@@ -300,8 +355,8 @@ class HipEngine(object):
         self._check(self._lib.spfm_set_data_csc(
             self._h, n, d, self._keep[0][1], self._keep[1][1], self._keep[2][1],
             self._keep[3][1]))
+        self.n, self.d, self.nnz = n, d, int(self._keep[0][0][-1])
         self._keep = None
-        self.n, self.d = n, d
 
     def share_data(self, src, y=None):
         """Train on the device image of the matrix that engine ``src`` holds (no upload, no
@@ -313,7 +368,7 @@ class HipEngine(object):
             if ya.shape[0] != src.n:
                 raise ValueError("y has %d entries, X has %d rows" % (ya.shape[0], src.n))
         self._check(self._lib.spfm_share_data(self._h, src._h, yp))
-        self.n, self.d = src.n, src.d
+        self.n, self.d, self.nnz = src.n, src.d, src.nnz
 
     def set_sample_weight(self, sample_weight):
         """One weight per row of this engine's training data (``spfm_set_sample_weight``,
@@ -1673,6 +1728,36 @@ class HipEngine(object):
         nb = C.c_int64()
         self._check(self._lib.spfm_debug_write_probe(self._h, int(bytes_per_record), C.byref(nb)))
         return nb.value
+
+    def debug_stream_info(self, kind):
+        """Shape of the entry stream of ``kind`` ('rowblock', 'relaxed', 'pbcd', 'wide') that the
+        handle holds; ValueError if no epoch has built it yet.  See spfm.h."""
+        info = np.zeros(8, dtype=np.int64)
+        self._check(self._lib.spfm_debug_stream_info(self._h, _capi.STREAMS[kind],
+                                                     info.ctypes.data_as(_capi._lp)))
+        names = ("G", "nb", "NG", "long_thresh", "balance", "n_entries", "has_long", "device")
+        return dict(zip(names, (int(v) for v in info)))
+
+    def debug_stream_tables(self, kind):
+        """The tables of that stream, copied out of device memory: the dict of ``stream_build``
+        plus ``info``, ``batch_ptr`` (the steps the stream was built for) and, for 'relaxed',
+        ``skip``.  Needs the option ``debug_setup_any_size`` = 1 (set before the schedule)."""
+        info = self.debug_stream_info(kind)
+        nnz = self.nnz  # (the relaxed runs leave entries out: n_entries may be less)
+        t = _stream_arrays(kind, self.d, nnz, info["G"], info["nb"], info["NG"])
+        bp = np.zeros(info["nb"] + 1, dtype=np.int32)
+        skip = np.zeros(nnz, dtype=np.uint8) if kind == "relaxed" else None
+        self._check(self._lib.spfm_debug_stream_tables(
+            self._h, _capi.STREAMS[kind],
+            *(_stream_ptrs(t) + (None if skip is None else skip.ctypes.data_as(_capi._bp),
+                                 bp.ctypes.data_as(_capi._ip)))))
+        for name in ("src", "flags"):
+            if name in t:
+                t[name] = t[name][:info["n_entries"]]
+        t.update(info=info, batch_ptr=bp, n_entries=info["n_entries"])
+        if skip is not None:
+            t["skip"] = skip
+        return t
 
     def get_option(self, key):
         v = C.c_int()

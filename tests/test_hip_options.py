@@ -24,6 +24,8 @@ PARENT = {
     "colour_device_used": (0, [(0, -1, 0), (1, -1, 0)]),
     "debug_drop_group": (U, [(-2147483648, 0, U), (-1, 0, U), (2, 0, U), (2147483647, 0, U), (0, 0, U)]),
     "debug_keep_last_error": (U, [(0, 0, U), (1, 0, U), (2, 0, U), (-1, 0, U)]),
+    # (a test hook added after that record: a plain flag, default 0)
+    "debug_setup_any_size": (0, [(0, 0, 0), (1, 0, 1), (2, 0, 1), (-1, 0, 1)]),
     "debug_spin_max": (U, [(63, -1, U), (64, 0, U), (4096, 0, U), (2147483647, 0, U), (-2147483648, -1, U)]),
     "free_mem_mib": (FREE, [(0, -1, FREE), (1, -1, FREE)]),
     "fuse_chain": (1, [(0, 0, 0), (1, 0, 1), (2, 0, 1), (-1, 0, 1)]),
