@@ -306,6 +306,31 @@ int spfm_psgd_set_adaptive(spfm_handle h, int mode, double initial_accumulator,
  * spfm_psgd_set_adaptive. */
 int spfm_psgd_get_adaptive(spfm_handle h, double* acc_P, double* acc_w);
 
+/* Deterministic minibatch gradients for spfm_psgd_epoch.  The mode is
+ * handle state; 0 (the default) keeps the gradient scatter with hardware f64 atomics, whose sums
+ * are taken in the order the hardware delivers the terms.  In mode 1 every sum has a fixed order:
+ * with the minibatch the positions [pos, pos + B) of the visiting order,
+ *   grad_P[o, j, s] = sum over the rows of the minibatch that store column j, by ascending
+ *                     position, of the terms the default route adds; grad_w[j] likewise;
+ * a (minibatch, column) run longer than 256 entries is summed in pieces of 256, each from zero,
+ * and the pieces' sums are added in ascending order.  The result is a function of the data, the
+ * visiting order, batch_size and these constants -- not of the grid, the scheduling of waves,
+ * graph replay against eager launches, or the run; the terms themselves are the default route's,
+ * so the two routes differ in the order of additions only.  Per epoch the handle keeps a device
+ * plan (the stored entries sorted by minibatch and column), rebuilt only when the visiting order or
+ * batch_size differs from the planned one.  Every loss, degree 2..6, every fit_lower, k <= 256,
+ * both storage types, every regularizer of psgd, adaptive steps and sample weights are supported.
+ * SPFM_ERR_UNSUPPORTED in mode 1, before anything is launched: spfm_psgd_epoch_sharded or a handle
+ * with a communicator; the spfm_psgd_pairs_* / spfm_psgd_lists_* epoch and sample entries (their
+ * gradients are not covered); more than 2^31 - 1 stored entries.  SPFM_ERR_INVALID: a mode other
+ * than 0 / 1. */
+int spfm_psgd_set_deterministic(spfm_handle h, int mode);
+/* The mode and the figures of the last plan (any pointer may be NULL): its (minibatch, column)
+ * runs, the entries of the longest one, and the device bytes the mode holds on the handle (plan,
+ * sort buffers, per-minibatch state).  Zeros before the first plan and after new data. */
+int spfm_psgd_get_deterministic(spfm_handle h, int* mode, int64_t* segments,
+                                int64_t* longest_segment, int64_t* plan_bytes);
+
 /* Pairwise ranking fit: one pass of minibatch psgd over triples.  The
  * handle's data is the stacked matrix [X; Z] (contexts, then candidates; the targets are not
  * read).  Row k of `triples` (m, 3) is (anchor, plus, minus), three row indices into that matrix:

@@ -1080,6 +1080,26 @@ struct spfm_engine {
                        double power_t, int64_t batch_size, int fit_linear, int64_t* it) const;
     int psgd_set_adaptive(int mode, double g0, const double* acc_P, const double* acc_w);
     int psgd_get_adaptive(double* acc_P, double* acc_w);
+    // the deterministic gradient of the pointwise epoch: handle state.
+    // The plan of the last (visiting order, batch_size) -- dt_order is that order, dt_bs that
+    // batch size (0: no plan; new data clears it) -- the buffers of its build, and the per-batch
+    // dL / DP state of the two gradient kernels.  A moved buffer clears the graphs.
+    DevBuf dt_order, dt_len, dt_qoff, dt_keys, dt_vals, dt_entq, dt_recr, dt_recx, dt_segptr,
+        dt_segcol, dt_bseg, dt_tmp, dt_figs, dt_dl, dt_state;
+    int psgd_det = 0;
+    int64_t dt_bs = 0, dt_nseg = 0, dt_longest = 0, dt_bytes = 0;
+    int dt_grid = 0;  // workgroups of both gradient kernels: from the device, not from the data
+    int refuse_det(const char* what) {
+        if (psgd_det)
+            FAIL(SPFM_ERR_UNSUPPORTED, std::string(what) + ": not on a handle in deterministic "
+                                                           "mode (spfm_psgd_set_deterministic)");
+        return SPFM_OK;
+    }
+    int psgd_set_deterministic(int mode);
+    template <typename T>
+    int det_plan(int64_t batch_size);  // (re)builds the plan if the order or batch_size changed
+    template <typename T, int L>
+    int psgd_det_epoch_tl(const PsgdStep& st);
 
     // pairwise ranking fit: triples (anchor, plus, minus) of rows of the
     // handle's data [X; Z]; buffers of their own (sg_samples and pred_tmp are sized by n)

@@ -3,6 +3,10 @@
 #include "spfm_psgd_pairs.hip.h"
 #include "spfm_psgd_sample.hip.h"
 #include "spfm_psgd_lists.hip.h"
+#include "spfm_psgd_det.hip.h"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 using namespace spfm;
 
@@ -366,6 +370,150 @@ int spfm_engine::psgd_epoch_tl(const PsgdStep& st) {
     return psgd_batches_tl<L>(grad, weighted ? "psgd_w" : "psgd", (int64_t)sizeof(T), n, st);
 }
 
+// ================================================== deterministic gradient
+// The plan of the epoch whose order is in sg_samples: the stored entries, enumerated in visiting
+// order, stably sorted by (minibatch, column), and the tables of the runs.  Nothing is uploaded.
+// Kept while the order and batch_size stay what they were (the order is compared on the device
+// with the planned copy), so shuffle=False plans once.
+template <typename T>
+int spfm_engine::det_plan(int64_t batch_size) {
+    if (nnz > INT32_MAX)
+        FAIL(SPFM_ERR_UNSUPPORTED, "psgd (deterministic): more than 2^31 - 1 stored entries");
+    const int64_t N = nnz, nbat = cdiv(n, batch_size);
+    int* h_figs = reinterpret_cast<int*>(h_scalar + 4);
+    HIPC(dt_figs.alloc(sizeof(int) * 4));
+    int* figs = dt_figs.as<int>();  // segments, longest segment, orders differ
+    if (dt_bs == batch_size && dt_order.p) {
+        HIPC(hipMemsetAsync(figs + 2, 0, sizeof(int), stream));
+        hipLaunchKernelGGL(det_differ_kernel, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, stream,
+                           sg_samples.as<int32_t>(), dt_order.as<int32_t>(), n, figs + 2);
+        SPFM_TRY(download(h_figs, figs + 2, 1));
+        HIPC(hipStreamSynchronize(stream));
+        if (!h_figs[0]) return SPFM_OK;
+    }
+    dt_bs = 0;
+    const size_t nz = (size_t)(N > 0 ? N : 1);
+    const void* old[] = {dt_recr.p, dt_recx.p, dt_segptr.p, dt_segcol.p, dt_bseg.p};
+    HIPC(dt_order.alloc(sizeof(int32_t) * (size_t)n));
+    HIPC(dt_len.alloc(sizeof(int64_t) * (size_t)n));
+    HIPC(dt_qoff.alloc(sizeof(int64_t) * (size_t)n));
+    HIPC(dt_keys.alloc(sizeof(uint64_t) * 2 * nz));  // the sort's double buffer; the first half
+    HIPC(dt_vals.alloc(sizeof(uint32_t) * 2 * nz));  // holds flags and segment ids afterwards
+    HIPC(dt_entq.alloc(sizeof(int32_t) * nz));
+    HIPC(dt_recr.alloc(sizeof(int32_t) * nz));
+    HIPC(dt_recx.alloc(sizeof(T) * nz));
+    HIPC(dt_segptr.alloc(sizeof(int32_t) * (nz + 1)));
+    HIPC(dt_segcol.alloc(sizeof(int32_t) * nz));
+    HIPC(dt_bseg.alloc(sizeof(int32_t) * ((size_t)nbat + 1)));
+    const void* now[] = {dt_recr.p, dt_recx.p, dt_segptr.p, dt_segcol.p, dt_bseg.p};
+    if (memcmp(old, now, sizeof old) != 0) clear_graphs();
+    uint64_t* kin = dt_keys.as<uint64_t>();
+    uint64_t* kout = kin + nz;
+    uint32_t* vin = dt_vals.as<uint32_t>();
+    uint32_t* vout = vin + nz;
+    int32_t* flag = reinterpret_cast<int32_t*>(kin);  // (free once the sort has read its input)
+    int32_t* sid1 = flag + nz;
+    // the key bits that can differ: minibatch * d + column < nbat * d
+    const uint64_t kmax = (uint64_t)nbat * (uint64_t)d;
+    unsigned bits = 1;
+    while (bits < 64 && (kmax - 1) >> bits) ++bits;
+    size_t t1 = 0, t2 = 0, t3 = 0;
+    HIPC(rocprim::exclusive_scan(nullptr, t1, dt_len.as<int64_t>(), dt_qoff.as<int64_t>(),
+                                 (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), stream));
+    HIPC(rocprim::radix_sort_pairs(nullptr, t2, kin, kout, vin, vout, nz, 0u, bits, stream));
+    HIPC(rocprim::inclusive_scan(nullptr, t3, flag, sid1, nz, rocprim::plus<int32_t>(), stream));
+    HIPC(dt_tmp.alloc(std::max(t1, std::max(t2, t3))));
+    HIPC(hipMemsetAsync(figs, 0, sizeof(int) * 4, stream));
+    HIPC(hipMemsetAsync(dt_bseg.p, 0, sizeof(int32_t) * ((size_t)nbat + 1), stream));
+    HIPC(hipMemsetAsync(dt_segptr.p, 0, sizeof(int32_t), stream));  // (no entry at all: no segment)
+    if (N > 0) {
+        hipLaunchKernelGGL(det_rowlen_kernel, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, stream,
+                           sg_samples.as<int32_t>(), rptr.as<int64_t>(), n, dt_len.as<int64_t>());
+        t1 = dt_tmp.bytes;
+        HIPC(rocprim::exclusive_scan(dt_tmp.p, t1, dt_len.as<int64_t>(), dt_qoff.as<int64_t>(),
+                                     (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), stream));
+        hipLaunchKernelGGL(det_enum_kernel, dim3(cdiv(n, kBlock / 16)), dim3(kBlock), 0, stream,
+                           sg_samples.as<int32_t>(), rptr.as<int64_t>(), ridx.as<int32_t>(),
+                           dt_qoff.as<int64_t>(), n, batch_size, d, kin, vin,
+                           dt_entq.as<int32_t>());
+        t2 = dt_tmp.bytes;
+        HIPC(rocprim::radix_sort_pairs(dt_tmp.p, t2, kin, kout, vin, vout, (size_t)N, 0u, bits,
+                                       stream));
+        hipLaunchKernelGGL((det_head_kernel<T>), dim3(cdiv(N, kBlock)), dim3(kBlock), 0, stream,
+                           kout, vout, dt_entq.as<int32_t>(), sg_samples.as<int32_t>(),
+                           rptr.as<int64_t>(), rval.as<T>(), dt_qoff.as<int64_t>(), N, batch_size,
+                           dt_recr.as<int32_t>(), dt_recx.as<T>(), flag);
+        t3 = dt_tmp.bytes;
+        HIPC(rocprim::inclusive_scan(dt_tmp.p, t3, flag, sid1, (size_t)N,
+                                     rocprim::plus<int32_t>(), stream));
+        hipLaunchKernelGGL(det_seg_kernel, dim3(cdiv(N, kBlock)), dim3(kBlock), 0, stream, kout,
+                           flag, sid1, N, d, nbat, dt_segptr.as<int32_t>(),
+                           dt_segcol.as<int32_t>(), dt_bseg.as<int32_t>(), figs);
+        hipLaunchKernelGGL(det_longest_kernel, dim3(cdiv(N, kBlock)), dim3(kBlock), 0, stream,
+                           dt_segptr.as<int32_t>(), N, figs);
+    }
+    HIPC(hipMemcpyAsync(dt_order.p, sg_samples.p, sizeof(int32_t) * (size_t)n,
+                        hipMemcpyDeviceToDevice, stream));
+    HIPC(hipGetLastError());
+    SPFM_TRY(download(h_figs, figs, 2));
+    HIPC(hipStreamSynchronize(stream));
+    dt_nseg = h_figs[0];
+    dt_longest = h_figs[1];
+    dt_bs = batch_size;
+    return SPFM_OK;
+}
+
+// the two deterministic gradient kernels in front of the shared minibatch driver
+template <typename T, int L>
+int spfm_engine::psgd_det_epoch_tl(const PsgdStep& st) {
+    if (!dt_grid) {
+        int cus = 0;
+        HIPC(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+        dt_grid = 4 * std::max(cus, 1);
+    }
+    const int64_t bmax = std::min<int64_t>(st.batch_size, n);
+    const void *o1 = dt_dl.p, *o2 = dt_state.p;
+    HIPC(dt_dl.alloc(sizeof(double) * (size_t)bmax));
+    HIPC(dt_state.alloc(sizeof(double) * (size_t)bmax * n_orders * (st.degree - 1) * k));
+    if (dt_dl.p != o1 || dt_state.p != o2) clear_graphs();
+    dt_bytes = 0;
+    for (const DevBuf* b : {&dt_order, &dt_len, &dt_qoff, &dt_keys, &dt_vals, &dt_entq, &dt_recr,
+                            &dt_recx, &dt_segptr, &dt_segcol, &dt_bseg, &dt_tmp, &dt_figs, &dt_dl,
+                            &dt_state})
+        dt_bytes += (int64_t)b->bytes;
+    const DetPlan pl{dt_bseg.as<int32_t>(), dt_segptr.as<int32_t>(), dt_segcol.as<int32_t>(),
+                     dt_recr.as<int32_t>()};
+    auto grad = [&](int64_t pos, int B, int, bool table) {
+        const PsgdBatch* sched = table ? sg_sched.as<PsgdBatch>() : (const PsgdBatch*)nullptr;
+        int* idx = table ? sg_idx.as<int>() : (int*)nullptr;
+#define SPFM_ROWSTATE(WA, wa)                                                                    \
+    hipLaunchKernelGGL((psgd_rowstate_kernel<T, L, WA>), dim3(dt_grid), dim3(kBlock), 0, stream, \
+                       sg_samples.as<int32_t>() + pos, B, rptr.as<int64_t>(),                    \
+                       ridx.as<int32_t>(), rval.as<T>(), yy.as<T>(), Pt.as<double>(),            \
+                       w.as<double>(), lams.as<double>(), n_orders, k, d, st.degree, loss,       \
+                       dt_dl.as<double>(), dt_state.as<double>(), pred_tmp.as<double>() + pos,   \
+                       sched, idx, wa)
+        if (weighted)
+            SPFM_ROWSTATE(RowWeight, RowWeight{wrow.as<double>()});
+        else
+            SPFM_ROWSTATE(NoRowWeight, NoRowWeight{});
+#undef SPFM_ROWSTATE
+        hipLaunchKernelGGL((psgd_colgrad_kernel<T, L>), dim3(dt_grid), dim3(kBlock), 0, stream, pl,
+                           dt_recx.as<T>(), (int)(pos / st.batch_size), Pt.as<double>(),
+                           lams.as<double>(), dt_dl.as<double>(), dt_state.as<double>(), n_orders,
+                           k, d, st.degree, st.fit_linear, sg_gradP.as<double>(),
+                           sg_gradw.as<double>(), (const int*)idx);
+    };
+    return psgd_batches_tl<L>(grad, weighted ? "psgd_det_w" : "psgd_det", (int64_t)sizeof(T), n, st);
+}
+
+int spfm_engine::psgd_set_deterministic(int mode) {
+    if (mode != 0 && mode != 1)
+        FAIL(SPFM_ERR_INVALID, "set_deterministic: mode must be 0 (off) or 1 (on)");
+    psgd_det = mode;
+    return SPFM_OK;
+}
+
 // optimizer/psgd.py:125-199: one pass over indices_samples
 int spfm_engine::psgd_epoch(const PsgdStep& st, const int32_t* indices_samples, int64_t n_samples,
                             int64_t row_lo, double* sum_loss) {
@@ -375,6 +523,8 @@ int spfm_engine::psgd_epoch(const PsgdStep& st, const int32_t* indices_samples, 
     if (solver != SPFM_SOLVER_PSGD) FAIL(SPFM_ERR_INVALID, "engine is not configured for psgd");
     if (st.degree != top_degree) FAIL(SPFM_ERR_INVALID, "psgd: degree differs from configure()");
     const bool sharded = dist();
+    if (psgd_det && sharded)
+        FAIL(SPFM_ERR_UNSUPPORTED, "psgd: the deterministic mode does not run on several ranks");
     if (!indices_samples || !st.it || (!sharded && (n_samples != n || row_lo != 0)))
         FAIL(SPFM_ERR_INVALID, "psgd: indices_samples must list every sample once");
     if (sharded && (row_lo < 0 || row_lo + n > n_samples || n_samples > INT32_MAX))
@@ -400,7 +550,12 @@ int spfm_engine::psgd_epoch(const PsgdStep& st, const int32_t* indices_samples, 
         SPFM_TRY(upload_to(sg_samples.p, indices_samples, (size_t)n));
         HIPC(hipStreamSynchronize(stream));  // caller may reuse indices_samples
     }
-    SPFM_TRY(SPFM_DISPATCH(dtype, return SPFM_DISPATCH_L(k, return psgd_epoch_tl<T, L>(st))));
+    if (psgd_det) {  // (psgd_epoch_end sums the rows' losses in a fixed order on either route)
+        SPFM_TRY(SPFM_DISPATCH(dtype, return det_plan<T>(st.batch_size)));
+        SPFM_TRY(SPFM_DISPATCH(dtype, return SPFM_DISPATCH_L(k, return psgd_det_epoch_tl<T, L>(st))));
+    } else {
+        SPFM_TRY(SPFM_DISPATCH(dtype, return SPFM_DISPATCH_L(k, return psgd_epoch_tl<T, L>(st))));
+    }
     return psgd_epoch_end(pred_tmp.as<double>(), n, sum_loss);
 }
 
@@ -475,6 +630,7 @@ int spfm_engine::psgd_pairs_epoch_tl(const PsgdStep& st, int64_t m) {
 int spfm_engine::psgd_pairs_epoch(const PsgdStep& st, const int32_t* triples, int64_t m,
                                   double* sum_loss) {
     if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs: several ranks are not supported");
+    SPFM_TRY(refuse_det("psgd pairs"));
     SPFM_TRY(psgd_pairs_check("psgd pairs", st.degree, triples, m));
     if (const std::string e = st.check("psgd pairs"); !e.empty()) FAIL(SPFM_ERR_INVALID, e);
     if (m == 0) {
@@ -492,6 +648,7 @@ int spfm_engine::psgd_pairs_epoch(const PsgdStep& st, const int32_t* triples, in
 int spfm_engine::psgd_pairs_epoch_weighted(const PsgdStep& st, const int32_t* triples,
                                            const double* weights, int64_t m, double* sum_loss) {
     if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs: several ranks are not supported");
+    SPFM_TRY(refuse_det("psgd pairs"));
     SPFM_TRY(psgd_pairs_check("psgd pairs", st.degree, triples, m));
     if (const std::string e = st.check("psgd pairs"); !e.empty()) FAIL(SPFM_ERR_INVALID, e);
     if (m > 0 && !weights) FAIL(SPFM_ERR_INVALID, "psgd pairs: weights must hold m values");
@@ -659,6 +816,7 @@ int spfm_engine::psgd_pairs_sample_any(bool warp, int degree, int64_t n_negative
                                        int32_t* triples_out, double* scores_out,
                                        double* weights_out, int32_t* trials_out) {
     if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs sample: several ranks are not supported");
+    SPFM_TRY(refuse_det("psgd pairs sample"));
     SPFM_TRY(psgd_ready("psgd pairs sample", degree));
     if (!have_sampler)
         FAIL(SPFM_ERR_INVALID, "psgd pairs sample: call spfm_psgd_pairs_set_sampler first");
@@ -728,6 +886,7 @@ int spfm_engine::psgd_pairs_sample(int degree, int64_t n_negatives, int64_t n_ca
 // uploaded and nothing re-checked (the list is valid by construction)
 int spfm_engine::psgd_pairs_epoch_sampled(const PsgdStep& st, double* sum_loss) {
     if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd pairs: several ranks are not supported");
+    SPFM_TRY(refuse_det("psgd pairs"));
     SPFM_TRY(psgd_ready("psgd pairs", st.degree));
     if (!sampled)
         FAIL(SPFM_ERR_INVALID, "psgd pairs: the resident triple list is not the output of "
@@ -807,6 +966,7 @@ int spfm_engine::psgd_lists_run(const PsgdStep& st, int64_t n_lists, int M, int 
 int spfm_engine::psgd_lists_epoch(const PsgdStep& st, const int32_t* triples, int64_t m,
                                   int64_t n_negatives, int list_loss, double* sum_loss) {
     if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd lists: several ranks are not supported");
+    SPFM_TRY(refuse_det("psgd lists"));
     SPFM_TRY(psgd_lists_check("psgd lists", st.degree, triples, m, n_negatives, list_loss));
     if (const std::string e = st.check("psgd lists"); !e.empty()) FAIL(SPFM_ERR_INVALID, e);
     if (m == 0) {
@@ -825,6 +985,7 @@ int spfm_engine::psgd_lists_epoch(const PsgdStep& st, const int32_t* triples, in
 int spfm_engine::psgd_lists_epoch_sampled(const PsgdStep& st, int64_t n_negatives, int list_loss,
                                           const int32_t* list_order, double* sum_loss) {
     if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd lists: several ranks are not supported");
+    SPFM_TRY(refuse_det("psgd lists"));
     SPFM_TRY(psgd_ready("psgd lists", st.degree));
     if (!sampled)
         FAIL(SPFM_ERR_INVALID, "psgd lists: the resident triple list is not the output of "
@@ -896,6 +1057,7 @@ int spfm_psgd_epoch(spfm_handle h, int degree, double alpha, double beta, double
                     const int32_t* indices_samples, int64_t n_samples, int fit_linear,
                     int64_t* it, double* sum_loss) {
     SPFM_GUARD(h);
+    if (h->dist()) SPFM_TRY(h->refuse_det("psgd (several ranks)"));
     if (h->dist()) {
         h->err = "psgd: several ranks share this handle's communicator -- use spfm_psgd_epoch_sharded";
         return SPFM_ERR_INVALID;
@@ -911,6 +1073,7 @@ int spfm_psgd_epoch_sharded(spfm_handle h, int degree, double alpha, double beta
                             int fit_linear, int64_t* it, double* sum_loss) {
     SPFM_GUARD(h);
     SPFM_TRY(h->refuse_weighted("psgd (sharded)"));
+    SPFM_TRY(h->refuse_det("psgd (sharded)"));
     const PsgdStep st = h->psgd_step(degree, alpha, beta, gamma, eta0, learning_rate, power_t,
                                       batch_size, fit_linear, it);
     return h->psgd_epoch(st, indices_samples, n_global, row_lo, sum_loss);
@@ -925,6 +1088,22 @@ int spfm_psgd_set_adaptive(spfm_handle h, int mode, double initial_accumulator,
 int spfm_psgd_get_adaptive(spfm_handle h, double* acc_P, double* acc_w) {
     SPFM_GUARD(h);
     return h->psgd_get_adaptive(acc_P, acc_w);
+}
+
+int spfm_psgd_set_deterministic(spfm_handle h, int mode) {
+    SPFM_GUARD(h);
+    return h->psgd_set_deterministic(mode);
+}
+
+int spfm_psgd_get_deterministic(spfm_handle h, int* mode, int64_t* segments,
+                                int64_t* longest_segment, int64_t* plan_bytes) {
+    SPFM_GUARD(h);
+    const bool planned = h->dt_bs > 0;
+    if (mode) *mode = h->psgd_det;
+    if (segments) *segments = planned ? h->dt_nseg : 0;
+    if (longest_segment) *longest_segment = planned ? h->dt_longest : 0;
+    if (plan_bytes) *plan_bytes = planned ? h->dt_bytes : 0;
+    return SPFM_OK;
 }
 
 int spfm_psgd_pairs_set_sampler(spfm_handle h, int64_t n_ctx, int64_t n_cand,

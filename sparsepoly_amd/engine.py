@@ -1401,6 +1401,20 @@ class HipEngine(object):
             self._h, aP.ctypes.data_as(_capi._dp), aw.ctypes.data_as(_capi._dp)))
         return aP, aw
 
+    def psgd_set_deterministic(self, mode):
+        """Fixed-order minibatch gradients for every ``psgd_epoch`` of this handle
+        (``spfm_psgd_set_deterministic``): 0 off (f64 atomics), 1 on."""
+        self._check(self._lib.spfm_psgd_set_deterministic(self._h, int(mode)))
+
+    def psgd_get_deterministic(self):
+        """``(mode, segments, longest_segment, plan_bytes)``: the mode and the figures of the
+        last plan (``spfm_psgd_get_deterministic``); zeros before the first plan."""
+        mode = C.c_int()
+        fig = [C.c_int64() for _ in range(3)]
+        self._check(self._lib.spfm_psgd_get_deterministic(
+            self._h, C.byref(mode), *(C.byref(f) for f in fig)))
+        return (mode.value,) + tuple(f.value for f in fig)
+
     @staticmethod
     def _triples(triples):
         t = np.ascontiguousarray(triples, dtype=np.int32)

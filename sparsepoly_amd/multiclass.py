@@ -75,6 +75,7 @@ class OneVsRestClassifier(ClassifierMixin, BaseEstimator):
             cw = None
         for e in ests:
             e.class_weight = cw
+            e.deterministic = self.estimator.deterministic  # (a class attribute as well)
         max_concurrent = self.max_concurrent
         if max_concurrent is None and self.estimator.solver == "pbcd":
             max_concurrent = 1  # the whole GPU each, as a solo fit has it (see the class docstring)

@@ -855,6 +855,9 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                              % (self.regularizer, list(PSGD_REGULARIZERS)))
         if self.distributed:
             raise ValueError("the pairwise fit runs on one GPU (distributed=False).")
+        if self.deterministic:
+            raise ValueError("deterministic=True covers the pointwise psgd fit only; the pairwise "
+                             "gradients are summed with atomics.")
         self._get_loss(self.loss)
         self._check_adagrad(self.regularizer, False)
         if self._base_rate() not in _capi.LEARNING_RATE:

@@ -61,6 +61,10 @@ class _BaseSparseAllSubsets(ObjectiveMixin, InteractionMixin, RankingMixin, Base
         self.precision = precision
         self.device = device
 
+    # the factorization machines' switch for solver='psgd' (DESIGN.md section 19e); the solvers of
+    # this model are deterministic as they are and ignore it
+    deterministic = False
+
     def _new_engine(self):
         from .sparse_factorization_machines import _fit_device
 

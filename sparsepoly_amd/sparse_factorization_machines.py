@@ -172,6 +172,11 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
     # the signatures stay the reference's.
     adagrad_init = 1.0
 
+    # ``solver='psgd'``: minibatch gradients summed in a fixed order instead
+    # of with hardware atomics, so that two fits with one ``random_state`` give the same bits.  A
+    # plain class attribute like ``adagrad_init``; pcd and pbcd, deterministic as they are, ignore it.
+    deterministic = False
+
     # ------------------------------------------------------------------ helpers
     def _adagrad(self):
         return self.solver == "psgd" and self.learning_rate == "adagrad"
@@ -471,6 +476,8 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
         # cache hooks (include/spfm.h "host-stepped epochs")
         self._plugin_reg = None if self._is_builtin_regularizer(reg_obj) else reg_obj
         self._check_adagrad(reg_obj, self._plugin_reg is not None)
+        if self.solver == "psgd" and self.deterministic and self.distributed:
+            raise ValueError("deterministic=True runs on one GPU (distributed=False).")
         if sample_weight is not None:
             if self.distributed:
                 raise ValueError("sample_weight / class_weight run on one GPU "
@@ -592,6 +599,8 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
             self._live = (engine, scale)
             if self.solver == "psgd":
                 self._adagrad_begin(engine, self.P_.shape)
+                # (every fit: a warm_start session may hold the previous fit's setting)
+                engine.psgd_set_deterministic(int(bool(self.deterministic)))
                 # X.count_nonzero() (dataset.py:32,84): stored entries, n*d when dense
                 nnz = X.nnz if sp.issparse(X) else n_samples * n_features
                 converged, self.n_iter_ = self._fit_psgd(engine, n_samples, n_features,

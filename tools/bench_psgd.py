@@ -11,6 +11,9 @@ the adaptive rule alternate, host clock around epoch calls that end in a device 
 medians, all repeats and the spread go to ``profiles/adagrad_<engine tag>.json`` (one entry per
 regularizer; squared norms are skipped: adaptive steps refuse them).
 
+``--deterministic`` measures the fixed-order gradient against the atomic
+one on two handles that share one image, and the plan build; -> ``profiles/psgd_det_<tag>.json``.
+
 Algorithmic HBM bytes per epoch (f32 storage of X, f64 parameters):
   gradient pass   nnz * (4 idx + 4 val) + nnz * k * (8 read P + 8 atomic add)   [P/grad rows
                   are L2/LLC-resident; counted once per touch]
@@ -38,6 +41,9 @@ if "--learning-rate" in argv:
     at = argv.index("--learning-rate")
     rate = argv[at + 1]
     del argv[at:at + 2]
+deterministic = "--deterministic" in argv
+if deterministic:
+    argv.remove("--deterministic")
 regs = argv or ["l1", "l21", "squaredl12", "squaredl21"]
 X, y = make_problem(n, d, 50, 0)
 Xc = X.tocsc()
@@ -142,8 +148,82 @@ def compare_adagrad():
         f.write("\n")
 
 
+def compare_deterministic():
+    """the fixed-order gradient against the atomic one: two handles on one
+    image, alternating; then the plan build, as the difference between a deterministic epoch that
+    has to plan and the next one with the same order; -> profiles/psgd_det_<engine tag>.json"""
+    from sparsepoly_amd import _capi
+
+    steps = int(os.environ.get("STEPS", 5))
+    tag = _capi.load().spfm_build_tag().decode()
+    rows = []
+    for reg in regs:
+        engs = {}
+        for mode in ("atomic", "deterministic"):
+            eng = HipEngine(0, "f32")
+            if engs:
+                eng.share_data(engs["atomic"])
+            else:
+                eng.set_data(Xc, y)
+            eng.set_params(0.01 * np.random.RandomState(0).randn(1, k, d), np.zeros(d), np.ones(k))
+            eng.configure("psgd", "squared", reg, 2)
+            eng.psgd_set_deterministic(int(mode == "deterministic"))
+            engs[mode] = eng
+        idx = np.arange(n, dtype=np.int32)
+        args = (2, 1e-3, 1e-3, GAMMA[reg], 0.01, rate, 1.0, batch)
+        it = {m: 1 for m in engs}
+        times = {m: [] for m in engs}
+        for rep in range(steps + 1):  # rep 0: warm-up of both (plan and graph capture included)
+            for mode, eng in engs.items():
+                t0 = time.perf_counter()
+                _, it[mode] = eng.psgd_epoch(*args, idx, True, it[mode])
+                if rep:
+                    times[mode].append(time.perf_counter() - t0)
+        eng = engs["deterministic"]
+        plan = {"unshuffled": [], "shuffled": []}
+        rng = np.random.RandomState(1)
+        for rep in range(3):
+            for name in ("shuffled", "unshuffled"):  # each order differs from the planned one
+                order = rng.permutation(n).astype(np.int32) if name == "shuffled" else idx
+                dts = []
+                for _ in range(2):
+                    t0 = time.perf_counter()
+                    _, it["deterministic"] = eng.psgd_epoch(*args, order, True, it["deterministic"])
+                    dts.append(time.perf_counter() - t0)
+                plan[name].append(dts[0] - dts[1])
+        figs = eng.psgd_get_deterministic()
+        med = {m: float(np.median(v)) for m, v in times.items()}
+        row = dict(
+            tool="bench_psgd --deterministic", build_tag=tag, device=eng.device_name, reg=reg,
+            n=n, d=d, k=k, nnz=int(nnz), batch_size=batch, updates_per_epoch=nb, warmup=1,
+            runs=steps, learning_rate=rate,
+            atomic_epoch_ms=round(med["atomic"] * 1e3, 3),
+            atomic_epoch_ms_all=[round(v * 1e3, 3) for v in times["atomic"]],
+            deterministic_epoch_ms=round(med["deterministic"] * 1e3, 3),
+            deterministic_epoch_ms_all=[round(v * 1e3, 3) for v in times["deterministic"]],
+            deterministic_over_atomic=round(med["deterministic"] / med["atomic"], 4),
+            plan_build_ms={m: [round(v * 1e3, 3) for v in plan[m]] for m in plan},
+            segments=figs[1], longest_segment=figs[2], plan_bytes=figs[3],
+            plan_bytes_per_entry=round(figs[3] / nnz, 2),
+            timing="host clock around an epoch call that ends in a device synchronise; two "
+                   "handles on one image alternate, unshuffled order, both replayed from their "
+                   "own hipGraph; plan build = an epoch that plans minus the next one")
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        for e in reversed(list(engs.values())):
+            e.close()
+    out_dir = os.environ.get("SPFM_BENCH_OUT", os.path.join(ROOT, "profiles"))
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "psgd_det_%s.json" % tag), "w") as f:
+        json.dump(rows, f, indent=1)
+        f.write("\n")
+
+
 if rate == "adagrad":
     compare_adagrad()
+    sys.exit(0)
+if deterministic:
+    compare_deterministic()
     sys.exit(0)
 for reg in regs:
     eng = HipEngine(0, "f32")
