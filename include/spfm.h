@@ -331,6 +331,45 @@ int spfm_psgd_set_deterministic(spfm_handle h, int mode);
 int spfm_psgd_get_deterministic(spfm_handle h, int* mode, int64_t* segments,
                                 int64_t* longest_segment, int64_t* plan_bytes);
 
+/* Deterministic minibatch gradients for the triple epochs spfm_psgd_pairs_epoch,
+ * spfm_psgd_pairs_epoch_sampled and spfm_psgd_pairs_epoch_weighted.  A
+ * switch of its own: spfm_psgd_set_deterministic concerns spfm_psgd_epoch alone, and a handle
+ * where THAT switch is 1 keeps refusing the pair entries.  Mode 0 (the default) scatters every
+ * triple's terms with f64 atomics.  In mode 1 every sum has a fixed order and no float atomic is
+ * used: with the minibatch the triples at positions [pos, pos + B),
+ *   grad_P[o, j, s] = the sum over the triples r of the batch, ascending; within one triple the
+ *                     terms come in the order anchor, plus, minus:
+ *                       anchor   dL lams_s (D+_j - D-_j)    j stored in the anchor row
+ *                       plus    +dL lams_s  D+_j            j stored in the plus row
+ *                       minus   -dL lams_s  D-_j            j stored in the minus row
+ *   grad_w[j]       likewise of +dL z+_j and -dL z-_j (the anchors' columns receive no term),
+ * each term formed by the expressions of the default route.  A column stored in the plus and in
+ * the minus row of one triple contributes two terms, in that order.  A (minibatch, column) run
+ * longer than 256 terms is summed in pieces of 256, each from zero, and the pieces' sums are added
+ * in ascending order: the shape of a sum depends on the run's length alone.  A per-triple weight
+ * multiplies dL as on the default route; a triple of weight 0 keeps its terms, which are exact
+ * zeros (its dL and loss are set to 0, not multiplied), so the order is a function of the triple list and batch_size alone -- never of the
+ * weights, the grid, graph replay against eager launches, or the run.  The handle keeps a device
+ * plan built from the resident triple list (uploaded or sampled; budget 44 bytes per stored entry
+ * of a triple's three rows in f32 storage, 48 in f64, 28 per triple, and the sort's temporary
+ * storage -- 57 bytes per entry were measured; spfm_psgd_pairs_get_deterministic reports the
+ * bytes held), rebuilt only when that
+ * list or batch_size differs from the planned copy (compared on the device); new data, a new
+ * sampler and every other entry that fills the triple list drop it.
+ * spfm_psgd_pairs_sample and spfm_psgd_pairs_sample_warp hold no float atomic (integer draws,
+ * scores by a per-triple DP) and run unchanged in mode 1.
+ * SPFM_ERR_UNSUPPORTED in mode 1, before any gradient is launched and with the parameters as they
+ * were: spfm_psgd_lists_epoch and spfm_psgd_lists_epoch_sampled; a handle with a communicator;
+ * more than 2^31 - 1 plan records (stored entries of the three rows, summed over the list), or
+ * more than 2^30 triples in one minibatch.  SPFM_ERR_INVALID: a mode other than 0 / 1. */
+int spfm_psgd_pairs_set_deterministic(spfm_handle h, int mode);
+/* The mode and the figures of the last plan of the triple epochs, as
+ * spfm_psgd_get_deterministic reports them for the pointwise one: its (minibatch, column) runs,
+ * the terms of the longest one, and the device bytes the mode holds on the handle.  Zeros before
+ * the first plan and after the plan was dropped. */
+int spfm_psgd_pairs_get_deterministic(spfm_handle h, int* mode, int64_t* segments,
+                                      int64_t* longest_segment, int64_t* plan_bytes);
+
 /* Pairwise ranking fit: one pass of minibatch psgd over triples.  The
  * handle's data is the stacked matrix [X; Z] (contexts, then candidates; the targets are not
  * read).  Row k of `triples` (m, 3) is (anchor, plus, minus), three row indices into that matrix:

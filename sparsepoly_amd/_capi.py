@@ -99,6 +99,7 @@ SYMBOLS = [
     "spfm_psgd_lists_epoch", "spfm_psgd_lists_epoch_sampled", "spfm_psgd_lists_eval",
     "spfm_psgd_set_adaptive", "spfm_psgd_get_adaptive",
     "spfm_psgd_set_deterministic", "spfm_psgd_get_deterministic",
+    "spfm_psgd_pairs_set_deterministic", "spfm_psgd_pairs_get_deterministic",
     "spfm_host_epoch_begin",
     "spfm_host_pass_begin", "spfm_host_step_sums", "spfm_host_step_apply", "spfm_host_epoch_end", "spfm_comm_unique_id", "spfm_comm_init", "spfm_comm_init_shm", "spfm_peer_alloc", "spfm_peer_connect",
     "spfm_profile_enable", "spfm_profile_get", "spfm_profile_reset", "spfm_set_use_graph",
@@ -239,6 +240,8 @@ def load():
     L.spfm_psgd_get_adaptive.argtypes = [_h, _dp, _dp]
     L.spfm_psgd_set_deterministic.argtypes = [_h, C.c_int]
     L.spfm_psgd_get_deterministic.argtypes = [_h, C.POINTER(C.c_int), _lp, _lp, _lp]
+    L.spfm_psgd_pairs_set_deterministic.argtypes = [_h, C.c_int]
+    L.spfm_psgd_pairs_get_deterministic.argtypes = [_h, C.POINTER(C.c_int), _lp, _lp, _lp]
     L.spfm_host_epoch_begin.argtypes = [_h, C.c_int, C.c_int]
     L.spfm_host_pass_begin.argtypes = [_h, C.c_int]
     L.spfm_host_step_sums.argtypes = [_h, C.c_int, _dp]

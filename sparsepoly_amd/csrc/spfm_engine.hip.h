@@ -103,6 +103,8 @@ typedef struct ncclComm* ncclComm_t;
 // (`share`: the matrix image and the entry streams of co-tenant fits, spfm_share_data); the
 // memory is freed with its last holder.  `alloc` on a shared buffer detaches first, so a handle
 // can never write into -- or resize under -- memory that another handle reads.
+struct DetPlanBufs;  // spfm_psgd_plan.hip.h
+
 struct DevBuf {
     struct Block {
         void* p;
@@ -1098,14 +1100,53 @@ struct spfm_engine {
     int psgd_set_deterministic(int mode);
     template <typename T>
     int det_plan(int64_t batch_size);  // (re)builds the plan if the order or batch_size changed
+    // what this plan and the triples' one (section 19f) share: sort and run tables
+    // (spfm_psgd_plan.hip.h)
+    template <typename LenFn, typename EnumFn, typename HeadFn>
+    int det_plan_runs(DetPlanBufs b, size_t rec_bytes, size_t x_bytes, int64_t N, int64_t nbat,
+                      size_t t1, LenFn&& lengths, EnumFn&& enumerate, HeadFn&& head,
+                      int64_t& nseg, int64_t& longest);
     template <typename T, int L>
     int psgd_det_epoch_tl(const PsgdStep& st);
+    int det_grid_init() {  // dt_grid, once
+        if (!dt_grid) {
+            int cus = 0;
+            HIPC(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+            dt_grid = 4 * std::max(cus, 1);
+        }
+        return SPFM_OK;
+    }
+    // the deterministic gradient of the triple epochs (DESIGN.md section 19f;
+    // spfm_engine_psgd_pairs_det.hip): a switch of its own and a plan of its own, built from the
+    // resident triple list.  pd_trip is the planned copy of sg_triples[0, pd_m), pd_bs the planned
+    // batch size (0: no plan; new data, a new sampler and every entry that fills sg_triples for
+    // something else clear it).  A moved buffer clears the graphs.
+    DevBuf pd_trip, pd_len, pd_qoff, pd_keys, pd_vals, pd_entq, pd_rec, pd_recx, pd_segptr,
+        pd_segcol, pd_bseg, pd_tmp, pd_figs, pd_dl, pd_state;
+    int pairs_det = 0;
+    int64_t pd_bs = 0, pd_m = 0, pd_nseg = 0, pd_longest = 0, pd_bytes = 0;
+    int refuse_pairs_det(const char* what) {
+        if (pairs_det)
+            FAIL(SPFM_ERR_UNSUPPORTED,
+                 std::string(what) + ": not on a handle whose triple epochs are in deterministic "
+                                     "mode (spfm_psgd_pairs_set_deterministic)");
+        return SPFM_OK;
+    }
+    int psgd_pairs_set_deterministic(int mode);
+    template <typename T>
+    int pairs_det_plan_t(int64_t m, int64_t batch_size);  // (re)builds the plan if need be
+    int pairs_det_prepare(const PsgdStep& st, int64_t m);  // plan, state buffers, pd_bytes
+    template <typename T, int L, bool WT>
+    void pairs_det_launch_tl(int64_t pos, int B, bool table, const PsgdStep& st);
+    void pairs_det_launch(int64_t pos, int B, bool table, const PsgdStep& st, bool weighted);
 
     // pairwise ranking fit: triples (anchor, plus, minus) of rows of the
     // handle's data [X; Z]; buffers of their own (sg_samples and pred_tmp are sized by n)
     DevBuf sg_triples, sg_lossrow, sg_ordered;
     int psgd_pairs_check(const char* what, int degree, const int32_t* triples, int64_t m);
-    int pairs_reserve(int64_t m);  // sg_triples / sg_lossrow; a moved buffer clears the graphs
+    // sg_triples / sg_lossrow; a moved buffer clears the graphs.  keep_plan: the caller is a pair
+    // epoch, whose list the deterministic plan compares itself; every other entry drops that plan
+    int pairs_reserve(int64_t m, bool keep_plan = false);
     template <typename T, int L, bool WT>
     int psgd_pairs_epoch_tl(const PsgdStep& st, int64_t m);
     int psgd_pairs_epoch(const PsgdStep& st, const int32_t* triples, int64_t m, double* sum_loss);

@@ -244,6 +244,7 @@ int spfm_engine::data_installed(const double* y) {
     have_sampler = false;  // the positives and the drawn triples named rows of the old data
     sampled = false;
     dt_bs = 0;  // the deterministic psgd plan sorted the old data's entries
+    pd_bs = 0;  // and so did the plan of the triple epochs
     col_norm_reduced = false;
     invalidate(kInvSchedule | kInvGraphs);
     HIPC(viol_col.alloc(sizeof(double) * (size_t)d));

@@ -3,10 +3,7 @@
 #include "spfm_psgd_pairs.hip.h"
 #include "spfm_psgd_sample.hip.h"
 #include "spfm_psgd_lists.hip.h"
-#include "spfm_psgd_det.hip.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
+#include "spfm_psgd_plan.hip.h"
 
 using namespace spfm;
 
@@ -392,73 +389,37 @@ int spfm_engine::det_plan(int64_t batch_size) {
         if (!h_figs[0]) return SPFM_OK;
     }
     dt_bs = 0;
-    const size_t nz = (size_t)(N > 0 ? N : 1);
-    const void* old[] = {dt_recr.p, dt_recx.p, dt_segptr.p, dt_segcol.p, dt_bseg.p};
     HIPC(dt_order.alloc(sizeof(int32_t) * (size_t)n));
     HIPC(dt_len.alloc(sizeof(int64_t) * (size_t)n));
     HIPC(dt_qoff.alloc(sizeof(int64_t) * (size_t)n));
-    HIPC(dt_keys.alloc(sizeof(uint64_t) * 2 * nz));  // the sort's double buffer; the first half
-    HIPC(dt_vals.alloc(sizeof(uint32_t) * 2 * nz));  // holds flags and segment ids afterwards
-    HIPC(dt_entq.alloc(sizeof(int32_t) * nz));
-    HIPC(dt_recr.alloc(sizeof(int32_t) * nz));
-    HIPC(dt_recx.alloc(sizeof(T) * nz));
-    HIPC(dt_segptr.alloc(sizeof(int32_t) * (nz + 1)));
-    HIPC(dt_segcol.alloc(sizeof(int32_t) * nz));
-    HIPC(dt_bseg.alloc(sizeof(int32_t) * ((size_t)nbat + 1)));
-    const void* now[] = {dt_recr.p, dt_recx.p, dt_segptr.p, dt_segcol.p, dt_bseg.p};
-    if (memcmp(old, now, sizeof old) != 0) clear_graphs();
-    uint64_t* kin = dt_keys.as<uint64_t>();
-    uint64_t* kout = kin + nz;
-    uint32_t* vin = dt_vals.as<uint32_t>();
-    uint32_t* vout = vin + nz;
-    int32_t* flag = reinterpret_cast<int32_t*>(kin);  // (free once the sort has read its input)
-    int32_t* sid1 = flag + nz;
-    // the key bits that can differ: minibatch * d + column < nbat * d
-    const uint64_t kmax = (uint64_t)nbat * (uint64_t)d;
-    unsigned bits = 1;
-    while (bits < 64 && (kmax - 1) >> bits) ++bits;
-    size_t t1 = 0, t2 = 0, t3 = 0;
+    size_t t1 = 0;
     HIPC(rocprim::exclusive_scan(nullptr, t1, dt_len.as<int64_t>(), dt_qoff.as<int64_t>(),
                                  (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), stream));
-    HIPC(rocprim::radix_sort_pairs(nullptr, t2, kin, kout, vin, vout, nz, 0u, bits, stream));
-    HIPC(rocprim::inclusive_scan(nullptr, t3, flag, sid1, nz, rocprim::plus<int32_t>(), stream));
-    HIPC(dt_tmp.alloc(std::max(t1, std::max(t2, t3))));
-    HIPC(hipMemsetAsync(figs, 0, sizeof(int) * 4, stream));
-    HIPC(hipMemsetAsync(dt_bseg.p, 0, sizeof(int32_t) * ((size_t)nbat + 1), stream));
-    HIPC(hipMemsetAsync(dt_segptr.p, 0, sizeof(int32_t), stream));  // (no entry at all: no segment)
-    if (N > 0) {
+    auto lengths = [&]() -> int {
         hipLaunchKernelGGL(det_rowlen_kernel, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, stream,
                            sg_samples.as<int32_t>(), rptr.as<int64_t>(), n, dt_len.as<int64_t>());
-        t1 = dt_tmp.bytes;
-        HIPC(rocprim::exclusive_scan(dt_tmp.p, t1, dt_len.as<int64_t>(), dt_qoff.as<int64_t>(),
+        size_t tb = dt_tmp.bytes;
+        HIPC(rocprim::exclusive_scan(dt_tmp.p, tb, dt_len.as<int64_t>(), dt_qoff.as<int64_t>(),
                                      (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), stream));
+        return SPFM_OK;
+    };
+    auto enumerate = [&](uint64_t* key, uint32_t* val, int32_t* entq) {
         hipLaunchKernelGGL(det_enum_kernel, dim3(cdiv(n, kBlock / 16)), dim3(kBlock), 0, stream,
                            sg_samples.as<int32_t>(), rptr.as<int64_t>(), ridx.as<int32_t>(),
-                           dt_qoff.as<int64_t>(), n, batch_size, d, kin, vin,
-                           dt_entq.as<int32_t>());
-        t2 = dt_tmp.bytes;
-        HIPC(rocprim::radix_sort_pairs(dt_tmp.p, t2, kin, kout, vin, vout, (size_t)N, 0u, bits,
-                                       stream));
+                           dt_qoff.as<int64_t>(), n, batch_size, d, key, val, entq);
+    };
+    auto head = [&](const uint64_t* key, const uint32_t* val, const int32_t* entq, int32_t* flag) {
         hipLaunchKernelGGL((det_head_kernel<T>), dim3(cdiv(N, kBlock)), dim3(kBlock), 0, stream,
-                           kout, vout, dt_entq.as<int32_t>(), sg_samples.as<int32_t>(),
-                           rptr.as<int64_t>(), rval.as<T>(), dt_qoff.as<int64_t>(), N, batch_size,
+                           key, val, entq, sg_samples.as<int32_t>(), rptr.as<int64_t>(),
+                           rval.as<T>(), dt_qoff.as<int64_t>(), N, batch_size,
                            dt_recr.as<int32_t>(), dt_recx.as<T>(), flag);
-        t3 = dt_tmp.bytes;
-        HIPC(rocprim::inclusive_scan(dt_tmp.p, t3, flag, sid1, (size_t)N,
-                                     rocprim::plus<int32_t>(), stream));
-        hipLaunchKernelGGL(det_seg_kernel, dim3(cdiv(N, kBlock)), dim3(kBlock), 0, stream, kout,
-                           flag, sid1, N, d, nbat, dt_segptr.as<int32_t>(),
-                           dt_segcol.as<int32_t>(), dt_bseg.as<int32_t>(), figs);
-        hipLaunchKernelGGL(det_longest_kernel, dim3(cdiv(N, kBlock)), dim3(kBlock), 0, stream,
-                           dt_segptr.as<int32_t>(), N, figs);
-    }
+    };
+    SPFM_TRY(det_plan_runs({dt_keys, dt_vals, dt_entq, dt_recr, dt_recx, dt_segptr, dt_segcol,
+                            dt_bseg, dt_tmp, dt_figs},
+                           sizeof(int32_t), sizeof(T), N, nbat, t1, lengths, enumerate, head,
+                           dt_nseg, dt_longest));
     HIPC(hipMemcpyAsync(dt_order.p, sg_samples.p, sizeof(int32_t) * (size_t)n,
                         hipMemcpyDeviceToDevice, stream));
-    HIPC(hipGetLastError());
-    SPFM_TRY(download(h_figs, figs, 2));
-    HIPC(hipStreamSynchronize(stream));
-    dt_nseg = h_figs[0];
-    dt_longest = h_figs[1];
     dt_bs = batch_size;
     return SPFM_OK;
 }
@@ -466,11 +427,7 @@ int spfm_engine::det_plan(int64_t batch_size) {
 // the two deterministic gradient kernels in front of the shared minibatch driver
 template <typename T, int L>
 int spfm_engine::psgd_det_epoch_tl(const PsgdStep& st) {
-    if (!dt_grid) {
-        int cus = 0;
-        HIPC(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-        dt_grid = 4 * std::max(cus, 1);
-    }
+    SPFM_TRY(det_grid_init());
     const int64_t bmax = std::min<int64_t>(st.batch_size, n);
     const void *o1 = dt_dl.p, *o2 = dt_state.p;
     HIPC(dt_dl.alloc(sizeof(double) * (size_t)bmax));
@@ -592,7 +549,8 @@ int spfm_engine::psgd_pairs_check(const char* what, int degree, const int32_t* t
 
 // room for m triples and their losses (a new allocation changes the recorded kernel arguments);
 // whatever list was drawn on the device is about to be overwritten
-int spfm_engine::pairs_reserve(int64_t m) {
+int spfm_engine::pairs_reserve(int64_t m, bool keep_plan) {
+    if (!keep_plan) pd_bs = 0;
     sampled = false;
     sampled_weighted = false;
     const void *o1 = sg_triples.p, *o2 = sg_lossrow.p;
@@ -638,7 +596,7 @@ int spfm_engine::psgd_pairs_epoch(const PsgdStep& st, const int32_t* triples, in
         return SPFM_OK;
     }
     SPFM_TRY(ensure_pt());
-    SPFM_TRY(pairs_reserve(m));
+    SPFM_TRY(pairs_reserve(m, true));
     SPFM_TRY(upload_to(sg_triples.p, triples, 3 * (size_t)m));
     HIPC(hipStreamSynchronize(stream));  // caller may reuse triples
     return psgd_pairs_run(st, m, sum_loss);
@@ -661,7 +619,7 @@ int spfm_engine::psgd_pairs_epoch_weighted(const PsgdStep& st, const int32_t* tr
         return SPFM_OK;
     }
     SPFM_TRY(ensure_pt());
-    SPFM_TRY(pairs_reserve(m));
+    SPFM_TRY(pairs_reserve(m, true));
     SPFM_TRY(weights_reserve(m));
     SPFM_TRY(upload_to(sg_triples.p, triples, 3 * (size_t)m));
     SPFM_TRY(upload_to(sg_weights.p, weights, (size_t)m));
@@ -672,7 +630,16 @@ int spfm_engine::psgd_pairs_epoch_weighted(const PsgdStep& st, const int32_t* tr
 // the batches over the resident triple list sg_triples[0, m) and the sum of the triples' losses
 int spfm_engine::psgd_pairs_run(const PsgdStep& st, int64_t m, double* sum_loss, bool weighted) {
     p_valid = false;
-    if (weighted)
+    if (pairs_det) {  // the two fixed-order kernels behind the same driver
+        SPFM_TRY(pairs_det_prepare(st, m));
+        auto grad = [&](int64_t pos, int B, int, bool table) {
+            pairs_det_launch(pos, B, table, st, weighted);
+        };
+        const int64_t tsize = dtype == SPFM_F32 ? 4 : 8;
+        SPFM_TRY(SPFM_DISPATCH_L(k, return psgd_batches_tl<L>(
+                                        grad, weighted ? "psgd_pairs_det_w" : "psgd_pairs_det",
+                                        tsize, m, st)));
+    } else if (weighted)
         SPFM_TRY(SPFM_DISPATCH(dtype, return SPFM_DISPATCH_L(
                                           k, return psgd_pairs_epoch_tl<T, L, true>(st, m))));
     else
@@ -718,6 +685,7 @@ int spfm_engine::psgd_pairs_set_sampler(int64_t n_ctx, int64_t n_cand, const int
                                         const int32_t* forb_idx) {
     have_sampler = false;
     sampled = false;
+    pd_bs = 0;  // the deterministic plan of a list the old sampler drew
     have_proposal = have_posw = sampled_weighted = false;  // they go with the sampler
     if (!have_data) FAIL(SPFM_ERR_INVALID, "set_sampler: data is required");
     if (n_ctx < 1 || n_cand < 1 || n_ctx + n_cand != n)
@@ -967,6 +935,7 @@ int spfm_engine::psgd_lists_epoch(const PsgdStep& st, const int32_t* triples, in
                                   int64_t n_negatives, int list_loss, double* sum_loss) {
     if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd lists: several ranks are not supported");
     SPFM_TRY(refuse_det("psgd lists"));
+    SPFM_TRY(refuse_pairs_det("psgd lists"));
     SPFM_TRY(psgd_lists_check("psgd lists", st.degree, triples, m, n_negatives, list_loss));
     if (const std::string e = st.check("psgd lists"); !e.empty()) FAIL(SPFM_ERR_INVALID, e);
     if (m == 0) {
@@ -986,6 +955,7 @@ int spfm_engine::psgd_lists_epoch_sampled(const PsgdStep& st, int64_t n_negative
                                           const int32_t* list_order, double* sum_loss) {
     if (dist()) FAIL(SPFM_ERR_UNSUPPORTED, "psgd lists: several ranks are not supported");
     SPFM_TRY(refuse_det("psgd lists"));
+    SPFM_TRY(refuse_pairs_det("psgd lists"));
     SPFM_TRY(psgd_ready("psgd lists", st.degree));
     if (!sampled)
         FAIL(SPFM_ERR_INVALID, "psgd lists: the resident triple list is not the output of "

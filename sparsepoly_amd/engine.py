@@ -1415,6 +1415,22 @@ class HipEngine(object):
             self._h, C.byref(mode), *(C.byref(f) for f in fig)))
         return (mode.value,) + tuple(f.value for f in fig)
 
+    def psgd_pairs_set_deterministic(self, mode):
+        """Fixed-order minibatch gradients for the triple epochs of this handle --
+        ``psgd_pairs_epoch``, ``psgd_pairs_epoch_sampled``, ``psgd_pairs_epoch_weighted``
+        (``spfm_psgd_pairs_set_deterministic``): 0 off (f64 atomics), 1 on.
+        A switch of its own: ``psgd_set_deterministic`` concerns ``psgd_epoch`` alone."""
+        self._check(self._lib.spfm_psgd_pairs_set_deterministic(self._h, int(mode)))
+
+    def psgd_pairs_get_deterministic(self):
+        """``(mode, segments, longest_segment, plan_bytes)`` of the triple epochs' plan
+        (``spfm_psgd_pairs_get_deterministic``); zeros before the first plan."""
+        mode = C.c_int()
+        fig = [C.c_int64() for _ in range(3)]
+        self._check(self._lib.spfm_psgd_pairs_get_deterministic(
+            self._h, C.byref(mode), *(C.byref(f) for f in fig)))
+        return (mode.value,) + tuple(f.value for f in fig)
+
     @staticmethod
     def _triples(triples):
         t = np.ascontiguousarray(triples, dtype=np.int32)

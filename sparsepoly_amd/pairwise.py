@@ -855,9 +855,6 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                              % (self.regularizer, list(PSGD_REGULARIZERS)))
         if self.distributed:
             raise ValueError("the pairwise fit runs on one GPU (distributed=False).")
-        if self.deterministic:
-            raise ValueError("deterministic=True covers the pointwise psgd fit only; the pairwise "
-                             "gradients are summed with atomics.")
         self._get_loss(self.loss)
         self._check_adagrad(self.regularizer, False)
         if self._base_rate() not in _capi.LEARNING_RATE:
@@ -919,6 +916,10 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
             raise ValueError("objective %r is not supported. Choose from %s."
                              % (objective, list(OBJECTIVES)))
         listwise = objective != "pairwise"
+        if listwise and self.deterministic:
+            raise ValueError("deterministic=True covers objective='pairwise' (DESIGN.md section "
+                             "19f); the gradients of the lists (objective=%r) are summed with "
+                             "atomics." % (objective,))
         if listwise:
             check_lists(triples, n_negatives, objective)
         if sampler not in SAMPLERS:
@@ -1018,6 +1019,8 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
             engine.set_params(self.P_, self.w_, self.lams_)
             engine.configure("psgd", self.loss, self.regularizer, self.degree)
             self._adagrad_begin(engine, self.P_.shape)
+            if not listwise:  # (a list fit with it raised above)
+                engine.psgd_pairs_set_deterministic(int(bool(self.deterministic)))
             if sampler == "host" and sample_weight is not None:
                 lists = epoch_triples(rng, self.max_iter, interactions, triples, n_negatives,
                                       resample, self.shuffle, exclude, weights=sample_weight)

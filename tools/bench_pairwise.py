@@ -13,7 +13,11 @@ two of 64 attribute columns (one to three entries).  k = 30, degree 2, l1, logis
 The memory claim needs no run: 12 bytes per triple against two stored rows per triple.
 
 ``--profile-only``: warm-up and ``--runs`` epochs of both routes and nothing else, for a
-``rocprofv3 --kernel-trace --stats`` run of this tool."""
+``rocprofv3 --kernel-trace --stats`` run of this tool.
+
+``--deterministic`` measures the fixed-order triple gradient against the
+atomic one instead: two handles on one image, the epochs interleaved, and the plan build as an
+epoch that plans minus the next epoch over the same list."""
 import argparse
 import json
 import os
@@ -58,6 +62,70 @@ def build_stacked_rows(X, Z, t):
     return S, np.tile([1.0, -1.0], t.shape[0])
 
 
+def compare_deterministic(a, X, Z, t):
+    """``profiles/pairwise_det_<tag>.json``: median and range of the atomic and the fixed-order
+    epoch over the same uploaded list, the plan build, the plan's figures"""
+    B, C, m, k, d = X.shape[0], Z.shape[0], t.shape[0], a.k, X.shape[1]
+    P0 = 0.01 * np.random.RandomState(a.seed + 3).randn(1, k, d)
+    hyper = (2, 1e-3, 1e-3, 1e-4, 0.05, a.learning_rate, 1.0)
+    S1 = sp.vstack([X, Z], format="csr")
+    S1.sort_indices()
+    ts = (t + np.array([0, B, B])).astype(np.int32)
+    engs, it = {}, {}
+    for mode in ("atomic", "deterministic"):
+        eng = engs[mode] = HipEngine(0, "f32")
+        if mode == "atomic":
+            eng.set_data(S1, np.zeros(B + C))
+        else:
+            eng.share_data(engs["atomic"])
+        eng.set_params(P0, np.zeros(d), np.ones(k))
+        eng.configure("psgd", "logistic", "l1", 2)
+        eng.psgd_pairs_set_deterministic(int(mode == "deterministic"))
+        it[mode] = 1
+
+    def run(mode, triples=ts):
+        t0 = time.perf_counter()
+        _, it[mode] = engs[mode].psgd_pairs_epoch(*hyper, a.batch, triples, True, it[mode])
+        return time.perf_counter() - t0
+
+    times = {mode: [] for mode in engs}
+    for ep in range(a.warmup + a.runs):  # interleaved: drift of the machine hits both alike
+        for mode in engs:
+            dt = run(mode)
+            if ep >= a.warmup:
+                times[mode].append(dt)
+    plans = []
+    for _ in range(3):  # a list the plan has not seen, then the same list again
+        other = np.ascontiguousarray(ts[np.random.RandomState(len(plans)).permutation(m)])
+        plans.append(run("deterministic", other) - run("deterministic", other))
+    figs = engs["deterministic"].psgd_pairs_get_deterministic()
+    tag = _capi.load().spfm_build_tag().decode()
+    med = {r: float(np.median(v)) for r, v in times.items()}
+    out = dict(
+        tool="bench_pairwise --deterministic", build_tag=tag,
+        device=engs["atomic"].device_name, learning_rate=a.learning_rate, contexts=B,
+        candidates=C, features=d, k=k, triples=m, batch_size=a.batch,
+        updates_per_epoch=-(-m // a.batch), warmup=a.warmup, runs=a.runs,
+        atomic_epoch_ms=round(med["atomic"] * 1e3, 3),
+        atomic_epoch_ms_all=[round(v * 1e3, 3) for v in times["atomic"]],
+        deterministic_epoch_ms=round(med["deterministic"] * 1e3, 3),
+        deterministic_epoch_ms_all=[round(v * 1e3, 3) for v in times["deterministic"]],
+        deterministic_over_atomic=round(med["deterministic"] / med["atomic"], 4),
+        plan_build_ms=round(float(np.median(plans)) * 1e3, 3),
+        plan_build_ms_all=[round(v * 1e3, 3) for v in plans],
+        plan_runs=figs[1], plan_longest_run=figs[2], plan_bytes=figs[3],
+        timing="host clock around an epoch call that ends in a device synchronise; every epoch "
+               "uploads its 12 m bytes of triples; plan build = an epoch over a new list minus "
+               "the next epoch over the same list")
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "pairwise_det_%s.json" % tag), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out), flush=True)
+    for eng in engs.values():
+        eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument("--contexts", type=int, default=100_000)
@@ -75,6 +143,8 @@ def main():
     ap.add_argument("--learning-rate", default="optimal",
                     help="step rule of both routes; 'adagrad': per-feature AdaGrad steps on the "
                          "constant rate (DESIGN.md section 19d)")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="the fixed-order triple gradient against the atomic one (section 19f)")
     a = ap.parse_args()
 
     B, C, m, k = a.contexts, a.candidates, a.triples, a.k
@@ -85,6 +155,8 @@ def main():
     t[:, 0] = rng.randint(0, B, m)
     t[:, 1] = rng.randint(0, C, m)
     t[:, 2] = (t[:, 1] + rng.randint(1, C, m)) % C
+    if a.deterministic:
+        return compare_deterministic(a, X, Z, t)
     t0 = time.perf_counter()
     S2, y2 = build_stacked_rows(X, Z, t)
     build_s = time.perf_counter() - t0
