@@ -306,6 +306,51 @@ int spfm_psgd_set_adaptive(spfm_handle h, int mode, double initial_accumulator,
  * spfm_psgd_set_adaptive. */
 int spfm_psgd_get_adaptive(spfm_handle h, double* acc_P, double* acc_w);
 
+/* FTRL-Proximal steps for the minibatch fits: a third step rule for every
+ * epoch entry of the unit -- spfm_psgd_epoch and the pairs / lists epochs, uploaded or sampled,
+ * atomic or deterministic gradients.  The mode is handle state; the entries keep their signatures
+ * and their learning_rate gives the base rate eta of a minibatch (the estimators pass `constant`:
+ * eta = eta0).  State: z_P (n_orders, k, d) like P, n_P (n_orders, d), one f64 per order and column
+ * shared by the column's k components, z_w (d) and n_w (d).  With g the minibatch's MEAN gradient
+ * of column j of order o and g2 = sum_s g[s]^2:
+ *   g2 == 0: the column is not touched -- p, z, n stay bit for bit what they are (the lazy form:
+ *            p is refreshed only when its column receives a non-zero gradient, also when eta0,
+ *            beta or gamma changed since)
+ *   sigma    = (sqrt(n_P[o,j] + g2) - sqrt(n_P[o,j])) / eta
+ *   z[o,j,:] += g - sigma p[o,j,:];   n_P[o,j] += g2
+ *   denom    = (G0 + sqrt(n_P[o,j])) / eta + beta
+ *   l1 : p[o,j,s] = -soft(z[o,j,s], gamma) / denom
+ *   l21: p[o,j,:] = -max(0, 1 - gamma / ||z[o,j,:]||) z[o,j,:] / denom
+ * and, with fit_linear, w[j] likewise with z_w, n_w, alpha in beta's place and no sparse term.
+ * `it` advances as before.
+ *   mode                0 off: only the rule is switched off, no other argument is read and the
+ *                       state stays as it is | 1 FTRL-Proximal
+ *   G0, eta0            > 0, finite
+ *   z_P, z_w, n_P, n_w  the state to start from (a warm start): all four or none.  None (NULL): n
+ *                       starts at zero and z is derived on the device from the handle's current
+ *                       parameters and regularizer so that the closed form at n = 0 returns them,
+ *                       with denom0 = G0 / eta0 + beta:
+ *                         l1 : z = -(p denom0 + sign(p) gamma)
+ *                         l21: z = -(denom0 ||p_j|| + gamma) p_j / ||p_j||   (0 for a zero column)
+ *                         z_w = -w (G0 / eta0 + alpha)
+ *                       eta0, alpha, beta, gamma are read for this alone.
+ * A call with mode 1 always (re)sets the state; it survives spfm_set_params and epochs and is
+ * replaced by such a call or freed by spfm_destroy alone; a call that fails after its argument
+ * checks leaves the mode off and no state.  SPFM_ERR_INVALID: a mode other than 0 / 1, G0 or eta0 <= 0 or not
+ * finite, some but not all of the four arrays, a negative or non-finite n, a handle without
+ * parameters or not configured for psgd.  In mode 1 every epoch entry returns SPFM_ERR_INVALID
+ * before anything is launched (the parameters stay as they were) when the handle is configured
+ * with squaredl12 / squaredl21, when it has a communicator (several ranks), when the adaptive mode
+ * of spfm_psgd_set_adaptive is on as well, or when the parameters' n_orders / d / k changed since
+ * this call. */
+int spfm_psgd_set_ftrl(spfm_handle h, int mode, double G0, double eta0, double alpha, double beta,
+                       double gamma, const double* z_P, const double* z_w, const double* n_P,
+                       const double* n_w);
+/* The mode, G0 and the state as they stand (any pointer may be NULL).  SPFM_ERR_INVALID for an
+ * array before the first spfm_psgd_set_ftrl. */
+int spfm_psgd_get_ftrl(spfm_handle h, int* mode, double* G0, double* z_P, double* z_w,
+                       double* n_P, double* n_w);
+
 /* Deterministic minibatch gradients for spfm_psgd_epoch.  The mode is
  * handle state; 0 (the default) keeps the gradient scatter with hardware f64 atomics, whose sums
  * are taken in the order the hardware delivers the terms.  In mode 1 every sum has a fixed order:

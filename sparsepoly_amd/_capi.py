@@ -98,6 +98,7 @@ SYMBOLS = [
     "spfm_psgd_pairs_set_positive_weights", "spfm_psgd_pairs_sample_warp",
     "spfm_psgd_lists_epoch", "spfm_psgd_lists_epoch_sampled", "spfm_psgd_lists_eval",
     "spfm_psgd_set_adaptive", "spfm_psgd_get_adaptive",
+    "spfm_psgd_set_ftrl", "spfm_psgd_get_ftrl",
     "spfm_psgd_set_deterministic", "spfm_psgd_get_deterministic",
     "spfm_psgd_pairs_set_deterministic", "spfm_psgd_pairs_get_deterministic",
     "spfm_host_epoch_begin",
@@ -238,6 +239,8 @@ def load():
                                        _dp, _lp]
     L.spfm_psgd_set_adaptive.argtypes = [_h, C.c_int, C.c_double, _dp, _dp]
     L.spfm_psgd_get_adaptive.argtypes = [_h, _dp, _dp]
+    L.spfm_psgd_set_ftrl.argtypes = [_h, C.c_int] + [C.c_double] * 5 + [_dp] * 4
+    L.spfm_psgd_get_ftrl.argtypes = [_h, C.POINTER(C.c_int), _dp, _dp, _dp, _dp, _dp]
     L.spfm_psgd_set_deterministic.argtypes = [_h, C.c_int]
     L.spfm_psgd_get_deterministic.argtypes = [_h, C.POINTER(C.c_int), _lp, _lp, _lp]
     L.spfm_psgd_pairs_set_deterministic.argtypes = [_h, C.c_int]

@@ -1082,6 +1082,22 @@ struct spfm_engine {
                        double power_t, int64_t batch_size, int fit_linear, int64_t* it) const;
     int psgd_set_adaptive(int mode, double g0, const double* acc_P, const double* acc_w);
     int psgd_get_adaptive(double* acc_P, double* acc_w);
+    // FTRL-Proximal steps (spfm_engine_psgd_ftrl.hip): handle state.  z_P in
+    // the layout of Pt (n_orders, d, k), n_P (n_orders, d), z_w and n_w (d), sized at the setter
+    // (ftrl_orders, ftrl_d, ftrl_k) and written by it and by psgd_update_ftrl_kernel alone.  A
+    // moved buffer clears the graphs; ft_stage is the (k, d) image of a z_P on its way in or out,
+    // freed when the call that staged it ends.
+    DevBuf ft_zP, ft_zw, ft_nP, ft_nw, ft_stage;
+    int psgd_ftrl = 0;
+    double ftrl_g0 = 1.0;
+    int ftrl_orders = 0, ftrl_k = 0;
+    int32_t ftrl_d = 0;
+    int psgd_set_ftrl(int mode, double g0, double eta0, double alpha, double beta, double gamma,
+                      const double* z_P, const double* z_w, const double* n_P, const double* n_w);
+    int psgd_get_ftrl(int* mode, double* g0, double* z_P, double* z_w, double* n_P, double* n_w);
+    // the update of one minibatch on `grid` workgroups (b: eager; sched / idx: table-driven)
+    void psgd_ftrl_update(int grid, int fit_linear, const PsgdBatch& b, const PsgdBatch* sched,
+                          int* idx);
     // the deterministic gradient of the pointwise epoch: handle state.
     // The plan of the last (visiting order, batch_size) -- dt_order is that order, dt_bs that
     // batch size (0: no plan; new data clears it) -- the buffers of its build, and the per-batch

@@ -70,6 +70,12 @@ PsgdStep spfm_engine::psgd_step(int degree, double alpha, double beta, double ga
         st.adaptive_err = psgd_adaptive_error(
             reg == SPFM_REG_SQUAREDL12 || reg == SPFM_REG_SQUAREDL21, dist(),
             acc_orders == n_orders && acc_d == d);
+    st.ftrl = psgd_ftrl;
+    st.ftrl_g0 = ftrl_g0;
+    if (psgd_ftrl)
+        st.ftrl_err = psgd_ftrl_error(reg == SPFM_REG_SQUAREDL12 || reg == SPFM_REG_SQUAREDL21,
+                                      dist(), psgd_adaptive != 0,
+                                      ftrl_orders == n_orders && ftrl_d == d && ftrl_k == k);
     return st;
 }
 
@@ -180,9 +186,12 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
     int* h_done = reinterpret_cast<int*>(h_scalar + 4);
     // what follows a gradient, for both routes below: with a table (graph replay) the kernels
     // read the minibatch's scalars from sched[idx[1]] and the ones passed here are placeholders
-    // (adaptive steps: the kernel of DESIGN.md section 19d takes the update's place on both routes)
+    // (adaptive steps: the kernel of DESIGN.md section 19d takes the update's place on both routes;
+    // FTRL steps: the lazy kernel of section 19g, launched from its own unit)
     auto update = [&](const PsgdBatch& b, const PsgdBatch* sched, int* idx) {
-        if (st.adaptive)
+        if (st.ftrl)
+            psgd_ftrl_update(nb_dense, st.fit_linear, b, sched, idx);
+        else if (st.adaptive)
             hipLaunchKernelGGL((psgd_update_adaptive_kernel<L>), dim3(nb_dense), dim3(kBlock), 0,
                                stream, Pt.as<double>(), sg_gradP.as<double>(), w.as<double>(),
                                sg_gradw.as<double>(), sg_accP.as<double>(), sg_accw.as<double>(),
@@ -261,7 +270,7 @@ int spfm_engine::psgd_batches_tl(GradFn&& grad, const char* tag, int64_t tsize_,
         const std::string key = fkey(tag, {}, {st.degree, loss, reg, st.fit_linear, gridg, L,
                                                   tsize_, (int64_t)mich,
                                                   (int64_t)psgd_graph_sweeps,
-                                                  (int64_t)st.adaptive});
+                                                  (int64_t)st.adaptive, (int64_t)st.ftrl});
         int64_t done_b = 0;
         for (; done_b + kPsgdRun <= nbat; done_b += kPsgdRun) {
             int rc = run_cached(key, [&]() {

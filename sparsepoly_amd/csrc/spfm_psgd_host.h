@@ -22,9 +22,10 @@ struct PsgdBatch {
     int B;          // rows in the batch
     int pad;
     double cp, denp, strength, cw, denw;  // eta_P/B, 1+eta_P*beta, prox strength, eta_w/B, 1+eta_w*alpha
-    // adaptive steps only (zero otherwise): what psgd_update_adaptive_kernel forms a column's
-    // step from -- the base rates of this minibatch, the penalties as given, the accumulators'
-    // offset G0.  They travel in the table so that a replayed graph never holds a stale one.
+    // adaptive and FTRL steps only (zero otherwise): what psgd_update_adaptive_kernel and
+    // psgd_update_ftrl_kernel form a column's step from -- the base rates of this minibatch, the
+    // penalties as given, the accumulators' offset G0.  They travel in the table so that a
+    // replayed graph never holds a stale one.
     double eta_P, eta_w, alpha, beta, gamma, g0;
 };
 
@@ -61,6 +62,20 @@ inline const char* psgd_adaptive_error(bool squared_norm, bool ranks, bool acc_f
     return nullptr;
 }
 
+// FTRL-Proximal steps (spfm_psgd_set_ftrl): why a handle in that mode cannot
+// run an epoch, in the order the checks are made; nullptr: it can.
+inline const char* psgd_ftrl_error(bool squared_norm, bool ranks, bool adaptive, bool state_fit) {
+    if (squared_norm)
+        return "ftrl steps cannot be combined with squaredl12 / squaredl21: their prox couples "
+               "columns that now carry different steps";
+    if (ranks) return "ftrl steps are not supported with several ranks";
+    if (adaptive)
+        return "ftrl steps and adaptive steps are both switched on: switch one of them off";
+    if (!state_fit)
+        return "the ftrl state does not fit the parameters: call spfm_psgd_set_ftrl again";
+    return nullptr;
+}
+
 // What an epoch entry passes down to the minibatches: filled once in the extern "C" entry.
 struct PsgdStep {
     int degree;
@@ -74,6 +89,10 @@ struct PsgdStep {
     int adaptive = 0;
     double g0 = 0.0;
     const char* adaptive_err = nullptr;
+    // the handle's FTRL mode (0: off), its G0, and psgd_ftrl_error() of its state
+    int ftrl = 0;
+    double ftrl_g0 = 0.0;
+    const char* ftrl_err = nullptr;
 
     // the step-argument checks in `what`'s words; empty: none failed
     std::string check(const char* what) const {
@@ -81,6 +100,7 @@ struct PsgdStep {
                         : batch_size < 1   ? "batch_size must be >= 1"
                         : lr < 0 || lr > 3 ? "learning_rate is not supported."
                         : *it < 1          ? "it must be >= 1"
+                        : ftrl             ? ftrl_err
                         : adaptive         ? adaptive_err
                                            : nullptr;
         return e ? std::string(what) + ": " + e : std::string();
@@ -98,12 +118,13 @@ struct PsgdStep {
         e.strength = gamma * eta_P / (1 + eta_P * beta);
         e.cw = eta_w / (double)B;
         e.denw = 1 + eta_w * alpha;
-        e.eta_P = adaptive ? eta_P : 0.0;
-        e.eta_w = adaptive ? eta_w : 0.0;
-        e.alpha = adaptive ? alpha : 0.0;
-        e.beta = adaptive ? beta : 0.0;
-        e.gamma = adaptive ? gamma : 0.0;
-        e.g0 = adaptive ? g0 : 0.0;
+        const bool per_column = adaptive || ftrl;  // (both on: check() has refused the epoch)
+        e.eta_P = per_column ? eta_P : 0.0;
+        e.eta_w = per_column ? eta_w : 0.0;
+        e.alpha = per_column ? alpha : 0.0;
+        e.beta = per_column ? beta : 0.0;
+        e.gamma = per_column ? gamma : 0.0;
+        e.g0 = ftrl ? ftrl_g0 : adaptive ? g0 : 0.0;
         return e;
     }
 };

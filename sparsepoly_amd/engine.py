@@ -1401,6 +1401,40 @@ class HipEngine(object):
             self._h, aP.ctypes.data_as(_capi._dp), aw.ctypes.data_as(_capi._dp)))
         return aP, aw
 
+    def psgd_set_ftrl(self, mode, G0=1.0, eta0=1.0, alpha=0.0, beta=0.0, gamma=0.0, state=None):
+        """FTRL-Proximal steps for every psgd / pairs / lists epoch of this handle
+        (``spfm_psgd_set_ftrl``, DESIGN.md section 19g).  ``mode``: 0 off, 1 (or ``'ftrl'``) on;
+        ``state = (z_P (n_orders, k, d), z_w (d), n_P (n_orders, d), n_w (d))`` to go on from,
+        ``None``: ``n = 0`` and ``z`` derived on the device from the live parameters so that the
+        closed form at ``n = 0`` returns them (``eta0 .. gamma`` are read for that alone)."""
+        mode = 1 if mode == "ftrl" else int(mode)
+        ptrs = [None] * 4
+        if state is not None:
+            sizes = (self.n_orders * self.k * self.d, self.d, self.n_orders * self.d, self.d)
+            keep = [_capi.f64(a) for a in state]
+            if len(keep) != 4 or any(a.size != n for (a, _), n in zip(keep, sizes)):
+                raise ValueError("state must be (z_P, z_w, n_P, n_w) with n_orders * k * d, d, "
+                                 "n_orders * d and d values")
+            ptrs = [p for _, p in keep]
+        self._check(self._lib.spfm_psgd_set_ftrl(self._h, mode, float(G0), float(eta0),
+                                                 float(alpha), float(beta), float(gamma), *ptrs))
+
+    def psgd_get_ftrl(self):
+        """``(z_P (n_orders, k, d), z_w (d,), n_P (n_orders, d), n_w (d,))``: the FTRL state as it
+        stands (``spfm_psgd_get_ftrl``)."""
+        out = (np.empty((self.n_orders, self.k, self.d)), np.empty(self.d),
+               np.empty((self.n_orders, self.d)), np.empty(self.d))
+        self._check(self._lib.spfm_psgd_get_ftrl(
+            self._h, None, None, *(a.ctypes.data_as(_capi._dp) for a in out)))
+        return out
+
+    def psgd_ftrl_mode(self):
+        """``(mode, G0)`` of the handle's FTRL steps"""
+        mode, g0 = C.c_int(), C.c_double()
+        self._check(self._lib.spfm_psgd_get_ftrl(self._h, C.byref(mode), C.byref(g0), None, None,
+                                                 None, None))
+        return mode.value, g0.value
+
     def psgd_set_deterministic(self, mode):
         """Fixed-order minibatch gradients for every ``psgd_epoch`` of this handle
         (``spfm_psgd_set_deterministic``): 0 off (f64 atomics), 1 on."""

@@ -225,6 +225,11 @@ class FoldInMixin(object):
             self.adagrad_P_ = np.ascontiguousarray(
                 np.insert(self.adagrad_P_, [at] * n_new, 0.0, axis=1))
             self.adagrad_w_ = np.ascontiguousarray(np.insert(self.adagrad_w_, [at] * n_new, 0.0))
+        if hasattr(self, "ftrl_z_P_"):  # learning_rate='ftrl': likewise
+            for name in ("ftrl_z_P_", "ftrl_z_w_", "ftrl_n_P_", "ftrl_n_w_"):
+                a = getattr(self, name)
+                setattr(self, name,
+                        np.ascontiguousarray(np.insert(a, [at] * n_new, 0.0, axis=a.ndim - 1)))
         new_real, _ = _columns(self, d + n_new)
         assert (new_real[d:] == at + np.arange(n_new)).all()
         return np.arange(d, d + n_new)

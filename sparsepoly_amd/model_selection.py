@@ -184,7 +184,8 @@ def _clones(estimator, grid):
         e.set_params(**p)
         if getattr(estimator, "_validation", None) is not None:
             e._validation = estimator._validation  # set_validation: not a constructor keyword
-        for name in ("class_weight", "adagrad_init", "deterministic"):  # class attributes, set on the instance
+        # class attributes, set on the instance
+        for name in ("class_weight", "adagrad_init", "ftrl_init", "deterministic"):
             if name in vars(estimator):
                 setattr(e, name, vars(estimator)[name])
         return e

@@ -590,10 +590,76 @@ def _adaptive_state(adaptive, acc, P, dtype):
     return G0, (np.array(acc[0], dtype=dtype), np.array(acc[1], dtype=dtype))
 
 
+def ftrl_closed_form(z_P, z_w, n_P, n_w, G0, eta, alpha, beta, gamma, regularizer):
+    """(P, w) of the FTRL-Proximal state: the closed form every touched
+    column is refreshed with.  z_P (n_orders, k, d), n_P (n_orders, d), z_w / n_w (d,)."""
+    if regularizer not in ("l1", "l21"):
+        raise ValueError("ftrl steps cannot be combined with regularizer %r: its prox couples "
+                         "features that carry different steps" % (regularizer,))
+    den = ((G0 + np.sqrt(n_P)) / eta + beta)[:, None, :]
+    if regularizer == "l1":
+        P = -_soft(z_P, gamma) / den
+    else:
+        nr = np.sqrt((z_P ** 2).sum(axis=1, keepdims=True))
+        P = -np.where(nr > gamma, 1 - gamma / np.where(nr > 0, nr, 1), 0) * z_P / den
+    return P, -z_w / ((G0 + np.sqrt(n_w)) / eta + alpha)
+
+
+def ftrl_start(P, w, G0, eta0, alpha, beta, gamma, regularizer):
+    """the starting state ``(z_P, z_w, n_P, n_w)`` that ``spfm_psgd_set_ftrl`` derives when it is
+    given none: ``n = 0`` and the ``z`` whose closed form at ``n = 0`` is ``(P, w)``"""
+    P = P[None] if P.ndim == 2 else P
+    den0 = G0 / eta0 + beta
+    if regularizer == "l1":
+        z = -(P * den0 + np.sign(P) * gamma)
+    else:
+        nr = np.sqrt((P ** 2).sum(axis=1, keepdims=True))
+        z = -np.where(nr > 0, (den0 * nr + gamma) / np.where(nr > 0, nr, 1), 0) * P
+    return (z, -w * (G0 / eta0 + alpha), np.zeros((P.shape[0], P.shape[2]), dtype=P.dtype),
+            np.zeros(P.shape[2], dtype=P.dtype))
+
+
+def _ftrl_step(P, w, gP, gw, B, eta_P, eta_w, alpha, beta, gamma, regularizer, fit_linear, G0,
+               state):
+    """one minibatch of the FTRL-Proximal rule from the summed gradients; ``state`` (a list
+    ``[z_P, z_w, n_P, n_w]``) is updated in place.  A column whose mean gradient has squared norm 0
+    keeps its p, z and n: the lazy form.  -> (P, w)"""
+    z_P, z_w, n_P, n_w = state
+    if fit_linear:
+        gb = gw / B
+        n1 = n_w + gb ** 2
+        z_w += gb - (np.sqrt(n1) - np.sqrt(n_w)) / eta_w * w
+        touched = gb ** 2 != 0
+        n_w[:] = n1
+    gb = gP / B
+    g2 = (gb ** 2).sum(axis=1)
+    n1 = n_P + g2
+    z_P += gb - ((np.sqrt(n1) - np.sqrt(n_P)) / eta_P)[:, None, :] * P
+    n_P[:] = n1
+    Pn, wn = ftrl_closed_form(z_P, z_w, n_P, n_w, G0, eta_P, alpha, beta, gamma, regularizer)
+    if eta_w != eta_P:
+        wn = ftrl_closed_form(z_P, z_w, n_P, n_w, G0, eta_w, alpha, beta, gamma, regularizer)[1]
+    P = np.where((g2 != 0)[:, None, :], Pn, P)
+    return P, (np.where(touched, wn, w) if fit_linear else w)
+
+
+def _ftrl_state(ftrl, state, P, w, dtype, eta0, alpha, beta, gamma, regularizer):
+    """(G0 or None, [z_P, z_w, n_P, n_w] copies in ``dtype``) of the restatements' ``ftrl`` /
+    ``state``"""
+    if ftrl is None:
+        return None, state
+    G0 = 1.0 if ftrl is True or ftrl == "ftrl" else float(ftrl)
+    if not (G0 > 0 and np.isfinite(G0)):
+        raise ValueError("ftrl: G0 must be positive and finite")
+    if state is None:
+        state = ftrl_start(P, w, dtype(G0), eta0, alpha, beta, gamma, regularizer)
+    return G0, [np.array(a, dtype=dtype) for a in state]
+
+
 def restate_pairwise_epoch(P, w, lams, X, Z, triples, degree, loss="logistic", regularizer="l1",
                            alpha=1.0, beta=1.0, gamma=1.0, eta0=1.0, learning_rate="optimal",
                            power_t=1.0, batch_size=1, fit_linear=True, it=1, wide=False,
-                           weights=None, adaptive=None, acc=None):
+                           weights=None, adaptive=None, acc=None, ftrl=None, state=None):
     """Test aid, NumPy only: one epoch of the pairwise fit over ``triples`` (context / candidate
     numbering, visited in the order given) from ``P`` (n_orders, k, d) and ``w``.  Minibatch
     ``bi`` covers the triples ``[bi * batch_size, ...)``, the last one may be shorter; per batch
@@ -605,7 +671,11 @@ def restate_pairwise_epoch(P, w, lams, X, Z, triples, degree, loss="logistic", r
     ``adaptive``: ``None`` is the above; ``True`` / ``'adagrad'`` (G0 = 1)
     or a positive G0 steps every feature with ``eta / sqrt(G0 + A)`` -- ``learning_rate`` gives
     the base rate ``eta``, ``acc = (A_P (n_orders, d), A_w (d,))`` the accumulators to start from
-    (``None``: zeros) -- and the return value is ``(P, w, sum_loss, it, (A_P, A_w))``."""
+    (``None``: zeros) -- and the return value is ``(P, w, sum_loss, it, (A_P, A_w))``.
+
+    ``ftrl``: ``True`` / ``'ftrl'`` (G0 = 1) or a positive G0 runs the
+    FTRL-Proximal rule instead, from ``state = (z_P, z_w, n_P, n_w)`` (``None``: ``ftrl_start``
+    at the epoch's ``eta0 .. gamma``), and the return value is ``(P, w, sum_loss, it, state)``."""
     dtype = np.longdouble if wide else np.double
     P, w, lams = _as(dtype, P, w, lams)
     P = (P[None] if P.ndim == 2 else P).copy()
@@ -613,12 +683,18 @@ def restate_pairwise_epoch(P, w, lams, X, Z, triples, degree, loss="logistic", r
     t = np.asarray(triples, dtype=np.int64)
     sum_loss = dtype(0)
     G0, acc = _adaptive_state(adaptive, acc, P, dtype)
+    F0, state = _ftrl_state(ftrl, state, P, w, dtype, eta0, alpha, beta, gamma, regularizer)
     for pos in range(0, t.shape[0], int(batch_size)):
         tb = t[pos:pos + int(batch_size)]
         wb = None if weights is None else np.asarray(weights)[pos:pos + int(batch_size)]
         val, gP, gw = restate_pair_gradient(P, w, lams, X, Z, tb, degree, loss, wide, wb)
         sum_loss += val.sum()
         eta_P, eta_w = _psgd_eta(learning_rate, eta0, alpha, beta, power_t, it)
+        if F0 is not None:
+            P, w = _ftrl_step(P, w, gP, gw, tb.shape[0], eta_P, eta_w, alpha, beta, gamma,
+                              regularizer, fit_linear, F0, state)
+            it += 1
+            continue
         if G0 is not None:
             P, w = _adaptive_step(P, w, gP, gw, tb.shape[0], eta_P, eta_w, alpha, beta, gamma,
                                   regularizer, fit_linear, G0, acc)
@@ -630,6 +706,8 @@ def restate_pairwise_epoch(P, w, lams, X, Z, triples, degree, loss="logistic", r
         strength = gamma * eta_P / (1 + eta_P * beta)
         P = np.stack([_prox(regularizer, P[o], dtype(strength)) for o in range(P.shape[0])])
         it += 1
+    if F0 is not None:
+        return P, w, sum_loss, it, tuple(state)
     if G0 is not None:
         return P, w, sum_loss, it, acc
     return P, w, sum_loss, it
@@ -744,12 +822,14 @@ def restate_list_gradient(P, w, lams, X, Z, triples, n_negatives, degree, object
 def restate_list_epoch(P, w, lams, X, Z, triples, n_negatives, degree, objective="softmax",
                        loss="logistic", regularizer="l1", alpha=1.0, beta=1.0, gamma=1.0,
                        eta0=1.0, learning_rate="optimal", power_t=1.0, batch_size=1,
-                       fit_linear=True, it=1, wide=False, adaptive=None, acc=None):
+                       fit_linear=True, it=1, wide=False, adaptive=None, acc=None, ftrl=None,
+                       state=None):
     """Test aid, NumPy only: one epoch of the list fit over the grouped ``triples`` (lists
     visited in the order given).  ``restate_pairwise_epoch`` with lists as items: minibatch ``bi``
     covers the lists ``[bi * batch_size, ...)``, the step is ``eta / B`` with ``B`` lists.
     Returns ``(P, w, sum_loss over the lists, it)`` (new arrays); with ``adaptive`` / ``acc`` as in
-    ``restate_pairwise_epoch``, ``(P, w, sum_loss, it, (A_P, A_w))``."""
+    ``restate_pairwise_epoch``, ``(P, w, sum_loss, it, (A_P, A_w))``; with ``ftrl`` / ``state`` as
+    there, ``(P, w, sum_loss, it, state)``."""
     dtype = np.longdouble if wide else np.double
     P, w, lams = _as(dtype, P, w, lams)
     P = (P[None] if P.ndim == 2 else P).copy()
@@ -758,6 +838,7 @@ def restate_list_epoch(P, w, lams, X, Z, triples, n_negatives, degree, objective
     t = np.asarray(triples, dtype=np.int64)
     sum_loss = dtype(0)
     G0, acc = _adaptive_state(adaptive, acc, P, dtype)
+    F0, state = _ftrl_state(ftrl, state, P, w, dtype, eta0, alpha, beta, gamma, regularizer)
     for pos in range(0, t.shape[0] // M, int(batch_size)):
         tb = t[pos * M:(pos + int(batch_size)) * M]
         B = tb.shape[0] // M
@@ -765,6 +846,11 @@ def restate_list_epoch(P, w, lams, X, Z, triples, n_negatives, degree, objective
                                             wide)
         sum_loss += val.sum()
         eta_P, eta_w = _psgd_eta(learning_rate, eta0, alpha, beta, power_t, it)
+        if F0 is not None:
+            P, w = _ftrl_step(P, w, gP, gw, B, eta_P, eta_w, alpha, beta, gamma, regularizer,
+                              fit_linear, F0, state)
+            it += 1
+            continue
         if G0 is not None:
             P, w = _adaptive_step(P, w, gP, gw, B, eta_P, eta_w, alpha, beta, gamma, regularizer,
                                   fit_linear, G0, acc)
@@ -776,6 +862,8 @@ def restate_list_epoch(P, w, lams, X, Z, triples, n_negatives, degree, objective
         strength = gamma * eta_P / (1 + eta_P * beta)
         P = np.stack([_prox(regularizer, P[o], dtype(strength)) for o in range(P.shape[0])])
         it += 1
+    if F0 is not None:
+        return P, w, sum_loss, it, tuple(state)
     if G0 is not None:
         return P, w, sum_loss, it, acc
     return P, w, sum_loss, it

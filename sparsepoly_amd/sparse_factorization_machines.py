@@ -177,34 +177,63 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
     # plain class attribute like ``adagrad_init``; pcd and pbcd, deterministic as they are, ignore it.
     deterministic = False
 
+    # ``learning_rate='ftrl'`` (solver='psgd' and the ranker): G0 of the
+    # FTRL-Proximal steps, the counterpart of ``adagrad_init``.
+    ftrl_init = 1.0
+
     # ------------------------------------------------------------------ helpers
     def _adagrad(self):
         return self.solver == "psgd" and self.learning_rate == "adagrad"
 
+    def _ftrl(self):
+        return self.solver == "psgd" and self.learning_rate == "ftrl"
+
     def _base_rate(self):
-        """the rule the epoch entries tabulate: 'adagrad' scales the constant rate per feature"""
-        return "constant" if self._adagrad() else self.learning_rate
+        """the rule the epoch entries tabulate: 'adagrad' and 'ftrl' scale the constant rate per
+        feature"""
+        return "constant" if self._adagrad() or self._ftrl() else self.learning_rate
 
     def _check_adagrad(self, reg_obj, plugin):
-        """what ``learning_rate='adagrad'`` cannot be combined with, before any device work"""
-        if not self._adagrad():
+        """what ``learning_rate='adagrad'`` / ``'ftrl'`` cannot be combined with, before any device
+        work"""
+        if not (self._adagrad() or self._ftrl()):
             return
         from . import regularizer as _r
 
+        rule = "learning_rate=%r" % self.learning_rate
         if plugin:
-            raise ValueError("learning_rate='adagrad' needs one of the built-in regularizers "
+            raise ValueError(rule + " needs one of the built-in regularizers "
                              "'l1', 'l21' (the per-feature prox runs on the device).")
         if isinstance(reg_obj, (_r.SquaredL12, _r.SquaredL21)) or \
                 reg_obj in ("squaredl12", "squaredl21"):
-            raise ValueError("learning_rate='adagrad' cannot be combined with the squaredl12 / "
+            raise ValueError(rule + " cannot be combined with the squaredl12 / "
                              "squaredl21 regularizers: their prox couples features that now "
                              "carry different steps; choose 'l1' or 'l21'.")
         if self.distributed:
-            raise ValueError("learning_rate='adagrad' runs on one GPU (distributed=False).")
+            raise ValueError(rule + " runs on one GPU (distributed=False).")
+        if self._ftrl() and not (self.ftrl_init > 0 and self.eta0 > 0):
+            raise ValueError("learning_rate='ftrl' needs ftrl_init > 0 and eta0 > 0.")
+
+    _FTRL_STATE = ("ftrl_z_P_", "ftrl_z_w_", "ftrl_n_P_", "ftrl_n_w_")
 
     def _adagrad_begin(self, engine, shape):
-        """after set_params: switch the handle's mode; ``warm_start`` uploads the accumulators of
-        the previous fit again, like ``it_``"""
+        """after set_params and configure: switch the handle's modes; ``warm_start`` uploads the
+        accumulators (the FTRL state) of the previous fit again, like ``it_``"""
+        if self._ftrl():
+            state = None
+            if self.warm_start and all(hasattr(self, a) for a in self._FTRL_STATE):
+                state = tuple(np.ascontiguousarray(getattr(self, a), dtype=np.double)
+                              for a in self._FTRL_STATE)
+                want = (tuple(shape), (shape[2],), (shape[0], shape[2]), (shape[2],))
+                if tuple(a.shape for a in state) != want:
+                    raise ValueError("warm_start: the ftrl_*_ state does not fit this data and "
+                                     "configuration")
+            engine.psgd_set_ftrl(1, self.ftrl_init, self.eta0, self.alpha, self.beta, self.gamma,
+                                 state)
+            engine._ftrl = True
+        elif getattr(engine, "_ftrl", False):  # a kept session of an earlier ftrl fit
+            engine.psgd_set_ftrl(0)
+            engine._ftrl = False
         if not self._adagrad():
             if getattr(engine, "_adaptive", False):  # a kept session of an earlier adagrad fit
                 engine.psgd_set_adaptive(0)
@@ -223,6 +252,9 @@ class _BaseSparseFactorizationMachine(ObjectiveMixin, InteractionMixin, RankingM
     def _adagrad_end(self, engine):
         if self._adagrad():
             self.adagrad_P_, self.adagrad_w_ = engine.psgd_get_adaptive()
+        if self._ftrl():
+            for name, a in zip(self._FTRL_STATE, engine.psgd_get_ftrl()):
+                setattr(self, name, a)
 
     def _augment(self, X):
         """sparse_factorization_machines.py:86-92"""

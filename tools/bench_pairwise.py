@@ -142,7 +142,8 @@ def main():
     ap.add_argument("--profile-only", action="store_true")
     ap.add_argument("--learning-rate", default="optimal",
                     help="step rule of both routes; 'adagrad': per-feature AdaGrad steps on the "
-                         "constant rate (DESIGN.md section 19d)")
+                         "constant rate (DESIGN.md section 19d); 'ftrl': FTRL-Proximal steps "
+                         "(section 19g)")
     ap.add_argument("--deterministic", action="store_true",
                     help="the fixed-order triple gradient against the atomic one (section 19f)")
     a = ap.parse_args()
@@ -163,7 +164,8 @@ def main():
 
     P0 = 0.01 * np.random.RandomState(a.seed + 3).randn(1, k, d)
     adagrad = a.learning_rate == "adagrad"
-    hyper = (2, 1e-3, 1e-3, 1e-4, 0.05, "constant" if adagrad else a.learning_rate, 1.0)
+    ftrl = a.learning_rate == "ftrl"
+    hyper = (2, 1e-3, 1e-3, 1e-4, 0.05, "constant" if adagrad or ftrl else a.learning_rate, 1.0)
     pair = HipEngine(0, "f32")
     S1 = sp.vstack([X, Z], format="csr")
     S1.sort_indices()
@@ -179,6 +181,9 @@ def main():
     if adagrad:
         pair.psgd_set_adaptive(1)
         point.psgd_set_adaptive(1)
+    if ftrl:
+        for eng in (pair, point):
+            eng.psgd_set_ftrl(1, 1.0, hyper[4], hyper[1], hyper[2], hyper[3])
 
     state = {"pair": 1, "point": 1}
 
@@ -225,7 +230,8 @@ def main():
         timing="host clock around an epoch call that ends in a device synchronise; both routes "
                "include the upload of their visiting order (12 m / 8 m bytes)")
     os.makedirs(a.out, exist_ok=True)
-    path = os.path.join(a.out, "pairwise_%s%s.json" % ("adagrad_" if adagrad else "", tag))
+    path = os.path.join(a.out, "pairwise_%s%s.json" % (
+        "adagrad_" if adagrad else "ftrl_" if ftrl else "", tag))
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")

@@ -11,6 +11,12 @@ the adaptive rule alternate, host clock around epoch calls that end in a device 
 medians, all repeats and the spread go to ``profiles/adagrad_<engine tag>.json`` (one entry per
 regularizer; squared norms are skipped: adaptive steps refuse them).
 
+``--learning-rate ftrl`` measures the lazy FTRL-Proximal update the same way
+against both: ``constant``, ``adagrad`` and ``ftrl`` epochs alternate on one handle -- P and w are
+shared, so this times the kernels and says nothing about any rule's fit; -> ``profiles/ftrl_<engine tag>.json`` (one entry per regularizer and shape;
+``SPFM_BENCH_D`` with ``SPFM_BENCH_BATCH`` held gives the wide shape where most columns of a
+minibatch are untouched).
+
 ``--deterministic`` measures the fixed-order gradient against the atomic
 one on two handles that share one image, and the plan build; -> ``profiles/psgd_det_<tag>.json``.
 
@@ -148,6 +154,87 @@ def compare_adagrad():
         f.write("\n")
 
 
+def compare_ftrl():
+    """the three update kernels on one handle, alternating; -> profiles/ftrl_<engine tag>.json
+    (appended to: one run per shape)"""
+    from sparsepoly_amd import _capi
+
+    steps = int(os.environ.get("STEPS", 5))
+    tag = _capi.load().spfm_build_tag().decode()
+    modes = ("constant", "adagrad", "ftrl")
+    rows = []
+    for reg in [r for r in regs if r in ("l1", "l21")]:
+        eng = HipEngine(0, "f32")
+        eng.set_data(Xc, y)
+        eng.set_params(0.01 * np.random.RandomState(0).randn(1, k, d), np.zeros(d), np.ones(k))
+        eng.configure("psgd", "squared", reg, 2)
+        idx = np.arange(n, dtype=np.int32)
+        hp = (1e-3, 1e-3, GAMMA[reg], 0.01)  # alpha, beta, gamma, eta0
+        args = (2,) + hp + ("constant", 1.0, batch, idx, True)
+        state = {"adagrad": (None, None), "ftrl": None}
+
+        # outside the timed window.  Each rule keeps its accumulators (z, n), but P and w are the
+        # handle's and are moved by all three: the kept z no longer corresponds to P when its turn
+        # comes again.  Harmless for timing; no loss is reported per rule for that reason.
+        def switch(mode):
+            eng.psgd_set_adaptive(int(mode == "adagrad"), 1.0, *state["adagrad"])
+            eng.psgd_set_ftrl(int(mode == "ftrl"), 1.0, hp[3], hp[0], hp[1], hp[2],
+                              state["ftrl"] if mode == "ftrl" else None)
+
+        def keep(mode):
+            if mode == "adagrad":
+                state[mode] = eng.psgd_get_adaptive()
+            elif mode == "ftrl":
+                state[mode] = eng.psgd_get_ftrl()
+
+        it = 1
+        times = {m: [] for m in modes}
+        for rep in range(steps + 1):  # rep 0: warm-up of all three (graph capture included)
+            for mode in modes:
+                switch(mode)
+                t0 = time.perf_counter()
+                sl, it = eng.psgd_epoch(*args, it)
+                dt = time.perf_counter() - t0
+                keep(mode)
+                if rep:
+                    times[mode].append(dt)
+        upd = {}
+        eng.profile_enable(True)  # eager launches under the HIP-event profiler: the kernels' times
+        for mode in modes:
+            switch(mode)
+            eng.profile_reset()
+            sl, it = eng.psgd_epoch(*args, it)
+            keep(mode)
+            for which, name in ((1, "update_"), (0, "grad_")):
+                ms, launches, _ = eng.profile_get(which)
+                upd[name + mode] = round(ms * 1e3 / launches, 2)
+        eng.profile_enable(False)
+        touched = float(np.mean(state["ftrl"][2] > 0))
+        row = dict(
+            tool="bench_psgd --learning-rate ftrl", build_tag=tag, device=eng.device_name,
+            reg=reg, n=n, d=d, k=k, nnz=int(nnz), batch_size=batch, updates_per_epoch=nb,
+            warmup=1, runs=steps, profiled_us_per_batch=upd,
+            columns_ever_touched=round(touched, 4),
+            timing="host clock around an epoch call that ends in a device synchronise; the three "
+                   "rules alternate on one handle and share its P and w, each replayed from its "
+                   "own hipGraph")
+        for m in modes:
+            row[m + "_epoch_ms"] = round(float(np.median(times[m])) * 1e3, 3)
+            row[m + "_epoch_ms_all"] = [round(v * 1e3, 3) for v in times[m]]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        eng.close()
+    out_dir = os.environ.get("SPFM_BENCH_OUT", os.path.join(ROOT, "profiles"))
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "ftrl_%s.json" % tag)
+    if os.path.exists(path):
+        with open(path) as f:
+            rows = json.load(f) + rows
+    with open(path, "w") as f:
+        json.dump(rows, f, indent=1)
+        f.write("\n")
+
+
 def compare_deterministic():
     """the fixed-order gradient against the atomic one: two handles on one
     image, alternating; then the plan build, as the difference between a deterministic epoch that
@@ -221,6 +308,9 @@ def compare_deterministic():
 
 if rate == "adagrad":
     compare_adagrad()
+    sys.exit(0)
+if rate == "ftrl":
+    compare_ftrl()
     sys.exit(0)
 if deterministic:
     compare_deterministic()
