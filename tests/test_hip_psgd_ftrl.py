@@ -43,33 +43,47 @@ def _closed(z, n, eta, pen, gamma, reg):
 
 
 class Reference(object):
-    """the rule over epochs of minibatches on P (n_orders, d, k), gradients from the oracle"""
+    """the rule over epochs of minibatches on P (n_orders, d, k), gradients from the oracle;
+    ``hp``: what the setter derives the starting state with (``state`` None), ``it``: the number
+    of the first minibatch"""
 
-    def __init__(self, oracle, X, y, P0, w0, lams, degree, reg, gamma):
+    def __init__(self, oracle, X, y, P0, w0, lams, degree, reg, gamma, loss="squared",
+                 fit_linear=True, hp=HP, it=1, state=None):
         from sparsepoly_amd.pairwise import ftrl_start   # (pinned by test_psgd_ftrl_host.py)
 
         self.o, self.X, self.y, self.lams, self.degree, self.reg = oracle, X, y, lams, degree, reg
-        self.P, self.w, self.it = np.ascontiguousarray(P0.swapaxes(1, 2)), w0.copy(), 1
-        z, self.zw, n, self.nw = ftrl_start(P0, w0, G0, HP["eta0"], HP["alpha"], HP["beta"],
-                                            gamma, reg)
-        self.z, self.n = np.ascontiguousarray(z.swapaxes(1, 2)), n
+        self.loss, self.fit_linear = loss, fit_linear
+        self.P, self.w, self.it = np.ascontiguousarray(P0.swapaxes(1, 2)), w0.copy(), it
+        if state is None:
+            state = ftrl_start(P0, w0, G0, hp["eta0"], hp["alpha"], hp["beta"], gamma, reg)
+        z, zw, n, nw = (np.array(a, dtype=np.double) for a in state)
+        self.z, self.zw, self.n, self.nw = np.ascontiguousarray(z.swapaxes(1, 2)), zw, n, nw
 
-    def epoch(self, idx, batch, gamma, alpha, beta, eta0):
+    def epoch(self, idx, batch, gamma, alpha, beta, eta0, learning_rate="constant", power_t=1.0):
+        """-> the sum of the rows' losses; minibatch number ``it`` steps with the rates
+        ``_psgd_eta`` tabulates for it: ``eta_P`` in P's sigma and denominator, ``eta_w`` in w's"""
+        from sparsepoly_amd.pairwise import _psgd_eta
+
+        sum_loss = 0.0
         for pos in range(0, idx.size, batch):
             rows = idx[pos:pos + batch]
             Pc, wc = self.P.copy(), self.w.copy()
-            self.o.psgd_epoch(Pc, wc, self.o.CSR(self.X[rows]), self.y[rows], self.lams,
-                              self.degree, 0.0, 0.0, 0.0, self.reg, "squared",
-                              np.arange(rows.size, dtype=np.int32), True, 1.0, "constant", 1.0,
-                              rows.size, 1)
-            for p, z, n, pen, r in ((self.P, self.z, self.n, beta, self.reg),
-                                    (self.w[:, None], self.zw[:, None], self.nw, alpha, None)):
-                g = p - (Pc if r else wc[:, None])
+            sl, _ = self.o.psgd_epoch(Pc, wc, self.o.CSR(self.X[rows]), self.y[rows], self.lams,
+                                      self.degree, 0.0, 0.0, 0.0, self.reg, self.loss,
+                                      np.arange(rows.size, dtype=np.int32), self.fit_linear, 1.0,
+                                      "constant", 1.0, rows.size, 1)
+            sum_loss += sl
+            eta_P, eta_w = _psgd_eta(learning_rate, eta0, alpha, beta, power_t, self.it)
+            for p, z, n, pen, r, eta in (
+                    (self.P, self.z, self.n, beta, self.reg, eta_P),
+                    (self.w[:, None], self.zw[:, None], self.nw, alpha, None, eta_w)):
+                g = p - (Pc if r else wc[:, None])   # (fit_linear off: the oracle leaves w, g = 0)
                 g2 = (g ** 2).sum(axis=-1)
-                z += g - ((np.sqrt(n + g2) - np.sqrt(n)) / eta0)[..., None] * p
+                z += g - ((np.sqrt(n + g2) - np.sqrt(n)) / eta)[..., None] * p
                 n += g2
-                p[...] = np.where((g2 != 0)[..., None], _closed(z, n, eta0, pen, gamma, r), p)
+                p[...] = np.where((g2 != 0)[..., None], _closed(z, n, eta, pen, gamma, r), p)
             self.it += 1
+        return sum_loss
 
     def state(self):
         return (self.P.swapaxes(1, 2), self.w, self.z.swapaxes(1, 2), self.zw, self.n, self.nw)
