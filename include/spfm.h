@@ -744,6 +744,24 @@ int spfm_debug_exchange_cost(spfm_handle h, int groups, int ncols, int readers_m
  * 0.0, then the parts in ascending order.  groups <= 256, ncols in [1, 64]. */
 int spfm_debug_sweep_sums(spfm_handle h, int groups, int ncols, int nv, int step,
                           const double* vals, double* out);
+/* diagnostic: one dependent step's chain -- the step size, the prox and the regularizer-cache
+ * recurrence of pcd.py:61-68 -- on given column values, with an exact answer
+ * (tests/test_chain_host.py, tests/test_hip_chain.py).  The production device functions run as the
+ * passes call them: form 0, one wave calls pcd_chain_lanes<degree> as the control wave of the
+ * 64-column pass does (valid = lane < ncols, last = ncols - 1; ncols in [1, 64]; degree 2..6 or
+ * 0 = all-subsets); form 1, a workgroup of eight waves calls pcd_chain_waves<2> as the wide pass
+ * does (ncols in [1, 512], degree 2).  reg: SPFM_REG_L1, SPFM_REG_SQUAREDL12 (degree 2) or
+ * SPFM_REG_OMEGATI.  Column q enters with its coordinate p_old[q] and the step's column sums g[q]
+ * (sum of dloss * dA) and hsum[q] (sum of dA^2); lam, mu, beta, gamma, eta as in pcd.py.
+ * cache_in[degree + 1] is the regularizer cache in front of column 0 (squaredl12: [0] = sum |p|;
+ * omegati: [t] = e_t(|p|), t = 1..degree-1 read; all-subsets: [0] = prod (1 + |p|)); p_new[ncols]
+ * receives the new coordinates, cache_out[degree + 1] the cache behind the last column (entries the
+ * chain does not own are copied through).  The omegati clip ticks spfm_debug_branch_counts.
+ * SPFM_ERR_INVALID: any other form, regularizer, degree, combination of them, or column count. */
+int spfm_debug_chain(spfm_handle h, int form, int reg, int degree, int ncols, const double* p_old,
+                     const double* g, const double* hsum, double lam, double mu, double beta,
+                     double gamma, double eta, const double* cache_in, double* p_new,
+                     double* cache_out);
 
 /* Diagnostic for the counter calibration (profiles/r03_fetch_calibration.txt): one launch that
  * reads the persistent pass's entry stream (slot bounds, rows, values of every step, with the

@@ -106,6 +106,7 @@ SYMBOLS = [
     "spfm_profile_enable", "spfm_profile_get", "spfm_profile_reset", "spfm_set_use_graph",
     "spfm_set_option", "spfm_get_option", "spfm_debug_prb_stamps", "spfm_debug_hop_latency", "spfm_debug_exchange_cost",
     "spfm_debug_sweep_sums",
+    "spfm_debug_chain",
     "spfm_debug_branch_counts", "spfm_debug_stream_probe", "spfm_debug_write_probe",
     "spfm_stream_build", "spfm_debug_stream_info", "spfm_debug_stream_tables",
     "spfm_gram_csr_dense", "spfm_gram_csr_csr",
@@ -263,6 +264,8 @@ def load():
     L.spfm_debug_hop_latency.argtypes = [_h, C.c_int, C.c_int, _dp, _ip]
     L.spfm_debug_exchange_cost.argtypes = [_h, C.c_int, C.c_int, C.c_int, C.c_int, _dp]
     L.spfm_debug_sweep_sums.argtypes = [_h, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp]
+    L.spfm_debug_chain.argtypes = ([_h] + [C.c_int] * 4 + [_dp] * 3 + [C.c_double] * 5
+                                   + [_dp] * 3)
     L.spfm_peer_alloc.argtypes = [_h, C.c_char_p]
     L.spfm_peer_connect.argtypes = [_h, C.c_int, C.c_int, C.c_char_p]
     L.spfm_debug_branch_counts.argtypes = [_h, C.POINTER(C.c_uint32), C.c_int]

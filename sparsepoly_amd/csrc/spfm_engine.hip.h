@@ -1599,3 +1599,4 @@ hipError_t spfm_branch_counts_wide(unsigned* out, int reset);
 hipError_t spfm_branch_counts_pbcd(unsigned* out, int reset);
 hipError_t spfm_branch_counts_pbprb_f32(unsigned* out, int reset);
 hipError_t spfm_branch_counts_pbprb_f64(unsigned* out, int reset);
+hipError_t spfm_branch_counts_chain_probe(unsigned* out, int reset);

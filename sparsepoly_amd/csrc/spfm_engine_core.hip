@@ -1771,7 +1771,7 @@ int spfm_debug_branch_counts(spfm_handle h, unsigned* out8, int reset) {
     hipError_t (*const units[])(unsigned*, int) = {
         spfm_branch_counts_pcd,       spfm_branch_counts_prb_f32,   spfm_branch_counts_prb_f64,
         spfm_branch_counts_wide,      spfm_branch_counts_pbcd,      spfm_branch_counts_pbprb_f32,
-        spfm_branch_counts_pbprb_f64};
+        spfm_branch_counts_pbprb_f64, spfm_branch_counts_chain_probe};
     for (auto unit : units)
         if (unit(out8, reset) != hipSuccess) return SPFM_ERR_RUNTIME;
     return SPFM_OK;

@@ -1762,6 +1762,28 @@ class HipEngine(object):
             vals.ctypes.data_as(_capi._dp), out.ctypes.data_as(_capi._dp)))
         return out
 
+    def debug_chain(self, form, regularizer, degree, p_old, g, hsum, lam, mu, beta, gamma, eta,
+                    cache_in):
+        """One dependent step's chain on given column values, by the production device
+        functions: form 0 the one-wave chain (up to 64 columns, degree 2..6 or 0 = all-subsets),
+        form 1 the wide chain (up to 512 columns, degree 2).  Returns (p_new[ncols],
+        cache_out[degree + 1]); see spfm.h."""
+        p_old, g, hsum, cache_in = (np.ascontiguousarray(v, dtype=np.float64)
+                                    for v in (p_old, g, hsum, cache_in))
+        ncols = p_old.size
+        if not (p_old.ndim == g.ndim == hsum.ndim == cache_in.ndim == 1
+                and g.size == hsum.size == ncols and cache_in.size == int(degree) + 1):
+            raise ValueError("debug_chain: p_old, g, hsum of one length, cache_in of degree + 1")
+        p_new = np.zeros(max(ncols, 1), dtype=np.float64)
+        cache_out = np.zeros(int(degree) + 1, dtype=np.float64)
+        self._check(self._lib.spfm_debug_chain(
+            self._h, int(form), _capi.REGULARIZERS[regularizer], int(degree), int(ncols),
+            p_old.ctypes.data_as(_capi._dp), g.ctypes.data_as(_capi._dp),
+            hsum.ctypes.data_as(_capi._dp), float(lam), float(mu), float(beta), float(gamma),
+            float(eta), cache_in.ctypes.data_as(_capi._dp), p_new.ctypes.data_as(_capi._dp),
+            cache_out.ctypes.data_as(_capi._dp)))
+        return p_new[:ncols], cache_out
+
     def debug_prb_stamps(self):
         buf = np.zeros(16 * 512, dtype=np.int64)
         nv = self._lib.spfm_debug_prb_stamps(self._h, buf.ctypes.data_as(_capi._lp), buf.size)
