@@ -1496,6 +1496,42 @@ int spfm_bank_set_partition(spfm_handle h, int64_t slab_nnz);
 int spfm_bank_info(spfm_handle h, int64_t* out4);
 int spfm_bank_release(spfm_handle h);
 
+/* -- consensus interactions over the bank ---------------------------------
+ * Which feature pairs the members of the resident bank agree on.  `block` names a block of the
+ * image whose degree is 2 or -1 (all-subsets); with W_f[j, j'] = sum_s lams_s p_sj p_sj' over the
+ * components of member f alone, for every pair j < j' < d_view:
+ *   count[j, j'] = #{f : |W_f[j, j']| > tol}   (strictly greater)
+ *   n_pos[j, j'] = #{f : W_f[j, j'] > tol}
+ *   sum[j, j']   = the sum of W_f[j, j'] over the counted members, added in member order
+ * hist and list form W_f by the chain of v_mfma_f64_16x16x4_f64 steps over s = 0, 4, 8, ... of
+ * spfm_interaction_stats / _list run on member f alone (its components padded with zeros to a
+ * multiple of 4): a member's values carry the bits of its own one-model calls.  One workgroup
+ * owns a pair and walks the members in order, so no count and no bit of a sum depends on
+ * tile_budget (tiles of 64 x 64 pairs per launch; 0 = the default).
+ *
+ * spfm_bank_interaction_hist: hist[c], c = 0..F, the pairs of the view with count = c (hist[0]
+ * completes d_view (d_view - 1) / 2); per_member[f] the pairs member f kept, what
+ * spfm_interaction_stats counts for it.
+ * spfm_bank_interaction_list: every pair with count >= min_count, sorted by (row, col).  n_out
+ * always receives the number of such pairs; above `capacity` -> SPFM_ERR_INVALID naming it, the
+ * arrays are left untouched.
+ * spfm_bank_interaction_counts: the three numbers at L given pairs (either order of the two ids;
+ * zeros where they are equal), one thread per pair over the members and their components in
+ * order: per member the arithmetic of spfm_interaction_values.
+ * Errors: no bank set, tol < 0 or NaN, d_view outside [1, d], min_count outside [1, F],
+ * tile_budget or capacity < 0, an id outside the view, NULL outputs -> SPFM_ERR_INVALID; a block
+ * of another degree -> SPFM_ERR_UNSUPPORTED.  The scratch is kept between calls and freed by
+ * spfm_bank_release, spfm_bank_set and spfm_destroy. */
+int spfm_bank_interaction_hist(spfm_handle h, int block, int32_t d_view, double tol,
+                               int64_t tile_budget, int64_t* hist /* F + 1 */,
+                               int64_t* per_member /* F */);
+int spfm_bank_interaction_list(spfm_handle h, int block, int32_t d_view, double tol, int min_count,
+                               int64_t tile_budget, int64_t capacity, int32_t* rows, int32_t* cols,
+                               int32_t* count, int32_t* n_pos, double* sum, int64_t* n_out);
+int spfm_bank_interaction_counts(spfm_handle h, int block, int32_t d_view, double tol, int64_t L,
+                                 const int32_t* rows, const int32_t* cols, int32_t* count,
+                                 int32_t* n_pos, double* sum);
+
 /* -- fold-in of new columns -------------------------------------------------------------------
  * Estimate the parameters of single columns (a new user, a new item, a column that collected new
  * rows) with every other parameter fixed.  The model, the blocks and the coefficient table are

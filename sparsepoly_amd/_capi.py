@@ -125,6 +125,7 @@ SYMBOLS = [
     "spfm_bank_set", "spfm_bank_scores", "spfm_bank_argmax", "spfm_bank_losses", "spfm_bank_mean",
     "spfm_bank_group_sums", "spfm_bank_group_auc", "spfm_bank_group_curve",
     "spfm_bank_set_partition", "spfm_bank_info", "spfm_bank_release",
+    "spfm_bank_interaction_hist", "spfm_bank_interaction_list", "spfm_bank_interaction_counts",
     "spfm_foldin_csr", "spfm_foldin_set_partition", "spfm_foldin_info",
 ]
 INTERACTION_BLOCK_MAX_BYTES = 1 << 30  # SPFM_INTERACTION_BLOCK_MAX_BYTES
@@ -328,6 +329,11 @@ def load():
     L.spfm_bank_set_partition.argtypes = [_h, C.c_int64]
     L.spfm_bank_info.argtypes = [_h, _lp]
     L.spfm_bank_release.argtypes = [_h]
+    _bint = [_h, C.c_int, C.c_int32, C.c_double]
+    L.spfm_bank_interaction_hist.argtypes = _bint + [C.c_int64, _lp, _lp]
+    L.spfm_bank_interaction_list.argtypes = _bint + [C.c_int, C.c_int64, C.c_int64, _ip, _ip, _ip,
+                                                     _ip, _dp, _lp]
+    L.spfm_bank_interaction_counts.argtypes = _bint + [C.c_int64, _ip, _ip, _ip, _ip, _dp]
     L.spfm_foldin_csr.argtypes = [_h, C.c_int64, _lp, _ip, _dp, _dp, C.c_int, _ip, _ip, _dp,
                                   C.c_int, C.c_double, C.c_int, C.c_int64, _ip, C.c_double,
                                   C.c_double, C.c_int, C.c_double, _dp, _lp, _ip, _ip, _dp, _dp,

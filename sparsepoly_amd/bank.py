@@ -28,6 +28,7 @@ import scipy.sparse as sp
 
 from . import _capi
 from . import engine as _engine
+from .interactions import _NO_DEGREE2, InteractionMixin
 from .ranking import _canonical, _restate_output, _spec
 from .sparse_factorization_machines import _fit_device
 
@@ -97,7 +98,8 @@ class ModelBank(object):
         self._d_model = d_model
         self.n_models = len(specs)
         blocks = [(0, degree)] + ([(1, 2)] if lower else [])
-        ks = [s[3].shape[1] for s in specs]
+        self._blocks = blocks
+        ks =[s[3].shape[1] for s in specs]
         self.koff = np.concatenate([[0], np.cumsum(ks)]).astype(np.int32)
         # feature-major, stacked: block q of every member transposed and side by side
         Pt = np.empty((len(blocks), d_model, int(self.koff[-1])))
@@ -255,6 +257,74 @@ class ModelBank(object):
                                  % (self.n_models, weights.shape))
         return self._engine.bank_mean(self._X(X), weights)
 
+    # ------------------------------------------- consensus interactions
+    def _pair_view(self, what, include_augmented):
+        """(the bank's degree-2 block, features in view); the refusals of every pair call"""
+        if self._engine is None:
+            raise ValueError("this ModelBank is closed")
+        spec = getattr(self.estimators[0], "_block_spec", None)
+        n_dummy = 0 if spec is None else spec(what, 2)[1]  # ValueError: no degree-2 block
+        for q, (_, deg) in enumerate(self._blocks):
+            if deg in (2, -1):
+                return q, self._d_model if include_augmented else self._d_model - n_dummy
+        raise ValueError(_NO_DEGREE2 % (what, self._blocks[0][1]))
+
+    def interaction_frequency_stats(self, tol=0.0, include_augmented=False, tile_budget=0):
+        """How often the members agree on a pair: dict ``histogram`` (int64, F + 1: entry ``c`` is
+        the number of pairs ``j < j'`` in view with ``|W_f[j, j']| > tol`` for exactly ``c``
+        members), ``per_member`` (int64, F: the pairs member ``f`` kept, its own
+        ``interaction_stats(tol)["nnz"]``) and ``n_pairs``.  ``W_f`` is member f's pairwise weight
+        of the degree-2 block, with the bits of its own ``interactions()``.  ``tile_budget``: tiles
+        per launch (0: the default); no number depends on it."""
+        tol = _check_tol("interaction_frequency_stats()", tol)
+        q, dv = self._pair_view("interaction_frequency_stats()", include_augmented)
+        hist, per = self._engine.bank_interaction_hist(q, dv, tol, tile_budget)
+        return dict(histogram=hist, per_member=per, n_pairs=dv * (dv - 1) // 2)
+
+    def stable_interactions(self, min_count, tol=0.0, max_pairs=10_000_000,
+                            include_augmented=False, tile_budget=0):
+        """Every pair that at least ``min_count`` members kept (``|W_f| > tol``), as arrays
+        ``(rows, cols, count, n_pos, sum)`` sorted by (row, col): ``count`` members kept it,
+        ``n_pos`` of them with ``W_f > tol``, ``sum`` adds their ``W_f`` in member order.
+        ``ValueError`` naming the count when it exceeds ``max_pairs``."""
+        what = "stable_interactions()"
+        tol = _check_tol(what, tol)
+        min_count = _check_min_count(what, min_count, self.n_models)
+        q, dv = self._pair_view(what, include_augmented)
+        hist, _ = self._engine.bank_interaction_hist(q, dv, tol, tile_budget)
+        n = int(hist[min_count:].sum())
+        if n > max_pairs:
+            raise ValueError("%s: %d pairs have |W| > %g in at least %d members, more than "
+                             "max_pairs=%d" % (what, n, tol, min_count, max_pairs))
+        return self._engine.bank_interaction_list(q, dv, tol, min_count, n, tile_budget)
+
+    def top_stable_interactions(self, K, tol=0.0, max_pairs=10_000_000, include_augmented=False,
+                                tile_budget=0):
+        """The ``K`` pairs the members agree on most, ordered by ``count`` descending, then
+        ``|sum|`` descending, then row, then column; same arrays as ``stable_interactions``,
+        fewer than ``K`` when fewer pairs were kept by any member."""
+        what = "top_stable_interactions()"
+        if int(K) != K or int(K) < 0:
+            raise ValueError("%s: K must be an integer >= 0" % what)
+        stats = self.interaction_frequency_stats(tol, include_augmented, tile_budget)
+        c_star = _top_min_count(stats["histogram"], int(K))
+        out = self.stable_interactions(c_star, tol, max_pairs, include_augmented, tile_budget)
+        keep = _stable_order(*out)[:int(K)]
+        return tuple(a[keep] for a in out)
+
+    def interaction_counts(self, rows, cols, tol=0.0, include_augmented=False):
+        """dict ``count``, ``n_pos`` (int32) and ``sum`` at the pairs ``(rows[q], cols[q])``
+        (either order of the two ids; zeros where they are equal): one device thread per pair over
+        the members and their components in order -- per member the arithmetic of
+        ``interaction_values``."""
+        what = "interaction_counts()"
+        tol = _check_tol(what, tol)
+        q, dv = self._pair_view(what, include_augmented)
+        rows = InteractionMixin._interaction_ids(rows, dv, "rows")
+        cols = InteractionMixin._interaction_ids(cols, dv, "cols")
+        count, npos, sums = self._engine.bank_interaction_counts(q, dv, rows, cols, tol)
+        return dict(count=count, n_pos=npos, sum=sums)
+
     def set_partition(self, slab_nnz=0):
         """Stored entries per slab of the following calls (0: the default).  No bit of a score,
         an argmax or a mean depends on it; a loss sum is reproducible for one slab size."""
@@ -293,6 +363,33 @@ METRICS = ("loss",) + tuple(sorted(_capi.BANK_METRICS))
 # the SPFM_BANK_CURVE_VALUES values of one (member, set) of spfm_bank_group_curve, in its order
 CURVE_FIELDS = ("average_precision", "best_f1", "f1_threshold", "f1_tp", "f1_fp", "ks",
                 "ks_threshold", "ks_tp", "ks_fp", "pos_weight", "neg_weight")
+
+
+def _check_tol(what, tol):
+    if not float(tol) >= 0.0:
+        raise ValueError("%s: tol must be >= 0" % what)
+    return float(tol)
+
+
+def _check_min_count(what, min_count, F):
+    if int(min_count) != min_count or not 1 <= int(min_count) <= F:
+        raise ValueError("%s: min_count must be an integer in [1, %d] (the bank has %d members)"
+                         % (what, F, F))
+    return int(min_count)
+
+
+def _top_min_count(histogram, K):
+    """The largest count ``c >= 1`` whose tail ``sum(histogram[c:])`` still holds ``K`` pairs (1
+    when none does): listing from there up gives the ``K`` most frequent pairs and no more than
+    one count level of surplus."""
+    tail = np.cumsum(np.asarray(histogram)[:0:-1])[::-1]  # tail[c - 1] = pairs with count >= c
+    ok = np.flatnonzero(tail >= K)
+    return int(ok[-1]) + 1 if ok.size else 1
+
+
+def _stable_order(rows, cols, count, n_pos, sums):
+    """indices by ``count`` descending, ``|sum|`` descending, row, column"""
+    return np.lexsort((cols, rows, -np.abs(sums), -count.astype(np.int64)))
 
 
 def _group_args(n, F, y, groups, n_groups, sample_weight, metrics, default_loss):

@@ -37,6 +37,7 @@
 
 namespace spfm {
 struct IntArgs;  // spfm_interactions.hip.h
+struct BiArgs;   // spfm_bank_interactions.hip.h
 void schedule_exact(int64_t, int32_t, const int64_t*, const int32_t*, const int32_t*, int,
                     std::vector<int32_t>&);
 void schedule_colored(int64_t, int32_t, const int64_t*, const int32_t*, const int32_t*, int,
@@ -1519,6 +1520,28 @@ struct spfm_engine {
     int auc_finish(const BankCall& c);
     void auc_empty(const BankCall& c);
     void auc_release();
+
+    // ------------------------------- consensus interactions over the bank
+    // (spfm_engine_bank_interactions.hip): per feature pair the number of
+    // members that kept it, formed from the resident image tile by tile.  Read-only views of the
+    // bank; the scratch is kept between calls and freed by bank_release.
+    DevBuf bi_flag, bi_pos, bi_ids, bi_tot, bi_tmp;  // union compaction
+    DevBuf bi_mask;                                  // members with a non-zero per tile row
+    DevBuf bi_hist, bi_cnt, bi_keys, bi_vals, bi_keys2, bi_vals2;  // histogram / list
+    DevBuf bi_io, bi_out;                            // point queries
+    int bi_du = 0, bi_T = 0;                         // of the last compaction
+    void bank_interaction_release();
+    int bank_interaction_prepare(const char* what, int block, int32_t d_view, double tol,
+                                 int64_t tile_budget, bool compact, BiArgs* a);
+    int bank_interaction_run(int mode, BiArgs a, int64_t tile_budget);
+    int bank_interaction_hist(int block, int32_t d_view, double tol, int64_t tile_budget,
+                              int64_t* hist, int64_t* per_member);
+    int bank_interaction_list(int block, int32_t d_view, double tol, int min_count,
+                              int64_t tile_budget, int64_t capacity, int32_t* rows, int32_t* cols,
+                              int32_t* count, int32_t* n_pos, double* sum, int64_t* n_out);
+    int bank_interaction_counts(int block, int32_t d_view, double tol, int64_t L,
+                                const int32_t* rows, const int32_t* cols, int32_t* count,
+                                int32_t* n_pos, double* sum);
 
     // ------------------------------- fold-in of new columns (spfm_engine_foldin.hip)
     // With every other column fixed the model output is affine in the parameters of one column j:

@@ -43,6 +43,7 @@ void spfm_engine::bank_release() {
                       &bk_gacc, &bk_akey, &bk_ameta, &bk_arow, &bk_aw, &bk_askey, &bk_asrow,
                       &bk_atmp, &bk_asets, &bk_ablk, &bk_aout, &bk_cblk, &bk_cout})
         b->release();
+    bank_interaction_release();
     bk_have = false;
     bk_F = bk_S = bk_d = bk_blocks = 0;
 }

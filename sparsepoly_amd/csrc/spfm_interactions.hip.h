@@ -203,6 +203,18 @@ __device__ __forceinline__ void int_tile_product(const double* Ag, const double*
     }
 }
 
+// tile number -> (ti <= tj), row-major over the upper triangle of T x T tiles
+__device__ __forceinline__ void int_tile_coords(long long t, long long T, long long& ti,
+                                                long long& tj) {
+    const double tw = 2.0 * (double)T + 1.0;
+    ti = (long long)((tw - sqrt(tw * tw - 8.0 * (double)t)) * 0.5);
+    if (ti < 0) ti = 0;
+    if (ti > T - 1) ti = T - 1;
+    while (ti + 1 < T && (ti + 1) * T - (ti + 1) * ti / 2 <= t) ++ti;
+    while (ti > 0 && ti * T - ti * (ti - 1) / 2 > t) --ti;
+    tj = ti + (t - (ti * T - ti * (ti - 1) / 2));
+}
+
 // LDS of the two staging tiles
 static inline size_t int_stage_lds_bytes() { return sizeof(double) * 2 * kIntTile * kIntLd; }
 
@@ -272,15 +284,9 @@ __global__ __launch_bounds__(kBlock) void int_tile_kernel(IntArgs a) {
     __shared__ unsigned sHist[MODE == INT_HIST ? kIntHistBins : 1];
     __shared__ IntRec red[kBlock / kWave];
 
-    // tile number -> (ti <= tj), row-major over the upper triangle
-    const long long t = a.tile0 + blockIdx.x, T = a.T;
-    const double tw = 2.0 * (double)T + 1.0;
-    long long ti = (long long)((tw - sqrt(tw * tw - 8.0 * (double)t)) * 0.5);
-    if (ti < 0) ti = 0;
-    if (ti > T - 1) ti = T - 1;
-    while (ti + 1 < T && (ti + 1) * T - (ti + 1) * ti / 2 <= t) ++ti;
-    while (ti > 0 && ti * T - ti * (ti - 1) / 2 > t) --ti;
-    const long long tj = ti + (t - (ti * T - ti * (ti - 1) / 2));
+    const long long t = a.tile0 + blockIdx.x;
+    long long ti, tj;
+    int_tile_coords(t, a.T, ti, tj);
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wr = wave >> 1, wc = wave & 1;

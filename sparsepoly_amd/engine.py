@@ -1110,6 +1110,61 @@ class HipEngine(object):
         self._check(self._lib.spfm_bank_release(self._h))
         self.bank_shape = None
 
+    # ------------------------- consensus interactions over the bank (spfm.h)
+    def _bank_interaction_head(self, what, block, d_view, tol):
+        if getattr(self, "bank_shape", None) is None:
+            raise ValueError("%s: call bank_set first" % what)
+        return self._h, int(block), int(d_view), float(tol)
+
+    def bank_interaction_hist(self, block, d_view, tol=0.0, tile_budget=0):
+        """``spfm_bank_interaction_hist``: ``(hist int64 (F + 1), per_member int64 (F))`` --
+        the pairs ``j < j' < d_view`` by the number of members with ``|W_f| > tol``, and every
+        member's own kept pairs."""
+        head = self._bank_interaction_head("bank_interaction_hist", block, d_view, tol)
+        F = self.bank_shape[0]
+        hist, per = np.zeros(F + 1, dtype=np.int64), np.zeros(F, dtype=np.int64)
+        self._check(self._lib.spfm_bank_interaction_hist(
+            *head, int(tile_budget), hist.ctypes.data_as(_capi._lp),
+            per.ctypes.data_as(_capi._lp)))
+        return hist, per
+
+    def bank_interaction_list(self, block, d_view, tol, min_count, capacity, tile_budget=0,
+                              out=None):
+        """``spfm_bank_interaction_list``: ``(rows, cols, count, n_pos, sum)`` of every pair kept
+        by at least ``min_count`` members, sorted by (row, col).  ``ValueError`` naming the number
+        of such pairs when it exceeds ``capacity``; nothing is written then.  ``out``: the five
+        arrays to fill (int32 x 4, float64; ``capacity`` long), for callers that own them."""
+        head = self._bank_interaction_head("bank_interaction_list", block, d_view, tol)
+        capacity = int(capacity)
+        if out is None:
+            out = [np.zeros(max(capacity, 1), dtype=np.int32) for _ in range(4)]
+            out.append(np.zeros(max(capacity, 1)))
+        for a, dt in zip(out, (np.int32,) * 4 + (np.float64,)):
+            if a.dtype != dt or a.ndim != 1 or a.shape[0] < capacity or not a.flags.c_contiguous:
+                raise ValueError("bank_interaction_list: out must hold four int32 arrays and a "
+                                 "float64 array of at least `capacity` entries")
+        n = C.c_int64()
+        self._check(self._lib.spfm_bank_interaction_list(
+            *head, int(min_count), int(tile_budget), capacity,
+            *[a.ctypes.data_as(_capi._ip) for a in out[:4]], out[4].ctypes.data_as(_capi._dp),
+            C.byref(n)))
+        return tuple(a[:n.value].copy() for a in out)
+
+    def bank_interaction_counts(self, block, d_view, rows, cols, tol=0.0):
+        """``spfm_bank_interaction_counts``: ``(count, n_pos, sum)`` at the pairs
+        ``(rows[q], cols[q])`` (zeros where the two ids are equal)."""
+        head = self._bank_interaction_head("bank_interaction_counts", block, d_view, tol)
+        ra, rp = _capi.i32(rows)
+        ca, cp = _capi.i32(cols)
+        if ra.ndim != 1 or ra.shape != ca.shape:
+            raise ValueError("rows and cols must be 1-d arrays of one length")
+        L = ra.shape[0]
+        count, npos, sums = np.zeros(L, dtype=np.int32), np.zeros(L, dtype=np.int32), np.zeros(L)
+        self._check(self._lib.spfm_bank_interaction_counts(
+            *head, L, rp, cp, count.ctypes.data_as(_capi._ip), npos.ctypes.data_as(_capi._ip),
+            sums.ctypes.data_as(_capi._dp)))
+        return count, npos, sums
+
     # ------------------------- fold-in of new columns: per-column convex solves (spfm.h)
     def foldin(self, X, y, blocks, coef, fit_linear, offset, loss, cols, alpha, beta, max_iter=50,
                tol=1e-8):

@@ -324,6 +324,64 @@ def restate_degrees(P_block, lams, tol=0.0, W=None):
                 strongest=strongest)
 
 
+# ------------------------------------------------------------------ consensus over a model bank
+def restate_bank_counts(P_blocks, lams_list, tol=0.0):
+    """``ModelBank.interaction_frequency_stats`` / ``stable_interactions`` restated in NumPy on
+    dense ``W_f``: a test aid, quadratic in ``d``.  ``P_blocks``: per member its (k_f, d) degree-2
+    block, ``lams_list`` its ``lams``.  Returns a dict: ``count``, ``n_pos`` (int64 (d, d)) and
+    ``sum`` ((d, d), the kept ``W_f`` added in member order), filled above the diagonal only;
+    ``histogram`` (F + 1) and ``per_member`` (F) over the pairs ``j < j'``."""
+    if not float(tol) >= 0.0:
+        raise ValueError("restate_bank_counts(): tol must be >= 0")
+    if len(P_blocks) != len(lams_list) or not len(P_blocks):
+        raise ValueError("restate_bank_counts(): one lams per member, at least one member")
+    d = np.shape(P_blocks[0])[1]
+    upper = np.triu(np.ones((d, d), dtype=bool), k=1)
+    count = np.zeros((d, d), dtype=np.int64)
+    n_pos = np.zeros((d, d), dtype=np.int64)
+    total = np.zeros((d, d))
+    per_member = np.zeros(len(P_blocks), dtype=np.int64)
+    for f, (P, lams) in enumerate(zip(P_blocks, lams_list)):
+        W = _dense_w(P, lams)
+        kept = upper & (np.abs(W) > tol)
+        count += kept
+        n_pos += kept & (W > tol)
+        total += np.where(kept, W, 0.0)
+        per_member[f] = kept.sum()
+    histogram = np.bincount(count[upper], minlength=len(P_blocks) + 1).astype(np.int64)
+    return dict(count=count, n_pos=n_pos, sum=total, histogram=histogram, per_member=per_member)
+
+
+def stability_selection(est, X, y, n_subsamples, fraction=0.5, random_state=None, **bank_kw):
+    """Stability selection of feature pairs: ``n_subsamples`` clones of ``est`` are fitted on
+    random subsamples of the rows -- 0/1 ``sample_weight`` masks holding ``round(fraction n)`` rows
+    each, over ONE device image (``fit_concurrently(..., sample_weights=masks)``) -- and returned
+    resident as a ``ModelBank`` (``bank_kw`` goes to it).  Its ``interaction_frequency_stats`` and
+    ``stable_interactions`` then give every pair's selection frequency.  The masks are kept as
+    ``bank.subsample_masks_`` (bool, (n_subsamples, n))."""
+    from sklearn.base import clone
+    from sklearn.utils import check_random_state
+
+    from .bank import ModelBank
+    from .concurrent import fit_concurrently
+
+    n = X.shape[0]
+    if int(n_subsamples) != n_subsamples or not 1 <= int(n_subsamples):
+        raise ValueError("stability_selection(): n_subsamples must be an integer >= 1")
+    if not 0.0 < float(fraction) <= 1.0:
+        raise ValueError("stability_selection(): fraction must be in (0, 1]")
+    m = min(n, max(1, int(round(float(fraction) * n))))
+    rng = check_random_state(random_state)
+    masks = np.zeros((int(n_subsamples), n), dtype=bool)
+    for mask in masks:
+        mask[rng.choice(n, size=m, replace=False)] = True
+    clones = [clone(est) for _ in masks]
+    fit_concurrently(clones, X, y, sample_weights=[mask.astype(np.double) for mask in masks])
+    bank = ModelBank(clones, **bank_kw)
+    bank.subsample_masks_ = masks
+    return bank
+
+
 # ------------------------------------------------------------------ the notebook's metrics
 def _true_support(W_true):
     """(rows, cols, values) of the non-zeros of the symmetric ``W_true`` above the diagonal"""
