@@ -567,6 +567,34 @@ int spfm_psgd_lists_eval(spfm_handle h, int degree, int fit_linear, const int32_
                          int64_t m, int64_t n_negatives, int list_loss, double* sum_loss,
                          int64_t* n_first);
 
+/* In-batch softmax: the training item is a positive pair (context row,
+ * candidate row) of the stacked image [X; Z], and the other positives of its minibatch are its
+ * negatives.  `pairs` (m, 2) is visited in the order given, minibatch = positions
+ * [pos, pos + n), n <= batch_size (the last may be short); it is uploaded per epoch.  With
+ *   s[q, q'] = sum_o sum_s lams_s a_s^{degree-o}(x_{b_q} + z_{c_q'}) + <w, z_{c_q'}>
+ * column q' != q is left out of row q when c_q' == c_q (the same candidate) or b_q' == b_q (a
+ * known positive of the same context), and
+ *   loss_q = -s[q, q] + log sum_{q' admitted} exp(s[q, q'])     (max-subtracted, f64)
+ * A row whose only admitted column is itself has loss exactly 0 and sends no gradient.  The n x n
+ * logits are 64 x 64 tiles of the f64 matrix instruction over the two towers of section 15;
+ * nothing of size n x n is stored.  batch_size, eta / n, sum_loss and `it` count positives;
+ * penalties, step sizes, prox and the psgd options (adaptive and FTRL steps included) are those of
+ * spfm_psgd_epoch.  The gradient is summed with f64 atomics: there is no deterministic form.
+ * Checked on the host before anything is launched (the parameters stay as they were):
+ * SPFM_ERR_INVALID: a row outside [0, n), a column stored in a context row and in a candidate
+ * row, m < 1, batch_size < 1, the step argument errors of spfm_psgd_epoch;
+ * SPFM_ERR_UNSUPPORTED: a handle with a communicator, a handle in either deterministic mode
+ * (spfm_psgd_set_deterministic, spfm_psgd_pairs_set_deterministic), a handle with sample weights,
+ * more than 2^20 positives in a minibatch.  There is no cap on the towers' width. */
+int spfm_psgd_inbatch_epoch(spfm_handle h, int degree, double alpha, double beta, double gamma,
+                            double eta0, int learning_rate, double power_t, int64_t batch_size,
+                            const int32_t* pairs /* (m,2) */, int64_t m, int fit_linear,
+                            int64_t* it, double* sum_loss);
+/* The same minibatches at the live device parameters, nothing updated (the parameters keep their
+ * bits): sum_loss = sum of the positives' losses.  Same argument errors. */
+int spfm_psgd_inbatch_eval(spfm_handle h, int degree, int64_t batch_size,
+                           const int32_t* pairs /* (m,2) */, int64_t m, double* sum_loss);
+
 /* -- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------
  * Rows are sharded; the column partial sums of every step are all-reduced
  * (sum, f64) so that every rank applies the identical prox.  id is an opaque

@@ -1225,6 +1225,23 @@ struct spfm_engine {
     int psgd_lists_eval(int degree, int fit_linear, const int32_t* triples, int64_t m,
                         int64_t n_negatives, int list_loss, double* sum_loss, int64_t* n_first);
 
+    // in-batch softmax (spfm_engine_psgd_inbatch.hip): the positives of a
+    // minibatch are each other's negatives.  The epoch's pair list and losses, and the images
+    // of ONE minibatch -- towers U / V (ib_Bpad, ib_Rp), colconst, their upstream gradients, the
+    // softmax statistics -- sized by min(batch_size, m).  A moved buffer clears the graphs.
+    DevBuf ib_pairs, ib_loss, ib_U, ib_V, ib_dU, ib_dV, ib_cc, ib_part, ib_mx, ib_rz, ib_diag;
+    int ib_R = 0, ib_Rp = 0, ib_Bpad = 0, ib_strip_tiles = 1, ib_nstrips = 1;
+    int psgd_inbatch_check(const char* what, int degree, int64_t batch_size, const int32_t* pairs,
+                           int64_t m);
+    int inbatch_prepare(int degree, int64_t batch_size, const int32_t* pairs, int64_t m);
+    template <typename T, int L>
+    void inbatch_launch_tl(int64_t pos, int B, bool table, int degree, int fit_linear, bool eval);
+    void inbatch_launch(int64_t pos, int B, bool table, int degree, int fit_linear, bool eval);
+    int psgd_inbatch_run(const PsgdStep& st, int64_t m);  // the batches (spfm_engine_psgd.hip)
+    int psgd_inbatch_epoch(const PsgdStep& st, const int32_t* pairs, int64_t m, double* sum_loss);
+    int psgd_inbatch_eval(int degree, int64_t batch_size, const int32_t* pairs, int64_t m,
+                          double* sum_loss);
+
     // ------------------------------- objective terms, held-out set (spfm_engine_objective.hip)
     // Read-only views of the live state: they use buffers of their own, neither of the
     // P / Pt validity flags changes, nothing an epoch reads is written.

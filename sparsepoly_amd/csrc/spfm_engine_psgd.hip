@@ -1029,6 +1029,20 @@ int spfm_engine::psgd_lists_eval(int degree, int fit_linear, const int32_t* trip
     return SPFM_OK;
 }
 
+// ====================================================== in-batch softmax
+// the batches over the resident pair list: the six launches of spfm_engine_psgd_inbatch.hip as
+// the gradient (the recorded kernel arguments hold the images' shape: part of the graph key)
+int spfm_engine::psgd_inbatch_run(const PsgdStep& st, int64_t m) {
+    p_valid = false;
+    auto grad = [&](int64_t pos, int B, int, bool table) {
+        inbatch_launch(pos, B, table, st.degree, st.fit_linear, false);
+    };
+    const std::string tag =
+        "psgd_inbatch|" + std::to_string(ib_Bpad) + "|" + std::to_string(ib_Rp);
+    const int64_t tsize = dtype == SPFM_F32 ? 4 : 8;
+    return SPFM_DISPATCH_L(k, return psgd_batches_tl<L>(grad, tag.c_str(), tsize, m, st));
+}
+
 extern "C" {
 
 int spfm_psgd_epoch(spfm_handle h, int degree, double alpha, double beta, double gamma,

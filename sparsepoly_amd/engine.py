@@ -1741,6 +1741,40 @@ class HipEngine(object):
             int(n_negatives), self._list_loss(list_loss), C.byref(sl), C.byref(nf)))
         return sl.value, nf.value
 
+    @staticmethod
+    def _pairs(pairs):
+        t = np.ascontiguousarray(pairs, dtype=np.int32)
+        if t.ndim != 2 or t.shape[1] != 2:
+            raise ValueError("pairs must have shape (m, 2), got %r" % (t.shape,))
+        return t
+
+    def psgd_inbatch_epoch(self, degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                           batch_size, pairs, fit_linear, it):
+        """One pass of minibatch psgd with the in-batch softmax:
+        ``pairs`` (m, 2) holds the positives as rows (context, candidate) of ``[X; Z]``, visited
+        in the order given; the other positives of a minibatch are a positive's negatives
+        (``spfm_psgd_inbatch_epoch``).  Returns (sum_loss over the positives, it)."""
+        t = self._pairs(pairs)
+        itc = C.c_int64(int(it))
+        sl = C.c_double()
+        lr = (_capi.LEARNING_RATE[learning_rate] if isinstance(learning_rate, str)
+              else int(learning_rate))
+        self._check(self._lib.spfm_psgd_inbatch_epoch(
+            self._h, int(degree), float(alpha), float(beta), float(gamma), float(eta0), lr,
+            float(power_t), int(batch_size), t.ctypes.data_as(_capi._ip), t.shape[0],
+            int(bool(fit_linear)), C.byref(itc), C.byref(sl)))
+        return sl.value, itc.value
+
+    def psgd_inbatch_eval(self, degree, batch_size, pairs):
+        """The sum of the positives' in-batch softmax losses over the same minibatches at the
+        live device parameters; nothing is updated (``spfm_psgd_inbatch_eval``)."""
+        t = self._pairs(pairs)
+        sl = C.c_double()
+        self._check(self._lib.spfm_psgd_inbatch_eval(
+            self._h, int(degree), int(batch_size), t.ctypes.data_as(_capi._ip), t.shape[0],
+            C.byref(sl)))
+        return sl.value
+
     # ------------------------------------------------------------- multi-GPU
     @staticmethod
     def comm_unique_id():

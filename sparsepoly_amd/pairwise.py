@@ -23,6 +23,8 @@ training item (``restate_list_scores`` / ``restate_list_g
 ``sampler='warp'``, ``proposal=`` and ``sample_weight=`` are DESIGN.md section 19c: a weight per
 triple, a weighted integer draw (``quantise_proposal`` / ``proposal_cum``) and the rank-weighted
 sampler (``restate_warp``).
+``sampler='in_batch'`` is DESIGN.md section 19h: no negatives are drawn, the positives of a
+minibatch are each other's negatives (``restate_inbatch_gradient`` / ``restate_inbatch_epoch``).
 There is no CPU path of the fit: without the library or a GPU it raises.
 """
 import numpy as np
@@ -134,7 +136,7 @@ def check_triples(triples, B, C):
     return np.ascontiguousarray(t, dtype=np.int32)
 
 
-SAMPLERS = ("host", "uniform", "dynamic", "warp")
+SAMPLERS = ("host", "uniform", "dynamic", "warp", "in_batch")
 _MASK64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
@@ -884,6 +886,117 @@ def epoch_lists(rng, n_epochs, interactions=None, triples=None, n_negatives=1, r
         yield out
 
 
+# ------------------------------------------------------------------ in-batch softmax (19h)
+def check_pairs(pairs, B, C):
+    """``(m, 2)`` int32 positives ``(b, c)`` in context / candidate numbering, checked against
+    ``B`` contexts and ``C`` candidates.  Needs no device."""
+    t = np.asarray(pairs)
+    if t.ndim != 2 or t.shape[1] != 2:
+        raise ValueError("pairs must have shape (m, 2), got %r" % (t.shape,))
+    if t.shape[0] == 0 or t.shape[0] >= 2 ** 31:
+        raise ValueError("pairs must hold 1 <= m < 2**31 rows, got %d" % t.shape[0])
+    if not np.issubdtype(t.dtype, np.integer) and not np.all(t == np.floor(t)):
+        raise ValueError("pairs must hold integers")
+    t = t.astype(np.int64)
+    if t[:, 0].min() < 0 or t[:, 0].max() >= B:
+        raise ValueError("pairs: context index out of range [0, %d)" % B)
+    if t[:, 1].min() < 0 or t[:, 1].max() >= C:
+        raise ValueError("pairs: candidate index out of range [0, %d)" % C)
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def restate_inbatch_gradient(P, w, lams, X, Z, pairs, degree, wide=False):
+    """Test aid, NumPy only: ``(losses (n,), grad_P (n_orders, k, d), grad_w (d,))`` of ONE
+    minibatch of the in-batch softmax over the positives ``pairs``
+    ``(n, 2)`` (context / candidate numbering).  Row ``q`` scores every candidate ``c_q'`` of the
+    batch on the dense summed row ``x_{b_q} + z_{c_q'}``, score by score -- the tower identity of
+    the device is NOT used here; column ``q' != q`` is left out when ``c_q' == c_q`` or
+    ``b_q' == b_q``; ``loss_q = -s[q, q] + log sum exp`` over the admitted columns,
+    max-subtracted.  ``grad_w`` is formed from the ``z`` alone: the coefficients of a row sum to
+    zero and the context's columns are exactly zero."""
+    dtype = np.longdouble if wide else np.double
+    P, w, lams = _as(dtype, P, w, lams)
+    P = P[None] if P.ndim == 2 else P
+    Xd, Zd = _dense_sides(X, Z, dtype)
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    b, c = pr[:, 0], pr[:, 1]
+    n = pr.shape[0]
+    adm = ~((b[:, None] == b[None, :]) | (c[:, None] == c[None, :])) | np.eye(n, dtype=bool)
+    lin = Zd[c] @ w
+    val = np.zeros(n, dtype=dtype)
+    gP = np.zeros_like(P)
+    gw = np.zeros_like(w)
+    for q in range(n):
+        V = Xd[b[q]][None, :] + Zd[c]
+        f, dps = _rows_output(P, lams, V, degree)
+        s = f + lin
+        mx = s[adm[q]].max()
+        ex = np.where(adm[q], np.exp(np.where(adm[q], s - mx, 0)), 0)
+        z = ex.sum()
+        coef = ex / z
+        coef[q] -= 1
+        val[q] = (mx - s[q]) + np.log(z)
+        gw += coef @ Zd[c]
+        x = V[:, None, :]
+        for o in range(P.shape[0]):
+            dprev = np.broadcast_to(x, (n, P.shape[1], V.shape[1]))
+            for tt in range(1, degree - o):
+                dprev = x * (dps[o][tt][:, :, None] - P[o][None] * dprev)
+            gP[o] += np.einsum("r,s,rsj->sj", coef, lams, dprev)
+    return val, gP, gw
+
+
+def restate_inbatch_epoch(P, w, lams, X, Z, pairs, degree, regularizer="l1", alpha=1.0, beta=1.0,
+                          gamma=1.0, eta0=1.0, learning_rate="optimal", power_t=1.0,
+                          batch_size=1, fit_linear=True, it=1, wide=False, adaptive=None,
+                          acc=None, ftrl=None, state=None):
+    """Test aid, NumPy only: one epoch of the in-batch softmax fit over ``pairs`` (visited in the
+    order given).  ``restate_list_epoch`` with positives as items: minibatch ``bi`` covers the
+    positions ``[bi * batch_size, ...)`` and is its own candidate set, the step is ``eta / n``.
+    Returns ``(P, w, sum_loss, it)`` (new arrays); with ``adaptive`` / ``acc`` or ``ftrl`` /
+    ``state`` as in ``restate_pairwise_epoch``, a fifth item."""
+    dtype = np.longdouble if wide else np.double
+    P, w, lams = _as(dtype, P, w, lams)
+    P = (P[None] if P.ndim == 2 else P).copy()
+    w = w.copy()
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    sum_loss = dtype(0)
+    G0, acc = _adaptive_state(adaptive, acc, P, dtype)
+    F0, state = _ftrl_state(ftrl, state, P, w, dtype, eta0, alpha, beta, gamma, regularizer)
+    for pos in range(0, pr.shape[0], int(batch_size)):
+        pb = pr[pos:pos + int(batch_size)]
+        B = pb.shape[0]
+        val, gP, gw = restate_inbatch_gradient(P, w, lams, X, Z, pb, degree, wide)
+        sum_loss += val.sum()
+        eta_P, eta_w = _psgd_eta(learning_rate, eta0, alpha, beta, power_t, it)
+        it += 1
+        if F0 is not None:
+            P, w = _ftrl_step(P, w, gP, gw, B, eta_P, eta_w, alpha, beta, gamma, regularizer,
+                              fit_linear, F0, state)
+        elif G0 is not None:
+            P, w = _adaptive_step(P, w, gP, gw, B, eta_P, eta_w, alpha, beta, gamma, regularizer,
+                                  fit_linear, G0, acc)
+        else:
+            if fit_linear:
+                w = (w - gw * (eta_w / B)) / (1 + eta_w * alpha)
+            P = (P - gP * (eta_P / B)) / (1 + eta_P * beta)
+            strength = gamma * eta_P / (1 + eta_P * beta)
+            P = np.stack([_prox(regularizer, P[o], dtype(strength)) for o in range(P.shape[0])])
+    if F0 is not None:
+        return P, w, sum_loss, it, tuple(state)
+    if G0 is not None:
+        return P, w, sum_loss, it, acc
+    return P, w, sum_loss, it
+
+
+def epoch_pairs(rng, n_epochs, pairs, shuffle=False):
+    """The pair list of every epoch of a ``sampler='in_batch'`` fit, in the order the device
+    visits it: with ``shuffle`` permuted by ``rng.permutation(m)`` before every epoch."""
+    pairs = np.asarray(pairs, dtype=np.int32)
+    for ep in range(n_epochs):
+        yield pairs[rng.permutation(pairs.shape[0])] if shuffle else pairs
+
+
 # ------------------------------------------------------------------ the estimator
 class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
     """Factorization machine trained for an order: minibatch psgd on the pairwise loss
@@ -998,7 +1111,16 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
           ``triples`` one value per triple.  It multiplies the triple's loss and gradient.
 
         The mean loss of the stopping rule stays ``sum_loss / m`` with ``m`` the number of
-        triples, not the weight sum."""
+        triples, not the weight sum.
+
+        ``sampler='in_batch'`` (with ``objective='softmax'`` and
+        ``n_negatives=1``): no negative is drawn; the positives of a minibatch are each other's
+        negatives, up to ``batch_size - 1`` of them, left out of a row where they share its
+        candidate or its context.  ``interactions`` gives the positives in canonical CSR order;
+        ``triples`` is accepted too, and only its ``(b, c+)`` columns are read (``c-`` is
+        ignored).  ``shuffle`` permutes the positives before every epoch; ``batch_size``, the
+        mean loss of the stopping rule and ``it_`` count positives.  Not with ``exclude``,
+        ``proposal``, ``sample_weight`` or ``deterministic=True``."""
         self._check_config()
         if objective not in OBJECTIVES:
             raise ValueError("objective %r is not supported. Choose from %s."
@@ -1008,14 +1130,26 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
             raise ValueError("deterministic=True covers objective='pairwise' (DESIGN.md section "
                              "19f); the gradients of the lists (objective=%r) are summed with "
                              "atomics." % (objective,))
-        if listwise:
+        if listwise and sampler != "in_batch":  # (in-batch: no lists; its own checks below)
             check_lists(triples, n_negatives, objective)
         if sampler not in SAMPLERS:
             raise ValueError("sampler %r is not supported. Choose from %s."
                              % (sampler, list(SAMPLERS)))
+        in_batch = sampler == "in_batch"
+        if in_batch:
+            if objective != "softmax":
+                raise ValueError("sampler='in_batch' is the in-batch softmax: it needs "
+                                 "objective='softmax', got %r" % (objective,))
+            if n_negatives != 1:
+                raise ValueError("sampler='in_batch' draws no negatives: n_negatives must be 1, "
+                                 "got %r" % (n_negatives,))
+            for name, given in (("exclude", exclude), ("proposal", proposal),
+                                ("sample_weight", sample_weight)):
+                if given is not None:
+                    raise ValueError("sampler='in_batch' does not take %s" % name)
         if (interactions is None) == (triples is None):
             raise ValueError("exactly one of interactions and triples must be given")
-        if sampler != "host" and triples is not None:
+        if sampler not in ("host", "in_batch") and triples is not None:
             raise ValueError("sampler=%r draws the negatives on the device: give interactions, "
                              "not triples" % (sampler,))
         if int(n_candidates) != n_candidates or n_candidates < 1:
@@ -1059,7 +1193,7 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                 raise ValueError("interactions has no stored entry")
             if exclude is not None:
                 exclude = _pattern(exclude, B, C, "exclude")
-            if sampler != "host":
+            if sampler not in ("host", "in_batch"):
                 if int(n_negatives) != n_negatives or n_negatives < 1:
                     raise ValueError("n_negatives must be an integer >= 1, got %r"
                                      % (n_negatives,))
@@ -1109,7 +1243,15 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
             self._adagrad_begin(engine, self.P_.shape)
             if not listwise:  # (a list fit with it raised above)
                 engine.psgd_pairs_set_deterministic(int(bool(self.deterministic)))
-            if sampler == "host" and sample_weight is not None:
+            if in_batch:  # the positives alone: canonical CSR order, or the triples' (b, c+)
+                if interactions is not None:
+                    pos = np.stack([np.repeat(np.arange(B), np.diff(interactions.indptr)),
+                                    interactions.indices], axis=1)
+                else:
+                    pos = triples[:, :2]
+                objective = "in_batch"
+                lists = epoch_pairs(rng, self.max_iter, pos, self.shuffle)
+            elif sampler == "host" and sample_weight is not None:
                 lists = epoch_triples(rng, self.max_iter, interactions, triples, n_negatives,
                                       resample, self.shuffle, exclude, weights=sample_weight)
             elif sampler == "host":
@@ -1174,7 +1316,11 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
         step = (self.degree, self.alpha, self.beta, self.gamma, self.eta0, self._base_rate(),
                 self.power_t, batch_size)
         for epoch, t in enumerate(lists):
-            if objective != "pairwise" and isinstance(t, np.ndarray):
+            if objective == "in_batch":  # (m, 2) positives; the items are positives
+                m = t.shape[0]
+                sum_loss, self.it_ = engine.psgd_inbatch_epoch(
+                    *step, t + np.array([0, B], dtype=np.int32), self.fit_linear, self.it_)
+            elif objective != "pairwise" and isinstance(t, np.ndarray):
                 m = t.shape[0] // n_negatives
                 stacked = t + np.array([0, B, B], dtype=np.int32)  # rows of [X; Z]
                 sum_loss, self.it_ = engine.psgd_lists_epoch(
@@ -1318,6 +1464,31 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
             engine.close()
         q = t.shape[0] // int(n_negatives)
         return sum_loss / q, n_first / q
+
+    def in_batch_loss(self, X, Z, pairs, batch_size):
+        """The mean in-batch softmax loss of the fitted model over the
+        positives ``pairs`` ``(m, 2)`` -- rows ``(b, c)``, context / candidate numbering -- cut
+        into minibatches of ``batch_size`` in the order given, on the device
+        (``spfm_psgd_inbatch_eval``)."""
+        if not hasattr(self, "P_"):
+            raise NotFittedError("Estimator not fitted.")
+        self._check_config()
+        if int(batch_size) != batch_size or batch_size < 1:
+            raise ValueError("batch_size must be an integer >= 1, got %r" % (batch_size,))
+        Xa, Za = _prepare(self, X, Z)
+        t = check_pairs(pairs, Xa.shape[0], Za.shape[0])
+        S = sp.vstack([Xa, Za], format="csr")
+        S.sort_indices()
+        engine = self._new_engine()
+        try:
+            engine.set_data(S, np.zeros(S.shape[0]))
+            engine.set_params(np.ascontiguousarray(self.P_, dtype=np.double), self.w_, self.lams_)
+            engine.configure("psgd", self.loss, self.regularizer, self.degree)
+            sum_loss = engine.psgd_inbatch_eval(
+                self.degree, int(batch_size), t + np.array([0, Xa.shape[0]], dtype=np.int32))
+        finally:
+            engine.close()
+        return sum_loss / t.shape[0]
 
     def decision_function(self, rows):
         """The model output of every row of ``rows`` (n, d), e.g. of ``x_b + z_c``."""
