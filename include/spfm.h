@@ -595,6 +595,39 @@ int spfm_psgd_inbatch_epoch(spfm_handle h, int degree, double alpha, double beta
 int spfm_psgd_inbatch_eval(spfm_handle h, int degree, int64_t batch_size,
                            const int32_t* pairs /* (m,2) */, int64_t m, double* sum_loss);
 
+/* Full-catalogue softmax: the training item is a positive pair (context
+ * row, candidate row) of the stacked image [X; Z], and EVERY candidate the context has not
+ * interacted with is its negative.  The contexts (rows [0, B)), the candidates (rows [B, B + C)),
+ * the positives and the forbidden CSR F are those spfm_psgd_pairs_set_sampler left on the handle.
+ * `pairs` (m, 2) is visited in the order given, minibatch = positions [pos, pos + n),
+ * n <= batch_size (the last may be short); it is uploaded per epoch.  With
+ *   s[q, c] = sum_o sum_s lams_s a_s^{degree-o}(x_{b_q} + z_c) + <w, z_c>          c in [0, C)
+ * candidate c is part of row q iff c == c_q or c is not in F[b_q], and
+ *   loss_q = -s[q, c_q] + log sum_{c admitted} exp(s[q, c])     (max-subtracted, f64)
+ * Two positions with one context are two rows; each masks the other's positive.  The n x C
+ * logits are 64 x 64 tiles of the f64 matrix instruction over the context tower of the minibatch
+ * and the catalogue tower; the masks are formed per tile from F and nothing of size n x C is
+ * stored.  batch_size, eta / n, sum_loss and `it` count positives; penalties, step sizes, prox
+ * and the psgd options (adaptive and FTRL steps included) are those of spfm_psgd_epoch.  The
+ * gradient is summed with f64 atomics: there is no deterministic form.
+ * Checked on the host before anything is launched (the parameters stay as they were):
+ * SPFM_ERR_INVALID: no sampler on the handle, a pair whose context is outside [0, B) or whose
+ * candidate is outside [B, B + C), a pair that is not one of the sampler's positives, m < 1,
+ * batch_size < 1, the step argument errors of spfm_psgd_epoch;
+ * SPFM_ERR_UNSUPPORTED: a handle with a communicator, a handle in either deterministic mode
+ * (spfm_psgd_set_deterministic, spfm_psgd_pairs_set_deterministic), a handle with sample weights,
+ * more than 2^20 positives in a minibatch, C > 2^20, a catalogue tower and gradient
+ * (2 x Cpad x Rp doubles) above 1 GiB.  There is no cap on the towers' width. */
+int spfm_psgd_full_epoch(spfm_handle h, int degree, double alpha, double beta, double gamma,
+                         double eta0, int learning_rate, double power_t, int64_t batch_size,
+                         const int32_t* pairs /* (m,2) */, int64_t m, int fit_linear,
+                         int64_t* it, double* sum_loss);
+/* The same rows at the live device parameters, nothing updated (the parameters keep their bits):
+ * sum_loss = sum of the positives' losses.  A row's loss does not depend on its minibatch.  Same
+ * argument errors. */
+int spfm_psgd_full_eval(spfm_handle h, int degree, int64_t batch_size,
+                        const int32_t* pairs /* (m,2) */, int64_t m, double* sum_loss);
+
 /* -- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------
  * Rows are sharded; the column partial sums of every step are all-reduced
  * (sum, f64) so that every rank applies the identical prox.  id is an opaque

@@ -98,6 +98,7 @@ SYMBOLS = [
     "spfm_psgd_pairs_set_positive_weights", "spfm_psgd_pairs_sample_warp",
     "spfm_psgd_lists_epoch", "spfm_psgd_lists_epoch_sampled", "spfm_psgd_lists_eval",
     "spfm_psgd_inbatch_epoch", "spfm_psgd_inbatch_eval",
+    "spfm_psgd_full_epoch", "spfm_psgd_full_eval",
     "spfm_psgd_set_adaptive", "spfm_psgd_get_adaptive",
     "spfm_psgd_set_ftrl", "spfm_psgd_get_ftrl",
     "spfm_psgd_set_deterministic", "spfm_psgd_get_deterministic",
@@ -244,6 +245,8 @@ def load():
                                           C.c_double, C.c_int, C.c_double, C.c_int64, _ip,
                                           C.c_int64, C.c_int, _lp, _dp]
     L.spfm_psgd_inbatch_eval.argtypes = [_h, C.c_int, C.c_int64, _ip, C.c_int64, _dp]
+    L.spfm_psgd_full_epoch.argtypes = L.spfm_psgd_inbatch_epoch.argtypes
+    L.spfm_psgd_full_eval.argtypes = L.spfm_psgd_inbatch_eval.argtypes
     L.spfm_psgd_set_adaptive.argtypes = [_h, C.c_int, C.c_double, _dp, _dp]
     L.spfm_psgd_get_adaptive.argtypes = [_h, _dp, _dp]
     L.spfm_psgd_set_ftrl.argtypes = [_h, C.c_int] + [C.c_double] * 5 + [_dp] * 4

@@ -1242,6 +1242,30 @@ struct spfm_engine {
     int psgd_inbatch_eval(int degree, int64_t batch_size, const int32_t* pairs, int64_t m,
                           double* sum_loss);
 
+    // full-catalogue softmax (spfm_engine_psgd_full.hip): every candidate
+    // the context has not interacted with is a negative.  B, C and the forbidden CSR are the
+    // sampler's (sm_fptr / sm_fidx; h_sm_posptr / h_sm_posidx: the host copy of its positives, for
+    // the check that a pair is one of them).  The epoch's pair list and losses, the context tower
+    // of ONE minibatch (fl_Bpad, fl_Rp) and the catalogue tower (fl_Cpad, fl_Rp) with their
+    // gradients and the softmax statistics.  A moved buffer clears the graphs.
+    DevBuf fl_pairs, fl_loss, fl_U, fl_dU, fl_Vc, fl_dVc, fl_cc, fl_part, fl_mx, fl_rz, fl_spos;
+    std::vector<int64_t> h_sm_posptr;
+    std::vector<int32_t> h_sm_posidx;
+    const void *fl_fptr_seen = nullptr, *fl_fidx_seen = nullptr;  // what the graphs recorded
+    int fl_R = 0, fl_Rp = 0, fl_Bpad = 0, fl_Cpad = 0;
+    int fl_st_tiles = 1, fl_st_strips = 1, fl_gu_tiles = 1, fl_gu_strips = 1, fl_gv_tiles = 1,
+        fl_gv_strips = 1;
+    int psgd_full_check(const char* what, int degree, int64_t batch_size, const int32_t* pairs,
+                        int64_t m);
+    int full_prepare(int degree, int64_t batch_size, const int32_t* pairs, int64_t m);
+    template <typename T, int L>
+    void full_launch_tl(int64_t pos, int B, bool table, int degree, int fit_linear, bool eval);
+    void full_launch(int64_t pos, int B, bool table, int degree, int fit_linear, bool eval);
+    int psgd_full_run(const PsgdStep& st, int64_t m);  // the batches (spfm_engine_psgd.hip)
+    int psgd_full_epoch(const PsgdStep& st, const int32_t* pairs, int64_t m, double* sum_loss);
+    int psgd_full_eval(int degree, int64_t batch_size, const int32_t* pairs, int64_t m,
+                       double* sum_loss);
+
     // ------------------------------- objective terms, held-out set (spfm_engine_objective.hip)
     // Read-only views of the live state: they use buffers of their own, neither of the
     // P / Pt validity flags changes, nothing an epoch reads is written.

@@ -738,6 +738,8 @@ int spfm_engine::psgd_pairs_set_sampler(int64_t n_ctx, int64_t n_cand, const int
     sm_nctx = n_ctx;
     sm_ncand = n_cand;
     sm_npos = npos;
+    h_sm_posptr.assign(pos_ptr, pos_ptr + n_ctx + 1);  // (section 19i checks its pairs against them)
+    h_sm_posidx.assign(pos_idx, pos_idx + npos);
     have_sampler = true;
     return SPFM_OK;
 }
@@ -1039,6 +1041,20 @@ int spfm_engine::psgd_inbatch_run(const PsgdStep& st, int64_t m) {
     };
     const std::string tag =
         "psgd_inbatch|" + std::to_string(ib_Bpad) + "|" + std::to_string(ib_Rp);
+    const int64_t tsize = dtype == SPFM_F32 ? 4 : 8;
+    return SPFM_DISPATCH_L(k, return psgd_batches_tl<L>(grad, tag.c_str(), tsize, m, st));
+}
+
+// ====================================================== full-catalogue softmax
+// the batches over the resident pair list: the eight launches of spfm_engine_psgd_full.hip as the
+// gradient (the recorded kernel arguments hold the towers' shapes: part of the graph key)
+int spfm_engine::psgd_full_run(const PsgdStep& st, int64_t m) {
+    p_valid = false;
+    auto grad = [&](int64_t pos, int B, int, bool table) {
+        full_launch(pos, B, table, st.degree, st.fit_linear, false);
+    };
+    const std::string tag = "psgd_full|" + std::to_string(fl_Bpad) + "|" +
+                            std::to_string(fl_Cpad) + "|" + std::to_string(fl_Rp);
     const int64_t tsize = dtype == SPFM_F32 ? 4 : 8;
     return SPFM_DISPATCH_L(k, return psgd_batches_tl<L>(grad, tag.c_str(), tsize, m, st));
 }

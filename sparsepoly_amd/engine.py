@@ -1775,6 +1775,34 @@ class HipEngine(object):
             C.byref(sl)))
         return sl.value
 
+    def psgd_full_epoch(self, degree, alpha, beta, gamma, eta0, learning_rate, power_t,
+                        batch_size, pairs, fit_linear, it):
+        """One pass of minibatch psgd with the full-catalogue softmax:
+        ``pairs`` (m, 2) holds the positives as rows (context, candidate) of ``[X; Z]``, visited
+        in the order given; every candidate outside the context's row of the forbidden set that
+        ``psgd_pairs_set_sampler`` left on the handle is a negative (``spfm_psgd_full_epoch``).
+        Returns (sum_loss over the positives, it)."""
+        t = self._pairs(pairs)
+        itc = C.c_int64(int(it))
+        sl = C.c_double()
+        lr = (_capi.LEARNING_RATE[learning_rate] if isinstance(learning_rate, str)
+              else int(learning_rate))
+        self._check(self._lib.spfm_psgd_full_epoch(
+            self._h, int(degree), float(alpha), float(beta), float(gamma), float(eta0), lr,
+            float(power_t), int(batch_size), t.ctypes.data_as(_capi._ip), t.shape[0],
+            int(bool(fit_linear)), C.byref(itc), C.byref(sl)))
+        return sl.value, itc.value
+
+    def psgd_full_eval(self, degree, batch_size, pairs):
+        """The sum of the positives' full-catalogue softmax losses at the live device parameters;
+        nothing is updated (``spfm_psgd_full_eval``)."""
+        t = self._pairs(pairs)
+        sl = C.c_double()
+        self._check(self._lib.spfm_psgd_full_eval(
+            self._h, int(degree), int(batch_size), t.ctypes.data_as(_capi._ip), t.shape[0],
+            C.byref(sl)))
+        return sl.value
+
     # ------------------------------------------------------------- multi-GPU
     @staticmethod
     def comm_unique_id():

@@ -25,6 +25,8 @@ triple, a weighted integer draw (``quantise_proposal`` / ``proposal_cum``) and t
 sampler (``restate_warp``).
 ``sampler='in_batch'`` is DESIGN.md section 19h: no negatives are drawn, the positives of a
 minibatch are each other's negatives (``restate_inbatch_gradient`` / ``restate_inbatch_epoch``).
+``sampler='full'`` is DESIGN.md section 19i: every candidate the context has not interacted with
+is a negative (``restate_full_gradient`` / ``restate_full_epoch``).
 There is no CPU path of the fit: without the library or a GPU it raises.
 """
 import numpy as np
@@ -136,7 +138,7 @@ def check_triples(triples, B, C):
     return np.ascontiguousarray(t, dtype=np.int32)
 
 
-SAMPLERS = ("host", "uniform", "dynamic", "warp", "in_batch")
+SAMPLERS = ("host", "uniform", "dynamic", "warp", "in_batch", "full")
 _MASK64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
@@ -997,6 +999,93 @@ def epoch_pairs(rng, n_epochs, pairs, shuffle=False):
         yield pairs[rng.permutation(pairs.shape[0])] if shuffle else pairs
 
 
+# ------------------------------------------------------------------ full-catalogue softmax (19i)
+def restate_full_gradient(P, w, lams, X, Z, pairs, F, degree, wide=False):
+    """Test aid, NumPy only: ``(losses (n,), grad_P (n_orders, k, d), grad_w (d,))`` of ONE
+    minibatch of the full-catalogue softmax over the positives ``pairs``
+    ``(n, 2)`` (context / candidate numbering).  Row ``q`` scores EVERY candidate ``c`` on the
+    dense summed row ``x_{b_q} + z_c``, score by score -- the tower identity of the device is NOT
+    used here; ``c`` is admitted iff ``c == c_q`` or ``c`` is not stored in row ``b_q`` of the
+    forbidden pattern ``F`` ``(B, C)``; ``loss_q = -s[q, c_q] + log sum exp`` over the admitted
+    candidates, max-subtracted.  ``grad_w`` is formed from the ``z`` alone: the coefficients of a
+    row sum to zero and the context's columns are exactly zero."""
+    dtype = np.longdouble if wide else np.double
+    P, w, lams = _as(dtype, P, w, lams)
+    P = P[None] if P.ndim == 2 else P
+    Xd, Zd = _dense_sides(X, Z, dtype)
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    n, C = pr.shape[0], Zd.shape[0]
+    forb = np.asarray(sp.csr_matrix(F).todense()) != 0
+    lin = Zd @ w
+    val = np.zeros(n, dtype=dtype)
+    gP = np.zeros_like(P)
+    gw = np.zeros_like(w)
+    for q in range(n):
+        b, cq = pr[q]
+        adm = ~forb[b]
+        adm[cq] = True
+        V = Xd[b][None, :] + Zd
+        f, dps = _rows_output(P, lams, V, degree)
+        s = f + lin
+        mx = s[adm].max()
+        ex = np.where(adm, np.exp(np.where(adm, s - mx, 0)), 0)
+        z = ex.sum()
+        coef = ex / z
+        coef[cq] -= 1
+        val[q] = (mx - s[cq]) + np.log(z)
+        gw += coef @ Zd
+        x = V[:, None, :]
+        for o in range(P.shape[0]):
+            dprev = np.broadcast_to(x, (C, P.shape[1], V.shape[1]))
+            for tt in range(1, degree - o):
+                dprev = x * (dps[o][tt][:, :, None] - P[o][None] * dprev)
+            gP[o] += np.einsum("r,s,rsj->sj", coef, lams, dprev)
+    return val, gP, gw
+
+
+def restate_full_epoch(P, w, lams, X, Z, pairs, F, degree, regularizer="l1", alpha=1.0, beta=1.0,
+                       gamma=1.0, eta0=1.0, learning_rate="optimal", power_t=1.0, batch_size=1,
+                       fit_linear=True, it=1, wide=False, adaptive=None, acc=None, ftrl=None,
+                       state=None):
+    """Test aid, NumPy only: one epoch of the full-catalogue softmax fit over ``pairs`` (visited
+    in the order given) with the forbidden pattern ``F``.  ``restate_inbatch_epoch`` with
+    ``restate_full_gradient`` as the minibatch's gradient; the step is ``eta / n``.  Returns
+    ``(P, w, sum_loss, it)`` (new arrays); with ``adaptive`` / ``acc`` or ``ftrl`` / ``state`` as
+    in ``restate_pairwise_epoch``, a fifth item."""
+    dtype = np.longdouble if wide else np.double
+    P, w, lams = _as(dtype, P, w, lams)
+    P = (P[None] if P.ndim == 2 else P).copy()
+    w = w.copy()
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    sum_loss = dtype(0)
+    G0, acc = _adaptive_state(adaptive, acc, P, dtype)
+    F0, state = _ftrl_state(ftrl, state, P, w, dtype, eta0, alpha, beta, gamma, regularizer)
+    for pos in range(0, pr.shape[0], int(batch_size)):
+        pb = pr[pos:pos + int(batch_size)]
+        B = pb.shape[0]
+        val, gP, gw = restate_full_gradient(P, w, lams, X, Z, pb, F, degree, wide)
+        sum_loss += val.sum()
+        eta_P, eta_w = _psgd_eta(learning_rate, eta0, alpha, beta, power_t, it)
+        it += 1
+        if F0 is not None:
+            P, w = _ftrl_step(P, w, gP, gw, B, eta_P, eta_w, alpha, beta, gamma, regularizer,
+                              fit_linear, F0, state)
+        elif G0 is not None:
+            P, w = _adaptive_step(P, w, gP, gw, B, eta_P, eta_w, alpha, beta, gamma, regularizer,
+                                  fit_linear, G0, acc)
+        else:
+            if fit_linear:
+                w = (w - gw * (eta_w / B)) / (1 + eta_w * alpha)
+            P = (P - gP * (eta_P / B)) / (1 + eta_P * beta)
+            strength = gamma * eta_P / (1 + eta_P * beta)
+            P = np.stack([_prox(regularizer, P[o], dtype(strength)) for o in range(P.shape[0])])
+    if F0 is not None:
+        return P, w, sum_loss, it, tuple(state)
+    if G0 is not None:
+        return P, w, sum_loss, it, acc
+    return P, w, sum_loss, it
+
+
 # ------------------------------------------------------------------ the estimator
 class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
     """Factorization machine trained for an order: minibatch psgd on the pairwise loss
@@ -1120,6 +1209,13 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
         ``triples`` is accepted too, and only its ``(b, c+)`` columns are read (``c-`` is
         ignored).  ``shuffle`` permutes the positives before every epoch; ``batch_size``, the
         mean loss of the stopping rule and ``it_`` count positives.  Not with ``exclude``,
+        ``proposal``, ``sample_weight`` or ``deterministic=True``.
+
+        ``sampler='full'`` (with ``objective='softmax'`` and
+        ``n_negatives=1``): the full softmax.  Every positive of ``interactions`` is trained
+        against every candidate that row ``b`` of ``interactions`` and of ``exclude`` does not
+        store, formed in tiles on the device; no negative is drawn.  ``shuffle``, ``batch_size``,
+        the stopping rule and ``it_`` are as for ``'in_batch'``.  Not with ``triples``,
         ``proposal``, ``sample_weight`` or ``deterministic=True``."""
         self._check_config()
         if objective not in OBJECTIVES:
@@ -1147,6 +1243,20 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                                 ("sample_weight", sample_weight)):
                 if given is not None:
                     raise ValueError("sampler='in_batch' does not take %s" % name)
+        full = sampler == "full"
+        if full:
+            if objective != "softmax":
+                raise ValueError("sampler='full' is the full-catalogue softmax: it needs "
+                                 "objective='softmax', got %r" % (objective,))
+            if n_negatives != 1:
+                raise ValueError("sampler='full' draws no negatives: n_negatives must be 1, "
+                                 "got %r" % (n_negatives,))
+            for name, given in (("proposal", proposal), ("sample_weight", sample_weight)):
+                if given is not None:
+                    raise ValueError("sampler='full' does not take %s" % name)
+            if triples is not None:
+                raise ValueError("sampler='full' takes its forbidden set from interactions: "
+                                 "give interactions, not triples")
         if (interactions is None) == (triples is None):
             raise ValueError("exactly one of interactions and triples must be given")
         if sampler not in ("host", "in_batch") and triples is not None:
@@ -1251,6 +1361,12 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
                     pos = triples[:, :2]
                 objective = "in_batch"
                 lists = epoch_pairs(rng, self.max_iter, pos, self.shuffle)
+            elif full:  # the positives in canonical CSR order; B, C and F through the sampler
+                engine.psgd_pairs_set_sampler(B, C, interactions, forbidden)
+                pos = np.stack([np.repeat(np.arange(B), np.diff(interactions.indptr)),
+                                interactions.indices], axis=1)
+                objective = "full"
+                lists = epoch_pairs(rng, self.max_iter, pos, self.shuffle)
             elif sampler == "host" and sample_weight is not None:
                 lists = epoch_triples(rng, self.max_iter, interactions, triples, n_negatives,
                                       resample, self.shuffle, exclude, weights=sample_weight)
@@ -1316,10 +1432,12 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
         step = (self.degree, self.alpha, self.beta, self.gamma, self.eta0, self._base_rate(),
                 self.power_t, batch_size)
         for epoch, t in enumerate(lists):
-            if objective == "in_batch":  # (m, 2) positives; the items are positives
+            if objective in ("in_batch", "full"):  # (m, 2) positives; the items are positives
                 m = t.shape[0]
-                sum_loss, self.it_ = engine.psgd_inbatch_epoch(
-                    *step, t + np.array([0, B], dtype=np.int32), self.fit_linear, self.it_)
+                run = engine.psgd_inbatch_epoch if objective == "in_batch" else \
+                    engine.psgd_full_epoch
+                sum_loss, self.it_ = run(*step, t + np.array([0, B], dtype=np.int32),
+                                         self.fit_linear, self.it_)
             elif objective != "pairwise" and isinstance(t, np.ndarray):
                 m = t.shape[0] // n_negatives
                 stacked = t + np.array([0, B, B], dtype=np.int32)  # rows of [X; Z]
@@ -1489,6 +1607,38 @@ class SparseFactorizationMachineRanker(_BaseSparseFactorizationMachine):
         finally:
             engine.close()
         return sum_loss / t.shape[0]
+
+    def full_softmax_loss(self, X, Z, interactions, exclude=None, batch_size=4096):
+        """The mean full-catalogue cross-entropy of the fitted model over
+        the stored entries of ``interactions``: each against every candidate that its context's
+        row of ``interactions`` and of ``exclude`` does not store, on the device
+        (``spfm_psgd_full_eval``).  ``batch_size`` sizes the launches, not the result."""
+        if not hasattr(self, "P_"):
+            raise NotFittedError("Estimator not fitted.")
+        self._check_config()
+        if int(batch_size) != batch_size or batch_size < 1:
+            raise ValueError("batch_size must be an integer >= 1, got %r" % (batch_size,))
+        Xa, Za = _prepare(self, X, Z)
+        B, C = Xa.shape[0], Za.shape[0]
+        if not sp.issparse(interactions):
+            interactions = sp.csr_matrix(np.asarray(interactions))
+        I, F = _forbidden(interactions, exclude, B, C)
+        if I.nnz == 0:
+            raise ValueError("interactions has no stored entry")
+        pos = np.stack([np.repeat(np.arange(B), np.diff(I.indptr)), I.indices], axis=1)
+        S = sp.vstack([Xa, Za], format="csr")
+        S.sort_indices()
+        engine = self._new_engine()
+        try:
+            engine.set_data(S, np.zeros(S.shape[0]))
+            engine.set_params(np.ascontiguousarray(self.P_, dtype=np.double), self.w_, self.lams_)
+            engine.configure("psgd", self.loss, self.regularizer, self.degree)
+            engine.psgd_pairs_set_sampler(B, C, I, F)
+            sum_loss = engine.psgd_full_eval(self.degree, int(batch_size),
+                                             (pos + np.array([0, B])).astype(np.int32))
+        finally:
+            engine.close()
+        return sum_loss / pos.shape[0]
 
     def decision_function(self, rows):
         """The model output of every row of ``rows`` (n, d), e.g. of ``x_b + z_c``."""
